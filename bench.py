@@ -2,6 +2,7 @@
 """bench.py -- Bellman-sweep throughput of the HIP hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload car7d] [--fibers F] [--scaling strong|weak]
+                    [--dump-outputs DIR]
 
 One "step" = one Bellman sweep over a batch of synthetic fibers: for every varying dimension k = 0..d-1, F fibers
 (x N_k nodes) go through the batched bellman_vi kernel (c3sc_hip_bellman_fibers); the sweep ends the way a value-iteration
@@ -37,6 +38,8 @@ sys.path.insert(0, ROOT)
 
 FP64_PEAK_TFLOPS = 78.6  # MI355X datasheet FP64 vector = FP64 matrix; the microarch guide lists no f64 row
 HBM_PEAK_GBS = 8000.0    # MI355X_MICROARCH.md: 8.0 TB/s spec
+DUMP_BYTES = 64_000_000  # --dump-outputs: cap on the files written, headers included
+DUMP_SEED = 0xD0517      # --dump-outputs: rows sampled when a step's outputs exceed the cap
 REFERENCE_CPU = {"value": 3.26e5, "unit": "nodes/s", "cores": 1,
                  "what": "the reference's own bellman_vi (src/*.c, gcc -O2 -ftree-vectorize, 1 thread; 5.76e4 with 8 OpenMP threads), "
                          "car7d batch, measured by the survey on the build container's Xeon @2.1 GHz (SURVEY.md section 6); "
@@ -371,6 +374,24 @@ def kernel_resources(kernel):
             "source": "hipcc -Rpass-analysis=kernel-resource-usage at build time"}
 
 
+def dump_outputs(path, out_t, dev):
+    """--dump-outputs: the last timed step's outputs out_t[k] (F_loc, N_k) float64, one DIR/out_k<k>.npy per varying dimension.
+    All rows when they fit in DUMP_BYTES, else one seeded sample of rows (ascending, the same for every k); the sample depends
+    only on F_loc and the shapes, so two builds run with the same arguments dump the same fibers."""
+    import torch
+
+    F = out_t[0].shape[0]
+    n = min(F, (DUMP_BYTES - 4096 * len(out_t)) // sum(8 * t.shape[1] for t in out_t))  # 4 KB per file for the .npy header
+    rows = np.arange(F) if n == F else np.sort(np.random.default_rng(DUMP_SEED).choice(F, size=n, replace=False))
+    rows_t = torch.from_numpy(rows).to(dev)
+    os.makedirs(path, exist_ok=True)
+    files = []
+    for k, t in enumerate(out_t):
+        files.append(f"out_k{k}.npy")
+        np.save(os.path.join(path, files[-1]), t.index_select(0, rows_t).cpu().numpy())
+    return {"dir": path, "files": files, "rows": int(n), "of_rows": int(F), "sample_seed": DUMP_SEED if n < F else None}
+
+
 def main():
     if len(sys.argv) >= 5 and sys.argv[1] == "--cpu-worker":  # child of cpu_baseline: before anything touches torch / the GPU
         _cpu_worker(sys.argv[2], float(sys.argv[3]), int(sys.argv[4]))
@@ -394,7 +415,13 @@ def main():
     ap.add_argument("--solver-budget", type=float, default=20.0)
     ap.add_argument("--cpu-budget", type=float, default=12.0)
     ap.add_argument("--cpu-procs", type=int, default=None, help="worker processes of the CPU baseline (default min(16, cores))")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write rank 0's Bellman outputs of the last timed step as DIR/out_k<k>.npy (float64, "
+                         "one per varying dimension): a fixed, seeded sample of the fibers, the same rows for every dimension, "
+                         f"at most {DUMP_BYTES // 1000000} MB in all")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
@@ -551,6 +578,8 @@ def main():
         step(True, args.overlap)
     fence()
     elapsed = time.perf_counter() - t0
+    # before the untimed steps below, which write into the same out_t
+    dump = dump_outputs(args.dump_outputs, out_t, dev) if args.dump_outputs and rank == 0 else None
     # the same steps the other way (untimed for `value`): with the launches of a step on one stream (default: the per-kernel
     # durations behind `roofline` are then what rocprofv3 sees) or spread over three streams by the library (--overlap)
     other = None
@@ -639,6 +668,7 @@ def main():
             "failure_handling": "a rank whose launch or staging copy fails still enters the all-gather (rows marked NaN) and all ranks stop "
                                 "together (cross_device.hip step_fibers, comm_rccl.hip c3sc_hip_comm_exchange; tests/test_distributed.py)"}
         res["step_launch_mode"] = "overlapped (c3sc_hip_bellman_fibers_all, three streams)" if args.overlap else "one stream, d launches in order"
+        res["dump_outputs"] = dump
         if other is not None:
             res["other_mode_step"] = {
                 "mode": "one stream, d launches in order" if args.overlap else "overlapped (c3sc_hip_bellman_fibers_all, three streams)",
