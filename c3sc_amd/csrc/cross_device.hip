@@ -1241,6 +1241,21 @@ struct c3sc_cross_dev {
 
 static size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 
+// columns of the register image of a global-scratch core step with n columns (core_step_global<NR>)
+static int pad_cols(int n) { return n <= 32 ? 32 : n <= 40 ? 40 : 48; }
+
+// A global-scratch step writes m x NR doubles of its scratch block (the padding columns too): refuse, before anything is launched,
+// a step that would run past its block into the next one
+static int check_scratch(c3sc_hip_ctx *c, const c3sc_cross_dev *x, int k, int dir, int nr, const char *who)
+{
+    const size_t m = (size_t)x->N[k] * (dir == 0 ? x->r[k] : x->r[k + 1]);
+    if (m * nr * sizeof(double) <= x->work_stride) return C3SC_OK;
+    char msg[160];
+    snprintf(msg, sizeof msg, "%s: core step %d (%zu rows padded to %d columns) exceeds its scratch block of %zu doubles", who, k, m, nr,
+             x->work_stride / sizeof(double));
+    return fail(c, C3SC_ERR_UNSUPPORTED, msg);
+}
+
 static int memo_shift_of(size_t cap)
 {
     int shift = 64;
@@ -1343,10 +1358,15 @@ int c3sc_hip_cross_setup(c3sc_hip_ctx *c, const size_t *ranks, const int32_t *co
     x->off_flags = off; off += up256(MAXD * (sizeof(int) + sizeof(unsigned long long)) + 64);
     x->off_steps = off; off += up256(2 * MAXD * sizeof(CoreArgs) + 64);
     // scratch of a factorisation that does not fit LDS: one block per core step of an iteration (the batched confirmation runs all
-    // 2 d steps side by side; the sequential iteration uses the first block)
-    for (int k = 0; k < d; k++) { // the global-scratch core step pads the columns of its matrix to 32 / 40 / 48 (core_step_global)
-        const size_t rmaxk = (size_t)std::max(x->r[k], x->r[k + 1]), rowsk = rmaxk * x->N[k];
-        wmax = std::max(wmax, rowsk * (rmaxk <= 32 ? 32 : rmaxk <= 40 ? 40 : 48));
+    // 2 d steps side by side; the sequential iteration uses the first block).  The global-scratch core step pads the columns of
+    // its matrix to 32 / 40 / 48 (core_step_global); the confirmation launches EVERY step with the padding of the largest rank of
+    // the train, so a block holds the rows of any step at that padding (with unequal grids a step of small ranks on a long
+    // dimension has more rows than the step of the largest rank)
+    int rmax = 1;
+    for (int k = 0; k <= d; k++) rmax = std::max(rmax, x->r[k]);
+    for (int k = 0; k < d; k++) {
+        const size_t rowsk = (size_t)std::max(x->r[k], x->r[k + 1]) * x->N[k];
+        wmax = std::max(wmax, rowsk * pad_cols(rmax));
     }
     x->work_stride = up256(wmax * sizeof(double));
     x->off_work = off; off += 2 * (size_t)d * x->work_stride;
@@ -1558,6 +1578,13 @@ static int cross_iteration_impl(c3sc_hip_ctx *c, c3sc_hip_ctx *pol, long long po
     auto setJ = [&](int k) { return (int32_t *)(x->slab + x->offJ[k]); };
     auto outOf = [&](int k) { return (double *)(x->slab + x->offOut[k]); };
     auto nextList = [&](int k) { return next_list(x, k, comm == nullptr); };
+    for (int s = 0; s < 2 * d; s++) { // the global-scratch steps below all use the first scratch block
+        const int half = s / d, k = half == 0 ? s : 2 * d - 1 - s;
+        const int r0 = x->r[k], r1 = x->r[k + 1];
+        if ((half == 0 ? k == d - 1 : k == 0) || ((size_t)r0 * r1 * x->N[k] * sizeof(double) <= LDS_CAP_BYTES && r0 <= LDSR && r1 <= LDSR)) continue;
+        const int rc = check_scratch(c, x, k, half, pad_cols(half == 0 ? r1 : r0), "cross_iteration");
+        if (rc != C3SC_OK) return rc;
+    }
     // the first step's fiber list; every later one is written by the core step before it
     hipLaunchKernelGGL(k_cross_idx, dim3(1), dim3(256), 0, st, nextList(0));
     for (int s = 0; s < 2 * d; s++) {
@@ -1701,6 +1728,15 @@ int c3sc_hip_cross_confirm(c3sc_hip_ctx *c, int *confirmed, void *stream)
         if (!P.copy_only) maxmn = std::max(maxmn, (size_t)P.r0 * P.r1 * P.N * sizeof(double));
         if (P.r0 > LDSR || P.r1 > LDSR) maxmn = LDS_CAP_BYTES + 1; // a rank above 32: the global-scratch form for all steps
     }
+    int maxr = 1;
+    for (int k = 0; k <= d; k++) maxr = std::max(maxr, x->r[k]);
+    if (maxmn > LDS_CAP_BYTES) // every step on its own block at the padding of the largest rank
+        for (int s = 0; s < 2 * d; s++) {
+            const int half = s / d, k = half == 0 ? s : 2 * d - 1 - s;
+            if (h[s].copy_only) continue;
+            const int rc = check_scratch(c, x, k, half, pad_cols(maxr), "cross_confirm");
+            if (rc != C3SC_OK) return rc;
+        }
     HIPCHK(c, hipMemsetAsync(mismatch, 0, sizeof(int), st));
     HIPCHK(c, hipMemcpyAsync(x->slab + x->off_steps, h, 2 * d * sizeof(CoreArgs), hipMemcpyHostToDevice, st));
     // every step in LDS, or -- if one of them does not fit (rank 16 on 101 nodes is 207 KB) -- every step on its own block of
@@ -1708,8 +1744,6 @@ int c3sc_hip_cross_confirm(c3sc_hip_ctx *c, int *confirmed, void *stream)
     if (maxmn <= LDS_CAP_BYTES)
         hipLaunchKernelGGL(k_cross_confirm<true>, dim3(2 * d), dim3(NT), maxmn, st, (const CoreArgs *)(x->slab + x->off_steps));
     else {
-        int maxr = 1;
-        for (int k = 0; k <= d; k++) maxr = std::max(maxr, x->r[k]);
         const size_t lds = (size_t)MAXR * MAXR * sizeof(double);
         const CoreArgs *steps = (const CoreArgs *)(x->slab + x->off_steps);
         if (maxr <= 32) hipLaunchKernelGGL(k_cross_confirm_g<32>, dim3(2 * d), dim3(NT), lds, st, steps);

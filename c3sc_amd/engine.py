@@ -77,6 +77,13 @@ def load_library():
         L.c3sc_hip_timer_start.argtypes = [C.c_void_p, C.c_void_p]
         L.c3sc_hip_timer_stop.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
         L.c3sc_hip_upload_value_device.argtypes = [C.c_void_p, c_size_p, C.POINTER(C.c_void_p), C.c_void_p]
+        # device-resident cross (include/c3sc_hip.h); index sets are int32 tuple arrays, one pointer per core step
+        L.c3sc_hip_cross_setup.argtypes = [C.c_void_p, c_size_p, C.POINTER(c_i32_p), C.POINTER(c_i32_p), C.c_int]
+        L.c3sc_hip_cross_iteration.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.c3sc_hip_cross_confirm.argtypes = [C.c_void_p, c_int_p, C.c_void_p]
+        L.c3sc_hip_cross_options.argtypes = [C.c_void_p, C.c_int, C.c_double]
+        L.c3sc_hip_cross_fetch.argtypes = [C.c_void_p, C.POINTER(c_double_p), C.POINTER(c_i32_p), C.POINTER(c_i32_p),
+                                           C.POINTER(C.c_ulonglong), C.c_void_p]
         _LIB = L
     return _LIB
 
