@@ -13,6 +13,8 @@
 
 #include "../../include/c3sc_hip.h"
 #include "kernel_common.hpp"
+#include "kernel_rollout.hpp"
+#include "model_tables.hpp"
 #include "registry.hpp"
 
 namespace c3sc {
@@ -131,28 +133,7 @@ using namespace c3sc;
 // Besides the trigonometric tables, any other expensive univariate function of a grid coordinate is tabulated
 // here with the host's IEEE arithmetic (correctly rounded division, the same result the device's division sequence
 // gives): the car models' speed factor v / (0.2 (1 + v/8)) costs a ~15-instruction dependent chain per node otherwise.
-static int model_ntab(int model)
-{
-    if (model == C3SC_MODEL_SKID5D) return 2; // cos / sin of the orientation x2
-    return model == C3SC_MODEL_DUBINS3D ? 2 : (model == C3SC_MODEL_SCAR4D ? 3 : ((model == C3SC_MODEL_CAR7D || model == C3SC_MODEL_PERCH7D) ? 4 : 0));
-}
-static int model_tab_dim(int model, int t)
-{
-    if (model == C3SC_MODEL_PERCH7D) return t < 2 ? 2 : 3; // cos / sin of the pitch x2, cos / sin of the elevator angle x3
-    if (model == C3SC_MODEL_CAR7D) return t == 2 ? 5 : (t == 3 ? 3 : 2);
-    if (model == C3SC_MODEL_SCAR4D) return t == 2 ? 3 : 2;
-    return 2;
-}
-static double model_table_value(int model, int t, double xv)
-{
-    if (t == 0) return cos(xv);
-    if (t == 1) return sin(xv);
-    if (model == C3SC_MODEL_PERCH7D) return t == 2 ? cos(xv) : sin(xv);
-    if (model == C3SC_MODEL_CAR7D && t == 2) return tan(xv);
-    if (model == C3SC_MODEL_CAR7D && t == 3) return xv / (0.2 * (1.0 + xv / 8.0));
-    if (model == C3SC_MODEL_SCAR4D && t == 2) return (1.0 / (1.0 + (xv / 8.0))) * (xv / 0.2); /* scar.c:68-71 with L = 0.2, vcar = 8 */
-    return tan(xv);
-}
+// model_ntab / model_tab_dim / model_table_value: model_tables.hpp (the rollouts evaluate them on the device as well)
 static int model_ncf(int model) { return model == C3SC_MODEL_SCAR4D ? 1 : (model == C3SC_MODEL_COTHRUST6D ? 3 : 0); }
 static double model_cand_feature(int model, int q, const double *u)
 {
@@ -217,6 +198,7 @@ static const KernelEntry *find_kernel(int model, int d, int rank_needed, int N, 
     const KernelEntry *best = nullptr;
     const bool small = (variant == C3SC_VARIANT_AUTO) && F < SMALL_BATCH_FIBERS;
     for (const auto &e : kernel_registry()) {
+        if (!is_fiber_variant(e.variant)) continue;
         if (e.model != model || e.d != d || e.rp < rank_needed || e.max_n < N) continue;
         if (skip && std::find(skip->begin(), skip->end(), &e) != skip->end()) continue;
         if (e.k >= 0 && e.k != k) continue;
@@ -238,14 +220,14 @@ static int pick_rp(int d, int maxrank, int model, int variant)
     int rp = 0;
     if (variant != C3SC_VARIANT_AUTO)
         for (const auto &e : kernel_registry())
-            if (e.d == d && e.variant == variant && (model == 0 || e.model == model) && e.rp >= maxrank && (rp == 0 || e.rp < rp)) rp = e.rp;
+            if (is_fiber_variant(e.variant) && e.d == d && e.variant == variant && (model == 0 || e.model == model) && e.rp >= maxrank && (rp == 0 || e.rp < rp)) rp = e.rp;
     if (rp) return rp;
     if (model != 0) // the padded classes compiled for THIS model (another model of the same dimension may offer others)
         for (const auto &e : kernel_registry())
-            if (e.d == d && e.model == model && e.rp >= maxrank && (rp == 0 || e.rp < rp)) rp = e.rp;
+            if (is_fiber_variant(e.variant) && e.d == d && e.model == model && e.rp >= maxrank && (rp == 0 || e.rp < rp)) rp = e.rp;
     if (rp) return rp;
     for (const auto &e : kernel_registry())
-        if (e.d == d && e.rp >= maxrank && (rp == 0 || e.rp < rp)) rp = e.rp;
+        if (is_fiber_variant(e.variant) && e.d == d && e.rp >= maxrank && (rp == 0 || e.rp < rp)) rp = e.rp;
     return rp;
 }
 
@@ -299,6 +281,7 @@ void c3sc_hip_ctx_destroy(c3sc_hip_ctx *c)
     if (c->d_status) (void)hipFree(c->d_status);
     if (c->d_dbg) (void)hipFree(c->d_dbg);
     if (c->scratch) (void)hipFree(c->scratch);
+    if (c->sim_state) (void)hipFree(c->sim_state);
     if (c->pinned) (void)hipHostFree(c->pinned);
     c3sc_hip_cross_free(c);
     for (int i = 0; i < c3sc_hip_ctx::NSIDE; i++) {
@@ -1125,6 +1108,197 @@ int c3sc_hip_get_status(c3sc_hip_ctx *c, unsigned *flags, int clear)
         HIPCHK(c, hipMemset(c->d_status, 0, sizeof(unsigned)));
         c->status_cache = 0;
     }
+    return C3SC_OK;
+}
+
+// ------------------------------------------------------------------ closed-loop rollouts (kernel_rollout.hpp)
+int c3sc_hip_set_interp(c3sc_hip_ctx *c, int constelm)
+{
+    if (!c) return C3SC_ERR_ARG;
+    c->constelm = constelm ? 1 : 0;
+    return C3SC_OK;
+}
+
+// one 1-D launch covers a call: 2^31 lanes stay below the launch limit of 2^32 work-items
+static const size_t SIM_MAX_TRAJ = (size_t)1 << 31;
+
+static const KernelEntry *find_sim_kernel(int variant, int model, int d, int rp)
+{
+    for (const auto &e : kernel_registry())
+        if (e.variant == variant && e.model == model && e.d == d && e.rp == rp) return &e;
+    return nullptr;
+}
+
+static int check_bounds_set(c3sc_hip_ctx *c, const char *what)
+{
+    for (int m = 0; m < c->d; m++)
+        if (c->bctype[m] != C3SC_ABSORB && c->bctype[m] != C3SC_PERIODIC && c->bctype[m] != C3SC_REFLECT)
+            return fail(c, C3SC_ERR_ARG, what); // the host code asserts ("No boundary specified!")
+    return C3SC_OK;
+}
+
+int c3sc_hip_stencil_points(c3sc_hip_ctx *c, size_t n, const double *d_x, double *d_out, int32_t *d_absorbed, void *stream)
+{
+    KArgs A;
+    int rc = fill_args(c, 0, 0, A, false);
+    if (rc != C3SC_OK) return rc;
+    rc = check_bounds_set(c, "stencil_points: every dimension needs a boundary type");
+    if (rc != C3SC_OK) return rc;
+    if (n == 0) return C3SC_OK;
+    if (!d_x || !d_out) return fail(c, C3SC_ERR_ARG, "stencil_points: null buffer");
+    if (n > SIM_MAX_TRAJ) return fail(c, C3SC_ERR_ARG, "stencil_points: more than 2^31 points in one call");
+    const KernelEntry *e = find_sim_kernel(VARIANT_STENCIL_POINTS, 0, c->d, c->rp);
+    if (!e) return fail(c, C3SC_ERR_UNSUPPORTED, "stencil_points: no instantiation for this (dim, padded rank)");
+    SimK S;
+    std::memset(&S, 0, sizeof(S));
+    S.n = (long)n;
+    S.constelm = c->constelm;
+    S.x0 = d_x;
+    S.out = d_out;
+    S.absorbed = d_absorbed;
+    LaunchIO io{c->arena, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream, &S};
+    c->last_kernel = e->name;
+    g_launches++;
+    c->status_cache_valid = false;
+    HIPCHK(c, e->fn(A, io));
+    return C3SC_OK;
+}
+
+int c3sc_hip_simulate(c3sc_hip_ctx *c, const c3sc_hip_sim_args *a, void *stream)
+{
+    if (!c) return C3SC_ERR_ARG;
+    if (!a) return fail(c, C3SC_ERR_ARG, "simulate: null argument struct");
+    if (c->model == C3SC_MODEL_TABLE) return fail(c, C3SC_ERR_UNSUPPORTED, "simulate: the TABLE model has no device dynamics");
+    if (!c->have_mca || c->model == 0) return fail(c, C3SC_ERR_ARG, "simulate: mca and model must be set");
+    if (a->box ? c->box_du == 0 : c->ncand == 0)
+        return fail(c, C3SC_ERR_ARG, a->box ? "simulate: set_control_box first" : "simulate: set_controls first");
+    if (a->box && model_ncf(c->model) != 0 && c->model != C3SC_MODEL_COTHRUST6D)
+        return fail(c, C3SC_ERR_UNSUPPORTED, "simulate: this model needs transcendental functions of the control in a box");
+    KArgs A;
+    int rc = fill_args(c, 0, 0, A, false);
+    if (rc != C3SC_OK) return rc;
+    rc = check_bounds_set(c, "simulate: every dimension needs a boundary type");
+    if (rc != C3SC_OK) return rc;
+    if (!(a->dt > 0.0) || !std::isfinite(a->dt)) return fail(c, C3SC_ERR_ARG, "simulate: dt must be positive and finite");
+    if (a->nsteps > (size_t)1 << 30) return fail(c, C3SC_ERR_ARG, "simulate: nsteps too large");
+    if (a->n > SIM_MAX_TRAJ) return fail(c, C3SC_ERR_ARG, "simulate: more than 2^31 trajectories in one call (split the batch, traj_offset)");
+    if (a->save_every == 0 && (a->d_traj || a->d_u)) return fail(c, C3SC_ERR_ARG, "simulate: d_traj / d_u need save_every > 0");
+    if (a->save_every > a->nsteps && a->save_every > 1 && (a->d_traj || a->d_u))
+        return fail(c, C3SC_ERR_ARG, "simulate: save_every larger than nsteps");
+    if (a->steps_per_launch < 0) return fail(c, C3SC_ERR_ARG, "simulate: steps_per_launch < 0");
+    const KernelEntry *e = find_sim_kernel(VARIANT_ROLLOUT, c->model, c->d, c->rp);
+    if (!e) return fail(c, C3SC_ERR_UNSUPPORTED, "simulate: no rollout instantiation for this model at this padded rank");
+    if (a->n == 0) return C3SC_OK;
+    if (!a->d_x0) return fail(c, C3SC_ERR_ARG, "simulate: null d_x0");
+    const int d = c->d;
+    const size_t n = a->n;
+    const size_t bytes = n * (size_t)(d + 2) * sizeof(double);
+    if (bytes > c->sim_state_bytes) {
+        if (c->sim_state) HIPCHK(c, hipFree(c->sim_state));
+        c->sim_state = nullptr;
+        c->sim_state_bytes = 0;
+        HIPCHK(c, hipMalloc(&c->sim_state, bytes));
+        c->sim_state_bytes = bytes;
+    }
+    double *st_x = (double *)c->sim_state, *st_cost = st_x + n * d;
+    long long *st_exit = (long long *)(st_cost + n);
+    A.cmode = a->box ? 1 : 0;
+    A.ugrid = c->box_grid;
+    A.upolish = c->box_polish;
+    for (int i = 0; i < c->box_du; i++) { A.ulb[i] = c->box_lb[i]; A.uub[i] = c->box_ub[i]; }
+    SimK S;
+    std::memset(&S, 0, sizeof(S));
+    S.n = (long)n;
+    S.traj_offset = (long long)a->traj_offset;
+    S.nsteps = (int)a->nsteps;
+    S.save_every = (int)a->save_every;
+    S.wrap = a->wrap_periodic ? 1 : 0;
+    S.constelm = c->constelm;
+    S.seed = a->seed;
+    S.dt = a->dt;
+    S.sqdt = std::sqrt(a->dt);
+    S.x0 = a->d_x0;
+    S.noise = a->d_noise;
+    S.x = st_x;
+    S.cost = st_cost;
+    S.exit_step = st_exit;
+    S.traj = a->d_traj;
+    S.u = a->d_u;
+    S.vend = a->d_vend;
+    const int chunk = a->steps_per_launch > 0 ? a->steps_per_launch : 64;
+    c->last_kernel = e->name;
+    c->status_cache_valid = false;
+    int s0 = 0;
+    do { // at least one launch: nsteps = 0 still tests x_0 and evaluates V_end
+        S.s0 = s0;
+        S.s1 = (int)std::min<long long>((long long)s0 + chunk, (long long)a->nsteps);
+        LaunchIO io{c->arena, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream, &S};
+        g_launches++;
+        const hipError_t he = e->fn(A, io);
+        if (he == hipErrorNotSupported) return fail(c, C3SC_ERR_UNSUPPORTED, "simulate: this rollout kernel has no box minimiser");
+        HIPCHK(c, he);
+        s0 = S.s1;
+    } while (s0 < (int)a->nsteps);
+    hipStream_t sm = (hipStream_t)stream;
+    if (a->d_xfinal) HIPCHK(c, hipMemcpyAsync(a->d_xfinal, st_x, n * d * sizeof(double), hipMemcpyDeviceToDevice, sm));
+    if (a->d_cost) HIPCHK(c, hipMemcpyAsync(a->d_cost, st_cost, n * sizeof(double), hipMemcpyDeviceToDevice, sm));
+    if (a->d_exit) HIPCHK(c, hipMemcpyAsync(a->d_exit, st_exit, n * sizeof(int64_t), hipMemcpyDeviceToDevice, sm));
+    return C3SC_OK;
+}
+
+int c3sc_hip_simulate_host(c3sc_hip_ctx *c, const c3sc_hip_sim_args *h)
+{
+    if (!c) return C3SC_ERR_ARG;
+    if (!h) return fail(c, C3SC_ERR_ARG, "simulate_host: null argument struct");
+    if (h->n == 0) return c3sc_hip_simulate(c, h, nullptr);
+    if (!h->d_x0) return fail(c, C3SC_ERR_ARG, "simulate_host: null x0");
+    if (h->n > SIM_MAX_TRAJ || h->nsteps > ((size_t)1 << 30)) return fail(c, C3SC_ERR_ARG, "simulate_host: sizes too large");
+    if (h->save_every == 0 && (h->d_traj || h->d_u)) return fail(c, C3SC_ERR_ARG, "simulate: d_traj / d_u need save_every > 0");
+    if (c->d == 0) return fail(c, C3SC_ERR_ARG, "simulate_host: set_grid first");
+    const size_t n = h->n, d = (size_t)c->d, du = (size_t)(h->box ? c->box_du : c->du);
+    const size_t se = h->save_every, nrow = se ? h->nsteps / se + 1 : 0, nurow = se ? (h->nsteps + se - 1) / se : 0;
+    const size_t nnoise = h->d_noise ? n * h->nsteps * d : 0;
+    // staging buffer: [x0 | noise | traj | u | cost | exit | vend | xfinal]
+    size_t off[9];
+    const size_t sz[8] = {n * d, nnoise, h->d_traj ? n * nrow * d : 0, h->d_u ? n * nurow * du : 0, n, n, n, n * d};
+    off[0] = 0;
+    for (int i = 0; i < 8; i++) off[i + 1] = off[i] + ((sz[i] + 31) & ~(size_t)31);
+    HIPCHK(c, hipSetDevice(c->device));
+    double *buf = nullptr;
+    HIPCHK(c, hipMalloc((void **)&buf, off[8] * sizeof(double)));
+    c3sc_hip_sim_args a = *h;
+    a.d_x0 = buf + off[0];
+    a.d_noise = h->d_noise ? buf + off[1] : nullptr;
+    a.d_traj = h->d_traj ? buf + off[2] : nullptr;
+    a.d_u = h->d_u ? buf + off[3] : nullptr;
+    a.d_cost = buf + off[4];
+    a.d_exit = (int64_t *)(buf + off[5]);
+    a.d_vend = buf + off[6];
+    a.d_xfinal = buf + off[7];
+    int rc = C3SC_OK;
+    hipError_t e = hipMemcpy((void *)a.d_x0, h->d_x0, sz[0] * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess && nnoise) e = hipMemcpy((void *)a.d_noise, h->d_noise, nnoise * sizeof(double), hipMemcpyHostToDevice);
+    if (e != hipSuccess) rc = fail(c, C3SC_ERR_HIP, hipGetErrorString(e));
+    if (rc == C3SC_OK) rc = c3sc_hip_simulate(c, &a, nullptr);
+    struct { void *dst; const void *src; size_t bytes; } back[6] = {
+        {h->d_traj, a.d_traj, sz[2] * sizeof(double)}, {h->d_u, a.d_u, sz[3] * sizeof(double)}, {h->d_cost, a.d_cost, n * sizeof(double)},
+        {h->d_exit, a.d_exit, n * sizeof(int64_t)}, {h->d_vend, a.d_vend, n * sizeof(double)}, {h->d_xfinal, a.d_xfinal, n * d * sizeof(double)}};
+    for (int i = 0; i < 6 && rc == C3SC_OK; i++)
+        if (back[i].dst && back[i].bytes) {
+            e = hipMemcpy(back[i].dst, back[i].src, back[i].bytes, hipMemcpyDeviceToHost);
+            if (e != hipSuccess) rc = fail(c, C3SC_ERR_HIP, hipGetErrorString(e));
+        }
+    (void)hipFree(buf);
+    return rc;
+}
+
+int c3sc_hip_normals(uint64_t seed, uint64_t traj0, size_t ntraj, uint64_t step0, size_t nsteps, int dw, double *out)
+{
+    if (!out || dw < 1 || dw > MAXD) return C3SC_ERR_ARG;
+    for (size_t t = 0; t < ntraj; t++)
+        for (size_t k = 0; k < nsteps; k++)
+            for (int j = 0; j < dw; j++)
+                out[(t * nsteps + k) * dw + j] = philox_normal(seed, traj0 + t, (uint32_t)(step0 + k), (uint32_t)j);
     return C3SC_OK;
 }
 

@@ -64,6 +64,10 @@ struct c3sc_hip_ctx {
     // scratch for the *_host convenience calls
     void *scratch = nullptr;
     size_t scratch_bytes = 0;
+    // c3sc_hip_simulate: trajectory state between the launches of one call ([n][d] x, [n] cost, [n] exit step)
+    void *sim_state = nullptr;
+    size_t sim_state_bytes = 0;
+    int constelm = 0; // c3sc_hip_set_interp: off-grid evaluation as the reference's CONSTELM (nearest node per dimension)
     // pinned, device-mapped host block for small *_host batches (read and written by the kernel in place)
     void *pinned = nullptr, *pinned_dev = nullptr;
     size_t pinned_bytes = 0;

@@ -1,0 +1,429 @@
+// kernel_rollout.hpp -- batched closed-loop rollouts of the implicit policy (c3sc_hip_simulate) and the off-grid stencil
+// they are built on (c3sc_hip_stencil_points).  DESIGN.md 4.8.
+//
+// One lane per trajectory.  A step of a lane is c3control_simulate's step (c3sc_bellman.c) with the host callbacks
+// replaced by the device model: the off-grid stencil of mca_get_neighbor_node_costs at the controller's input, the
+// per-lane minimiser the Bellman kernels use (node_backup over the candidate list, node_backup_box in a control box), then
+// one Euler-Maruyama step with the model's diagonal diffusion.  Trajectory state stays in registers for the steps of a
+// launch and goes to device memory between launches (a call is cut into launches of a bounded number of steps).
+//
+// Lanes are independent trajectories.  The kernels' own boundary branches, exit freeze and workgroup tail are selects (tail
+// lanes repeat the last trajectory and store the same bits to the same addresses); the device libm (cos / sin / tan of the
+// models' tables at an off-grid state) and the box minimiser do branch per lane.  That is harmless because nothing here is
+// lane-distributed: the candidate table lives in LDS (CandLds, wave-uniform addresses), not in VGPR lanes read by v_readlane.
+// tests/test_rollout_isa.py checks the ISA (global loads only; no scratch at the benchmark's ranks).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <type_traits>
+
+#include "kernel_common.hpp"
+#include "model_tables.hpp"
+#include "philox.hpp"
+#include "registry.hpp"
+
+namespace c3sc {
+
+// argument block of one rollout / stencil-points launch (by value: kernarg space, wave-uniform)
+struct SimK {
+    long n;                 // trajectories (points) of the call
+    long long traj_offset;  // global index of trajectory 0 (Philox counter)
+    int s0, s1;             // steps [s0, s1) of this launch
+    int nsteps;             // steps of the call: the launch with s1 == nsteps also tests x_nsteps and writes V_end
+    int save_every;         // 0: nothing saved
+    int wrap;               // map periodic dimensions into [lb, ub) before the controller sees the state
+    int constelm;           // off-grid interpolation of a CONSTELM value function
+    unsigned long long seed;
+    double dt, sqdt;
+    const double *x0;       // [n][D]: initial states (rollouts, read when s0 == 0) / the points (stencil_points)
+    const double *noise;    // [n][nsteps][D] standard normals, or null: Philox (philox.hpp)
+    double *x;              // [n][D] state between launches
+    double *cost;           // [n] discounted cost so far
+    long long *exit_step;   // [n] -1 while running
+    double *traj;           // [n][nsteps / save_every + 1][D] or null
+    double *u;              // [n][ceil(nsteps / save_every)][DU] or null
+    double *vend;           // [n] or null
+    double *out;            // stencil_points: [n][2D + 1]
+    int32_t *absorbed;      // stencil_points: [n] or null
+};
+
+template <int B, int E, class F>
+__device__ __forceinline__ void static_for(F &&f)
+{
+    if constexpr (B < E) {
+        f(std::integral_constant<int, B>{});
+        static_for<B + 1, E>(f);
+    }
+}
+
+// valuef_eval's cell of coordinate x on the grid g[0..N) (c3sc_cross.c: clamp, then the bisection): node i and the weight
+// of node i + 1.  The bisection runs a wave-uniform number of rounds (enough for N), each a select: the same cell as the
+// host's `while (hi - lo > 1)` without a lane-dependent trip count.
+__device__ inline void offgrid_cell(const double *__restrict__ g, int N, double x, int constelm, int &i, double &w)
+{
+    int nit = 0;
+    while ((1 << nit) < N - 1) nit++; // wave-uniform
+    int lo = 0, hi = N - 1;
+    for (int it = 0; it < nit; it++) {
+        const int mid = (lo + hi) >> 1;
+        const bool go = hi - lo > 1, le = g[mid] <= x;
+        lo = (go && le) ? mid : lo;
+        hi = (go && !le) ? mid : hi;
+    }
+    const double g0 = g[0], gn = g[N - 1], gl = g[lo], gr = g[lo + 1];
+    const double wi = (x - gl) / (gr - gl);
+    i = (x <= g0) ? 0 : ((x >= gn) ? N - 2 : lo);
+    w = (x <= g0) ? 0.0 : ((x >= gn) ? 1.0 : wi);
+    w = constelm ? ((w < 0.5) ? 0.0 : 1.0) : w; // the nearer node's value holds on its cell
+}
+
+// entry e of core m interpolated between nodes i and i + 1 (padded layout of k_pad_core)
+template <int RP>
+__device__ __forceinline__ double core_at(const double *__restrict__ G, int per, int i, double w, int e)
+{
+    return (1.0 - w) * G[(size_t)i * per + e] + w * G[(size_t)(i + 1) * per + e];
+}
+
+// v[0], with v rotated left by one (v[k] = v[k+1], v[RP-1] = the old v[0]): a rolled loop over a reads "v[a]" this way --
+// indexing the register vector with the loop counter would move it to scratch
+template <int RP>
+__device__ __forceinline__ double rot_left(double (&v)[RP])
+{
+    const double h = v[0];
+#pragma unroll
+    for (int k = 0; k + 1 < RP; k++) v[k] = v[k + 1];
+    v[RP - 1] = h;
+    return h;
+}
+
+// mca_get_neighbor_node_costs (c3sc_bellman.c; nodeutil.c:718-816) at an arbitrary state x: V[2m], V[2m+1] = the
+// interpolant at the (-, +) neighbour one grid spacing away in dim m (boundary rules of the host code), V[2D] = the
+// interpolant at x.  Inside an obstacle every entry is the value at x and ab = -1.
+// Neighbour m differs from x in coordinate m only: V(y) = L_m G_m(y_m) R_{m+1} with the prefix L_m = G_0(x_0) ... G_{m-1}
+// (x_{m-1}) and the suffix R_{m+1} = G_{m+1}(x_{m+1}) ... G_{D-1}(x_{D-1}).  The suffixes are formed once (D-1 vectors in
+// registers), the prefix is carried along the forward sweep: about 3 D r^2 multiply-adds per point instead of (2D+1) D r^2.
+template <int D, int RP>
+__device__ inline void offgrid_stencil(const KArgs &A, const double *__restrict__ ro, const double (&x)[D], int constelm,
+                                       double (&V)[2 * D + 1], int &ab)
+{
+    static_assert(D >= 2, "dimension");
+    ab = in_obstacle<D>(A, ro, x) ? -1 : 0;
+    int ic[D];
+    double wc[D];
+#pragma unroll
+    for (int m = 0; m < D; m++) offgrid_cell(ro + A.xg_off[m], A.ngrid[m], x[m], constelm, ic[m], wc[m]);
+    double R[D][RP]; // R[m] = suffix from core m on (m = 1 .. D-1)
+    {
+        const double *G = ro + A.core_off[D - 1];
+#pragma unroll
+        for (int a = 0; a < RP; a++) R[D - 1][a] = core_at<RP>(G, RP, ic[D - 1], wc[D - 1], a);
+    }
+    static_for<1, D - 1>([&](auto mc) { // m = D-2 .. 1 (compile-time indices: R stays in registers)
+        constexpr int m = D - 1 - decltype(mc)::value;
+        const double *G = ro + A.core_off[m];
+#pragma unroll
+        for (int a = 0; a < RP; a++) R[m][a] = 0.0;
+#pragma unroll 1
+        for (int a = 0; a < RP; a++) { // row a of G_m(x_m) R_{m+1}, shifted in at the end: R[m][a] after RP rounds
+            double s = 0.0;
+#pragma unroll
+            for (int b = 0; b < RP; b++) s += core_at<RP>(G, RP * RP, ic[m], wc[m], a + b * RP) * R[m + 1][b];
+            (void)rot_left<RP>(R[m]);
+            R[m][RP - 1] = s;
+        }
+    });
+    double L[RP];
+    static_for<0, D>([&](auto mc) {
+        constexpr int m = decltype(mc)::value;
+        const double *g = ro + A.xg_off[m];
+        const int N = A.ngrid[m];
+        const double xm = x[m], lb = g[0], ub = g[N - 1], h = g[1] - g[0];
+        const int bc = A.bctype[m];
+        const bool interior = ((xm + h) < ub) && (xm - h > lb);
+        const bool left = !interior && ((xm - h) <= lb), right = !interior && !left;
+        double yl = xm - h, yr = xm + h;
+        const double yl_per = (xm > lb) ? ub - (h - (xm - lb)) : (ub - (lb - xm)) - h;
+        const double yr_per = (xm < ub) ? lb + (h - (ub - xm)) : (lb + (xm - ub)) + h;
+        yl = left ? ((bc == C3SC_PERIODIC) ? yl_per : lb) : yl;
+        yr = right ? ((bc == C3SC_PERIODIC) ? yr_per : ub) : yr;
+        int il, ir;
+        double wl, wr;
+        offgrid_cell(g, N, yl, constelm, il, wl);
+        offgrid_cell(g, N, yr, constelm, ir, wr);
+        const double *G = ro + A.core_off[m];
+        double vl = 0.0, vr = 0.0;
+        {
+            if constexpr (m == 0) {
+#pragma unroll
+                for (int b = 0; b < RP; b++) {
+                    vl += core_at<RP>(G, RP, il, wl, b) * R[1][b];
+                    vr += core_at<RP>(G, RP, ir, wr, b) * R[1][b];
+                    L[b] = core_at<RP>(G, RP, ic[0], wc[0], b);
+                }
+            } else if constexpr (m == D - 1) {
+                double vx = 0.0;
+#pragma unroll
+                for (int a = 0; a < RP; a++) {
+                    vl += L[a] * core_at<RP>(G, RP, il, wl, a);
+                    vr += L[a] * core_at<RP>(G, RP, ir, wr, a);
+                    vx += L[a] * core_at<RP>(G, RP, ic[m], wc[m], a);
+                }
+                V[2 * D] = vx;
+            } else {
+                // L_m G_m(y) R_{m+1} row by row; the row loops stay rolled (a fully unrolled r x r product keeps all its
+                // loads in flight: hundreds of VGPRs), and L is read by rotating it instead of indexing it with the row
+                auto through = [&](int iy, double wy) {
+                    double v = 0.0;
+#pragma unroll 1
+                    for (int a = 0; a < RP; a++) {
+                        const double la = rot_left<RP>(L);
+                        double t = 0.0;
+#pragma unroll
+                        for (int b = 0; b < RP; b++) t += core_at<RP>(G, RP * RP, iy, wy, a + b * RP) * R[m + 1][b];
+                        v += la * t;
+                    }
+                    return v;
+                };
+                vl = through(il, wl);
+                vr = through(ir, wr);
+                double Ln[RP];
+#pragma unroll
+                for (int b = 0; b < RP; b++) Ln[b] = 0.0;
+#pragma unroll 1
+                for (int a = 0; a < RP; a++) {
+                    const double la = rot_left<RP>(L);
+#pragma unroll
+                    for (int b = 0; b < RP; b++) Ln[b] += la * core_at<RP>(G, RP * RP, ic[m], wc[m], a + b * RP);
+                }
+#pragma unroll
+                for (int b = 0; b < RP; b++) L[b] = Ln[b];
+            }
+        }
+        V[2 * m] = vl;
+        V[2 * m + 1] = vr;
+    });
+#pragma unroll
+    for (int e = 0; e < 2 * D; e++) V[e] = (ab != 0) ? V[2 * D] : V[e];
+}
+
+// x with its periodic dimensions mapped into [lb, ub) (the examples' state_transform, e.g. dubinscar.c:168)
+template <int D>
+__device__ inline void wrap_periodic(const KArgs &A, const double *__restrict__ ro, const double (&x)[D], double (&y)[D])
+{
+#pragma unroll
+    for (int m = 0; m < D; m++) {
+        const double *g = ro + A.xg_off[m];
+        const double lb = g[0], ub = g[A.ngrid[m] - 1], len = ub - lb;
+        double v = x[m] - floor((x[m] - lb) / len) * len;
+        v = (v >= ub) ? v - len : v;
+        v = (v < lb) ? v + len : v;
+        y[m] = (A.bctype[m] == C3SC_PERIODIC) ? v : x[m];
+    }
+}
+
+template <int MID, class Model>
+__device__ inline void offgrid_tables(const double (&x)[Model::D], double (&tv)[Model::NTAB > 0 ? Model::NTAB : 1])
+{
+    tv[0] = 0.0;
+#pragma unroll
+    for (int t = 0; t < Model::NTAB; t++) tv[t] = model_table_value(MID, t, x[Model::tab_dim(t)]);
+}
+
+template <int D, int RP>
+__global__ void __launch_bounds__(256) k_stencil_points(const KArgs A, const SimK S, const double *__restrict__ ro)
+{
+    const long i = min((long)blockIdx.x * blockDim.x + threadIdx.x, S.n - 1); // tail lanes repeat the last point
+    double x[D], V[2 * D + 1];
+#pragma unroll
+    for (int m = 0; m < D; m++) x[m] = S.x0[(size_t)i * D + m];
+    int ab;
+    offgrid_stencil<D, RP>(A, ro, x, S.constelm, V, ab);
+#pragma unroll
+    for (int e = 0; e < 2 * D + 1; e++) S.out[(size_t)i * (2 * D + 1) + e] = V[e];
+    if (S.absorbed) S.absorbed[i] = ab;
+}
+
+// BOX: the instantiation also serves the control-box minimiser (A.cmode == 1, a wave-uniform switch)
+template <int MID, class Model, int RP, bool BOX>
+__global__ void __launch_bounds__(256) k_rollout(const KArgs A, const SimK S, const double *__restrict__ ro)
+{
+    constexpr int D = Model::D, DU = Model::DU, NT = Model::NTAB > 0 ? Model::NTAB : 1, NCFa = Model::NCF > 0 ? Model::NCF : 1;
+    extern __shared__ double smem[];
+    CandLds<Model> cr;
+    cr.tb = smem;
+    if (A.cmode == 0) {
+        for (int c0 = 0; c0 < A.ncand; c0 += 64) { // every wave writes the same rows
+            CandRegs<Model> cr0;
+            cr0.load(A, ro, c0);
+            cr.fill(smem, cr0, A.ncand, c0);
+        }
+        __syncthreads();
+    }
+    const long i = min((long)blockIdx.x * blockDim.x + threadIdx.x, S.n - 1); // tail lanes repeat the last trajectory
+    const int se = S.save_every;
+    const long nrow = se > 0 ? S.nsteps / se + 1 : 0, nurow = se > 0 ? (S.nsteps + se - 1) / se : 0;
+    double x[D], J;
+    long long ex;
+    if (S.s0 == 0) {
+#pragma unroll
+        for (int m = 0; m < D; m++) x[m] = S.x0[(size_t)i * D + m];
+        J = 0.0;
+        ex = -1;
+        if (S.traj)
+#pragma unroll
+            for (int m = 0; m < D; m++) S.traj[(size_t)i * nrow * D + m] = x[m];
+    } else {
+#pragma unroll
+        for (int m = 0; m < D; m++) x[m] = S.x[(size_t)i * D + m];
+        J = S.cost[i];
+        ex = S.exit_step[i];
+    }
+    const double beta = A.discount, dt = S.dt;
+    unsigned st = 0;
+    // exit at x_s: outside [lb, ub] on an absorbing dimension or inside an obstacle; the exit cost is charged once
+    auto exit_test = [&](int s, double disc) {
+        const bool inobs = in_obstacle<D>(A, ro, x);
+        bool out = false;
+#pragma unroll
+        for (int m = 0; m < D; m++) {
+            const double *g = ro + A.xg_off[m];
+            out = out || ((A.bctype[m] == C3SC_ABSORB) && ((x[m] < g[0]) || (x[m] > g[A.ngrid[m] - 1])));
+        }
+        const bool now = (ex < 0) && (inobs || out);
+        const double term = inobs ? Model::obscost(A.prm, x) : Model::boundcost(A.prm, x);
+        J = now ? J + disc * term : J;
+        ex = now ? (long long)s : ex;
+    };
+    for (int s = S.s0; s < S.s1; s++) {
+        const double disc = exp(-beta * ((double)s * dt));
+        exit_test(s, disc);
+        const bool alive = ex < 0;
+        double xin[D];
+        if (S.wrap) wrap_periodic<D>(A, ro, x, xin);
+        else
+#pragma unroll
+            for (int m = 0; m < D; m++) xin[m] = x[m];
+        double V[2 * D + 1];
+        int ab;
+        offgrid_stencil<D, RP>(A, ro, xin, S.constelm, V, ab);
+        double tv[NT];
+        offgrid_tables<MID, Model>(xin, tv);
+        double u[DU], cf[NCFa];
+#pragma unroll
+        for (int q = 0; q < NCFa; q++) cf[q] = 0.0;
+        bool boxed = false;
+        if constexpr (BOX) {
+            if (A.cmode == 1) {
+                boxed = true;
+                double uo[DU];
+                (void)node_backup_box<Model>(A, xin, tv, V, ab, uo, st, false, nullptr);
+#pragma unroll
+                for (int k = 0; k < DU; k++) u[k] = uo[k];
+                if constexpr (requires { Model::CF_FROM_U; }) Model::features(u, cf);
+            }
+        }
+        if (!boxed) {
+            int ui;
+            (void)node_backup<Model, 1, 1, CandLds<Model>>(A, ro, xin, tv, cr, V, ab, ui, st);
+            const int uc = ui >= 0 ? ui : 0;
+#pragma unroll
+            for (int k = 0; k < DU; k++) u[k] = (ui >= 0) ? ro[A.cands_off + uc * DU + k] : 0.0; // obstacle: u = 0
+#pragma unroll
+            for (int q = 0; q < Model::NCF; q++) cf[q] = ro[A.cfeat_off + uc * Model::NCF + q];
+        }
+#pragma unroll
+        for (int k = 0; k < DU; k++) u[k] = alive ? u[k] : 0.0;
+        if (S.u && se > 0 && s % se == 0)
+#pragma unroll
+            for (int k = 0; k < DU; k++) S.u[((size_t)i * nurow + s / se) * DU + k] = u[k];
+        const double stage = Model::stage(A.prm, x, u);
+        J = alive ? J + disc * stage * dt : J;
+        // the dynamics at x itself (the controller may have seen the wrapped state)
+        double tvx[NT];
+        if (S.wrap) offgrid_tables<MID, Model>(x, tvx);
+        else
+#pragma unroll
+            for (int t = 0; t < NT; t++) tvx[t] = tv[t];
+        typename Model::Node nd;
+        Model::prep(A.prm, x, tvx, nd);
+        double b[D], sg[D];
+        Model::drift(A.prm, nd, x, u, cf, b);
+        Model::sigma(A.prm, x, u, sg);
+        double xi[D];
+        if (S.noise)
+#pragma unroll
+            for (int m = 0; m < D; m++) xi[m] = S.noise[((size_t)i * S.nsteps + s) * D + m];
+        else
+#pragma unroll
+            for (int m = 0; m < D; m++) xi[m] = philox_normal(S.seed, (unsigned long long)(S.traj_offset + i), (unsigned)s, (unsigned)m);
+#pragma unroll
+        for (int m = 0; m < D; m++) {
+            double acc = x[m] + b[m] * dt; // c3control_simulate's order
+            acc += sg[m] * S.sqdt * xi[m];
+            x[m] = alive ? acc : x[m];
+        }
+        if (S.traj && se > 0 && (s + 1) % se == 0)
+#pragma unroll
+            for (int m = 0; m < D; m++) S.traj[((size_t)i * nrow + (s + 1) / se) * D + m] = x[m];
+    }
+    if (S.s1 == S.nsteps) { // the final state: its exit test and the value there
+        exit_test(S.nsteps, exp(-beta * ((double)S.nsteps * dt)));
+        if (S.vend) {
+            double xin[D], V[2 * D + 1];
+            int ab;
+            if (S.wrap) wrap_periodic<D>(A, ro, x, xin);
+            else
+#pragma unroll
+                for (int m = 0; m < D; m++) xin[m] = x[m];
+            offgrid_stencil<D, RP>(A, ro, xin, S.constelm, V, ab);
+            S.vend[i] = V[2 * D];
+        }
+    }
+#pragma unroll
+    for (int m = 0; m < D; m++) S.x[(size_t)i * D + m] = x[m];
+    S.cost[i] = J;
+    S.exit_step[i] = ex;
+    if (st) atomicOr(A.status, st);
+}
+
+template <int MID, class Model, int RP, bool BOX>
+hipError_t launch_rollout(const KArgs &A, const LaunchIO &io)
+{
+    if (A.cmode == 1 && !BOX) return hipErrorNotSupported;
+    const SimK &S = *(const SimK *)io.sim;
+    const size_t shmem = (A.cmode == 0 ? (size_t)CandLds<Model>::doubles(A.ncand) : 1) * sizeof(double);
+    auto kern = k_rollout<MID, Model, RP, BOX>;
+    static LaunchCache cache;
+    int blocks_per_cu = 1, num_cu = 256;
+    hipError_t e = cache.prepare((const void *)kern, 256, shmem, blocks_per_cu, num_cu);
+    if (e != hipSuccess) return e;
+    const long grid = (S.n + 255) / 256;
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), shmem, io.stream, A, S, io.ro);
+    return hipGetLastError();
+}
+
+template <int D, int RP>
+hipError_t launch_stencil_points(const KArgs &A, const LaunchIO &io)
+{
+    const SimK &S = *(const SimK *)io.sim;
+    const long grid = (S.n + 255) / 256;
+    hipLaunchKernelGGL((k_stencil_points<D, RP>), dim3((unsigned)grid), dim3(256), 0, io.stream, A, S, io.ro);
+    return hipGetLastError();
+}
+
+#ifndef C3SC_CAT
+#define C3SC_CAT2(a, b) a##b
+#define C3SC_CAT(a, b) C3SC_CAT2(a, b)
+#endif
+
+// one rollout kernel per (model, padded rank); BOX = 1 where the model's Bellman kernels serve the control box too
+#define C3SC_REG_ROLLOUT(MODEL_ID, RP, BOX, ...)                                                               \
+    static Registrar C3SC_CAT(reg_roll_, __COUNTER__)(KernelEntry{                                            \
+        MODEL_ID, __VA_ARGS__::D, RP, 0, VARIANT_ROLLOUT, 0, -1, &launch_rollout<MODEL_ID, __VA_ARGS__, RP, BOX>, \
+        "k_rollout<" #__VA_ARGS__ "," #RP ">"});
+#define C3SC_REG_STENCIL_POINTS(DIM, RP)                                                                       \
+    static Registrar C3SC_CAT(reg_stp_, __COUNTER__)(KernelEntry{                                             \
+        0, DIM, RP, 0, VARIANT_STENCIL_POINTS, 0, -1, &launch_stencil_points<DIM, RP>,                           \
+        "k_stencil_points<" #DIM "," #RP ">"});
+
+} // namespace c3sc

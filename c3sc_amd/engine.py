@@ -32,7 +32,17 @@ EXPORTS = [
     "c3sc_hip_policy_fibers_box_host",
     "c3sc_hip_stencil_fibers_host", "c3sc_hip_stencil_fibers_nb", "c3sc_hip_stencil_fibers_nb_host", "c3sc_hip_sync", "c3sc_hip_get_status", "c3sc_hip_last_kernel",
     "c3sc_hip_debug_read", "c3sc_hip_launch_count", "c3sc_hip_timer_start", "c3sc_hip_timer_stop", "c3sc_hip_peak_fma_f64", "c3sc_hip_peak_mfma_f64",
+    "c3sc_hip_set_interp", "c3sc_hip_stencil_points", "c3sc_hip_simulate", "c3sc_hip_simulate_host", "c3sc_hip_normals",
 ]
+
+class SimArgs(C.Structure):
+    """struct c3sc_hip_sim_args (include/c3sc_hip.h)"""
+    _fields_ = [("n", C.c_size_t), ("d_x0", C.c_void_p), ("dt", C.c_double), ("nsteps", C.c_size_t),
+                ("traj_offset", C.c_uint64), ("seed", C.c_uint64), ("d_noise", C.c_void_p), ("wrap_periodic", C.c_int),
+                ("box", C.c_int), ("steps_per_launch", C.c_int), ("save_every", C.c_size_t), ("d_traj", C.c_void_p),
+                ("d_u", C.c_void_p), ("d_cost", C.c_void_p), ("d_exit", C.c_void_p), ("d_vend", C.c_void_p),
+                ("d_xfinal", C.c_void_p)]
+
 
 VARIANT_AUTO, VARIANT_FIBER_PER_WAVE, VARIANT_FIBER_PER_LANE, VARIANT_FIBER_PAIR, VARIANT_FIBER_QUAD = 0, 1, 2, 3, 4
 
@@ -84,8 +94,23 @@ def load_library():
         L.c3sc_hip_cross_options.argtypes = [C.c_void_p, C.c_int, C.c_double]
         L.c3sc_hip_cross_fetch.argtypes = [C.c_void_p, C.POINTER(c_double_p), C.POINTER(c_i32_p), C.POINTER(c_i32_p),
                                            C.POINTER(C.c_ulonglong), C.c_void_p]
+        L.c3sc_hip_set_interp.argtypes = [C.c_void_p, C.c_int]
+        L.c3sc_hip_stencil_points.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.c3sc_hip_simulate.argtypes = [C.c_void_p, C.POINTER(SimArgs), C.c_void_p]
+        L.c3sc_hip_normals.argtypes = [C.c_uint64, C.c_uint64, C.c_size_t, C.c_uint64, C.c_size_t, C.c_int, c_double_p]
         _LIB = L
     return _LIB
+
+
+def normals(seed: int, traj0: int, ntraj: int, step0: int, nsteps: int, dw: int) -> np.ndarray:
+    """Host twin of the rollouts' noise (c3sc_hip_normals): (ntraj, nsteps, dw) standard normals, the device's bits."""
+    L = load_library()
+    out = np.empty((ntraj, nsteps, dw), dtype=np.float64)
+    rc = L.c3sc_hip_normals(C.c_uint64(seed), C.c_uint64(traj0), C.c_size_t(ntraj), C.c_uint64(step0), C.c_size_t(nsteps),
+                            C.c_int(dw), out.ctypes.data_as(c_double_p))
+    if rc != 0:
+        raise C3scHipError(f"c3sc_hip_normals failed (code {rc})")
+    return out
 
 
 def _f64(a):
@@ -255,6 +280,66 @@ class BellmanEngine:
                                                  absorbed_t.data_ptr() if absorbed_t is not None else None,
                                                  stream_ptr), "stencil_fibers")
         return costs_t
+
+    # ------------------------------------------------------------------ closed-loop rollouts of the implicit policy
+    def set_interp(self, constelm: bool):
+        """Off-grid evaluation as a CONSTELM value function (nearest node per dimension) instead of multilinear."""
+        self._chk(self.L.c3sc_hip_set_interp(self.h, C.c_int(1 if constelm else 0)), "set_interp")
+
+    def stencil_points(self, x_t, out_t=None, absorbed_t=None, stream_ptr: Optional[int] = None):
+        """Device API (c3sc_hip_stencil_points): x_t float64 CUDA tensor (n, d) of arbitrary states; returns
+        (values (n, 2d+1), absorbed int32 (n,)) -- mca_get_neighbor_node_costs per state."""
+        import torch
+
+        assert x_t.is_cuda and x_t.dtype == torch.float64 and x_t.is_contiguous() and x_t.shape[1] == self.d
+        n = x_t.shape[0]
+        if out_t is None:
+            out_t = torch.empty((n, 2 * self.d + 1), dtype=torch.float64, device=x_t.device)
+        if absorbed_t is None:
+            absorbed_t = torch.empty((n,), dtype=torch.int32, device=x_t.device)
+        if stream_ptr is None:
+            stream_ptr = torch.cuda.current_stream(x_t.device).cuda_stream
+        self._chk(self.L.c3sc_hip_stencil_points(self.h, n, x_t.data_ptr(), out_t.data_ptr(), absorbed_t.data_ptr(),
+                                                 C.c_void_p(stream_ptr)), "stencil_points")
+        return out_t, absorbed_t
+
+    def simulate(self, x0_t, dt: float, nsteps: int, seed: int = 0, noise_t=None, wrap_periodic: bool = False,
+                 save_every: int = 0, traj_offset: int = 0, box: bool = False, steps_per_launch: int = 0,
+                 stream_ptr: Optional[int] = None):
+        """Device API (c3sc_hip_simulate): x0_t float64 CUDA tensor (n, d).  Returns a dict of CUDA tensors: cost (n,),
+        exit (int64, -1 = never), vend (n,), xfinal (n, d) and, with save_every > 0, traj (n, nsteps//save_every + 1, d)
+        and u (n, ceil(nsteps/save_every), du).  noise_t: float64 (n, nsteps, d) standard normals, else Philox(seed)."""
+        import torch
+
+        assert x0_t.is_cuda and x0_t.dtype == torch.float64 and x0_t.is_contiguous() and x0_t.shape[1] == self.d
+        n, d, dev = x0_t.shape[0], self.d, x0_t.device
+        du = getattr(self, "box_du", self.w.du) if box else self.w.du
+        res = {"cost": torch.empty((n,), dtype=torch.float64, device=dev),
+               "exit": torch.empty((n,), dtype=torch.int64, device=dev),
+               "vend": torch.empty((n,), dtype=torch.float64, device=dev),
+               "xfinal": torch.empty((n, d), dtype=torch.float64, device=dev)}
+        a = SimArgs()
+        a.n, a.d_x0, a.dt, a.nsteps = n, x0_t.data_ptr(), float(dt), int(nsteps)
+        a.traj_offset, a.seed, a.wrap_periodic, a.box = int(traj_offset), int(seed), int(bool(wrap_periodic)), int(bool(box))
+        a.steps_per_launch, a.save_every = int(steps_per_launch), int(save_every)
+        if noise_t is not None:
+            assert noise_t.is_cuda and noise_t.dtype == torch.float64 and noise_t.is_contiguous()
+            assert tuple(noise_t.shape) == (n, nsteps, d)
+            a.d_noise = noise_t.data_ptr()
+        if save_every > 0:
+            res["traj"] = torch.empty((n, nsteps // save_every + 1, d), dtype=torch.float64, device=dev)
+            res["u"] = torch.empty((n, (nsteps + save_every - 1) // save_every, du), dtype=torch.float64, device=dev)
+            a.d_traj, a.d_u = res["traj"].data_ptr(), res["u"].data_ptr()
+        a.d_cost, a.d_exit, a.d_vend, a.d_xfinal = (res["cost"].data_ptr(), res["exit"].data_ptr(), res["vend"].data_ptr(),
+                                                    res["xfinal"].data_ptr())
+        if stream_ptr is None:
+            stream_ptr = torch.cuda.current_stream(dev).cuda_stream
+        self._chk(self.L.c3sc_hip_simulate(self.h, C.byref(a), C.c_void_p(stream_ptr)), "simulate")
+        return res
+
+    def simulate_rc(self, args: "SimArgs", stream_ptr: int = 0) -> int:
+        """c3sc_hip_simulate's return code as is (for callers that check the error codes)."""
+        return int(self.L.c3sc_hip_simulate(self.h, C.byref(args), C.c_void_p(stream_ptr)))
 
     def bellman_fibers_host(self, k: int, idx: np.ndarray, want_uidx=True, want_absorbed=True):
         """Host-buffer API (what the C facade's bellman_vi uses): numpy in, numpy out, synchronous."""

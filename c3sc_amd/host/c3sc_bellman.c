@@ -1546,6 +1546,56 @@ int c3control_controller(double t, const double *x, double *u, void *args)
     return out;
 }
 
+static int sim_batch_reject(const char *msg)
+{
+    fprintf(stderr, "c3control_simulate_batch: %s\n", msg);
+    return C3SC_ERR_ARG;
+}
+
+int c3control_simulate_batch(struct C3Control *c, size_t ntraj, const double *x0, double dt, size_t nsteps, uint64_t seed,
+                             const double *noise, int wrap_periodic, size_t save_every, double *traj, double *utraj, double *cost,
+                             long *exit_step, double *vend)
+{ /* new: ntraj closed loops of the implicit policy on the device (c3sc_hip_simulate_host): the policy_sim value function, the
+     opt_sim minimiser (candidate list or control box) and the device model; prevpol is neither read nor written (both
+     minimisers ignore the starting point) */
+    if (c == NULL) return sim_batch_reject("null control");
+    if (c->dp->model == 0) return sim_batch_reject("no device model (c3control_set_device_model): host callbacks cannot run on the device");
+    if (c->policy_sim == NULL || c->opt_sim == NULL) return sim_batch_reject("no implicit policy (c3control_add_policy_sim)");
+    if (c->transform_sim != NULL && !wrap_periodic)
+        return sim_batch_reject("a state transform is a host callback the device cannot call; pass wrap_periodic = 1 if it only wraps periodic angles");
+    if (c->dw != c->dx) return sim_batch_reject("the device models have dw = dx (diagonal diffusion)");
+    if (ntraj == 0) return 0;
+    if (x0 == NULL) return sim_batch_reject("null x0");
+    if (!(dt > 0.0) || !isfinite(dt)) return sim_batch_reject("dt must be positive and finite");
+    if ((traj != NULL || utraj != NULL) && save_every == 0) return sim_batch_reject("traj / utraj need save_every > 0");
+    if (ntraj > ((size_t)1 << 31) || nsteps > ((size_t)1 << 30)) return sim_batch_reject("more than 2^31 trajectories or 2^30 steps");
+    const int brute = c3opt_is_bruteforce(c->opt_sim);
+    if (!brute && c3opt_get_d(c->opt_sim) > C3SC_MAX_DU) return sim_batch_reject("the box minimiser handles up to C3SC_MAX_DU controls");
+    if (c3opt_get_d(c->opt_sim) != c->du) return sim_batch_reject("opt_sim's dimension differs from the control dimension");
+    struct ControlParams *cp = control_params_create(c->dx, c->dw, c->dp, c->mca, c->work, c->opt_sim);
+    struct c3sc_hip_ctx *ctx = sync_device_ctx(cp, workspace_get_hip_ctx(c->work), c->policy_sim);
+    control_params_destroy(cp);
+    c3sc_hip_sim_args a;
+    memset(&a, 0, sizeof(a));
+    a.n = ntraj;
+    a.d_x0 = x0;
+    a.dt = dt;
+    a.nsteps = nsteps;
+    a.seed = seed;
+    a.d_noise = noise;
+    a.wrap_periodic = wrap_periodic;
+    a.box = !brute;
+    a.save_every = save_every;
+    a.d_traj = traj;
+    a.d_u = utraj;
+    a.d_cost = cost;
+    a.d_exit = (int64_t *)exit_step;
+    a.d_vend = vend;
+    const int rc = c3sc_hip_simulate_host(ctx, &a);
+    if (rc != C3SC_OK) fprintf(stderr, "c3control_simulate_batch: %s (code %d)\n", c3sc_hip_last_error(ctx), rc);
+    return rc;
+}
+
 int c3control_simulate(struct C3Control *c, const double *x0, double dt, size_t nsteps, const double *noise, double *traj,
                        double *utraj)
 { /* new: the closed-loop tail the examples run through cdyn (e.g. lqg2d.c:346-383) as plain Euler(-Maruyama):

@@ -116,6 +116,26 @@ int c3control_controller(double t, const double *x, double *u, void *args /* str
 /* new: Euler(-Maruyama) closed loop in place of the cdyn integrators the examples use; traj (nsteps+1) x dx */
 int c3control_simulate(struct C3Control *, const double *x0, double dt, size_t nsteps, const double *noise, double *traj,
                        double *utraj);
+/* new: ntraj closed loops at once on the GPU (libc3sc_hip.so: c3sc_hip_simulate, one lane per trajectory).  Host arrays:
+ *   x0 ntraj x dx; noise NULL (Philox normals keyed by (seed, trajectory, step, component)) or ntraj x nsteps x dx standard normals;
+ *   traj ntraj x (nsteps/save_every + 1) x dx, utraj ntraj x ceil(nsteps/save_every) x du (NULL, or save_every > 0);
+ *   cost[ntraj] = sum_{n < exit} e^{-beta n dt} stage(x_n, u_n) dt + e^{-beta exit dt} (boundcost | obscost)(x_exit), beta the
+ *   control's discount; exit_step[ntraj] = first n with x_n outside an absorbing face or inside an obstacle (-1: never; the state
+ *   is frozen from then on); vend[ntraj] = value of policy_sim at the final state.  Any output may be NULL.
+ * The controller is the implicit policy of c3control_add_policy_sim: policy_sim's value function, opt_sim's minimiser (BRUTEFORCE
+ * list or the box minimiser) and the DEVICE model (c3control_set_device_model; the host callbacks are not used).  prevpol is neither
+ * read nor written: both minimisers ignore the starting point.
+ * wrap_periodic = 1 maps the PERIODIC coordinates into [lb, ub) before the controller sees the state -- what the examples'
+ * state_transform does on their domains: dubinscar.c:168 (heading in [-pi, pi]) and both skidding cars (scar.c orientation,
+ * skidding5d/scar.c orientation, both on [-pi, pi]; the transform keeps x = pi where the wrap gives -pi, the same point of the
+ * periodic grid).  A transform_sim set with wrap_periodic = 0 is rejected: it is a host
+ * callback the device cannot call.
+ * Returns 0, or non-zero with a message on stderr: C3SC_ERR_ARG (no device model, no policy_sim, transform without wrap, dw != dx,
+ * null x0, dt <= 0, save_every = 0 with traj / utraj, sizes), C3SC_ERR_UNSUPPORTED (no rollout kernel for this model at this
+ * rank), C3SC_ERR_HIP. */
+int c3control_simulate_batch(struct C3Control *, size_t ntraj, const double *x0, double dt, size_t nsteps, uint64_t seed,
+                             const double *noise, int wrap_periodic, size_t save_every, double *traj, double *utraj, double *cost,
+                             long *exit_step, double *vend);
 
 /* ---- solver loops over the own cross driver (valuefunc.h: valuef_interp) ---- */
 #include <stdio.h>

@@ -219,6 +219,66 @@ int c3sc_hip_bellman_fibers_host(c3sc_hip_ctx *ctx, int k, size_t F, const int32
 int c3sc_hip_stencil_fibers_host(c3sc_hip_ctx *ctx, int k, size_t F, const int32_t *h_idx, double *h_costs,
                                  int32_t *h_absorbed);
 
+/* Closed-loop policy rollouts on the device (new; the reference runs them one state at a time on the host:
+ * c3control_add_policy_sim + c3control_controller + an Euler integration, e.g. dubinscar.c:376-382, lqg2d.c:346-353).
+ *
+ * c3sc_hip_set_interp: constelm = 1 evaluates the value function off the grid as a CONSTELM ValueF does (valuef_eval: the
+ * nearer node of each cell), 0 (default) piecewise multilinearly.
+ *
+ * c3sc_hip_stencil_points: mca_get_neighbor_node_costs (nodeutil.c:718-816) for n states at once: the 2d+1 values of the
+ * interpolant of the uploaded value function around each state x (d_x double [n*d], device).  d_out double [n*(2d+1)]:
+ * out[i*(2d+1) + 2m + {0,1}] = value at the (-,+) neighbour one grid spacing away in dim m (boundary branches of the host
+ * code: absorbing / reflecting faces clamp to the bound, periodic ones wrap), [.. + 2d] = value at x.  d_absorbed int32 [n]
+ * or NULL: -1 inside an obstacle (then all 2d+1 entries are the value at x), 0 otherwise.  set_grid / set_boundary (no
+ * C3SC_EB_NONE dimension) / upload_value must have been called.  Asynchronous on `stream`. */
+int c3sc_hip_set_interp(c3sc_hip_ctx *ctx, int constelm);
+int c3sc_hip_stencil_points(c3sc_hip_ctx *ctx, size_t n, const double *d_x, double *d_out, int32_t *d_absorbed, void *stream);
+
+/* c3sc_hip_simulate: n trajectories of the implicit policy of the uploaded value function, one GPU lane each.  Step k of a
+ * trajectory (x_k its state, t_k = k dt):
+ *   exit test    x_k outside [lb, ub] on an ABSORB dimension or inside an obstacle: the trajectory stops at k (exit_step = k),
+ *                pays e^{-beta t_k} (obscost if inside an obstacle, else boundcost)(x_k) and keeps its state from then on;
+ *                REFLECT and PERIODIC dimensions never stop a trajectory.  x_nsteps is tested as well.
+ *   controller   y = x_k (wrap_periodic: its PERIODIC coordinates mapped into [lb, ub)); the off-grid stencil at y, then the
+ *                minimiser the Bellman kernels use: the candidate list (box = 0; first minimum, strict '<') or the control box
+ *                (box = 1, c3sc_hip_set_control_box).  Inside an obstacle u = 0 (bellman_optimal's absorbed branch).
+ *   cost         + e^{-beta t_k} stage(x_k, u_k) dt, beta = the discount of set_mca
+ *   dynamics     x_{k+1} = x_k + b(x_k, u_k) dt + s(x_k, u_k) * sqrt(dt) xi_k (diagonal diffusion, dw = d), c3control_simulate's step
+ * The noise xi is d_noise when given, else Philox4x32-10 + Box-Muller keyed by (seed, traj_offset + i, k, component): the bits
+ * of a trajectory depend on its global index only, not on n or on how a batch is split (c3sc_hip_normals is the host twin).
+ * The call is cut into launches of steps_per_launch steps (0 = 64); the state is kept in a buffer of the context between them.
+ * Errors: C3SC_ERR_ARG (state not set, null x0, dt <= 0, a C3SC_EB_NONE dimension, save_every = 0 with d_traj / d_u ...),
+ * C3SC_ERR_UNSUPPORTED (the TABLE model, no rollout instantiation for this model at this padded rank, a box without one).
+ * n is at most 2^31 per call (split larger batches with traj_offset).  The state between launches lives in ONE buffer of the
+ * context: calls on the same context must not overlap (same stream, or synchronise between them); use one context per stream.
+ * last_kernel names the rollout kernel.  Asynchronous on `stream`. */
+typedef struct c3sc_hip_sim_args {
+    size_t n;                /* trajectories */
+    const double *d_x0;      /* [n*d] initial states */
+    double dt;
+    size_t nsteps;
+    uint64_t traj_offset;    /* global index of trajectory 0 (noise counter) */
+    uint64_t seed;
+    const double *d_noise;   /* [n*nsteps*d] standard normals or NULL (seeded Philox); wins when non-NULL */
+    int wrap_periodic;
+    int box;                 /* 0: candidate list (set_controls), 1: control box (set_control_box) */
+    int steps_per_launch;    /* 0 = 64 */
+    size_t save_every;       /* 0 = none; else states k = 0, s, 2s, ... <= nsteps and controls k = 0, s, ... < nsteps */
+    double *d_traj;          /* [n][nsteps/save_every + 1][d] or NULL */
+    double *d_u;             /* [n][ceil(nsteps/save_every)][du] or NULL (0 after exit) */
+    double *d_cost;          /* [n] discounted cost J or NULL */
+    int64_t *d_exit;         /* [n] exit step, -1 = never, or NULL */
+    double *d_vend;          /* [n] interpolant at the final state (wrapped like the controller's input) or NULL */
+    double *d_xfinal;        /* [n*d] final state or NULL */
+} c3sc_hip_sim_args;
+int c3sc_hip_simulate(c3sc_hip_ctx *ctx, const c3sc_hip_sim_args *args, void *stream);
+/* the same with HOST arrays in every pointer of args (d_* names notwithstanding): staged through device memory, synchronous.
+ * This is what libc3sc.so's c3control_simulate_batch calls. */
+int c3sc_hip_simulate_host(c3sc_hip_ctx *ctx, const c3sc_hip_sim_args *args);
+/* host twin of the rollouts' noise: out[(t*nsteps + k)*dw + j] = the normal of component j at step step0 + k of trajectory
+ * traj0 + t under `seed` -- the same bits the device draws (philox.hpp) */
+int c3sc_hip_normals(uint64_t seed, uint64_t traj0, size_t ntraj, uint64_t step0, size_t nsteps, int dw, double *out);
+
 /* Device-resident core steps of the cross approximation that calls the path (valuefunc.c:603-767 hands bellman_vi to C3's
  * ftapprox_cross; c3sc_amd/host/c3sc_cross.c is this library's driver).  A cross iteration is 2 d sequential core steps of
  * r_k r_{k+1} fibers each; with fibers on the GPU and factorisation + node memo on the host a sweep is host-bound.  These
