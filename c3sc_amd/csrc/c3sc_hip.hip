@@ -14,6 +14,7 @@
 #include "../../include/c3sc_hip.h"
 #include "kernel_common.hpp"
 #include "kernel_rollout.hpp"
+#include "kernel_rollout_ode.hpp"
 #include "model_tables.hpp"
 #include "registry.hpp"
 
@@ -1284,6 +1285,174 @@ int c3sc_hip_simulate_host(c3sc_hip_ctx *c, const c3sc_hip_sim_args *h)
         {h->d_traj, a.d_traj, sz[2] * sizeof(double)}, {h->d_u, a.d_u, sz[3] * sizeof(double)}, {h->d_cost, a.d_cost, n * sizeof(double)},
         {h->d_exit, a.d_exit, n * sizeof(int64_t)}, {h->d_vend, a.d_vend, n * sizeof(double)}, {h->d_xfinal, a.d_xfinal, n * d * sizeof(double)}};
     for (int i = 0; i < 6 && rc == C3SC_OK; i++)
+        if (back[i].dst && back[i].bytes) {
+            e = hipMemcpy(back[i].dst, back[i].src, back[i].bytes, hipMemcpyDeviceToHost);
+            if (e != hipSuccess) rc = fail(c, C3SC_ERR_HIP, hipGetErrorString(e));
+        }
+    (void)hipFree(buf);
+    return rc;
+}
+
+// ------------------------------------------------------------------ closed-loop integration (kernel_rollout_ode.hpp)
+static const size_t ODE_MAX_EVALS = (size_t)1 << 40; // controller evaluations per lane of one call (substep indices stay exact)
+
+// nsub = dt_out / dt_int, an integer to 1e-9 relative (dt_int = 0: 1); 0 when it is not
+static long long ode_nsub(double dt_out, double dt_int)
+{
+    if (dt_int == 0.0) return 1;
+    const double r = dt_out / dt_int, q = std::nearbyint(r);
+    if (!(q >= 1.0) || !(std::fabs(r - q) <= 1e-9 * q) || q > (double)(1 << 30)) return 0;
+    return (long long)q;
+}
+
+// a stop box: host (lo[d], hi[d]); lo > hi or a NaN is an error
+static bool ode_box_ok(const double *b, int d)
+{
+    if (!b) return true;
+    for (int m = 0; m < d; m++)
+        if (!(b[m] <= b[d + m])) return false;
+    return true;
+}
+
+int c3sc_hip_integrate(c3sc_hip_ctx *c, const c3sc_hip_ode_args *a, void *stream)
+{
+    if (!c) return C3SC_ERR_ARG;
+    if (!a) return fail(c, C3SC_ERR_ARG, "integrate: null argument struct");
+    if (c->model == C3SC_MODEL_TABLE) return fail(c, C3SC_ERR_UNSUPPORTED, "integrate: the TABLE model has no device dynamics");
+    if (!c->have_mca || c->model == 0) return fail(c, C3SC_ERR_ARG, "integrate: mca and model must be set");
+    if (a->box ? c->box_du == 0 : c->ncand == 0)
+        return fail(c, C3SC_ERR_ARG, a->box ? "integrate: set_control_box first" : "integrate: set_controls first");
+    if (a->box && model_ncf(c->model) != 0 && c->model != C3SC_MODEL_COTHRUST6D)
+        return fail(c, C3SC_ERR_UNSUPPORTED, "integrate: this model needs transcendental functions of the control in a box");
+    KArgs A;
+    int rc = fill_args(c, 0, 0, A, false);
+    if (rc != C3SC_OK) return rc;
+    rc = check_bounds_set(c, "integrate: every dimension needs a boundary type");
+    if (rc != C3SC_OK) return rc;
+    if (!(a->dt_out > 0.0) || !std::isfinite(a->dt_out)) return fail(c, C3SC_ERR_ARG, "integrate: dt_out must be positive and finite");
+    if (!(a->dt_int >= 0.0) || !std::isfinite(a->dt_int)) return fail(c, C3SC_ERR_ARG, "integrate: dt_int must be >= 0 and finite");
+    const long long nsub = ode_nsub(a->dt_out, a->dt_int);
+    if (nsub == 0) return fail(c, C3SC_ERR_ARG, "integrate: dt_out / dt_int is not an integer (to 1e-9 relative)");
+    if (a->method != C3SC_ODE_FORWARD_EULER && a->method != C3SC_ODE_RK4)
+        return fail(c, C3SC_ERR_ARG, "integrate: method must be C3SC_ODE_FORWARD_EULER or C3SC_ODE_RK4");
+    const int nstage = a->method == C3SC_ODE_RK4 ? 4 : 1;
+    if (a->nout > (size_t)1 << 30) return fail(c, C3SC_ERR_ARG, "integrate: nout too large");
+    if ((size_t)nsub * a->nout * nstage > ODE_MAX_EVALS) return fail(c, C3SC_ERR_ARG, "integrate: more than 2^40 controller evaluations per trajectory");
+    if (a->n > SIM_MAX_TRAJ) return fail(c, C3SC_ERR_ARG, "integrate: more than 2^31 trajectories in one call (split the batch)");
+    if (a->save_every == 0 && (a->d_traj || a->d_u)) return fail(c, C3SC_ERR_ARG, "integrate: d_traj / d_u need save_every > 0");
+    if (a->save_every > a->nout && a->save_every > 1 && (a->d_traj || a->d_u))
+        return fail(c, C3SC_ERR_ARG, "integrate: save_every larger than nout");
+    if (a->evals_per_launch < 0) return fail(c, C3SC_ERR_ARG, "integrate: evals_per_launch < 0");
+    if (!ode_box_ok(a->goal, c->d) || !ode_box_ok(a->keep, c->d))
+        return fail(c, C3SC_ERR_ARG, "integrate: a stop box has lo > hi (or a NaN)");
+    const KernelEntry *e = find_sim_kernel(VARIANT_ROLLOUT_ODE, c->model, c->d, c->rp);
+    if (!e) return fail(c, C3SC_ERR_UNSUPPORTED, "integrate: no integrate instantiation for this model at this padded rank");
+    if (a->n == 0) return C3SC_OK;
+    if (!a->d_x0) return fail(c, C3SC_ERR_ARG, "integrate: null d_x0");
+    const int d = c->d;
+    const size_t n = a->n;
+    const size_t bytes = n * (size_t)(d + 3) * sizeof(double); // x | cost | stop_step | stop_reason
+    if (bytes > c->sim_state_bytes) {
+        if (c->sim_state) HIPCHK(c, hipFree(c->sim_state));
+        c->sim_state = nullptr;
+        c->sim_state_bytes = 0;
+        HIPCHK(c, hipMalloc(&c->sim_state, bytes));
+        c->sim_state_bytes = bytes;
+    }
+    double *st_x = (double *)c->sim_state, *st_cost = st_x + n * d;
+    long long *st_stop = (long long *)(st_cost + n);
+    int32_t *st_why = (int32_t *)(st_stop + n);
+    A.cmode = a->box ? 1 : 0;
+    A.ugrid = c->box_grid;
+    A.upolish = c->box_polish;
+    for (int i = 0; i < c->box_du; i++) { A.ulb[i] = c->box_lb[i]; A.uub[i] = c->box_ub[i]; }
+    OdeK S;
+    std::memset(&S, 0, sizeof(S));
+    S.n = (long)n;
+    S.nsub = (int)nsub;
+    S.nout = (int)a->nout;
+    S.nstage = nstage;
+    S.save_every = (int)a->save_every;
+    S.wrap = a->wrap_periodic ? 1 : 0;
+    S.constelm = c->constelm;
+    S.h = a->dt_int == 0.0 ? a->dt_out : a->dt_int;
+    S.dt_out = a->dt_out;
+    S.has_goal = a->goal ? 1 : 0;
+    S.has_keep = a->keep ? 1 : 0;
+    for (int m = 0; m < d; m++) {
+        S.goal_lo[m] = a->goal ? a->goal[m] : 0.0;
+        S.goal_hi[m] = a->goal ? a->goal[d + m] : 0.0;
+        S.keep_lo[m] = a->keep ? a->keep[m] : -INFINITY;
+        S.keep_hi[m] = a->keep ? a->keep[d + m] : INFINITY;
+    }
+    S.x0 = a->d_x0;
+    S.x = st_x;
+    S.cost = st_cost;
+    S.stop_step = st_stop;
+    S.stop_reason = st_why;
+    S.traj = a->d_traj;
+    S.u = a->d_u;
+    S.vend = a->d_vend;
+    const long long ktot = nsub * (long long)a->nout;
+    const long long chunk = std::max<long long>(1, (a->evals_per_launch > 0 ? a->evals_per_launch : 256) / nstage);
+    c->last_kernel = e->name;
+    c->status_cache_valid = false;
+    long long k0 = 0;
+    do { // at least one launch: nout = 0 still tests x_0 and evaluates V_end
+        S.k0 = k0;
+        S.k1 = std::min(k0 + chunk, ktot);
+        LaunchIO io{c->arena, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream, &S};
+        g_launches++;
+        const hipError_t he = e->fn(A, io);
+        if (he == hipErrorNotSupported) return fail(c, C3SC_ERR_UNSUPPORTED, "integrate: this integrate kernel has no box minimiser");
+        HIPCHK(c, he);
+        k0 = S.k1;
+    } while (k0 < ktot);
+    hipStream_t sm = (hipStream_t)stream;
+    if (a->d_xfinal) HIPCHK(c, hipMemcpyAsync(a->d_xfinal, st_x, n * d * sizeof(double), hipMemcpyDeviceToDevice, sm));
+    if (a->d_cost) HIPCHK(c, hipMemcpyAsync(a->d_cost, st_cost, n * sizeof(double), hipMemcpyDeviceToDevice, sm));
+    if (a->d_stop_step) HIPCHK(c, hipMemcpyAsync(a->d_stop_step, st_stop, n * sizeof(int64_t), hipMemcpyDeviceToDevice, sm));
+    if (a->d_stop_reason) HIPCHK(c, hipMemcpyAsync(a->d_stop_reason, st_why, n * sizeof(int32_t), hipMemcpyDeviceToDevice, sm));
+    return C3SC_OK;
+}
+
+int c3sc_hip_integrate_host(c3sc_hip_ctx *c, const c3sc_hip_ode_args *h)
+{
+    if (!c) return C3SC_ERR_ARG;
+    if (!h) return fail(c, C3SC_ERR_ARG, "integrate_host: null argument struct");
+    if (h->n == 0) return c3sc_hip_integrate(c, h, nullptr);
+    if (!h->d_x0) return fail(c, C3SC_ERR_ARG, "integrate_host: null x0");
+    if (h->n > SIM_MAX_TRAJ || h->nout > ((size_t)1 << 30)) return fail(c, C3SC_ERR_ARG, "integrate_host: sizes too large");
+    if (h->save_every == 0 && (h->d_traj || h->d_u)) return fail(c, C3SC_ERR_ARG, "integrate: d_traj / d_u need save_every > 0");
+    if (c->d == 0) return fail(c, C3SC_ERR_ARG, "integrate_host: set_grid first");
+    const size_t n = h->n, d = (size_t)c->d, du = (size_t)(h->box ? c->box_du : c->du);
+    const size_t se = h->save_every, nrow = se ? h->nout / se + 1 : 0, nurow = se ? (h->nout + se - 1) / se : 0;
+    // staging buffer: [x0 | traj | u | cost | stop_step | stop_reason | vend | xfinal]
+    size_t off[9];
+    const size_t sz[8] = {n * d, h->d_traj ? n * nrow * d : 0, h->d_u ? n * nurow * du : 0, n, n, n, n, n * d};
+    off[0] = 0;
+    for (int i = 0; i < 8; i++) off[i + 1] = off[i] + ((sz[i] + 31) & ~(size_t)31);
+    HIPCHK(c, hipSetDevice(c->device));
+    double *buf = nullptr;
+    HIPCHK(c, hipMalloc((void **)&buf, off[8] * sizeof(double)));
+    c3sc_hip_ode_args a = *h;
+    a.d_x0 = buf + off[0];
+    a.d_traj = h->d_traj ? buf + off[1] : nullptr;
+    a.d_u = h->d_u ? buf + off[2] : nullptr;
+    a.d_cost = buf + off[3];
+    a.d_stop_step = (int64_t *)(buf + off[4]);
+    a.d_stop_reason = (int32_t *)(buf + off[5]);
+    a.d_vend = buf + off[6];
+    a.d_xfinal = buf + off[7];
+    int rc = C3SC_OK;
+    hipError_t e = hipMemcpy((void *)a.d_x0, h->d_x0, sz[0] * sizeof(double), hipMemcpyHostToDevice);
+    if (e != hipSuccess) rc = fail(c, C3SC_ERR_HIP, hipGetErrorString(e));
+    if (rc == C3SC_OK) rc = c3sc_hip_integrate(c, &a, nullptr);
+    struct { void *dst; const void *src; size_t bytes; } back[7] = {
+        {h->d_traj, a.d_traj, sz[1] * sizeof(double)}, {h->d_u, a.d_u, sz[2] * sizeof(double)}, {h->d_cost, a.d_cost, n * sizeof(double)},
+        {h->d_stop_step, a.d_stop_step, n * sizeof(int64_t)}, {h->d_stop_reason, a.d_stop_reason, n * sizeof(int32_t)},
+        {h->d_vend, a.d_vend, n * sizeof(double)}, {h->d_xfinal, a.d_xfinal, n * d * sizeof(double)}};
+    for (int i = 0; i < 7 && rc == C3SC_OK; i++)
         if (back[i].dst && back[i].bytes) {
             e = hipMemcpy(back[i].dst, back[i].src, back[i].bytes, hipMemcpyDeviceToHost);
             if (e != hipSuccess) rc = fail(c, C3SC_ERR_HIP, hipGetErrorString(e));

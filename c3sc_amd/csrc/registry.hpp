@@ -23,9 +23,9 @@ struct LaunchIO {
     const void *sim = nullptr; // rollout / off-grid stencil kernels only: their SimK argument block (kernel_rollout.hpp)
 };
 
-// KernelEntry::variant of the rollout and off-grid stencil kernels (c3sc_hip_simulate / c3sc_hip_stencil_points): not
-// Bellman-operator kernels, so the fiber paths never select them (find_kernel, pick_rp)
-constexpr int VARIANT_ROLLOUT = 100, VARIANT_STENCIL_POINTS = 101;
+// KernelEntry::variant of the rollout, off-grid stencil and integrate kernels (c3sc_hip_simulate / c3sc_hip_stencil_points /
+// c3sc_hip_integrate): not Bellman-operator kernels, so the fiber paths never select them (find_kernel, pick_rp)
+constexpr int VARIANT_ROLLOUT = 100, VARIANT_STENCIL_POINTS = 101, VARIANT_ROLLOUT_ODE = 102;
 __host__ __device__ constexpr bool is_fiber_variant(int v) { return v < VARIANT_ROLLOUT; }
 
 typedef hipError_t (*launch_fn)(const KArgs &A, const LaunchIO &io);

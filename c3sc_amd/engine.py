@@ -33,6 +33,7 @@ EXPORTS = [
     "c3sc_hip_stencil_fibers_host", "c3sc_hip_stencil_fibers_nb", "c3sc_hip_stencil_fibers_nb_host", "c3sc_hip_sync", "c3sc_hip_get_status", "c3sc_hip_last_kernel",
     "c3sc_hip_debug_read", "c3sc_hip_launch_count", "c3sc_hip_timer_start", "c3sc_hip_timer_stop", "c3sc_hip_peak_fma_f64", "c3sc_hip_peak_mfma_f64",
     "c3sc_hip_set_interp", "c3sc_hip_stencil_points", "c3sc_hip_simulate", "c3sc_hip_simulate_host", "c3sc_hip_normals",
+    "c3sc_hip_integrate", "c3sc_hip_integrate_host",
 ]
 
 class SimArgs(C.Structure):
@@ -42,6 +43,19 @@ class SimArgs(C.Structure):
                 ("box", C.c_int), ("steps_per_launch", C.c_int), ("save_every", C.c_size_t), ("d_traj", C.c_void_p),
                 ("d_u", C.c_void_p), ("d_cost", C.c_void_p), ("d_exit", C.c_void_p), ("d_vend", C.c_void_p),
                 ("d_xfinal", C.c_void_p)]
+
+
+ODE_FORWARD_EULER, ODE_RK4 = 0, 1  # C3SC_ODE_*
+_ODE_METHODS = {"forward-euler": ODE_FORWARD_EULER, "euler": ODE_FORWARD_EULER, "rk4": ODE_RK4}
+
+
+class OdeArgs(C.Structure):
+    """struct c3sc_hip_ode_args (include/c3sc_hip.h)"""
+    _fields_ = [("n", C.c_size_t), ("d_x0", C.c_void_p), ("dt_out", C.c_double), ("dt_int", C.c_double), ("nout", C.c_size_t),
+                ("method", C.c_int), ("wrap_periodic", C.c_int), ("box", C.c_int), ("evals_per_launch", C.c_int),
+                ("goal", C.c_void_p), ("keep", C.c_void_p), ("save_every", C.c_size_t), ("d_traj", C.c_void_p),
+                ("d_u", C.c_void_p), ("d_cost", C.c_void_p), ("d_stop_step", C.c_void_p), ("d_stop_reason", C.c_void_p),
+                ("d_vend", C.c_void_p), ("d_xfinal", C.c_void_p)]
 
 
 VARIANT_AUTO, VARIANT_FIBER_PER_WAVE, VARIANT_FIBER_PER_LANE, VARIANT_FIBER_PAIR, VARIANT_FIBER_QUAD = 0, 1, 2, 3, 4
@@ -97,6 +111,8 @@ def load_library():
         L.c3sc_hip_set_interp.argtypes = [C.c_void_p, C.c_int]
         L.c3sc_hip_stencil_points.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.c3sc_hip_simulate.argtypes = [C.c_void_p, C.POINTER(SimArgs), C.c_void_p]
+        L.c3sc_hip_integrate.argtypes = [C.c_void_p, C.POINTER(OdeArgs), C.c_void_p]
+        L.c3sc_hip_integrate_host.argtypes = [C.c_void_p, C.POINTER(OdeArgs)]
         L.c3sc_hip_normals.argtypes = [C.c_uint64, C.c_uint64, C.c_size_t, C.c_uint64, C.c_size_t, C.c_int, c_double_p]
         _LIB = L
     return _LIB
@@ -340,6 +356,55 @@ class BellmanEngine:
     def simulate_rc(self, args: "SimArgs", stream_ptr: int = 0) -> int:
         """c3sc_hip_simulate's return code as is (for callers that check the error codes)."""
         return int(self.L.c3sc_hip_simulate(self.h, C.byref(args), C.c_void_p(stream_ptr)))
+
+    def integrate(self, x0_t, dt_out: float, nout: int, method: str = "rk4", dt_int: Optional[float] = None, goal=None,
+                  keep_in=None, wrap_periodic: bool = False, box: bool = False, save_every: int = 0, evals_per_launch: int = 0,
+                  stream_ptr: Optional[int] = None):
+        """Device API (c3sc_hip_integrate): deterministic closed loops of the implicit policy, nout outer steps of dt_out, each
+        dt_out / dt_int substeps of "forward-euler" or "rk4" (dt_int None: one substep).  goal / keep_in: (lo, hi) sequences of
+        d values (+-inf allowed) or None.  x0_t float64 CUDA tensor (n, d).  Returns a dict of CUDA tensors: cost (n,),
+        stop_step (int64, -1 = never), stop_reason (int32: 0 running, 1 absorbing face, 2 obstacle, 3 goal, 4 keep-in left),
+        vend (n,), xfinal (n, d) and, with save_every > 0, traj (n, nout//save_every + 1, d) and u (n, ceil(nout/save_every), du)."""
+        import torch
+
+        assert x0_t.is_cuda and x0_t.dtype == torch.float64 and x0_t.is_contiguous() and x0_t.shape[1] == self.d
+        if method not in _ODE_METHODS:
+            raise ValueError(f"integrate: unknown method {method!r} (forward-euler, rk4)")
+        n, d, dev = x0_t.shape[0], self.d, x0_t.device
+        du = getattr(self, "box_du", self.w.du) if box else self.w.du
+        res = {"cost": torch.empty((n,), dtype=torch.float64, device=dev),
+               "stop_step": torch.empty((n,), dtype=torch.int64, device=dev),
+               "stop_reason": torch.empty((n,), dtype=torch.int32, device=dev),
+               "vend": torch.empty((n,), dtype=torch.float64, device=dev),
+               "xfinal": torch.empty((n, d), dtype=torch.float64, device=dev)}
+        a = OdeArgs()
+        a.n, a.d_x0, a.dt_out, a.nout = n, x0_t.data_ptr(), float(dt_out), int(nout)
+        a.dt_int = 0.0 if dt_int is None else float(dt_int)
+        a.method, a.wrap_periodic, a.box = _ODE_METHODS[method], int(bool(wrap_periodic)), int(bool(box))
+        a.evals_per_launch, a.save_every = int(evals_per_launch), int(save_every)
+        boxes = {}
+        for key, b in (("goal", goal), ("keep", keep_in)):
+            if b is not None:
+                arr = np.ascontiguousarray(np.concatenate([np.asarray(b[0], dtype=np.float64).reshape(-1),
+                                                           np.asarray(b[1], dtype=np.float64).reshape(-1)]))
+                if arr.shape[0] != 2 * d:
+                    raise ValueError(f"integrate: {key} needs (lo, hi) of {d} values each")
+                boxes[key] = arr
+                setattr(a, key, arr.ctypes.data)
+        if save_every > 0:
+            res["traj"] = torch.empty((n, nout // save_every + 1, d), dtype=torch.float64, device=dev)
+            res["u"] = torch.empty((n, (nout + save_every - 1) // save_every, du), dtype=torch.float64, device=dev)
+            a.d_traj, a.d_u = res["traj"].data_ptr(), res["u"].data_ptr()
+        a.d_cost, a.d_stop_step, a.d_stop_reason = res["cost"].data_ptr(), res["stop_step"].data_ptr(), res["stop_reason"].data_ptr()
+        a.d_vend, a.d_xfinal = res["vend"].data_ptr(), res["xfinal"].data_ptr()
+        if stream_ptr is None:
+            stream_ptr = torch.cuda.current_stream(dev).cuda_stream
+        self._chk(self.L.c3sc_hip_integrate(self.h, C.byref(a), C.c_void_p(stream_ptr)), "integrate")
+        return res
+
+    def integrate_rc(self, args: "OdeArgs", stream_ptr: int = 0) -> int:
+        """c3sc_hip_integrate's return code as is (for callers that check the error codes)."""
+        return int(self.L.c3sc_hip_integrate(self.h, C.byref(args), C.c_void_p(stream_ptr)))
 
     def bellman_fibers_host(self, k: int, idx: np.ndarray, want_uidx=True, want_absorbed=True):
         """Host-buffer API (what the C facade's bellman_vi uses): numpy in, numpy out, synchronous."""

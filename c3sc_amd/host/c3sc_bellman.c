@@ -1596,6 +1596,175 @@ int c3control_simulate_batch(struct C3Control *c, size_t ntraj, const double *x0
     return rc;
 }
 
+/* cdyn's integrator names (the examples' integrator_create_controlled) -> C3SC_ODE_*, -1 if unknown */
+static int ode_method(const char *name)
+{
+    if (name == NULL) return -1;
+    if (strcmp(name, "forward-euler") == 0) return C3SC_ODE_FORWARD_EULER;
+    if (strcmp(name, "rk4") == 0) return C3SC_ODE_RK4;
+    return -1;
+}
+
+static int integrate_reject(const char *who, const char *msg)
+{
+    fprintf(stderr, "%s: %s\n", who, msg);
+    return C3SC_ERR_ARG;
+}
+
+/* the checks c3control_integrate and c3control_integrate_batch share; *nsub out */
+static int integrate_check(const char *who, size_t dx, const char *method, double dt_int, double dt_out, size_t nout,
+                           const double *goal, const double *keep, size_t *nsub)
+{
+    if (ode_method(method) < 0) return integrate_reject(who, "method must be \"forward-euler\" or \"rk4\"");
+    if (!(dt_out > 0.0) || !isfinite(dt_out)) return integrate_reject(who, "dt_out must be positive and finite");
+    if (!(dt_int >= 0.0) || !isfinite(dt_int)) return integrate_reject(who, "dt_int must be >= 0 and finite");
+    *nsub = 1;
+    if (dt_int > 0.0) {
+        const double r = dt_out / dt_int, q = nearbyint(r);
+        if (!(q >= 1.0) || !(fabs(r - q) <= 1e-9 * q) || q > (double)(1 << 30))
+            return integrate_reject(who, "dt_out / dt_int is not an integer (to 1e-9 relative)");
+        *nsub = (size_t)q;
+    }
+    if (nout > ((size_t)1 << 30)) return integrate_reject(who, "nout too large");
+    for (size_t m = 0; m < dx; m++) {
+        if (goal != NULL && !(goal[m] <= goal[dx + m])) return integrate_reject(who, "the goal box has lo > hi");
+        if (keep != NULL && !(keep[m] <= keep[dx + m])) return integrate_reject(who, "the keep-in box has lo > hi");
+    }
+    return 0;
+}
+
+int c3control_integrate(struct C3Control *c, const char *method, double dt_int, double dt_out, size_t nout, const double *x0,
+                        const double *goal, const double *keep, double *traj, double *utraj, double *cost, long *stop_step,
+                        int *stop_reason)
+{ /* new: the examples' cdyn tail (integrator_create_controlled + trajectory_step + the goal test, e.g. dubinscar.c:379-412)
+     for one trajectory, over the user's callbacks and c3control_controller; the host twin of c3sc_hip_integrate */
+    const char *who = "c3control_integrate";
+    if (c == NULL || x0 == NULL) return integrate_reject(who, "null control or x0");
+    if (c->policy_sim == NULL || c->opt_sim == NULL) return integrate_reject(who, "no implicit policy (c3control_add_policy_sim)");
+    if (c->dp->drift == NULL || c->dp->stagecost == NULL || c->dp->boundcost == NULL || c->dp->obscost == NULL)
+        return integrate_reject(who, "the host callbacks (drift, stagecost, boundcost, obscost) are needed");
+    size_t nsub;
+    int rc = integrate_check(who, c->dx, method, dt_int, dt_out, nout, goal, keep, &nsub);
+    if (rc != 0) return rc;
+    const int rk4 = ode_method(method) == C3SC_ODE_RK4;
+    const size_t dx = c->dx, du = c->du, nstage = rk4 ? 4 : 1;
+    const double h = dt_int > 0.0 ? dt_int : dt_out, beta = c->dp->discount;
+    double *x = xcalloc(dx, sizeof(double)), *y = xcalloc(dx, sizeof(double)), *b = xcalloc(dx, sizeof(double));
+    double *ks = xcalloc(dx, sizeof(double)), *u = xcalloc(du, sizeof(double));
+    memcpy(x, x0, dx * sizeof(double));
+    double J = 0.0;
+    long stp = -1;
+    int why = 0;
+    if (traj) memcpy(traj, x, dx * sizeof(double));
+    for (size_t j = 0; j <= nout && rc == 0; j++) {
+        /* the stops at x_j: exit (1 face / 2 obstacle, charged once), goal (3), keep-in (4) */
+        const int inobs = boundary_in_obstacle(c->bound, x) != 0;
+        int out = 0, ingoal = goal != NULL, outkeep = 0;
+        for (size_t m = 0; m < dx; m++) {
+            out |= boundary_type_dim(c->bound, m, 0) == ABSORB && (x[m] < c->xgrid[m][0] || x[m] > c->xgrid[m][c->ngrid[m] - 1]);
+            if (goal != NULL) ingoal = ingoal && goal[m] < x[m] && x[m] < goal[dx + m];
+            if (keep != NULL) outkeep |= x[m] < keep[m] || x[m] > keep[dx + m];
+        }
+        if (inobs || out) {
+            double term = 0.0;
+            rc = inobs ? c->dp->obscost(x, &term) : c->dp->boundcost((double)j * dt_out, x, &term);
+            J += exp(-beta * ((double)j * dt_out)) * term;
+            why = inobs ? 2 : 1;
+        } else if (ingoal) why = 3;
+        else if (outkeep) why = 4;
+        if (why != 0) { stp = (long)j; break; }
+        if (j == nout) break;
+        for (size_t sub = 0; sub < nsub && rc == 0; sub++) {
+            const double t = (double)(j * nsub + sub) * h;
+            double cs = 0.0;
+            for (size_t q = 0; q < nstage && rc == 0; q++) {
+                const double a = q == 0 ? 0.0 : (q == 3 ? h : h / 2), wq = (q == 0 || q == 3) ? 1.0 : 2.0;
+                for (size_t m = 0; m < dx; m++) y[m] = q == 0 ? x[m] : x[m] + a * b[m];
+                rc = c3control_controller(t + a, y, u, c);
+                double stage = 0.0;
+                if (rc == 0) rc = c->dp->stagecost(t + a, y, u, &stage, NULL);
+                if (rc == 0) rc = drift_eval(c->dp->drift, t + a, y, u, b, NULL);
+                if (rc != 0) break;
+                if (q == 0 && sub == 0 && utraj) memcpy(utraj + j * du, u, du * sizeof(double));
+                const double cq = exp(-beta * (t + a)) * stage;
+                cs = q == 0 ? cq : cs + wq * cq;
+                for (size_t m = 0; m < dx; m++) ks[m] = q == 0 ? b[m] : ks[m] + wq * b[m];
+            }
+            if (rc != 0) break;
+            if (!rk4) {
+                J = J + cs * h;
+                for (size_t m = 0; m < dx; m++) x[m] = x[m] + ks[m] * h;
+            } else {
+                J = J + h / 6.0 * cs;
+                for (size_t m = 0; m < dx; m++) x[m] = x[m] + h / 6.0 * ks[m];
+            }
+        }
+        if (traj) memcpy(traj + (j + 1) * dx, x, dx * sizeof(double));
+    }
+    if (stp >= 0) /* frozen from the stop on */
+        for (size_t j = (size_t)stp; j < nout; j++) {
+            if (traj) memcpy(traj + (j + 1) * dx, x, dx * sizeof(double));
+            if (utraj) memset(utraj + j * du, 0, du * sizeof(double));
+        }
+    if (cost) *cost = J;
+    if (stop_step) *stop_step = stp;
+    if (stop_reason) *stop_reason = why;
+    free(x); free(y); free(b); free(ks); free(u);
+    return rc;
+}
+
+int c3control_integrate_batch(struct C3Control *c, size_t ntraj, const double *x0, const char *method, double dt_int, double dt_out,
+                              size_t nout, const double *goal, const double *keep, int wrap_periodic, size_t save_every, double *traj,
+                              double *utraj, double *cost, long *stop_step, int *stop_reason, double *vend)
+{ /* new: ntraj closed loops of c3control_integrate on the device (c3sc_hip_integrate_host): the policy_sim value function, the
+     opt_sim minimiser and the device model, as c3control_simulate_batch */
+    const char *who = "c3control_integrate_batch";
+    if (c == NULL) return integrate_reject(who, "null control");
+    if (c->dp->model == 0) return integrate_reject(who, "no device model (c3control_set_device_model): host callbacks cannot run on the device");
+    if (c->policy_sim == NULL || c->opt_sim == NULL) return integrate_reject(who, "no implicit policy (c3control_add_policy_sim)");
+    if (c->transform_sim != NULL && !wrap_periodic)
+        return integrate_reject(who, "a state transform is a host callback the device cannot call; pass wrap_periodic = 1 if it only wraps periodic angles");
+    size_t nsub;
+    int rc = integrate_check(who, c->dx, method, dt_int, dt_out, nout, goal, keep, &nsub);
+    if (rc != 0) return rc;
+    if (ntraj == 0) return 0;
+    if (x0 == NULL) return integrate_reject(who, "null x0");
+    if ((traj != NULL || utraj != NULL) && save_every == 0) return integrate_reject(who, "traj / utraj need save_every > 0");
+    if (ntraj > ((size_t)1 << 31)) return integrate_reject(who, "more than 2^31 trajectories");
+    const int brute = c3opt_is_bruteforce(c->opt_sim);
+    if (!brute && c3opt_get_d(c->opt_sim) > C3SC_MAX_DU) return integrate_reject(who, "the box minimiser handles up to C3SC_MAX_DU controls");
+    if (c3opt_get_d(c->opt_sim) != c->du) return integrate_reject(who, "opt_sim's dimension differs from the control dimension");
+    struct ControlParams *cp = control_params_create(c->dx, c->dw, c->dp, c->mca, c->work, c->opt_sim);
+    struct c3sc_hip_ctx *ctx = sync_device_ctx(cp, workspace_get_hip_ctx(c->work), c->policy_sim);
+    control_params_destroy(cp);
+    int32_t *why = stop_reason ? xcalloc(ntraj, sizeof(int32_t)) : NULL;
+    c3sc_hip_ode_args a;
+    memset(&a, 0, sizeof(a));
+    a.n = ntraj;
+    a.d_x0 = x0;
+    a.dt_out = dt_out;
+    a.dt_int = dt_int;
+    a.nout = nout;
+    a.method = ode_method(method);
+    a.wrap_periodic = wrap_periodic;
+    a.box = !brute;
+    a.goal = goal;
+    a.keep = keep;
+    a.save_every = save_every;
+    a.d_traj = traj;
+    a.d_u = utraj;
+    a.d_cost = cost;
+    a.d_stop_step = (int64_t *)stop_step;
+    a.d_stop_reason = why;
+    a.d_vend = vend;
+    rc = c3sc_hip_integrate_host(ctx, &a);
+    if (rc != C3SC_OK) fprintf(stderr, "%s: %s (code %d)\n", who, c3sc_hip_last_error(ctx), rc);
+    else if (why)
+        for (size_t i = 0; i < ntraj; i++) stop_reason[i] = (int)why[i];
+    free(why);
+    return rc;
+}
+
 int c3control_simulate(struct C3Control *c, const double *x0, double dt, size_t nsteps, const double *noise, double *traj,
                        double *utraj)
 { /* new: the closed-loop tail the examples run through cdyn (e.g. lqg2d.c:346-383) as plain Euler(-Maruyama):

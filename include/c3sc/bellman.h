@@ -136,6 +136,28 @@ int c3control_simulate(struct C3Control *, const double *x0, double dt, size_t n
 int c3control_simulate_batch(struct C3Control *, size_t ntraj, const double *x0, double dt, size_t nsteps, uint64_t seed,
                              const double *noise, int wrap_periodic, size_t save_every, double *traj, double *utraj, double *cost,
                              long *exit_step, double *vend);
+/* new: the examples' closed-loop tail without cdyn (integrator_create_controlled + trajectory_step + their goal test, e.g.
+ * dubinscar.c:379-412, perch.c:447-480) for ONE trajectory on the host, over the user's callbacks and c3control_controller
+ * (transform_sim as given): nout outer steps of dt_out, each dt_out / dt_int substeps (an integer to 1e-9 relative; dt_int = 0:
+ * one substep) of method "forward-euler" or "rk4" (cdyn's names; RK4 calls the controller at each of its four stages).  The
+ * discounted cost c' = e^{-beta t} stage(y, u(y)) is integrated as one more ODE component.  Stops are tested at x_0 .. x_nout,
+ * the first that holds wins: 1 outside an absorbing face / 2 inside an obstacle (both pay e^{-beta t} boundcost | obscost),
+ * 3 strictly inside goal = (lo[dx], hi[dx]), 4 outside keep = (lo[dx], hi[dx]) (either may be NULL; +-inf allowed).
+ * traj (nout+1) x dx and utraj nout x du (the control of the first stage of each outer step) may be NULL; after a stop the
+ * state is frozen and the controls are 0.  stop_step = -1 / stop_reason = 0: never stopped.  Returns 0, C3SC_ERR_ARG (with a
+ * message on stderr: method name, dt_out, a non-integer dt_out / dt_int, lo > hi in a box, no policy_sim or host callbacks),
+ * or a callback's non-zero return.  This is the reference c3sc_hip_integrate is tested against. */
+int c3control_integrate(struct C3Control *, const char *method, double dt_int, double dt_out, size_t nout, const double *x0,
+                        const double *goal, const double *keep, double *traj, double *utraj, double *cost, long *stop_step,
+                        int *stop_reason);
+/* new: ntraj such closed loops at once on the GPU (c3sc_hip_integrate_host): policy_sim's value function, opt_sim's minimiser
+ * (BRUTEFORCE list or the box minimiser) and the DEVICE model, as c3control_simulate_batch, with its rejections (no device
+ * model, no policy_sim, a transform_sim without wrap_periodic, sizes) and the checks of c3control_integrate.  Host arrays:
+ * x0 ntraj x dx; traj ntraj x (nout/save_every + 1) x dx and utraj ntraj x ceil(nout/save_every) x du (NULL, or save_every
+ * > 0); cost, stop_step, stop_reason, vend (value of policy_sim at the final state) [ntraj].  Any output may be NULL. */
+int c3control_integrate_batch(struct C3Control *, size_t ntraj, const double *x0, const char *method, double dt_int, double dt_out,
+                              size_t nout, const double *goal, const double *keep, int wrap_periodic, size_t save_every, double *traj,
+                              double *utraj, double *cost, long *stop_step, int *stop_reason, double *vend);
 
 /* ---- solver loops over the own cross driver (valuefunc.h: valuef_interp) ---- */
 #include <stdio.h>

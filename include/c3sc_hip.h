@@ -275,6 +275,61 @@ int c3sc_hip_simulate(c3sc_hip_ctx *ctx, const c3sc_hip_sim_args *args, void *st
 /* the same with HOST arrays in every pointer of args (d_* names notwithstanding): staged through device memory, synchronous.
  * This is what libc3sc.so's c3control_simulate_batch calls. */
 int c3sc_hip_simulate_host(c3sc_hip_ctx *ctx, const c3sc_hip_sim_args *args);
+
+/* c3sc_hip_integrate: deterministic closed loops x' = b(x, pi(x)) of the implicit policy of the uploaded value function, n
+ * trajectories, one GPU lane each -- the examples' cdyn tail (c3control_add_policy_sim + a controlled integrator + a goal test
+ * after every trajectory_step) on the device.  No diffusion (c3sc_hip_simulate is the stochastic path).
+ *   steps        nout outer steps of dt_out, each nsub = dt_out / dt_int integrator substeps of h = dt_int (dt_int = 0: nsub = 1,
+ *                h = dt_out); nsub must be an integer to 1e-9 relative.
+ *   method       C3SC_ODE_FORWARD_EULER: y + h b(y, pi(y)); C3SC_ODE_RK4: classical RK4, the controller evaluated at each of
+ *                the four stage states.
+ *   controller   pi(y) is c3sc_hip_simulate's: y (wrap_periodic: its PERIODIC coordinates mapped into [lb, ub)), the off-grid
+ *                stencil, the candidate list (box = 0) or the control box (box = 1, where the model's kernels serve one);
+ *                u = 0 inside an obstacle.  The drift is evaluated at the unwrapped y.
+ *   cost         one more ODE component c' = e^{-beta t} stage(y, pi(y)), same method and stage controls.  Forward Euler uses
+ *                c3sc_hip_simulate's arithmetic (c + e^{-beta t} stage h, x + b h): with nsub = 1 and no stop boxes its results
+ *                equal c3sc_hip_simulate's with an all-zero d_noise.  An exit pays e^{-beta t_j} (boundcost | obscost)(x_j)
+ *                as c3sc_hip_simulate does; goal and keep-in stops pay nothing.
+ *   stops        tested at every outer step j = 0 .. nout (t_j = j dt_out), the first that holds wins: 1 outside an ABSORB face,
+ *                2 inside an obstacle, 3 inside the goal box (lo < x < hi on every dimension; +-inf allowed), 4 outside the
+ *                keep-in box (x < lo or x > hi on some dimension).  A stopped lane is frozen: state and cost stay, saved
+ *                controls are 0.  d_goal / d_keep: HOST arrays [2*d] = (lo[d], hi[d]) or NULL; lo > hi is an error.
+ *   outputs      any may be NULL: d_cost[n], d_stop_step[n] (-1 = never), d_stop_reason[n] (0 = never), d_xfinal[n*d],
+ *                d_vend[n] (interpolant at the final state, wrapped like the controller's input); with save_every > 0
+ *                d_traj[n][nout/save_every + 1][d] (states at j = 0, s, 2s, ...) and d_u[n][ceil(nout/save_every)][du] (the
+ *                control of the first stage of outer steps j = 0, s, ...).
+ *   launches     a call is cut into launches of at most evals_per_launch controller evaluations per lane (0 = 256), rounded
+ *                to whole substeps (at least one); state, cost and stop fields stay in the context's buffer between them.
+ *                Results do not depend on evals_per_launch or on how a batch is split.
+ * Errors: C3SC_ERR_ARG (state not set, null x0, dt_out <= 0, dt_int < 0 or a non-integer nsub, a bad method, save_every misuse,
+ * inverted stop boxes), C3SC_ERR_UNSUPPORTED (the TABLE model, no integrate instantiation for this model at this padded rank, a
+ * box without one).  Calls on one context must not overlap with each other or with c3sc_hip_simulate (one state buffer).
+ * last_kernel names the k_rollout_ode kernel.  Asynchronous on `stream`. */
+enum { C3SC_ODE_FORWARD_EULER = 0, C3SC_ODE_RK4 = 1 };
+typedef struct c3sc_hip_ode_args {
+    size_t n;                /* trajectories */
+    const double *d_x0;      /* [n*d] initial states */
+    double dt_out;           /* outer step */
+    double dt_int;           /* integrator step (0: dt_out) */
+    size_t nout;             /* outer steps */
+    int method;              /* C3SC_ODE_* */
+    int wrap_periodic;
+    int box;                 /* 0: candidate list (set_controls), 1: control box (set_control_box) */
+    int evals_per_launch;    /* controller evaluations per lane per launch, 0 = 256 */
+    const double *goal;      /* host [2*d] (lo, hi) or NULL */
+    const double *keep;      /* host [2*d] (lo, hi) or NULL */
+    size_t save_every;       /* 0 = none */
+    double *d_traj;          /* [n][nout/save_every + 1][d] or NULL */
+    double *d_u;             /* [n][ceil(nout/save_every)][du] or NULL */
+    double *d_cost;          /* [n] or NULL */
+    int64_t *d_stop_step;    /* [n] or NULL */
+    int32_t *d_stop_reason;  /* [n] or NULL */
+    double *d_vend;          /* [n] or NULL */
+    double *d_xfinal;        /* [n*d] or NULL */
+} c3sc_hip_ode_args;
+int c3sc_hip_integrate(c3sc_hip_ctx *ctx, const c3sc_hip_ode_args *args, void *stream);
+/* the same with HOST arrays in every pointer of args: staged through device memory, synchronous (c3control_integrate_batch) */
+int c3sc_hip_integrate_host(c3sc_hip_ctx *ctx, const c3sc_hip_ode_args *args);
 /* host twin of the rollouts' noise: out[(t*nsteps + k)*dw + j] = the normal of component j at step step0 + k of trajectory
  * traj0 + t under `seed` -- the same bits the device draws (philox.hpp) */
 int c3sc_hip_normals(uint64_t seed, uint64_t traj0, size_t ntraj, uint64_t step0, size_t nsteps, int dw, double *out);
