@@ -193,17 +193,30 @@ static int upload_static(c3sc_hip_ctx *c)
 // (F = r_k r_{k+1}, a few hundred fibers) are latency-bound and take the per-wave kernel.
 static const size_t SMALL_BATCH_FIBERS = 16384;
 
+// every kernel entry a lookup for `model` may use: the compiled-in instantiations and, for a run-time compiled model (id >=
+// C3SC_MODEL_USER) or the model-independent kernels (model 0, which a run-time compile adds where the library lacks them),
+// the entries of rtc.hip
+template <class Fn>
+static void each_entry(int model, Fn &&f)
+{
+    for (const auto &e : kernel_registry()) f(e);
+    if (model == 0 || model >= C3SC_MODEL_USER) {
+        const RtcEntries r = rtc_entries();
+        for (int i = 0; i < r.n; i++) f(*r.e[i]);
+    }
+}
+
 static const KernelEntry *find_kernel(int model, int d, int rank_needed, int N, int variant, int k, size_t F = (size_t)-1,
                                       const std::vector<const KernelEntry *> *skip = nullptr)
 {
     const KernelEntry *best = nullptr;
     const bool small = (variant == C3SC_VARIANT_AUTO) && F < SMALL_BATCH_FIBERS;
-    for (const auto &e : kernel_registry()) {
-        if (!is_fiber_variant(e.variant)) continue;
-        if (e.model != model || e.d != d || e.rp < rank_needed || e.max_n < N) continue;
-        if (skip && std::find(skip->begin(), skip->end(), &e) != skip->end()) continue;
-        if (e.k >= 0 && e.k != k) continue;
-        if (variant != C3SC_VARIANT_AUTO && e.variant != variant) continue;
+    each_entry(model, [&](const KernelEntry &e) {
+        if (!is_fiber_variant(e.variant)) return;
+        if (e.model != model || e.d != d || e.rp < rank_needed || e.max_n < N) return;
+        if (skip && std::find(skip->begin(), skip->end(), &e) != skip->end()) return;
+        if (e.k >= 0 && e.k != k) return;
+        if (variant != C3SC_VARIANT_AUTO && e.variant != variant) return;
         auto pref = [small](int v) {
             if (small) return v == C3SC_VARIANT_FIBER_PER_WAVE ? 0 : (v == C3SC_VARIANT_FIBER_PAIR ? 1 : (v == C3SC_VARIANT_FIBER_QUAD ? 2 : 3));
             return v == C3SC_VARIANT_FIBER_PAIR ? 0 : (v == C3SC_VARIANT_FIBER_QUAD ? 1 : (v == C3SC_VARIANT_FIBER_PER_WAVE ? 2 : 3));
@@ -211,7 +224,7 @@ static const KernelEntry *find_kernel(int model, int d, int rank_needed, int N, 
         if (!best || e.rp < best->rp || (e.rp == best->rp && pref(e.variant) < pref(best->variant)) ||
             (e.rp == best->rp && e.variant == best->variant && e.npl < best->npl))
             best = &e;
-    }
+    });
     return best;
 }
 
@@ -220,15 +233,18 @@ static int pick_rp(int d, int maxrank, int model, int variant)
   // is forced (its padded ranks may differ from the other kernels': the quad kernel wants multiples of 4)
     int rp = 0;
     if (variant != C3SC_VARIANT_AUTO)
-        for (const auto &e : kernel_registry())
+        each_entry(model, [&](const KernelEntry &e) {
             if (is_fiber_variant(e.variant) && e.d == d && e.variant == variant && (model == 0 || e.model == model) && e.rp >= maxrank && (rp == 0 || e.rp < rp)) rp = e.rp;
+        });
     if (rp) return rp;
     if (model != 0) // the padded classes compiled for THIS model (another model of the same dimension may offer others)
-        for (const auto &e : kernel_registry())
+        each_entry(model, [&](const KernelEntry &e) {
             if (is_fiber_variant(e.variant) && e.d == d && e.model == model && e.rp >= maxrank && (rp == 0 || e.rp < rp)) rp = e.rp;
+        });
     if (rp) return rp;
-    for (const auto &e : kernel_registry())
+    each_entry(model, [&](const KernelEntry &e) {
         if (is_fiber_variant(e.variant) && e.d == d && e.rp >= maxrank && (rp == 0 || e.rp < rp)) rp = e.rp;
+    });
     return rp;
 }
 
@@ -244,8 +260,9 @@ extern "C" {
 int c3sc_hip_max_rank(int model, int d)
 { // largest FT rank any compiled kernel of this (model, state dimension) serves; 0 = none
     int rp = 0;
-    for (const auto &e : kernel_registry())
+    each_entry(model, [&](const KernelEntry &e) {
         if (e.model == model && e.d == d && e.rp > rp) rp = e.rp;
+    });
     return rp;
 }
 
@@ -357,6 +374,7 @@ int c3sc_hip_set_mca(c3sc_hip_ctx *c, double h2, const double *t, double discoun
 int c3sc_hip_set_model(c3sc_hip_ctx *c, int model, const double *params, int nparams)
 {
     if (!c || model <= 0 || nparams < 0 || nparams > C3SC_MAX_PARAMS) return fail(c, C3SC_ERR_ARG, "set_model: bad arguments");
+    if (model >= C3SC_MODEL_USER && !rtc_model_known(model)) return fail(c, C3SC_ERR_ARG, "set_model: no run-time model has this id");
     c->model = model;
     std::memset(c->prm, 0, sizeof(c->prm));
     for (int i = 0; i < nparams; i++) c->prm[i] = params[i];
@@ -643,7 +661,7 @@ static int launch_bellman(c3sc_hip_ctx *c, int k, size_t F, const int32_t *d_idx
         }
         c->last_kernel = e->name;
         arm_memo(c, e, A);
-        he = e->fn(A, io);
+        he = launch_entry(*e, A, io);
         if (he != hipErrorOutOfMemory && he != hipErrorNotSupported) break;
         c->memo.applied = false;
         if (getenv("C3SC_VERBOSE")) fprintf(stderr, "c3sc: %s declined (%s), trying the next instantiation\n", e->name, hipGetErrorName(he));
@@ -746,7 +764,7 @@ static int launch_box(c3sc_hip_ctx *c, int k, size_t F, const int32_t *d_idx, co
     LaunchIO io{c->arena, d_idx, d_out, nullptr, d_absorbed, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream};
     g_launches++;
     c->status_cache_valid = false;
-    const hipError_t he = e->fn(A, io);
+    const hipError_t he = launch_entry(*e, A, io);
     if (he == hipErrorNotSupported) return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_box: no box-minimiser instantiation for this model");
     HIPCHK(c, he);
     return C3SC_OK;
@@ -854,7 +872,7 @@ static int launch_tables(c3sc_hip_ctx *c, int k, size_t F, const int32_t *d_idx,
     LaunchIO io{c->arena, d_idx, d_out, d_uidx, d_absorbed, nullptr, nullptr, d_tables, d_costs2, (hipStream_t)stream};
     g_launches++;
     c->status_cache_valid = false;
-    HIPCHK(c, e->fn(A, io));
+    HIPCHK(c, launch_entry(*e, A, io));
     return C3SC_OK;
 }
 
@@ -939,7 +957,7 @@ int c3sc_hip_stencil_fibers_nb(c3sc_hip_ctx *c, int k, size_t F, const int32_t *
     LaunchIO io{c->arena, d_idx, d_costs, nullptr, d_absorbed, d_nb_fixed, d_nb_vary, nullptr, nullptr, (hipStream_t)stream};
     g_launches++;
     c->status_cache_valid = false;
-    HIPCHK(c, e->fn(A, io));
+    HIPCHK(c, launch_entry(*e, A, io));
     return C3SC_OK;
 }
 
@@ -1125,9 +1143,11 @@ static const size_t SIM_MAX_TRAJ = (size_t)1 << 31;
 
 static const KernelEntry *find_sim_kernel(int variant, int model, int d, int rp)
 {
-    for (const auto &e : kernel_registry())
-        if (e.variant == variant && e.model == model && e.d == d && e.rp == rp) return &e;
-    return nullptr;
+    const KernelEntry *hit = nullptr;
+    each_entry(model, [&](const KernelEntry &e) {
+        if (!hit && e.variant == variant && e.model == model && e.d == d && e.rp == rp) hit = &e;
+    });
+    return hit;
 }
 
 static int check_bounds_set(c3sc_hip_ctx *c, const char *what)
@@ -1161,7 +1181,7 @@ int c3sc_hip_stencil_points(c3sc_hip_ctx *c, size_t n, const double *d_x, double
     c->last_kernel = e->name;
     g_launches++;
     c->status_cache_valid = false;
-    HIPCHK(c, e->fn(A, io));
+    HIPCHK(c, launch_entry(*e, A, io));
     return C3SC_OK;
 }
 
@@ -1235,7 +1255,7 @@ int c3sc_hip_simulate(c3sc_hip_ctx *c, const c3sc_hip_sim_args *a, void *stream)
         S.s1 = (int)std::min<long long>((long long)s0 + chunk, (long long)a->nsteps);
         LaunchIO io{c->arena, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream, &S};
         g_launches++;
-        const hipError_t he = e->fn(A, io);
+        const hipError_t he = launch_entry(*e, A, io);
         if (he == hipErrorNotSupported) return fail(c, C3SC_ERR_UNSUPPORTED, "simulate: this rollout kernel has no box minimiser");
         HIPCHK(c, he);
         s0 = S.s1;
@@ -1403,7 +1423,7 @@ int c3sc_hip_integrate(c3sc_hip_ctx *c, const c3sc_hip_ode_args *a, void *stream
         S.k1 = std::min(k0 + chunk, ktot);
         LaunchIO io{c->arena, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream, &S};
         g_launches++;
-        const hipError_t he = e->fn(A, io);
+        const hipError_t he = launch_entry(*e, A, io);
         if (he == hipErrorNotSupported) return fail(c, C3SC_ERR_UNSUPPORTED, "integrate: this integrate kernel has no box minimiser");
         HIPCHK(c, he);
         k0 = S.k1;

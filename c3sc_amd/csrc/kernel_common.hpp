@@ -1,9 +1,13 @@
 // kernel_common.hpp -- shared device code of the Bellman-backup kernels (gfx950, wave64).
 // Citations are relative to the reference tree (goroda/c3sc).
 #pragma once
+#ifdef __HIPCC_RTC__
+#include "rtc_prelude.hpp"
+#else
 #include <type_traits>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#endif
 
 #include "../../include/c3sc_hip.h"
 

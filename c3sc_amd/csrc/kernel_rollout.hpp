@@ -13,9 +13,11 @@
 // lane-distributed: the candidate table lives in LDS (CandLds, wave-uniform addresses), not in VGPR lanes read by v_readlane.
 // tests/test_rollout_isa.py checks the ISA (global loads only; no scratch at the benchmark's ranks).
 #pragma once
+#ifndef __HIPCC_RTC__
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
+#endif
 
 #include "kernel_common.hpp"
 #include "model_tables.hpp"
@@ -386,19 +388,25 @@ __global__ void __launch_bounds__(256) k_rollout(const KArgs A, const SimK S, co
     if (st) atomicOr(A.status, st);
 }
 
+#ifndef __HIPCC_RTC__
+// Launch geometry of k_rollout / k_rollout_ode (one lane per trajectory), shared with the module launcher of run-time compiled
+// models (rtc.hip): dynamic LDS holds the candidate table (cand_doubles = CandLds<Model>::doubles(ncand)); the box minimiser
+// reads none
+inline size_t rollout_shmem(int cmode, size_t cand_doubles) { return (cmode == 0 ? cand_doubles : 1) * sizeof(double); }
+inline unsigned rollout_grid(long n) { return (unsigned)((n + 255) / 256); }
+
 template <int MID, class Model, int RP, bool BOX>
 hipError_t launch_rollout(const KArgs &A, const LaunchIO &io)
 {
     if (A.cmode == 1 && !BOX) return hipErrorNotSupported;
     const SimK &S = *(const SimK *)io.sim;
-    const size_t shmem = (A.cmode == 0 ? (size_t)CandLds<Model>::doubles(A.ncand) : 1) * sizeof(double);
+    const size_t shmem = rollout_shmem(A.cmode, (size_t)CandLds<Model>::doubles(A.ncand));
     auto kern = k_rollout<MID, Model, RP, BOX>;
     static LaunchCache cache;
     int blocks_per_cu = 1, num_cu = 256;
     hipError_t e = cache.prepare((const void *)kern, 256, shmem, blocks_per_cu, num_cu);
     if (e != hipSuccess) return e;
-    const long grid = (S.n + 255) / 256;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), shmem, io.stream, A, S, io.ro);
+    hipLaunchKernelGGL(kern, dim3(rollout_grid(S.n)), dim3(256), shmem, io.stream, A, S, io.ro);
     return hipGetLastError();
 }
 
@@ -406,8 +414,7 @@ template <int D, int RP>
 hipError_t launch_stencil_points(const KArgs &A, const LaunchIO &io)
 {
     const SimK &S = *(const SimK *)io.sim;
-    const long grid = (S.n + 255) / 256;
-    hipLaunchKernelGGL((k_stencil_points<D, RP>), dim3((unsigned)grid), dim3(256), 0, io.stream, A, S, io.ro);
+    hipLaunchKernelGGL((k_stencil_points<D, RP>), dim3(rollout_grid(S.n)), dim3(256), 0, io.stream, A, S, io.ro);
     return hipGetLastError();
 }
 
@@ -425,5 +432,6 @@ hipError_t launch_stencil_points(const KArgs &A, const LaunchIO &io)
     static Registrar C3SC_CAT(reg_stp_, __COUNTER__)(KernelEntry{                                             \
         0, DIM, RP, 0, VARIANT_STENCIL_POINTS, 0, -1, &launch_stencil_points<DIM, RP>,                           \
         "k_stencil_points<" #DIM "," #RP ">"});
+#endif
 
 } // namespace c3sc

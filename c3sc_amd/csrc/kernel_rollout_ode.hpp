@@ -216,19 +216,19 @@ __global__ void __launch_bounds__(256) k_rollout_ode(const KArgs A, const OdeK S
     if (st) atomicOr(A.status, st);
 }
 
+#ifndef __HIPCC_RTC__
 template <int MID, class Model, int RP, bool BOX>
 hipError_t launch_rollout_ode(const KArgs &A, const LaunchIO &io)
 {
     if (A.cmode == 1 && !BOX) return hipErrorNotSupported;
     const OdeK &S = *(const OdeK *)io.sim;
-    const size_t shmem = (A.cmode == 0 ? (size_t)CandLds<Model>::doubles(A.ncand) : 1) * sizeof(double);
+    const size_t shmem = rollout_shmem(A.cmode, (size_t)CandLds<Model>::doubles(A.ncand));
     auto kern = k_rollout_ode<MID, Model, RP, BOX>;
     static LaunchCache cache;
     int blocks_per_cu = 1, num_cu = 256;
     hipError_t e = cache.prepare((const void *)kern, 256, shmem, blocks_per_cu, num_cu);
     if (e != hipSuccess) return e;
-    const long grid = (S.n + 255) / 256;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), shmem, io.stream, A, S, io.ro);
+    hipLaunchKernelGGL(kern, dim3(rollout_grid(S.n)), dim3(256), shmem, io.stream, A, S, io.ro);
     return hipGetLastError();
 }
 
@@ -237,5 +237,6 @@ hipError_t launch_rollout_ode(const KArgs &A, const LaunchIO &io)
     static Registrar C3SC_CAT(reg_rode_, __COUNTER__)(KernelEntry{                                                    \
         MODEL_ID, __VA_ARGS__::D, RP, 0, VARIANT_ROLLOUT_ODE, 0, -1, &launch_rollout_ode<MODEL_ID, __VA_ARGS__, RP, BOX>, \
         "k_rollout_ode<" #__VA_ARGS__ "," #RP ">"});
+#endif
 
 } // namespace c3sc

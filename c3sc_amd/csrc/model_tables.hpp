@@ -3,7 +3,9 @@
 // the rollouts of c3sc_hip_simulate need them at arbitrary states and evaluate the SAME expressions on the device (device
 // libm: within about an ulp of the host's).
 #pragma once
+#ifndef __HIPCC_RTC__
 #include <hip/hip_runtime.h>
+#endif
 
 #include "../../include/c3sc_hip.h"
 

@@ -25,7 +25,9 @@
 //   stage(prm, x, u)            stage cost
 //   boundcost(prm, x), obscost(prm, x)
 #pragma once
+#ifndef __HIPCC_RTC__
 #include <hip/hip_runtime.h>
+#endif
 
 namespace c3sc {
 

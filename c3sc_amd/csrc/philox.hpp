@@ -10,9 +10,13 @@
 // polynomials, every multiply-add an explicit fma, contraction off) so that host and device produce the SAME bits and the
 // noise costs no data-dependent branch.  Accuracy: a few ulp, far below what a noise sample needs.
 #pragma once
+#ifdef __HIPCC_RTC__
+#include "rtc_prelude.hpp"
+#else
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
+#endif
 
 namespace c3sc {
 

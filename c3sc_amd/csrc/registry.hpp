@@ -1,14 +1,17 @@
 // registry.hpp -- table of compiled kernel instantiations (model, dim, padded rank, nodes per lane).
 #pragma once
+#ifndef __HIPCC_RTC__
 #include <hip/hip_runtime.h>
 
 #include <mutex>
 #include <vector>
+#endif
 
 #include "kernel_common.hpp"
 
 namespace c3sc {
 
+#ifndef __HIPCC_RTC__ // the launch side is host code; run-time compiled device code (rtc.hip) sees only the variant ids below
 struct LaunchIO {
     const double *ro;
     const int32_t *idx;
@@ -22,11 +25,15 @@ struct LaunchIO {
     hipStream_t stream;
     const void *sim = nullptr; // rollout / off-grid stencil kernels only: their SimK argument block (kernel_rollout.hpp)
 };
+#endif
 
 // KernelEntry::variant of the rollout, off-grid stencil and integrate kernels (c3sc_hip_simulate / c3sc_hip_stencil_points /
 // c3sc_hip_integrate): not Bellman-operator kernels, so the fiber paths never select them (find_kernel, pick_rp)
 constexpr int VARIANT_ROLLOUT = 100, VARIANT_STENCIL_POINTS = 101, VARIANT_ROLLOUT_ODE = 102;
 __host__ __device__ constexpr bool is_fiber_variant(int v) { return v < VARIANT_ROLLOUT; }
+
+#ifndef __HIPCC_RTC__
+struct RtcLaunch; // rtc.hip: a kernel of a run-time compiled model (module function)
 
 typedef hipError_t (*launch_fn)(const KArgs &A, const LaunchIO &io);
 
@@ -40,8 +47,11 @@ struct KernelEntry {
     int k;       // dim_vary this instantiation is compiled for, -1 = any
     launch_fn fn;
     const char *name;
+    const RtcLaunch *rtc = nullptr; // set instead of fn for the kernels of a run-time compiled model (rtc_launch)
 };
 
+// the compiled-in instantiations; the kernels of run-time compiled models (ids >= C3SC_MODEL_USER) are kept apart, in
+// rtc.hip (rtc_entries), because this vector is read without a lock and find_kernel hands out pointers into it
 std::vector<KernelEntry> &kernel_registry();
 
 // What a launcher has to find out once per (kernel, device, dynamic-LDS size): the opt-in to more than 64 KiB of dynamic
@@ -87,5 +97,17 @@ struct LaunchCache {
 struct Registrar {
     explicit Registrar(const KernelEntry &e) { kernel_registry().push_back(e); }
 };
+
+// kernel entries of the run-time compiled models (rtc.hip): a snapshot that stays valid (entries are never removed or moved)
+struct RtcEntries {
+    const KernelEntry *const *e;
+    int n;
+};
+RtcEntries rtc_entries();
+// launch an entry of either kind
+hipError_t rtc_launch(const KernelEntry &e, const KArgs &A, const LaunchIO &io);
+bool rtc_model_known(int model); // an id c3sc_hip_model_compile returned
+inline hipError_t launch_entry(const KernelEntry &e, const KArgs &A, const LaunchIO &io) { return e.rtc ? rtc_launch(e, A, io) : e.fn(A, io); }
+#endif
 
 } // namespace c3sc

@@ -34,6 +34,7 @@ EXPORTS = [
     "c3sc_hip_debug_read", "c3sc_hip_launch_count", "c3sc_hip_timer_start", "c3sc_hip_timer_stop", "c3sc_hip_peak_fma_f64", "c3sc_hip_peak_mfma_f64",
     "c3sc_hip_set_interp", "c3sc_hip_stencil_points", "c3sc_hip_simulate", "c3sc_hip_simulate_host", "c3sc_hip_normals",
     "c3sc_hip_integrate", "c3sc_hip_integrate_host",
+    "c3sc_hip_model_compile", "c3sc_hip_model_code_object", "c3sc_hip_model_log",
 ]
 
 class SimArgs(C.Structure):
@@ -57,6 +58,15 @@ class OdeArgs(C.Structure):
                 ("d_u", C.c_void_p), ("d_cost", C.c_void_p), ("d_stop_step", C.c_void_p), ("d_stop_reason", C.c_void_p),
                 ("d_vend", C.c_void_p), ("d_xfinal", C.c_void_p)]
 
+
+class ModelSpec(C.Structure):
+    """struct c3sc_hip_model_spec (include/c3sc_hip.h)"""
+    _fields_ = [("source", C.c_char_p), ("name", C.c_char_p), ("d", C.c_int), ("du", C.c_int), ("udep_mask", C.c_uint),
+                ("uconst_mask", C.c_uint), ("stage_udep", C.c_int), ("box", C.c_int), ("nranks", C.c_int),
+                ("ranks", C.POINTER(C.c_int))]
+
+
+MODEL_USER = 1000  # C3SC_MODEL_USER: first id of the run-time compiled models
 
 VARIANT_AUTO, VARIANT_FIBER_PER_WAVE, VARIANT_FIBER_PER_LANE, VARIANT_FIBER_PAIR, VARIANT_FIBER_QUAD = 0, 1, 2, 3, 4
 
@@ -114,6 +124,10 @@ def load_library():
         L.c3sc_hip_integrate.argtypes = [C.c_void_p, C.POINTER(OdeArgs), C.c_void_p]
         L.c3sc_hip_integrate_host.argtypes = [C.c_void_p, C.POINTER(OdeArgs)]
         L.c3sc_hip_normals.argtypes = [C.c_uint64, C.c_uint64, C.c_size_t, C.c_uint64, C.c_size_t, C.c_int, c_double_p]
+        L.c3sc_hip_model_compile.argtypes = [C.POINTER(ModelSpec), c_int_p]
+        L.c3sc_hip_model_code_object.argtypes = [C.POINTER(ModelSpec), C.c_void_p, c_size_p]
+        L.c3sc_hip_model_log.restype = C.c_char_p
+        L.c3sc_hip_model_log.argtypes = []
         _LIB = L
     return _LIB
 
@@ -127,6 +141,53 @@ def normals(seed: int, traj0: int, ntraj: int, step0: int, nsteps: int, dw: int)
     if rc != 0:
         raise C3scHipError(f"c3sc_hip_normals failed (code {rc})")
     return out
+
+
+def _model_spec(source, d, du, ranks, box, udep_mask, uconst_mask, stage_udep, name):
+    rk = (C.c_int * max(1, len(ranks)))(*ranks)
+    spec = ModelSpec(source.encode(), name.encode() if name is not None else None, int(d), int(du), int(udep_mask),
+                     int(uconst_mask), 1 if stage_udep else 0, 1 if box else 0, len(ranks), rk if len(ranks) else None)
+    spec._keep = rk
+    return spec
+
+
+def _model_fail(rc, what):
+    log = load_library().c3sc_hip_model_log().decode(errors="replace")
+    raise C3scHipError(f"{what} failed (code {rc}): {log}", rc)
+
+
+def compile_model(source: str, d: int, du: int, ranks=(4, 8), box: bool = False, udep_mask: int = 0, uconst_mask: int = 0,
+                  stage_udep: bool = True, name: Optional[str] = None) -> int:
+    """Compile a device model from source (c3sc_hip_model_compile, include/c3sc_hip.h states the source contract) and return
+    its model id (>= MODEL_USER), usable wherever a built-in model id is.  No GPU is needed.  Raises C3scHipError with the
+    compiler's log on failure; the error code is args[1]."""
+    L = load_library()
+    spec = _model_spec(source, d, du, tuple(ranks), box, udep_mask, uconst_mask, stage_udep, name)
+    mid = C.c_int(0)
+    rc = L.c3sc_hip_model_compile(C.byref(spec), C.byref(mid))
+    if rc != 0:
+        _model_fail(rc, "c3sc_hip_model_compile")
+    return mid.value
+
+
+def code_object(source: str, d: int, du: int, ranks=(4, 8), box: bool = False, udep_mask: int = 0, uconst_mask: int = 0,
+                stage_udep: bool = True, name: Optional[str] = None) -> bytes:
+    """The gfx950 code object of this spec (c3sc_hip_model_code_object): the loaded one if compile_model already compiled the
+    spec, otherwise what compile_model would build now (its id and default name are in the kernel names), compiled and not
+    registered."""
+    L = load_library()
+    spec = _model_spec(source, d, du, tuple(ranks), box, udep_mask, uconst_mask, stage_udep, name)
+    cap = 16 << 20  # one compile when the code object fits; a larger one is compiled again into a buffer of its size
+    for _ in range(2):
+        buf = C.create_string_buffer(cap)
+        size = C.c_size_t(cap)
+        rc = L.c3sc_hip_model_code_object(C.byref(spec), buf, C.byref(size))
+        if rc == 0:
+            return buf.raw[:size.value]
+        if size.value <= cap:
+            break
+        cap = size.value
+    _model_fail(rc, "c3sc_hip_model_code_object")
 
 
 def _f64(a):

@@ -24,8 +24,10 @@
 #ifndef C3SC_HIP_H
 #define C3SC_HIP_H
 
+#ifndef __HIPCC_RTC__ /* run-time compiled device code (hipRTC) has no C headers: csrc/rtc_prelude.hpp */
 #include <stddef.h>
 #include <stdint.h>
+#endif
 
 #ifdef __cplusplus
 extern "C" {
@@ -60,7 +62,8 @@ enum {
     C3SC_MODEL_TPROB3D = 7,  /* the reference tests' 3-D problem: test/transition_prob/tprob_test.c f3 :223-251, s2, stagecost3d */
     C3SC_MODEL_SKID5D = 9,   /* examples/skidding5d/scar.c:39-176: 5-D skidding car (x, y, orientation, yaw rate, lateral speed), steering u */
     C3SC_MODEL_COTHRUST6D = 10, /* examples/cothrust2/copterposethrust.c:40-222: quadcopter position + velocity, controls (thrust, roll, pitch) */
-    C3SC_MODEL_TABLE = 100   /* host-evaluated callbacks (c3sc_hip_bellman_fibers_tables); not set with set_model */
+    C3SC_MODEL_TABLE = 100,  /* host-evaluated callbacks (c3sc_hip_bellman_fibers_tables); not set with set_model */
+    C3SC_MODEL_USER = 1000   /* first id of the run-time compiled models (c3sc_hip_model_compile) */
 };
 
 /* status bits accumulated by the kernels (c3sc_hip_get_status) */
@@ -405,6 +408,51 @@ int c3sc_hip_comm_rank(const c3sc_hip_comm *comm);
 int c3sc_hip_comm_allgather(c3sc_hip_comm *comm, const double *d_send, double *d_recv, size_t count, void *stream);
 int c3sc_hip_cross_set_comm(c3sc_hip_ctx *ctx, c3sc_hip_comm *comm);
 int c3sc_hip_comm_exchange(double *out, size_t F, size_t N, size_t lo, size_t hi, void *comm);
+
+/* ---- run-time compiled device models: a user's own dynamics on every device path
+ *
+ * c3sc_hip_model_compile compiles the device source of a model with hipRTC (loaded at first use) and returns a model id
+ * (>= C3SC_MODEL_USER) that c3sc_hip_set_model, the Bellman / box / simulate / integrate calls and the reference API's
+ * c3control_set_device_model accept like a built-in id.  No GPU is needed to compile: the code object is loaded on each
+ * device at its first launch there.  The source defines, for x[C3SC_D], u[C3SC_DU] and prm = the C3SC_MAX_PARAMS values of
+ * c3sc_hip_set_model (C3SC_D and C3SC_DU are defined for it; the library wraps it in a namespace of its own):
+ *
+ *   __device__ void   drift    (const double *prm, const double *x, const double *u, double *b);  b[C3SC_D]
+ *   __device__ void   sigma    (const double *prm, const double *x, const double *u, double *s);  diagonal diffusion, s[C3SC_D]
+ *   __device__ double stage    (const double *prm, const double *x, const double *u);
+ *   __device__ double boundcost(const double *prm, const double *x);
+ *   __device__ double obscost  (const double *prm, const double *x);
+ *
+ * The device libm (sin, cos, exp, ...) may be used.  Unlike the built-in models, whose transcendentals are host tables, these
+ * run on the device and differ from glibc's by about an ulp.  No #include is available to the source.
+ *   udep_mask    dims whose drift / diffusion read u (0 = all); uconst_mask: those of them that read nothing else (0 = none):
+ *                their rates are constants of the candidate.  stage_udep: the stage cost reads u.  Wrong masks give wrong values.
+ *   box          also compile the box-minimiser (continuous controls) kernels
+ *   ranks        padded FT ranks to compile, each in {4, 8, 12, 16, 20} (NULL / 0 = {4, 8}); a value function of higher
+ *                rank, and the fiber-pair / fiber-quad variants, give C3SC_ERR_UNSUPPORTED at use
+ * Compiled per rank: the fiber-per-wave Bellman kernels (1 and 2 nodes per lane: N <= 128), k_rollout, k_rollout_ode, and
+ * the model-independent stencil kernels of a (d, rank) the library lacks.  A compile takes seconds; the same spec compiled
+ * again returns the same id.  Compiles are serialised process-wide; models are never unloaded.
+ * Errors: C3SC_ERR_ARG (bad d / du / masks / ranks, a compile error: c3sc_hip_model_log has the compiler's message with the
+ * source's line), C3SC_ERR_UNSUPPORTED (hipRTC missing).  c3sc_hip_model_code_object copies the gfx950 code object (buf NULL:
+ * *size receives its size; otherwise *size is the capacity of buf on entry and the size on return): for a spec already
+ * compiled, the one its model loads; otherwise it compiles (nothing is registered or kept) what c3sc_hip_model_compile would
+ * build now -- the id and default name it would assign appear in the kernel names, so a compile of another model in between
+ * changes them.  Each call without a compiled model compiles again. */
+typedef struct c3sc_hip_model_spec {
+    const char *source;
+    const char *name;        /* [A-Za-z0-9_.-]{1,48}: appears in c3sc_hip_last_kernel; NULL = "model<id>" */
+    int d, du;               /* 2..10, 1..C3SC_MAX_DU */
+    unsigned udep_mask, uconst_mask;
+    int stage_udep;
+    int box;
+    int nranks;
+    const int *ranks;
+} c3sc_hip_model_spec;
+int c3sc_hip_model_compile(const c3sc_hip_model_spec *spec, int *model_id);
+int c3sc_hip_model_code_object(const c3sc_hip_model_spec *spec, void *buf, size_t *size);
+/* the compiler's log / the reason of the last failed model compile on this thread ("" if none) */
+const char *c3sc_hip_model_log(void);
 
 int c3sc_hip_sync(c3sc_hip_ctx *ctx, void *stream);
 int c3sc_hip_get_status(c3sc_hip_ctx *ctx, unsigned *flags, int clear);
