@@ -255,6 +255,16 @@ static bool zero_copy_batch(size_t bytes);
 static size_t align256(size_t x);
 static int fill_args(c3sc_hip_ctx *c, int k, size_t F, KArgs &A, bool need_model);
 
+// game mode is served by the game kernels of the model set now (set_model may have replaced the model set_game checked)
+static int check_game_model(c3sc_hip_ctx *c, const char *what)
+{
+    int du = 0;
+    bool game = false;
+    if (c->game_gsz > 0 && !(c->model >= C3SC_MODEL_USER && rtc_model_info(c->model, du, game) && game && du == c->du))
+        return fail(c, C3SC_ERR_UNSUPPORTED, what);
+    return C3SC_OK;
+}
+
 extern "C" {
 
 int c3sc_hip_max_rank(int model, int d)
@@ -389,6 +399,44 @@ int c3sc_hip_set_controls(c3sc_hip_ctx *c, int ncand, int du, const double *cand
     c->du = du;
     c->cands.assign(cands, cands + (size_t)ncand * du);
     c->static_dirty = true;
+    c->game_gsz = c->game_ngrp = c->game_order = 0;
+    return C3SC_OK;
+}
+
+int c3sc_hip_set_game(c3sc_hip_ctx *c, int du_min, int nu, const double *U, int nw, const double *W, int order)
+{
+    if (!c) return C3SC_ERR_ARG;
+    if (nu == 0) { // clear: the product list stays as a plain candidate list
+        c->game_gsz = c->game_ngrp = c->game_order = 0;
+        return C3SC_OK;
+    }
+    if (order != C3SC_GAME_MINMAX && order != C3SC_GAME_MAXMIN) return fail(c, C3SC_ERR_ARG, "set_game: order must be C3SC_GAME_MINMAX or C3SC_GAME_MAXMIN");
+    if (c->model == 0) return fail(c, C3SC_ERR_ARG, "set_game: set_model first");
+    if (c->model == C3SC_MODEL_TABLE) return fail(c, C3SC_ERR_UNSUPPORTED, "set_game: the TABLE model has no game kernels");
+    int mdu = 0;
+    bool has_game = false;
+    if (c->model < C3SC_MODEL_USER || !rtc_model_info(c->model, mdu, has_game))
+        return fail(c, C3SC_ERR_UNSUPPORTED, "set_game: games need a run-time compiled model (c3sc_hip_model_compile_ex with game = 1)");
+    if (!has_game) return fail(c, C3SC_ERR_UNSUPPORTED, "set_game: this model was compiled without game kernels (c3sc_hip_model_compile_ex, game = 1)");
+    if (nu < 0 || nw < 1 || du_min < 1 || du_min >= mdu || !U || !W)
+        return fail(c, C3SC_ERR_ARG, "set_game: du_min + du_max must equal the model's du, each at least 1, with nu, nw >= 1 and both lists given");
+    if ((long long)nu * nw > (1ll << 24)) return fail(c, C3SC_ERR_ARG, "set_game: nu * nw too large");
+    const int dmax = mdu - du_min, ncand = nu * nw;
+    std::vector<double> cands((size_t)ncand * mdu);
+    for (int iu = 0; iu < nu; iu++)
+        for (int iw = 0; iw < nw; iw++) { // u-major (MINMAX: groups are u) or w-major (MAXMIN: groups are w)
+            const size_t p = order == C3SC_GAME_MINMAX ? (size_t)iu * nw + iw : (size_t)iw * nu + iu;
+            double *row = cands.data() + p * mdu;
+            for (int i = 0; i < du_min; i++) row[i] = U[(size_t)iu * du_min + i];
+            for (int i = 0; i < dmax; i++) row[du_min + i] = W[(size_t)iw * dmax + i];
+        }
+    c->ncand = ncand;
+    c->du = mdu;
+    c->cands.swap(cands);
+    c->static_dirty = true;
+    c->game_order = order;
+    c->game_gsz = order == C3SC_GAME_MINMAX ? nw : nu;
+    c->game_ngrp = order == C3SC_GAME_MINMAX ? nu : nw;
     return C3SC_OK;
 }
 
@@ -614,6 +662,9 @@ static int fill_args(c3sc_hip_ctx *c, int k, size_t F, KArgs &A, bool need_model
     for (int i = 0; i < 2 * c->d; i++) A.t[i] = c->t[i];
     for (int i = 0; i < C3SC_MAX_PARAMS; i++) A.prm[i] = c->prm[i];
     A.status = c->d_status;
+    A.game_gsz = c->game_gsz; // 0 unless c3sc_hip_set_game: read by the game instantiations only
+    A.game_ngrp = c->game_ngrp;
+    A.game_order = c->game_order;
     { // ablation switches of the diagnostic build (make STAMPS=1); read once
         static const int dbg_env = [] { const char *e = getenv("C3SC_DBG"); return e ? atoi(e) : 0; }();
         A.dbg = dbg_env;
@@ -642,6 +693,14 @@ static int launch_bellman(c3sc_hip_ctx *c, int k, size_t F, const int32_t *d_idx
     KArgs A;
     int rc = fill_args(c, k, F, A, true);
     if (rc != C3SC_OK) return rc;
+    int variant = c->variant;
+    if (c->game_gsz > 0) { // only the per-wave kernel has a game form (AUTO picks it)
+        rc = check_game_model(c, "bellman_fibers: game mode needs a model compiled with game kernels of the game's du");
+        if (rc != C3SC_OK) return rc;
+        if (variant != C3SC_VARIANT_AUTO && variant != C3SC_VARIANT_FIBER_PER_WAVE)
+            return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers: game mode runs on the fiber-per-wave kernel only (the pair and quad variants have no game form)");
+        variant = C3SC_VARIANT_FIBER_PER_WAVE;
+    }
     if (F == 0) return C3SC_OK;
     if (!d_idx || !d_out) return fail(c, C3SC_ERR_ARG, "bellman_fibers: null buffer");
     A.forced = d_policy;
@@ -652,7 +711,7 @@ static int launch_bellman(c3sc_hip_ctx *c, int k, size_t F, const int32_t *d_idx
     std::vector<const KernelEntry *> declined;
     hipError_t he = hipSuccess;
     for (;;) {
-        const KernelEntry *e = find_kernel(c->model, c->d, c->rp, A.N, c->variant, k, F, &declined);
+        const KernelEntry *e = find_kernel(c->model, c->d, c->rp, A.N, variant, k, F, &declined);
         if (!e || e->rp != c->rp) {
             if (declined.empty()) return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers: no kernel instantiation for (model, dim, rank, N)");
             return fail(c, C3SC_ERR_UNSUPPORTED, he == hipErrorOutOfMemory
@@ -744,6 +803,7 @@ static int launch_box(c3sc_hip_ctx *c, int k, size_t F, const int32_t *d_idx, co
 {
     if (!c) return C3SC_ERR_ARG;
     if (c->box_du == 0) return fail(c, C3SC_ERR_ARG, "bellman_fibers_box: c3sc_hip_set_control_box first");
+    if (c->game_gsz > 0) return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_box: games have no control-box form");
     if (model_ncf(c->model) != 0 && c->model != C3SC_MODEL_COTHRUST6D) // cothrust forms its features from u on the device (models.hpp: CF_FROM_U)
         return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_box: this model needs transcendental functions of the control");
     KArgs A;
@@ -858,6 +918,7 @@ static int launch_tables(c3sc_hip_ctx *c, int k, size_t F, const int32_t *d_idx,
 {
     if (!c) return C3SC_ERR_ARG;
     const int saved_model = c->model;
+    if (c->game_gsz > 0) return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_tables: the TABLE model has no game kernels");
     c->model = C3SC_MODEL_TABLE; // fill_args only checks that a model is set
     KArgs A;
     int rc = fill_args(c, k, F, A, true);
@@ -1195,6 +1256,8 @@ int c3sc_hip_simulate(c3sc_hip_ctx *c, const c3sc_hip_sim_args *a, void *stream)
         return fail(c, C3SC_ERR_ARG, a->box ? "simulate: set_control_box first" : "simulate: set_controls first");
     if (a->box && model_ncf(c->model) != 0 && c->model != C3SC_MODEL_COTHRUST6D)
         return fail(c, C3SC_ERR_UNSUPPORTED, "simulate: this model needs transcendental functions of the control in a box");
+    if (a->box && c->game_gsz > 0) return fail(c, C3SC_ERR_UNSUPPORTED, "simulate: games have no control-box form");
+    if (check_game_model(c, "simulate: game mode needs a model compiled with game kernels") != C3SC_OK) return C3SC_ERR_UNSUPPORTED;
     KArgs A;
     int rc = fill_args(c, 0, 0, A, false);
     if (rc != C3SC_OK) return rc;
@@ -1344,6 +1407,8 @@ int c3sc_hip_integrate(c3sc_hip_ctx *c, const c3sc_hip_ode_args *a, void *stream
         return fail(c, C3SC_ERR_ARG, a->box ? "integrate: set_control_box first" : "integrate: set_controls first");
     if (a->box && model_ncf(c->model) != 0 && c->model != C3SC_MODEL_COTHRUST6D)
         return fail(c, C3SC_ERR_UNSUPPORTED, "integrate: this model needs transcendental functions of the control in a box");
+    if (a->box && c->game_gsz > 0) return fail(c, C3SC_ERR_UNSUPPORTED, "integrate: games have no control-box form");
+    if (check_game_model(c, "integrate: game mode needs a model compiled with game kernels") != C3SC_OK) return C3SC_ERR_UNSUPPORTED;
     KArgs A;
     int rc = fill_args(c, 0, 0, A, false);
     if (rc != C3SC_OK) return rc;

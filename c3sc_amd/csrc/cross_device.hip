@@ -1687,6 +1687,8 @@ int c3sc_hip_cross_wait_core(c3sc_hip_ctx *c, int k, double *h_core)
 int c3sc_hip_cross_iteration_pi(c3sc_hip_ctx *c, c3sc_hip_ctx *policy_ctx, long long policy_tag, void *stream)
 {
     if (!policy_ctx) return fail(c, C3SC_ERR_ARG, "cross_iteration_pi: null policy context");
+    if ((c && c->game_gsz > 0) || policy_ctx->game_gsz > 0)
+        return fail(c, C3SC_ERR_UNSUPPORTED, "cross_iteration_pi: policy iteration is not offered for games (c3sc_hip_set_game)");
     return cross_iteration_impl(c, policy_ctx, policy_tag, 0, stream);
 }
 

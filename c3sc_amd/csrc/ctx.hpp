@@ -30,6 +30,8 @@ struct c3sc_hip_ctx {
     double prm[C3SC_MAX_PARAMS] = {0};
     int ncand = 0, du = 0;
     std::vector<double> cands;
+    // zero-sum game (c3sc_hip_set_game): cands is the product list, game_ngrp groups of game_gsz; game_gsz = 0: no game
+    int game_gsz = 0, game_ngrp = 0, game_order = 0;
     // continuous controls (c3sc_hip_set_control_box)
     int box_du = 0, box_grid = 0, box_polish = 0;
     double box_lb[C3SC_MAX_DU] = {0}, box_ub[C3SC_MAX_DU] = {0};

@@ -61,6 +61,11 @@ struct KArgs {
     long quad_imgR_off[MAXD];  //             and of the transposed cores (suffix side); read through img_base by LDS-DMA
     long pair_img_off[MAXD];   // every core once more as the fiber-pair kernel's LDS image: [N][elems | 1] (k_core_image)
     int cends;                 // c3sc_hip_set_consistent_ends: see vary_neighbors
+    // zero-sum games (c3sc_hip_set_game), read by the GAME instantiations only: the candidate list is game_ngrp
+    // groups of game_gsz candidates (u-major for C3SC_GAME_MINMAX, w-major for C3SC_GAME_MAXMIN).  The three fields sit in
+    // alignment holes of this struct (game_ngrp, game_order below): its size and every other offset stay as they were, and with
+    // them the kernarg handling of every existing kernel (a larger KArgs moves the fiber-pair kernels' SGPR spills)
+    int game_gsz;
     // node memo of the device-resident cross iterations (cross_device.hip), applied in the epilogue of the fiber-per-wave kernel
     // when memo_keys != null: a node already stored in this sweep takes the stored value, a new one is stored
     // (bellman.c:1333-1353, 1412-1417)
@@ -68,14 +73,40 @@ struct KArgs {
     double *memo_vals;
     unsigned long long memo_capmask, memo_epoch_bits;
     int memo_shift;
+    int game_ngrp; // see game_gsz
     long long memo_stride[MAXD];
     unsigned long long *memo_counters; // [0] nodes stored, [3] table full
     const int *skip; // fiber-per-wave kernel: return at once when *skip != 0 (the caller already holds this batch's values)
     int memo_mode; // 0: the node's VALUE (bellman_vi's memo); 1: its POLICY, the winning candidate index of a live node
                    // (bellman_pi's per-node cache under key2, bellman.c:1806, 1877)
+    int game_order; // see game_gsz
     const double *img_base;    // the arena again, as a pointer that is NOT the kernels' `ro` argument: the LDS-DMA copy reads the
                                // images through it (see stage_core_image on why it must not be derived from `ro`)
 };
+
+// Pair index iu * nw + iw of the game candidate at list position p, and back (MINMAX: groups are u, the list is the pair order)
+__device__ inline int game_list_to_pair(const KArgs &A, int p)
+{
+    return A.game_order == C3SC_GAME_MAXMIN ? (p % A.game_gsz) * A.game_ngrp + p / A.game_gsz : p;
+}
+__device__ inline int game_pair_to_list(const KArgs &A, int i)
+{
+    return A.game_order == C3SC_GAME_MAXMIN ? (i % A.game_ngrp) * A.game_gsz + i / A.game_ngrp : i;
+}
+
+// The game instantiations of the kernels are those of a model wrapped in GameOf: k_fiber_per_wave, k_rollout and k_rollout_ode
+// pass model_game<Model>() to node_backup as GAME.  A wrapper rather than one more template parameter of the kernels keeps the
+// names (and the code) of every existing instantiation as they are.
+template <class M>
+struct GameOf : M {
+    static constexpr bool GAME = true;
+};
+template <class Model>
+constexpr bool model_game()
+{
+    if constexpr (requires { Model::GAME; }) return Model::GAME;
+    else return false;
+}
 
 // Output pointers of one launch (separate __restrict__ kernel parameters).
 struct KOut {
@@ -523,7 +554,12 @@ __device__ __forceinline__ void upwind_rates(double t, double t2, double b, doub
     pp = (b > 1e-14) ? half + tb : half;
 }
 
-template <class Model, int CG = 1, int CGD = 1, class Cand = CandRegs<Model>, bool SPLIT = true, class Pre = NoPre>
+// GAME (zero-sum games): the list is A.game_ngrp groups of A.game_gsz; the inner reduction runs inside a group
+// (max for C3SC_GAME_MINMAX, min for C3SC_GAME_MAXMIN), the outer one over the groups' winners.  Both keep the scan order (first
+// strict '<' / '>'), a skipped (stationary) candidate takes no part, a group with no candidate left takes no part in the outer
+// reduction.  Group ends are list positions, i.e. wave-uniform; the selection is selects only.  ui and fu are pair indices
+// iu * nw + iw.
+template <class Model, int CG = 1, int CGD = 1, class Cand = CandRegs<Model>, bool SPLIT = true, class Pre = NoPre, bool GAME = false>
 __device__ inline double node_backup(const KArgs &A, const double *__restrict__ ro, const double (&x)[Model::D],
                                      const double (&tv)[Model::NTAB > 0 ? Model::NTAB : 1], const Cand &cr,
                                      const double (&V)[2 * Model::D + 1], int ab, int &ui, unsigned &st, bool forced = false,
@@ -532,8 +568,13 @@ __device__ inline double node_backup(const KArgs &A, const double *__restrict__ 
     // forced (wave-uniform) = policy evaluation, bellman_pi (bellman.c:1702-1886): the candidate fu (per lane) is
     // applied instead of the minimiser's; same rates, same bellmanrhs.
     constexpr int D = Model::D, DU = Model::DU;
+    static_assert(!GAME || (CG == 1 && CGD == 1), "the game scan takes one candidate per trip");
     const int nc = __builtin_amdgcn_readfirstlane(A.ncand); // keeps the candidate loops' trip test on the scalar unit
     ui = -1;
+    // game: which reductions are maxima (wave-uniform), the group length, the forced pair as a list position
+    const bool omax = GAME && A.game_order == C3SC_GAME_MAXMIN, imax = GAME && !omax;
+    const int gsz = GAME ? __builtin_amdgcn_readfirstlane(A.game_gsz) : 1;
+    if constexpr (GAME) fu = (forced && fu >= 0) ? game_pair_to_list(A, fu) : fu;
     // Absorbed lanes (bellman.c:513-532) do not leave early: the scan below runs with the whole wave active and
     // the absorbed lanes' result is replaced at the end.  The lane-distributed tables (CandRegs, NodeRegs) are
     // read with v_readlane from lanes that a divergent branch could have switched off, and a register the
@@ -593,8 +634,11 @@ __device__ inline double node_backup(const KArgs &A, const double *__restrict__ 
         // Scan order and strict '<' are kept; a different winner is possible only between candidates whose
         // values agree to rounding.
         // best so far as the fraction bnum/bq; +inf loses to the first candidate that is not skipped
-        double bnum = __builtin_inf(), bq = 1.0;
+        double bnum = omax ? -__builtin_inf() : __builtin_inf(), bq = 1.0;
         bool anybad = false;
+        // game: the current group's winner inum/iq at position ii (-inf / +inf loses to the group's first valid candidate)
+        double inum = imax ? -__builtin_inf() : __builtin_inf(), iq = 1.0;
+        int ii = -1, gk = 0;
         constexpr unsigned UCm = Model::UCONST_MASK;
         constexpr bool ALLC = (UCm == UM) && !Model::STAGE_UDEP && Model::NCF == 0; // nothing per candidate needs x
         const double base0 = fma(h2l, stage0, PV0); // the candidate-independent part of every numerator (ALLC)
@@ -666,6 +710,29 @@ __device__ inline double node_backup(const KArgs &A, const double *__restrict__ 
                 if (CGD == 1 || c0 + q < nc) { // wave-uniform
                     const bool okc = !(Qq[q] < 1e-14); // nodeutil.c:365-367 returns 1; bellman.c:452 asserts.  Skip + flag.
                     anybad |= !okc;
+                    if (GAME && !forced) { // wave-uniform
+                        double lhs = numq[q] * iq, rhs = inum * Qq[q];
+                        pin_vgpr(lhs);
+                        pin_vgpr(rhs);
+                        const bool take = okc & (imax ? lhs > rhs : lhs < rhs);
+                        inum = take ? numq[q] : inum;
+                        iq = take ? Qq[q] : iq;
+                        ii = take ? c0 + q : ii;
+                        if (++gk == gsz) { // end of a group (wave-uniform): its winner against the groups' so far
+                            double olhs = inum * bq, orhs = bnum * iq;
+                            pin_vgpr(olhs);
+                            pin_vgpr(orhs);
+                            const bool otake = (ii >= 0) & (omax ? olhs > orhs : olhs < orhs);
+                            bnum = otake ? inum : bnum;
+                            bq = otake ? iq : bq;
+                            ui = otake ? ii : ui;
+                            inum = imax ? -__builtin_inf() : __builtin_inf();
+                            iq = 1.0;
+                            ii = -1;
+                            gk = 0;
+                        }
+                        continue;
+                    }
                     double lhs = numq[q] * bq, rhs = bnum * Qq[q];
                     pin_vgpr(lhs); // evaluated unconditionally: the compiler must not wrap them in a divergent branch
                     pin_vgpr(rhs);
@@ -686,6 +753,7 @@ __device__ inline double node_backup(const KArgs &A, const double *__restrict__ 
             const double pself = fma(-bq, inv, 1.0);
             best = (ui >= 0) ? fma(pself, V[2 * D], bnum * inv) : 0.0;
         }
+        if constexpr (GAME) ui = (ui >= 0) ? game_list_to_pair(A, ui) : ui;
         best = (ab != 0) ? absorbed_cost : best;
         ui = (ab != 0) ? -1 : ui;
         return best;
@@ -693,8 +761,10 @@ __device__ inline double node_backup(const KArgs &A, const double *__restrict__ 
     // Candidates are evaluated CG at a time (CG = 1 where registers are tight): one candidate is a ~40-deep
     // chain of dependent f64 operations (rates -> Q -> 1/Q -> dt -> value), and with one or two wavefronts per
     // SIMD nothing else hides that latency, so independent candidates are interleaved.
-    double bestg = __builtin_inf();
+    double bestg = omax ? -__builtin_inf() : __builtin_inf();
     bool anybad_g = false;
+    double ibest = imax ? -__builtin_inf() : __builtin_inf(); // game: the current group's winner (see the undiscounted scan)
+    int ii_g = -1, gk_g = 0;
     // every candidate only adds rates to Q0, so dt_c <= h2/Q0: if beta*h2/Q0 is small on every lane, the discount
     // factor of every candidate takes the polynomial and the per-candidate wave vote is not needed
     const bool all_small = __all(discl * h2l < 0.0078125 * Q0);
@@ -771,7 +841,19 @@ __device__ inline double node_backup(const KArgs &A, const double *__restrict__ 
             for (int q = 0; q < CG; q++) {
                 if (c0 + q < nc) {
                     if constexpr (CHECK) anybad_g |= !ok[q];
-                    if (__builtin_constant_p(forced) && !forced && !CHECK) { // the minimising kernels' fast path: compare, min, one select
+                    if (GAME && !forced) { // wave-uniform
+                        const bool take = ok[q] & (imax ? val[q] > ibest : val[q] < ibest);
+                        ibest = take ? val[q] : ibest;
+                        ii_g = take ? c0 + q : ii_g;
+                        if (++gk_g == gsz) { // end of a group
+                            const bool otake = (ii_g >= 0) & (omax ? ibest > bestg : ibest < bestg);
+                            bestg = otake ? ibest : bestg;
+                            ui = otake ? ii_g : ui;
+                            ibest = imax ? -__builtin_inf() : __builtin_inf();
+                            ii_g = -1;
+                            gk_g = 0;
+                        }
+                    } else if (__builtin_constant_p(forced) && !forced && !CHECK) { // the minimising kernels' fast path: compare, min, one select
                         ui = (val[q] < bestg) ? c0 + q : ui;
                         // v_min_f64 by hand: fmin() canonicalises the loop-carried operand first (a v_max_f64 x, x per candidate)
                         asm("v_min_f64 %0, %1, %2" : "=v"(bestg) : "v"(val[q]), "0"(bestg));
@@ -799,6 +881,7 @@ __device__ inline double node_backup(const KArgs &A, const double *__restrict__ 
         scan(std::true_type{}, E2{});
     if (anybad_g & (ab == 0)) st |= C3SC_STATUS_STATIONARY;
     best = (ui >= 0) ? bestg : 0.0;
+    if constexpr (GAME) ui = (ui >= 0) ? game_list_to_pair(A, ui) : ui;
     best = (ab != 0) ? absorbed_cost : best;
     ui = (ab != 0) ? -1 : ui;
     return best;

@@ -35,6 +35,7 @@ EXPORTS = [
     "c3sc_hip_set_interp", "c3sc_hip_stencil_points", "c3sc_hip_simulate", "c3sc_hip_simulate_host", "c3sc_hip_normals",
     "c3sc_hip_integrate", "c3sc_hip_integrate_host",
     "c3sc_hip_model_compile", "c3sc_hip_model_code_object", "c3sc_hip_model_log",
+    "c3sc_hip_set_game", "c3sc_hip_model_compile_ex", "c3sc_hip_model_code_object_ex",
 ]
 
 class SimArgs(C.Structure):
@@ -66,7 +67,14 @@ class ModelSpec(C.Structure):
                 ("ranks", C.POINTER(C.c_int))]
 
 
+class ModelSpecEx(C.Structure):
+    """struct c3sc_hip_model_spec_ex (include/c3sc_hip.h): the spec plus the game flag"""
+    _fields_ = [("base", ModelSpec), ("game", C.c_int)]
+
+
 MODEL_USER = 1000  # C3SC_MODEL_USER: first id of the run-time compiled models
+GAME_MINMAX, GAME_MAXMIN = 0, 1  # C3SC_GAME_*: upper value (min over u of max over w), lower value (max over w of min over u)
+_GAME_ORDERS = {"minmax": GAME_MINMAX, "upper": GAME_MINMAX, "maxmin": GAME_MAXMIN, "lower": GAME_MAXMIN}
 
 VARIANT_AUTO, VARIANT_FIBER_PER_WAVE, VARIANT_FIBER_PER_LANE, VARIANT_FIBER_PAIR, VARIANT_FIBER_QUAD = 0, 1, 2, 3, 4
 
@@ -128,6 +136,9 @@ def load_library():
         L.c3sc_hip_model_code_object.argtypes = [C.POINTER(ModelSpec), C.c_void_p, c_size_p]
         L.c3sc_hip_model_log.restype = C.c_char_p
         L.c3sc_hip_model_log.argtypes = []
+        L.c3sc_hip_model_compile_ex.argtypes = [C.POINTER(ModelSpecEx), c_int_p]
+        L.c3sc_hip_model_code_object_ex.argtypes = [C.POINTER(ModelSpecEx), C.c_void_p, c_size_p]
+        L.c3sc_hip_set_game.argtypes = [C.c_void_p, C.c_int, C.c_int, c_double_p, C.c_int, c_double_p, C.c_int]
         _LIB = L
     return _LIB
 
@@ -157,21 +168,26 @@ def _model_fail(rc, what):
 
 
 def compile_model(source: str, d: int, du: int, ranks=(4, 8), box: bool = False, udep_mask: int = 0, uconst_mask: int = 0,
-                  stage_udep: bool = True, name: Optional[str] = None) -> int:
+                  stage_udep: bool = True, name: Optional[str] = None, game: bool = False) -> int:
     """Compile a device model from source (c3sc_hip_model_compile, include/c3sc_hip.h states the source contract) and return
     its model id (>= MODEL_USER), usable wherever a built-in model id is.  No GPU is needed.  Raises C3scHipError with the
-    compiler's log on failure; the error code is args[1]."""
+    compiler's log on failure; the error code is args[1].  game=True (c3sc_hip_model_compile_ex) adds the game kernels that
+    BellmanEngine.set_game needs: the control vector is then (u, w) of the two players."""
     L = load_library()
     spec = _model_spec(source, d, du, tuple(ranks), box, udep_mask, uconst_mask, stage_udep, name)
     mid = C.c_int(0)
-    rc = L.c3sc_hip_model_compile(C.byref(spec), C.byref(mid))
+    if game:
+        ex = ModelSpecEx(spec, 1)
+        rc = L.c3sc_hip_model_compile_ex(C.byref(ex), C.byref(mid))
+    else:
+        rc = L.c3sc_hip_model_compile(C.byref(spec), C.byref(mid))
     if rc != 0:
         _model_fail(rc, "c3sc_hip_model_compile")
     return mid.value
 
 
 def code_object(source: str, d: int, du: int, ranks=(4, 8), box: bool = False, udep_mask: int = 0, uconst_mask: int = 0,
-                stage_udep: bool = True, name: Optional[str] = None) -> bytes:
+                stage_udep: bool = True, name: Optional[str] = None, game: bool = False) -> bytes:
     """The gfx950 code object of this spec (c3sc_hip_model_code_object): the loaded one if compile_model already compiled the
     spec, otherwise what compile_model would build now (its id and default name are in the kernel names), compiled and not
     registered."""
@@ -181,13 +197,26 @@ def code_object(source: str, d: int, du: int, ranks=(4, 8), box: bool = False, u
     for _ in range(2):
         buf = C.create_string_buffer(cap)
         size = C.c_size_t(cap)
-        rc = L.c3sc_hip_model_code_object(C.byref(spec), buf, C.byref(size))
+        if game:
+            rc = L.c3sc_hip_model_code_object_ex(C.byref(ModelSpecEx(spec, 1)), buf, C.byref(size))
+        else:
+            rc = L.c3sc_hip_model_code_object(C.byref(spec), buf, C.byref(size))
         if rc == 0:
             return buf.raw[:size.value]
         if size.value <= cap:
             break
         cap = size.value
     _model_fail(rc, "c3sc_hip_model_code_object")
+
+
+def game_split(index, nw: int):
+    """A reported game index (iu * nw + iw; -1 on absorbed nodes) as (iu, iw); works elementwise on arrays (-1 -> (-1, -1))."""
+    i = np.asarray(index)
+    iu = np.where(i < 0, -1, i // nw)
+    iw = np.where(i < 0, -1, i % nw)
+    if np.ndim(index) == 0:
+        return int(iu), int(iw)
+    return iu, iw
 
 
 def _f64(a):
@@ -261,6 +290,19 @@ class BellmanEngine:
         cd = _f64(cands)
         self._chk(self.L.c3sc_hip_set_controls(self.h, C.c_int(cd.shape[0]), C.c_int(cd.shape[1]),
                                                cd.ctypes.data_as(c_double_p)), "set_controls")
+
+    def set_game(self, U: np.ndarray, W: np.ndarray, order="minmax"):
+        """Zero-sum game over the product of the minimiser's list U (nu, du_min) and the maximiser's W (nw, du_max)
+        (c3sc_hip_set_game): order "minmax" (upper value) or "maxmin" (lower value).  The model must be compiled with game=True
+        and du = du_min + du_max.  Reported indices are iu * nw + iw (game_split).  set_controls ends game mode."""
+        u, w = _f64(np.atleast_2d(U)), _f64(np.atleast_2d(W))
+        o = _GAME_ORDERS[order] if isinstance(order, str) else int(order)
+        self._chk(self.L.c3sc_hip_set_game(self.h, C.c_int(u.shape[1]), C.c_int(u.shape[0]), u.ctypes.data_as(c_double_p),
+                                           C.c_int(w.shape[0]), w.ctypes.data_as(c_double_p), C.c_int(o)), "set_game")
+        self.game_nw = w.shape[0]
+
+    def clear_game(self):
+        self._chk(self.L.c3sc_hip_set_game(self.h, 0, 0, None, 0, None, 0), "set_game")
 
     def set_variant(self, variant: int):
         self._chk(self.L.c3sc_hip_set_variant(self.h, C.c_int(variant)), "set_variant")

@@ -460,6 +460,8 @@ double bellman_control(size_t du, const double *u, double *grad_u, void *args)
         res = diff_eval(dp->diff, p->time, x, u, diff, NULL); assert(res == 0);
         res = dp->stagecost(p->time, x, u, &stage, NULL); assert(res == 0);
         res = transition_assemble(dx, du, dw, p->mca->h2, p->mca->t, drift, NULL, diff, NULL, prob, NULL, dt, NULL, NULL);
+        if (res != 0 && c3opt_get_game(p->opt, NULL, NULL, NULL, NULL, NULL) >= 0)
+            return NAN; /* a game skips a stationary candidate, as the device does (c3opt_minimize's game scan drops NaN) */
         assert(res == 0); /* bellman.c:452 */
         val = bellmanrhs(dx, du, stage, NULL, dp->discount, prob, NULL, *dt, NULL, costs, NULL);
     }
@@ -547,6 +549,12 @@ static struct c3sc_hip_ctx *sync_device_ctx(struct ControlParams *cp, struct c3s
     sig = fnv(sig, &brute, sizeof(int));
     const int cends = boundary_get_consistent_ends(dp->bound);
     sig = fnv(sig, &cends, sizeof(int));
+    size_t gdu_min = 0, gnu = 0, gnw = 0;
+    const double *gU = NULL, *gW = NULL;
+    const int gorder = brute ? c3opt_get_game(cp->opt, &gdu_min, &gnu, &gU, &gnw, &gW) : -1;
+    if (gorder >= 0 && dp->model == 0) DIE("bellman_vi: games need a device model compiled with game kernels (c3sc_hip_model_compile_ex)");
+    sig = fnv(sig, &gorder, sizeof(int));
+    sig = fnv(sig, &gnu, sizeof(size_t));
     if (brute) sig = fnv(sig, c3opt_get_brute_vals(cp->opt), c3opt_get_nbrute(cp->opt) * odu * sizeof(double));
     else {
         const size_t g = c3opt_get_box_grid(cp->opt), pl = c3opt_get_box_polish(cp->opt);
@@ -562,7 +570,9 @@ static struct c3sc_hip_ctx *sync_device_ctx(struct ControlParams *cp, struct c3s
         hipok(ctx, c3sc_hip_set_mca(ctx, mca->h2, mca->t, dp->discount), "c3sc_hip_set_mca");
         hipok(ctx, c3sc_hip_set_consistent_ends(ctx, cends), "c3sc_hip_set_consistent_ends");
         if (dp->model != 0) hipok(ctx, c3sc_hip_set_model(ctx, dp->model, dp->prm, dp->nprm), "c3sc_hip_set_model");
-        if (brute)
+        if (brute && gorder >= 0)
+            hipok(ctx, c3sc_hip_set_game(ctx, (int)gdu_min, (int)gnu, gU, (int)gnw, gW, gorder), "c3sc_hip_set_game");
+        else if (brute)
             hipok(ctx, c3sc_hip_set_controls(ctx, (int)c3opt_get_nbrute(cp->opt), (int)odu, c3opt_get_brute_vals(cp->opt)), "c3sc_hip_set_controls");
         else
             hipok(ctx, c3sc_hip_set_control_box(ctx, (int)odu, c3opt_get_lb(cp->opt), c3opt_get_ub(cp->opt), (int)c3opt_get_box_grid(cp->opt),
@@ -889,9 +899,18 @@ size_t pi_param_get_niter_node_evals(const struct PIparam *p) { return p->niter_
 static double g_tp[4]; /* C3SC_PROFILE: core upload, flags + policy cache lookup, policy pass, evaluation pass */
 static size_t g_np;
 
+/* policy iteration is not offered for zero-sum games (it need not converge for them): refused, never run as the
+ * plain minimiser */
+static void refuse_game_pi(const struct c3Opt *opt, const char *who)
+{
+    if (opt != NULL && c3opt_is_bruteforce(opt) && c3opt_get_game(opt, NULL, NULL, NULL, NULL, NULL) >= 0)
+        DIE("%s: policy iteration is not offered for games (c3opt_set_brute_force_game); use value iteration", who);
+}
+
 static int pi_core(struct PIparam *pi, size_t F, size_t k0, const int32_t *idx, const double *x_in, double *out, int fast)
 {
     struct ControlParams *cp = pi->cp;
+    refuse_game_pi(cp->opt, "bellman_pi");
     struct MCAparam *mca = cp->mca;
     struct DPparam *dp = cp->dp;
     const size_t dx = mca->dx, N = mca->ngrid[k0];
@@ -1203,6 +1222,7 @@ struct PIparam *c3control_begin_pi(struct C3Control *c, struct ValueF *policy)
 
 void c3control_begin_pi_step(struct C3Control *c, struct PIparam *pi, struct ValueF *vf, struct c3Opt *opt)
 { /* c3control_step_pi before valuef_interp (bellman.c:2236-2249) */
+    refuse_game_pi(opt, "c3control_step_pi");
     c->cp_active = control_params_create(c->dx, c->dw, c->dp, c->mca, c->work, opt);
     pi_param_add_cp(pi, c->cp_active);
     pi_param_add_value(pi, vf);
@@ -1457,6 +1477,7 @@ struct ValueF *c3control_vi_solve(struct C3Control *c, size_t maxiter, double ab
 struct ValueF *c3control_pi_solve(struct C3Control *c, size_t maxiter, double abs_conv_tol, struct ValueF *policy,
                                   struct ApproxArgs *apargs, struct c3Opt *opt, int verbose, struct Diag **diag)
 { /* bellman.c:2343-2407 */
+    refuse_game_pi(opt, "c3control_pi_solve");
     struct ValueF *start = valuef_copy(policy);
     struct PIparam *poli = c3control_begin_pi(c, policy);
     double stot = 1.0;

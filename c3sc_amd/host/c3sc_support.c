@@ -416,6 +416,11 @@ struct c3Opt {
     size_t grid, polish;
     double (*f)(size_t, const double *, double *, void *);
     void *farg;
+    /* zero-sum game (c3opt_set_brute_force_game): vals is the product list of U (gnu x gdu_min) and W (gnw x (d - gdu_min)),
+     * u-major for C3SC_GAME_MINMAX, w-major for C3SC_GAME_MAXMIN; game = order + 1, 0 = a plain list */
+    int game;
+    size_t gdu_min, gnu, gnw;
+    double *gU, *gW;
 };
 
 struct c3Opt *c3opt_alloc(enum c3opt_alg alg, size_t d)
@@ -441,13 +446,66 @@ struct c3Opt *c3opt_copy(struct c3Opt *o)
     c->ub = xmalloc(o->d * sizeof(double));
     memcpy(c->lb, o->lb, o->d * sizeof(double));
     memcpy(c->ub, o->ub, o->d * sizeof(double));
+    if (o->game) {
+        c->gU = xmalloc(o->gnu * o->gdu_min * sizeof(double));
+        c->gW = xmalloc(o->gnw * (o->d - o->gdu_min) * sizeof(double));
+        memcpy(c->gU, o->gU, o->gnu * o->gdu_min * sizeof(double));
+        memcpy(c->gW, o->gW, o->gnw * (o->d - o->gdu_min) * sizeof(double));
+    }
     return c;
 }
 
-void c3opt_free(struct c3Opt *o) { if (o) { free(o->vals); free(o->lb); free(o->ub); free(o); } }
+void c3opt_free(struct c3Opt *o) { if (o) { free(o->vals); free(o->lb); free(o->ub); free(o->gU); free(o->gW); free(o); } }
+
+static void clear_game(struct c3Opt *o)
+{
+    free(o->gU);
+    free(o->gW);
+    o->gU = o->gW = NULL;
+    o->game = 0;
+    o->gdu_min = o->gnu = o->gnw = 0;
+}
+
+void c3opt_set_brute_force_game(struct c3Opt *o, size_t du_min, size_t nu, const double *U, size_t nw, const double *W, int order)
+{ /* the product list in the device's order (c3sc_hip_set_game) */
+    if (o->alg != BRUTEFORCE) { fprintf(stderr, "c3opt_set_brute_force_game: the c3Opt must be BRUTEFORCE\n"); exit(1); }
+    if (du_min < 1 || du_min >= o->d || nu < 1 || nw < 1 || U == NULL || W == NULL || (order != C3SC_GAME_MINMAX && order != C3SC_GAME_MAXMIN)) {
+        fprintf(stderr, "c3opt_set_brute_force_game: du_min in 1..d-1, nu, nw >= 1 and order C3SC_GAME_MINMAX / C3SC_GAME_MAXMIN\n");
+        exit(1);
+    }
+    const size_t d = o->d, dmax = d - du_min;
+    clear_game(o);
+    free(o->vals);
+    o->n = nu * nw;
+    o->vals = xmalloc(o->n * d * sizeof(double));
+    for (size_t iu = 0; iu < nu; iu++)
+        for (size_t iw = 0; iw < nw; iw++) {
+            const size_t p = order == C3SC_GAME_MINMAX ? iu * nw + iw : iw * nu + iu;
+            memcpy(o->vals + p * d, U + iu * du_min, du_min * sizeof(double));
+            memcpy(o->vals + p * d + du_min, W + iw * dmax, dmax * sizeof(double));
+        }
+    o->game = order + 1;
+    o->gdu_min = du_min; o->gnu = nu; o->gnw = nw;
+    o->gU = xmalloc(nu * du_min * sizeof(double));
+    o->gW = xmalloc(nw * dmax * sizeof(double));
+    memcpy(o->gU, U, nu * du_min * sizeof(double));
+    memcpy(o->gW, W, nw * dmax * sizeof(double));
+}
+
+int c3opt_get_game(const struct c3Opt *o, size_t *du_min, size_t *nu, const double **U, size_t *nw, const double **W)
+{
+    if (!o->game) return -1;
+    if (du_min) *du_min = o->gdu_min;
+    if (nu) *nu = o->gnu;
+    if (U) *U = o->gU;
+    if (nw) *nw = o->gnw;
+    if (W) *W = o->gW;
+    return o->game - 1;
+}
 
 void c3opt_set_brute_force_vals(struct c3Opt *o, size_t n, double *vals)
 {
+    clear_game(o);
     free(o->vals);
     o->n = n;
     o->vals = xmalloc(n * o->d * sizeof(double));
@@ -520,10 +578,39 @@ static int box_minimize(struct c3Opt *o, double *x, double *val)
     return 0;
 }
 
+static int game_minimize(struct c3Opt *o, double *x, double *val)
+{ /* node_backup's GAME scan: groups of the list in order, inner max (MINMAX) / min (MAXMIN) inside a group, outer min / max over the
+   * groups' winners; first strict '>' / '<' in both; a NaN value (a stationary candidate, bellman_control) takes no part; a group
+   * with nothing left takes no part; nothing left at all: value 0, u = 0 */
+    const int omax = o->game - 1 == C3SC_GAME_MAXMIN, imax = !omax;
+    const size_t gsz = omax ? o->gnu : o->gnw, ngrp = o->n / gsz;
+    double ob = omax ? -INFINITY : INFINITY;
+    long oi = -1;
+    for (size_t g = 0; g < ngrp; g++) {
+        double ib = imax ? -INFINITY : INFINITY;
+        long ii = -1;
+        for (size_t j = 0; j < gsz; j++) {
+            const size_t c = g * gsz + j;
+            const double v = o->f(o->d, o->vals + c * o->d, NULL, o->farg);
+            if (imax ? v > ib : v < ib) { ib = v; ii = (long)c; }
+        }
+        if (ii >= 0 && (omax ? ib > ob : ib < ob)) { ob = ib; oi = ii; }
+    }
+    if (oi < 0) {
+        memset(x, 0, o->d * sizeof(double));
+        *val = 0.0;
+        return 0;
+    }
+    memcpy(x, o->vals + (size_t)oi * o->d, o->d * sizeof(double));
+    *val = ob;
+    return 0;
+}
+
 int c3opt_minimize(struct c3Opt *o, double *x, double *val)
 {
     assert(o->f != NULL);
     if (o->alg != BRUTEFORCE) return box_minimize(o, x, val);
+    if (o->game) return game_minimize(o, x, val);
     /* candidates in list order, first strict minimum wins */
     assert(o->n > 0);
     size_t best = 0;

@@ -60,6 +60,12 @@ struct c3Opt *c3opt_alloc(enum c3opt_alg alg, size_t d); /* BRUTEFORCE: list sca
 struct c3Opt *c3opt_copy(struct c3Opt *);
 void c3opt_free(struct c3Opt *);
 void c3opt_set_brute_force_vals(struct c3Opt *, size_t n, double *vals /* n x d */);
+/* new: a zero-sum game on a BRUTEFORCE c3Opt allocated with d = du_min + du_max: the first du_min control
+ * components are the minimiser's (list U, nu x du_min), the rest the maximiser's (W, nw x du_max); the list becomes their product
+ * and c3opt_minimize returns the saddle pair, min over u of max over w (order C3SC_GAME_MINMAX = 0) or max over w of min over u
+ * (C3SC_GAME_MAXMIN = 1).  c3opt_set_brute_force_vals ends game mode.  Policy iteration refuses a game c3Opt. */
+void c3opt_set_brute_force_game(struct c3Opt *, size_t du_min, size_t nu, const double *U, size_t nw, const double *W, int order);
+int c3opt_get_game(const struct c3Opt *, size_t *du_min, size_t *nu, const double **U, size_t *nw, const double **W); /* order, or -1 */
 int c3opt_is_bruteforce(const struct c3Opt *);
 void c3opt_add_objective(struct c3Opt *, double (*f)(size_t, const double *, double *, void *), void *arg);
 int c3opt_minimize(struct c3Opt *, double *x, double *val); /* scan in order, strict '<' */

@@ -454,6 +454,39 @@ int c3sc_hip_model_code_object(const c3sc_hip_model_spec *spec, void *buf, size_
 /* the compiler's log / the reason of the last failed model compile on this thread ("" if none) */
 const char *c3sc_hip_model_log(void);
 
+/* ---- zero-sum stochastic games
+ * Two players share the control vector (u, w) of a run-time compiled model: the first du_min components belong to the
+ * minimiser, the remaining du_max to the maximiser, du_min + du_max = the model's du.  c3sc_hip_set_game builds the candidate
+ * list as the product of the minimiser's list U (nu x du_min, row-major) and the maximiser's W (nw x du_max) and makes the
+ * Bellman operator a min-max over it:
+ *   C3SC_GAME_MINMAX (default, the upper value)  min over u of max over w
+ *   C3SC_GAME_MAXMIN (the lower value)           max over w of min over u
+ * Per candidate everything is the plain scan's (rates, dead zone, Q, dt, discount, the stationary skip and its status bit).  The
+ * kernel reduces a grouped list (the library orders it u-major for MINMAX, w-major for MAXMIN): the inner reduction inside a
+ * group, the outer one over the groups.  Both keep the scan order: a min takes the first strict '<', a max the first strict
+ * '>'.  A stationary candidate (Q < 1e-14) is skipped and raises C3SC_STATUS_STATIONARY; a group whose members were all skipped
+ * takes no part in the outer reduction; with nothing left the node's value is 0 and its index -1.  With beta = 0 the scan
+ * compares fractions and divides once for the winner, as the plain scan does.
+ * The reported index (uidx) is the saddle pair iu * nw + iw in either order, -1 on absorbed nodes.  Policy evaluation
+ * (policy_fibers*) applies a given pair index (the forced path, unchanged).  Game mode is honoured by bellman_fibers(_all),
+ * the device-resident cross iterations, simulate and integrate (the controller applies the saddle pair; d_u holds the full
+ * du vector); cross_iteration_pi refuses it.  Only the fiber-per-wave kernel has a game form: a forced pair or quad variant,
+ * the control box and the box calls return C3SC_ERR_UNSUPPORTED; AUTO picks the per-wave kernel.
+ * nu = 0 clears game mode; so does c3sc_hip_set_controls.  Errors: C3SC_ERR_ARG (sizes that do not add up to the model's du,
+ * a bad order, null lists), C3SC_ERR_UNSUPPORTED (a built-in or the TABLE model, a model compiled without game kernels).
+ * Set the model first. */
+enum { C3SC_GAME_MINMAX = 0, C3SC_GAME_MAXMIN = 1 };
+int c3sc_hip_set_game(c3sc_hip_ctx *ctx, int du_min, int nu, const double *U, int nw, const double *W, int order);
+/* a run-time compiled model with game kernels: c3sc_hip_model_compile's spec plus a flag.  game = 1 adds the game forms of the
+ * per-wave, rollout and integrate kernels at every requested rank (box must be 0 then: C3SC_ERR_UNSUPPORTED); game = 0 is
+ * exactly c3sc_hip_model_compile.  c3sc_hip_model_code_object_ex is c3sc_hip_model_code_object for such a spec. */
+typedef struct c3sc_hip_model_spec_ex {
+    c3sc_hip_model_spec base;
+    int game;
+} c3sc_hip_model_spec_ex;
+int c3sc_hip_model_compile_ex(const c3sc_hip_model_spec_ex *spec, int *model_id);
+int c3sc_hip_model_code_object_ex(const c3sc_hip_model_spec_ex *spec, void *buf, size_t *size);
+
 int c3sc_hip_sync(c3sc_hip_ctx *ctx, void *stream);
 int c3sc_hip_get_status(c3sc_hip_ctx *ctx, unsigned *flags, int clear);
 /* name of the kernel the last launch used (for profiles) */
