@@ -2,7 +2,7 @@
 """bench.py -- Bellman-sweep throughput of the HIP hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload car7d] [--fibers F] [--scaling strong|weak]
-                    [--dump-outputs DIR]
+                    [--dump-outputs DIR] [--full]
 
 One "step" = one Bellman sweep over a batch of synthetic fibers: for every varying dimension k = 0..d-1, F fibers
 (x N_k nodes) go through the batched bellman_vi kernel (c3sc_hip_bellman_fibers); the sweep ends the way a value-iteration
@@ -16,11 +16,13 @@ over the N GPUs (north_star's strong-scaling target); --scaling weak: every rank
 With --gpus N > 1 and no launcher environment (WORLD_SIZE unset) the script starts its N ranks itself, as fresh child
 processes, before anything in the parent touches the GPU.
 
-Prints ONE JSON line on rank 0 (contract in the task description) with `roofline`, `cpu_baseline` and -- measured after
-the timed region through libc3sc.so on rank 0 at N = 1 -- `vi_sweep` (a whole value-iteration sweep of the solver: ms,
-node backups, kernel launches) and `vi_iters_to_tol` (the examples' outer loop under a wall-time budget).  The workload is
-BASELINE.json's headline config ("7D car rank-10": SURVEY.md 8d C4 = synthetic 7-D car, 41^7 grid, FT rank 10, 9
-brute-force controls).
+Prints ONE JSON line on rank 0 with the headline figure (`metric`, `value`, `unit`, `ms_per_step`, ...) and `roofline` (HIP
+events of the timed launches).  A plain run does only that: set up, warm up, time the steps, write --dump-outputs, print.
+--full also measures, after the timed region, what the headline figure does not need: at N = 1 `other_mode_step` (the same
+steps with the other launch mode), through libc3sc.so on rank 0 `vi_sweep` (a whole value-iteration sweep of the solver: ms,
+node backups, kernel launches) and `vi_iters_to_tol` (the examples' outer loop under a wall-time budget), and `cpu_baseline`;
+without it those keys are null.  The workload is BASELINE.json's headline config ("7D car rank-10": SURVEY.md 8d C4 =
+synthetic 7-D car, 41^7 grid, FT rank 10, 9 brute-force controls).
 """
 import argparse
 import glob
@@ -392,10 +394,14 @@ def dump_outputs(path, out_t, dev):
     return {"dir": path, "files": files, "rows": int(n), "of_rows": int(F), "sample_seed": DUMP_SEED if n < F else None}
 
 
-def main():
-    if len(sys.argv) >= 5 and sys.argv[1] == "--cpu-worker":  # child of cpu_baseline: before anything touches torch / the GPU
-        _cpu_worker(sys.argv[2], float(sys.argv[3]), int(sys.argv[4]))
-        return
+def extra_legs(args, world, use_dist):
+    """The measurements a run makes after its timed region beyond the headline figure: none without --full."""
+    return {"other_mode_step": args.full and not use_dist and not args.no_overlap_probe,
+            "solver": args.full and world == 1 and not args.no_solver,
+            "cpu_baseline": args.full and world == 1 and not args.no_cpu_baseline}
+
+
+def make_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
@@ -409,9 +415,13 @@ def main():
     ap.add_argument("--overlap", action="store_true",
                     help="issue the d independent launches of a step through c3sc_hip_bellman_fibers_all (three streams inside the library) "
                          "in the timed region; per-kernel durations then overlap, so `roofline` is taken from the step span")
-    ap.add_argument("--no-overlap-probe", action="store_true", help="skip the untimed second pass that times a step the other way")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-solver", action="store_true", help="skip the vi_sweep / vi_iters_to_tol measurements after the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline measurement, also run what it does not need: the untimed pass of the other launch "
+                         "mode (other_mode_step), the solver's sweeps through libc3sc.so (vi_sweep, vi_iters_to_tol) and the CPU "
+                         "baseline (cpu_baseline); without it those keys are null")
+    ap.add_argument("--no-overlap-probe", action="store_true", help="with --full: skip the untimed second pass that times a step the other way")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-solver", action="store_true", help="with --full: skip the vi_sweep / vi_iters_to_tol measurements after the timed region")
     ap.add_argument("--solver-budget", type=float, default=20.0)
     ap.add_argument("--cpu-budget", type=float, default=12.0)
     ap.add_argument("--cpu-procs", type=int, default=None, help="worker processes of the CPU baseline (default min(16, cores))")
@@ -419,6 +429,14 @@ def main():
                     help="after the timed steps, write rank 0's Bellman outputs of the last timed step as DIR/out_k<k>.npy (float64, "
                          "one per varying dimension): a fixed, seeded sample of the fibers, the same rows for every dimension, "
                          f"at most {DUMP_BYTES // 1000000} MB in all")
+    return ap
+
+
+def main():
+    if len(sys.argv) >= 5 and sys.argv[1] == "--cpu-worker":  # child of cpu_baseline: before anything touches torch / the GPU
+        _cpu_worker(sys.argv[2], float(sys.argv[3]), int(sys.argv[4]))
+        return
+    ap = make_parser()
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
@@ -457,6 +475,7 @@ def main():
         dist.init_process_group("nccl", device_id=dev)  # RCCL
     if world != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}")
+    legs = extra_legs(args, world, use_dist)
 
     w = wl.WORKLOADS[args.workload]()
     cores = wl.synth_cores(w)
@@ -581,9 +600,9 @@ def main():
     # before the untimed steps below, which write into the same out_t
     dump = dump_outputs(args.dump_outputs, out_t, dev) if args.dump_outputs and rank == 0 else None
     # the same steps the other way (untimed for `value`): with the launches of a step on one stream (default: the per-kernel
-    # durations behind `roofline` are then what rocprofv3 sees) or spread over three streams by the library (--overlap)
+    # durations behind `roofline` are then what rocprofv3 sees) or spread over three streams by the library (--overlap); --full only
     other = None
-    if not use_dist and not args.no_overlap_probe:
+    if legs["other_mode_step"]:
         step(False, not args.overlap)
         fence()
         t1 = time.perf_counter()
@@ -669,6 +688,8 @@ def main():
                                 "together (cross_device.hip step_fibers, comm_rccl.hip c3sc_hip_comm_exchange; tests/test_distributed.py)"}
         res["step_launch_mode"] = "overlapped (c3sc_hip_bellman_fibers_all, three streams)" if args.overlap else "one stream, d launches in order"
         res["dump_outputs"] = dump
+        res["full"] = args.full
+        res["other_mode_step"] = None
         if other is not None:
             res["other_mode_step"] = {
                 "mode": "one stream, d launches in order" if args.overlap else "overlapped (c3sc_hip_bellman_fibers_all, three streams)",
@@ -677,12 +698,12 @@ def main():
                 "what": "the same steps re-timed (wall clock over --steps steps, untimed for `value`) with the other launch mode; under "
                         "overlap the per-kernel durations of a profile overlap, so the default keeps one stream and `roofline` per kernel"}
         res["vi_sweep"], res["vi_iters_to_tol"] = None, None
-        if world == 1 and not args.no_solver:
+        if legs["solver"]:
             try:
                 res["vi_sweep"], res["vi_iters_to_tol"] = solver_measurements(args.workload, args.solver_budget)
             except Exception as e:  # the headline measurement above stands on its own
                 res["vi_sweep"] = {"error": repr(e)}
-        res["cpu_baseline"] = cpu_baseline(w, cores, args.cpu_budget, args.cpu_procs) if (world == 1 and not args.no_cpu_baseline) else None
+        res["cpu_baseline"] = cpu_baseline(w, cores, args.cpu_budget, args.cpu_procs) if legs["cpu_baseline"] else None
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(res) + "\n").encode())
     if use_dist:

@@ -55,3 +55,28 @@ def test_bench_cpu_baseline_worker_runs_without_gpu():
     out = subprocess.check_output([sys.executable, os.path.join(root, "bench.py"), "--cpu-worker", "car7d", "0.5", "3"], timeout=120)
     r = json.loads(out.decode().strip().splitlines()[-1])
     assert r["nodes"] > 0 and r["nodes"] % 41 == 0 and 0.5 <= r["seconds"] < 30 and r["chunks"] >= 1
+
+
+def test_bench_plain_run_measures_the_headline_only():
+    """bench.py without --full runs nothing after its timed region but the dump; --full brings back every other leg."""
+    import importlib.util
+    import os
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_cli", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    ap = bench.make_parser()
+
+    def legs(argv, world=1, use_dist=False):
+        return bench.extra_legs(ap.parse_args(argv), world, use_dist)
+
+    off = {"other_mode_step": False, "solver": False, "cpu_baseline": False}
+    assert legs(["--gpus", "1", "--steps", "3", "--warmup", "1"]) == off
+    assert legs(["--dump-outputs", "d", "--overlap"]) == off
+    assert legs(["--full"]) == {"other_mode_step": True, "solver": True, "cpu_baseline": True}
+    assert legs(["--full", "--no-solver", "--no-cpu-baseline"]) == {"other_mode_step": True, "solver": False, "cpu_baseline": False}
+    assert legs(["--full", "--no-overlap-probe"])["other_mode_step"] is False
+    # several ranks (or the single-rank RCCL rehearsal): the legs that need one GPU stay off
+    assert legs(["--full", "--gpus", "2"], world=2, use_dist=True) == off
+    assert legs(["--full"], world=1, use_dist=True) == {"other_mode_step": False, "solver": True, "cpu_baseline": True}

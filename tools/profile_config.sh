@@ -8,7 +8,7 @@ set -e
 TAG=$1; NODES=$2; FIB=$3; shift 3
 cd $GRAFT_REPO_ROOT; export TMPDIR=/tmp; O=$GRAFT_REPO_ROOT/gpurun_out
 A="$@ --no-cpu-baseline --no-solver --no-overlap-probe"
-timeout -k 10 300 python bench.py $@ --steps 10 --warmup 2 --no-solver --no-overlap-probe > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err; echo bench done
+timeout -k 10 300 python bench.py $@ --steps 10 --warmup 2 --full --no-solver --no-overlap-probe > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err; echo bench done
 rm -rf $O/p_st $O/p_1 $O/p_2 $O/p_3 $O/p_4
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/p_st -- python3 bench.py $A --steps 5 --warmup 1 > $O/${TAG}_bench_under_rocprof.json 2> $O/p_st.err; echo stats done
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/p_1 -- python3 bench.py $A --steps 2 --warmup 1 > /dev/null 2> $O/p_1.err; echo pmc1 done
