@@ -163,6 +163,8 @@ static size_t static_layout(c3sc_hip_ctx *c)
     }
     c->cfeat_off = (int)off;
     off += (size_t)model_ncf(c->model) * c->ncand;
+    c->hz_off = (int)off; // the horizon constants (c3sc_hip_set_horizon_step): zeros when horizon mode is off
+    off += 4;
     return (off + 15) & ~(size_t)15;
 }
 
@@ -182,6 +184,11 @@ static int upload_static(c3sc_hip_ctx *c)
     const int ncf = model_ncf(c->model);
     for (int q = 0; q < c->ncand * ncf; q++)
         st[c->cfeat_off + q] = model_cand_feature(c->model, q % ncf, c->cands.data() + (size_t)(q / ncf) * c->du);
+    if (c->hz_dt > 0.0) { // wave-uniform constants of the explicit scheme (kernel_common.hpp, node_backup HORIZON)
+        st[c->hz_off] = c->hz_dt;
+        st[c->hz_off + 1] = std::exp(-c->discount * c->hz_dt);
+        st[c->hz_off + 2] = c->hz_dt / c->h2;
+    }
     HIPCHK(c, hipMemcpy(c->arena, st.data(), st.size() * sizeof(double), hipMemcpyHostToDevice));
     c->static_dirty = false;
     return C3SC_OK;
@@ -255,6 +262,15 @@ static bool zero_copy_batch(size_t bytes);
 static size_t align256(size_t x);
 static int fill_args(c3sc_hip_ctx *c, int k, size_t F, KArgs &A, bool need_model);
 
+// horizon mode is served by the horizon kernels of the model set now (set_model may have replaced the model set_horizon_step
+// checked), and never together with a game
+static int check_horizon_model(c3sc_hip_ctx *c, const char *what)
+{
+    if (c->hz_dt > 0.0 && !(c->model >= C3SC_MODEL_USER && rtc_model_horizon(c->model) && c->game_gsz == 0))
+        return fail(c, C3SC_ERR_UNSUPPORTED, what);
+    return C3SC_OK;
+}
+
 // game mode is served by the game kernels of the model set now (set_model may have replaced the model set_game checked)
 static int check_game_model(c3sc_hip_ctx *c, const char *what)
 {
@@ -306,6 +322,7 @@ void c3sc_hip_ctx_destroy(c3sc_hip_ctx *c)
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->arena) (void)hipFree(c->arena);
+    if (c->hz_stack) (void)hipFree(c->hz_stack);
     if (c->d_status) (void)hipFree(c->d_status);
     if (c->d_dbg) (void)hipFree(c->d_dbg);
     if (c->scratch) (void)hipFree(c->scratch);
@@ -378,6 +395,28 @@ int c3sc_hip_set_mca(c3sc_hip_ctx *c, double h2, const double *t, double discoun
     c->discount = discount;
     for (int i = 0; i < 2 * c->d; i++) c->t[i] = t[i];
     c->have_mca = true;
+    if (c->hz_dt > 0.0) c->static_dirty = true; // the horizon constants depend on beta and h^2
+    return C3SC_OK;
+}
+
+int c3sc_hip_set_horizon_step(c3sc_hip_ctx *c, double dt)
+{
+    if (!c) return C3SC_ERR_ARG;
+    if (dt == 0.0) {
+        if (c->hz_dt > 0.0) c->static_dirty = true;
+        c->hz_dt = 0.0;
+        return C3SC_OK;
+    }
+    if (!(dt > 0.0) || !std::isfinite(dt)) return fail(c, C3SC_ERR_ARG, "set_horizon_step: dt must be positive and finite (0 clears)");
+    if (!c->have_mca) return fail(c, C3SC_ERR_ARG, "set_horizon_step: set_mca first");
+    if (c->model == 0) return fail(c, C3SC_ERR_ARG, "set_horizon_step: set_model first");
+    if (c->model < C3SC_MODEL_USER || !rtc_model_known(c->model))
+        return fail(c, C3SC_ERR_UNSUPPORTED, "set_horizon_step: horizon mode needs a run-time compiled model (c3sc_hip_model_compile_fh with horizon = 1)");
+    if (!rtc_model_horizon(c->model))
+        return fail(c, C3SC_ERR_UNSUPPORTED, "set_horizon_step: this model was compiled without horizon kernels (c3sc_hip_model_compile_fh, horizon = 1)");
+    if (c->game_gsz > 0) return fail(c, C3SC_ERR_UNSUPPORTED, "set_horizon_step: games have no horizon form");
+    c->hz_dt = dt;
+    c->static_dirty = true;
     return C3SC_OK;
 }
 
@@ -413,6 +452,7 @@ int c3sc_hip_set_game(c3sc_hip_ctx *c, int du_min, int nu, const double *U, int 
     if (order != C3SC_GAME_MINMAX && order != C3SC_GAME_MAXMIN) return fail(c, C3SC_ERR_ARG, "set_game: order must be C3SC_GAME_MINMAX or C3SC_GAME_MAXMIN");
     if (c->model == 0) return fail(c, C3SC_ERR_ARG, "set_game: set_model first");
     if (c->model == C3SC_MODEL_TABLE) return fail(c, C3SC_ERR_UNSUPPORTED, "set_game: the TABLE model has no game kernels");
+    if (c->hz_dt > 0.0) return fail(c, C3SC_ERR_UNSUPPORTED, "set_game: games have no horizon form (c3sc_hip_set_horizon_step(ctx, 0) first)");
     int mdu = 0;
     bool has_game = false;
     if (c->model < C3SC_MODEL_USER || !rtc_model_info(c->model, mdu, has_game))
@@ -564,6 +604,23 @@ static int make_quad_aux(c3sc_hip_ctx *c, void *stream)
     return C3SC_OK;
 }
 
+// cores in c3sc_hip_upload_value's host layout ([N_m][r_m][r_{m+1}], column-major per node) into the padded layout of k_pad_core
+// at padded rank rp; dst[m] is where core m goes
+static void pad_cores_host(int d, const int *ngrid, int rp, const size_t *ranks, const double *const *cores, double *const *dst)
+{
+    for (int m = 0; m < d; m++) {
+        const size_t r0 = ranks[m], r1 = ranks[m + 1];
+        const double *src = cores[m];
+        const size_t per = (m == 0 || m == d - 1) ? rp : (size_t)rp * rp;
+        for (int j = 0; j < ngrid[m]; j++)
+            for (size_t b = 0; b < r1; b++)
+                for (size_t a = 0; a < r0; a++) {
+                    const size_t w = (m == 0) ? b : ((m == d - 1) ? a : a + b * rp);
+                    dst[m][(size_t)j * per + w] = src[(size_t)j * r0 * r1 + a + b * r0];
+                }
+    }
+}
+
 int c3sc_hip_upload_value(c3sc_hip_ctx *c, const size_t *ranks, const double *const *cores)
 {
     size_t cd = 0;
@@ -571,22 +628,9 @@ int c3sc_hip_upload_value(c3sc_hip_ctx *c, const size_t *ranks, const double *co
     if (rc != C3SC_OK) return rc;
     const int d = c->d, rp = c->rp;
     std::vector<double> buf(cd, 0.0);
-    for (int m = 0; m < d; m++) {
-        const size_t r0 = ranks[m], r1 = ranks[m + 1];
-        double *dst = buf.data() + (c->core_off[m] - (long)c->static_doubles);
-        const double *src = cores[m];
-        const size_t per = (m == 0 || m == d - 1) ? rp : (size_t)rp * rp;
-        for (int j = 0; j < c->ngrid[m]; j++)
-            for (size_t b = 0; b < r1; b++)
-                for (size_t a = 0; a < r0; a++) {
-                    const double v = src[(size_t)j * r0 * r1 + a + b * r0];
-                    size_t w;
-                    if (m == 0) w = b;
-                    else if (m == d - 1) w = a;
-                    else w = a + b * rp;
-                    dst[(size_t)j * per + w] = v;
-                }
-    }
+    double *dst[MAXD];
+    for (int m = 0; m < d; m++) dst[m] = buf.data() + (c->core_off[m] - (long)c->static_doubles);
+    pad_cores_host(d, c->ngrid, rp, ranks, cores, dst);
     HIPCHK(c, hipMemcpy(c->arena + c->static_doubles, buf.data(), cd * sizeof(double), hipMemcpyHostToDevice));
     rc = make_quad_aux(c, nullptr);
     if (rc != C3SC_OK) return rc;
@@ -594,6 +638,61 @@ int c3sc_hip_upload_value(c3sc_hip_ctx *c, const size_t *ranks, const double *co
     // may launch on a non-blocking stream next
     HIPCHK(c, hipStreamSynchronize(nullptr));
     c->have_value = true;
+    return C3SC_OK;
+}
+
+int c3sc_hip_upload_value_stack(c3sc_hip_ctx *c, int nstack, const size_t *ranks, const double *const *cores)
+{
+    if (!c) return C3SC_ERR_ARG;
+    if (nstack == 0) {
+        if (c->hz_stack) HIPCHK(c, hipFree(c->hz_stack));
+        c->hz_stack = nullptr;
+        c->hz_nstack = 0;
+        return C3SC_OK;
+    }
+    if (nstack < 0 || !ranks || !cores) return fail(c, C3SC_ERR_ARG, "upload_value_stack: bad arguments");
+    if (c->d == 0 || !c->have_value) return fail(c, C3SC_ERR_ARG, "upload_value_stack: upload_value first (the stack shares its static section)");
+    if (static_layout(c) != c->static_doubles)
+        return fail(c, C3SC_ERR_ARG, "upload_value_stack: static data changed size after upload_value; upload the value again");
+    const int d = c->d;
+    std::vector<int> rps(nstack);
+    std::vector<long> offs((size_t)nstack * MAXD, 0);
+    size_t off = c->static_doubles;
+    for (int s = 0; s < nstack; s++) {
+        const size_t *r = ranks + (size_t)s * (d + 1);
+        if (r[0] != 1 || r[d] != 1) return fail(c, C3SC_ERR_ARG, "upload_value_stack: ranks[s][0] and ranks[s][d] must be 1");
+        size_t maxrank = 1;
+        for (int m = 0; m <= d; m++) {
+            if (r[m] < 1) return fail(c, C3SC_ERR_ARG, "upload_value_stack: rank < 1");
+            maxrank = std::max(maxrank, r[m]);
+        }
+        for (int m = 0; m < d; m++)
+            if (!cores[(size_t)s * d + m]) return fail(c, C3SC_ERR_ARG, "upload_value_stack: null core");
+        rps[s] = pick_rp(d, (int)maxrank, c->model, C3SC_VARIANT_AUTO);
+        if (rps[s] == 0) return fail(c, C3SC_ERR_UNSUPPORTED, "upload_value_stack: no kernel instantiation for a stage's (dim, rank)");
+        for (int m = 0; m < d; m++) {
+            offs[(size_t)s * MAXD + m] = (long)off;
+            const size_t per = (m == 0 || m == d - 1) ? rps[s] : (size_t)rps[s] * rps[s];
+            off += ((size_t)c->ngrid[m] * per + 15) & ~(size_t)15;
+        }
+    }
+    std::vector<double> buf(off - c->static_doubles, 0.0);
+    for (int s = 0; s < nstack; s++) {
+        double *dst[MAXD];
+        for (int m = 0; m < d; m++) dst[m] = buf.data() + (offs[(size_t)s * MAXD + m] - (long)c->static_doubles);
+        pad_cores_host(d, c->ngrid, rps[s], ranks + (size_t)s * (d + 1), cores + (size_t)s * d, dst);
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    if (c->hz_stack) HIPCHK(c, hipFree(c->hz_stack));
+    c->hz_stack = nullptr;
+    c->hz_nstack = 0;
+    HIPCHK(c, hipMalloc((void **)&c->hz_stack, off * sizeof(double)));
+    // the static section is copied from the arena at each simulate call (it may be rewritten in between)
+    HIPCHK(c, hipMemcpy(c->hz_stack + c->static_doubles, buf.data(), buf.size() * sizeof(double), hipMemcpyHostToDevice));
+    c->hz_stack_static = c->static_doubles;
+    c->hz_rp.swap(rps);
+    c->hz_core_off.swap(offs);
+    c->hz_nstack = nstack;
     return C3SC_OK;
 }
 
@@ -665,6 +764,7 @@ static int fill_args(c3sc_hip_ctx *c, int k, size_t F, KArgs &A, bool need_model
     A.game_gsz = c->game_gsz; // 0 unless c3sc_hip_set_game: read by the game instantiations only
     A.game_ngrp = c->game_ngrp;
     A.game_order = c->game_order;
+    A.hz_off = c->hz_dt > 0.0 ? c->hz_off : 0; // > 0 selects the horizon instantiations of a run-time compiled model
     { // ablation switches of the diagnostic build (make STAMPS=1); read once
         static const int dbg_env = [] { const char *e = getenv("C3SC_DBG"); return e ? atoi(e) : 0; }();
         A.dbg = dbg_env;
@@ -699,6 +799,13 @@ static int launch_bellman(c3sc_hip_ctx *c, int k, size_t F, const int32_t *d_idx
         if (rc != C3SC_OK) return rc;
         if (variant != C3SC_VARIANT_AUTO && variant != C3SC_VARIANT_FIBER_PER_WAVE)
             return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers: game mode runs on the fiber-per-wave kernel only (the pair and quad variants have no game form)");
+        variant = C3SC_VARIANT_FIBER_PER_WAVE;
+    }
+    if (c->hz_dt > 0.0) { // likewise in horizon mode
+        rc = check_horizon_model(c, "bellman_fibers: horizon mode needs a model compiled with horizon kernels (and no game)");
+        if (rc != C3SC_OK) return rc;
+        if (variant != C3SC_VARIANT_AUTO && variant != C3SC_VARIANT_FIBER_PER_WAVE)
+            return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers: horizon mode runs on the fiber-per-wave kernel only (the pair and quad variants have no horizon form)");
         variant = C3SC_VARIANT_FIBER_PER_WAVE;
     }
     if (F == 0) return C3SC_OK;
@@ -804,6 +911,7 @@ static int launch_box(c3sc_hip_ctx *c, int k, size_t F, const int32_t *d_idx, co
     if (!c) return C3SC_ERR_ARG;
     if (c->box_du == 0) return fail(c, C3SC_ERR_ARG, "bellman_fibers_box: c3sc_hip_set_control_box first");
     if (c->game_gsz > 0) return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_box: games have no control-box form");
+    if (c->hz_dt > 0.0) return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_box: horizon mode has no control-box form");
     if (model_ncf(c->model) != 0 && c->model != C3SC_MODEL_COTHRUST6D) // cothrust forms its features from u on the device (models.hpp: CF_FROM_U)
         return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_box: this model needs transcendental functions of the control");
     KArgs A;
@@ -919,6 +1027,7 @@ static int launch_tables(c3sc_hip_ctx *c, int k, size_t F, const int32_t *d_idx,
     if (!c) return C3SC_ERR_ARG;
     const int saved_model = c->model;
     if (c->game_gsz > 0) return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_tables: the TABLE model has no game kernels");
+    if (c->hz_dt > 0.0) return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_tables: the TABLE model has no horizon kernels");
     c->model = C3SC_MODEL_TABLE; // fill_args only checks that a model is set
     KArgs A;
     int rc = fill_args(c, k, F, A, true);
@@ -1258,9 +1367,25 @@ int c3sc_hip_simulate(c3sc_hip_ctx *c, const c3sc_hip_sim_args *a, void *stream)
         return fail(c, C3SC_ERR_UNSUPPORTED, "simulate: this model needs transcendental functions of the control in a box");
     if (a->box && c->game_gsz > 0) return fail(c, C3SC_ERR_UNSUPPORTED, "simulate: games have no control-box form");
     if (check_game_model(c, "simulate: game mode needs a model compiled with game kernels") != C3SC_OK) return C3SC_ERR_UNSUPPORTED;
+    const bool hz = c->hz_dt > 0.0; // horizon mode: one launch per step, step k's controller on the cores of V_{k+1}
+    if (hz) {
+        if (check_horizon_model(c, "simulate: horizon mode needs a model compiled with horizon kernels") != C3SC_OK) return C3SC_ERR_UNSUPPORTED;
+        if (a->box) return fail(c, C3SC_ERR_UNSUPPORTED, "simulate: horizon mode has no control-box form");
+        if (c->hz_nstack == 0) return fail(c, C3SC_ERR_ARG, "simulate: horizon mode needs the value stack (c3sc_hip_upload_value_stack)");
+        if (!(std::fabs(a->dt - c->hz_dt) <= 1e-12 * c->hz_dt))
+            return fail(c, C3SC_ERR_ARG, "simulate: in horizon mode dt must equal the horizon step (c3sc_hip_set_horizon_step)");
+        if (a->nsteps + 1 > (size_t)c->hz_nstack) return fail(c, C3SC_ERR_ARG, "simulate: nsteps exceeds the value stack (nstack - 1 stages)");
+    }
     KArgs A;
     int rc = fill_args(c, 0, 0, A, false);
     if (rc != C3SC_OK) return rc;
+    if (hz) {
+        if (c->hz_stack_static != c->static_doubles)
+            return fail(c, C3SC_ERR_ARG, "simulate: static data changed size after upload_value_stack; upload the stack again");
+        for (size_t s = 0; s <= a->nsteps; s++)
+            if (!find_sim_kernel(VARIANT_ROLLOUT, c->model, c->d, c->hz_rp[s]))
+                return fail(c, C3SC_ERR_UNSUPPORTED, "simulate: no rollout instantiation for a stage's padded rank");
+    }
     rc = check_bounds_set(c, "simulate: every dimension needs a boundary type");
     if (rc != C3SC_OK) return rc;
     if (!(a->dt > 0.0) || !std::isfinite(a->dt)) return fail(c, C3SC_ERR_ARG, "simulate: dt must be positive and finite");
@@ -1270,7 +1395,7 @@ int c3sc_hip_simulate(c3sc_hip_ctx *c, const c3sc_hip_sim_args *a, void *stream)
     if (a->save_every > a->nsteps && a->save_every > 1 && (a->d_traj || a->d_u))
         return fail(c, C3SC_ERR_ARG, "simulate: save_every larger than nsteps");
     if (a->steps_per_launch < 0) return fail(c, C3SC_ERR_ARG, "simulate: steps_per_launch < 0");
-    const KernelEntry *e = find_sim_kernel(VARIANT_ROLLOUT, c->model, c->d, c->rp);
+    const KernelEntry *e = find_sim_kernel(VARIANT_ROLLOUT, c->model, c->d, hz ? c->hz_rp[a->nsteps] : c->rp);
     if (!e) return fail(c, C3SC_ERR_UNSUPPORTED, "simulate: no rollout instantiation for this model at this padded rank");
     if (a->n == 0) return C3SC_OK;
     if (!a->d_x0) return fail(c, C3SC_ERR_ARG, "simulate: null d_x0");
@@ -1309,16 +1434,24 @@ int c3sc_hip_simulate(c3sc_hip_ctx *c, const c3sc_hip_sim_args *a, void *stream)
     S.traj = a->d_traj;
     S.u = a->d_u;
     S.vend = a->d_vend;
-    const int chunk = a->steps_per_launch > 0 ? a->steps_per_launch : 64;
+    const int chunk = hz ? 1 : (a->steps_per_launch > 0 ? a->steps_per_launch : 64);
     c->last_kernel = e->name;
     c->status_cache_valid = false;
+    if (hz) HIPCHK(c, hipMemcpyAsync(c->hz_stack, c->arena, c->static_doubles * sizeof(double), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     int s0 = 0;
     do { // at least one launch: nsteps = 0 still tests x_0 and evaluates V_end
         S.s0 = s0;
         S.s1 = (int)std::min<long long>((long long)s0 + chunk, (long long)a->nsteps);
-        LaunchIO io{c->arena, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream, &S};
+        const KernelEntry *ek = e;
+        double *ro = c->arena;
+        if (hz) { // the launch of step s0 (or the terminal-only launch of nsteps = 0) reads stage s1: V_{s0+1}, and V_nsteps at the end
+            for (int m = 0; m < c->d; m++) A.core_off[m] = c->hz_core_off[(size_t)S.s1 * MAXD + m];
+            ek = find_sim_kernel(VARIANT_ROLLOUT, c->model, c->d, c->hz_rp[S.s1]);
+            ro = c->hz_stack;
+        }
+        LaunchIO io{ro, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream, &S};
         g_launches++;
-        const hipError_t he = launch_entry(*e, A, io);
+        const hipError_t he = launch_entry(*ek, A, io);
         if (he == hipErrorNotSupported) return fail(c, C3SC_ERR_UNSUPPORTED, "simulate: this rollout kernel has no box minimiser");
         HIPCHK(c, he);
         s0 = S.s1;
@@ -1409,6 +1542,7 @@ int c3sc_hip_integrate(c3sc_hip_ctx *c, const c3sc_hip_ode_args *a, void *stream
         return fail(c, C3SC_ERR_UNSUPPORTED, "integrate: this model needs transcendental functions of the control in a box");
     if (a->box && c->game_gsz > 0) return fail(c, C3SC_ERR_UNSUPPORTED, "integrate: games have no control-box form");
     if (check_game_model(c, "integrate: game mode needs a model compiled with game kernels") != C3SC_OK) return C3SC_ERR_UNSUPPORTED;
+    if (c->hz_dt > 0.0) return fail(c, C3SC_ERR_UNSUPPORTED, "integrate: deterministic closed loops are not offered in horizon mode");
     KArgs A;
     int rc = fill_args(c, 0, 0, A, false);
     if (rc != C3SC_OK) return rc;

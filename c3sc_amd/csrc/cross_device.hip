@@ -1689,6 +1689,8 @@ int c3sc_hip_cross_iteration_pi(c3sc_hip_ctx *c, c3sc_hip_ctx *policy_ctx, long 
     if (!policy_ctx) return fail(c, C3SC_ERR_ARG, "cross_iteration_pi: null policy context");
     if ((c && c->game_gsz > 0) || policy_ctx->game_gsz > 0)
         return fail(c, C3SC_ERR_UNSUPPORTED, "cross_iteration_pi: policy iteration is not offered for games (c3sc_hip_set_game)");
+    if ((c && c->hz_dt > 0.0) || policy_ctx->hz_dt > 0.0)
+        return fail(c, C3SC_ERR_UNSUPPORTED, "cross_iteration_pi: policy iteration is not offered in horizon mode (c3sc_hip_set_horizon_step)");
     return cross_iteration_impl(c, policy_ctx, policy_tag, 0, stream);
 }
 

@@ -32,6 +32,16 @@ struct c3sc_hip_ctx {
     std::vector<double> cands;
     // zero-sum game (c3sc_hip_set_game): cands is the product list, game_ngrp groups of game_gsz; game_gsz = 0: no game
     int game_gsz = 0, game_ngrp = 0, game_order = 0;
+    // finite horizon (c3sc_hip_set_horizon_step): the step delta (0: off); {delta, exp(-beta delta), delta / h^2} sit at hz_off of
+    // the static section.  The value stack (c3sc_hip_upload_value_stack): one buffer [static copy | stage 0 cores | stage 1 ...]
+    // laid out for a static section of hz_stack_static doubles; stage s padded to hz_rp[s], its cores at hz_core_off[s * MAXD + m]
+    double hz_dt = 0.0;
+    int hz_off = 0;
+    double *hz_stack = nullptr;
+    size_t hz_stack_static = 0;
+    int hz_nstack = 0;
+    std::vector<int> hz_rp;
+    std::vector<long> hz_core_off;
     // continuous controls (c3sc_hip_set_control_box)
     int box_du = 0, box_grid = 0, box_polish = 0;
     double box_lb[C3SC_MAX_DU] = {0}, box_ub[C3SC_MAX_DU] = {0};

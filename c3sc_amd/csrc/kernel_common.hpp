@@ -50,6 +50,9 @@ struct KArgs {
     double *uopt;              // [F][N][du] minimiser per node (may be null)
     const double *forced_u;    // policy evaluation with continuous controls: [F][N][du] control to apply, or null
     int tbl_off;               // fiber-pair kernel: offset (doubles) of the candidate / node tables in dynamic LDS
+    int hz_off;                // horizon mode (c3sc_hip_set_horizon_step), read by the HORIZON instantiations
+                               // only: offset (doubles) into `ro` of {delta, exp(-beta delta), delta / h^2}.  It sits in the
+                               // alignment hole after tbl_off: KArgs keeps its size and every other offset
     // fiber-quad kernel (kernel_fiber_quad.hpp): extra copies of the cores made by k_quad_aux, offsets into `ro`
     long quad_coreT_off[MAXD]; // middle cores row-major (a*RP + b): the staged matrix of the suffix-side levels
     long quad_aop_off[MAXD];   // middle cores as MFMA A operands: [N][c | a][MB][C][64]
@@ -105,6 +108,20 @@ template <class Model>
 constexpr bool model_game()
 {
     if constexpr (requires { Model::GAME; }) return Model::GAME;
+    else return false;
+}
+
+// The finite-horizon instantiations are those of a model wrapped in HorizonOf, in the style of GameOf:
+// k_fiber_per_wave and k_rollout pass model_horizon<Model>() to node_backup as HORIZON, which then takes the explicit
+// finalisation with the fixed step delta instead of the per-candidate interpolation interval h^2 / Q.
+template <class M>
+struct HorizonOf : M {
+    static constexpr bool HORIZON = true;
+};
+template <class Model>
+constexpr bool model_horizon()
+{
+    if constexpr (requires { Model::HORIZON; }) return Model::HORIZON;
     else return false;
 }
 
@@ -559,7 +576,16 @@ __device__ __forceinline__ void upwind_rates(double t, double t2, double b, doub
 // strict '<' / '>'), a skipped (stationary) candidate takes no part, a group with no candidate left takes no part in the outer
 // reduction.  Group ends are list positions, i.e. wave-uniform; the selection is selects only.  ui and fu are pair indices
 // iu * nw + iw.
-template <class Model, int CG = 1, int CGD = 1, class Cand = CandRegs<Model>, bool SPLIT = true, class Pre = NoPre, bool GAME = false>
+//
+// HORIZON (finite-horizon problems): Kushner's explicit scheme with the fixed step delta in place of the
+// interpolation interval h^2 / Q.  V is the stencil of V_{n+1} and every candidate's value is
+//     g delta + exp(-beta delta) (V_self + (delta / h^2) (PV - Q V_self)),
+// i.e. transition probabilities delta p_i / h^2 and the self-loop 1 - Q delta / h^2.  No division: Q = 0 is a legal "stay"
+// candidate (it is neither skipped nor flagged STATIONARY).  A candidate with Q delta / h^2 > 1 (a negative self-loop) still
+// takes part and raises C3SC_STATUS_CFL.  Scan order, first strict '<', absorbed nodes and the forced path are the plain
+// scan's.  delta, exp(-beta delta) and delta / h^2 are wave-uniform host values in `ro` at A.hz_off.
+template <class Model, int CG = 1, int CGD = 1, class Cand = CandRegs<Model>, bool SPLIT = true, class Pre = NoPre, bool GAME = false,
+          bool HORIZON = false>
 __device__ inline double node_backup(const KArgs &A, const double *__restrict__ ro, const double (&x)[Model::D],
                                      const double (&tv)[Model::NTAB > 0 ? Model::NTAB : 1], const Cand &cr,
                                      const double (&V)[2 * Model::D + 1], int ab, int &ui, unsigned &st, bool forced = false,
@@ -627,6 +653,62 @@ __device__ inline double node_backup(const KArgs &A, const double *__restrict__ 
     }
     double best = 0.0;
     constexpr int NCFa = Model::NCF > 0 ? Model::NCF : 1;
+    if constexpr (HORIZON) {
+        static_assert(!GAME && CG == 1 && CGD == 1, "the horizon scan takes one candidate per trip and no game");
+        const double hdt = ro[A.hz_off], hdisc = ro[A.hz_off + 1], hdh2 = ro[A.hz_off + 2];
+        const double Vs = V[2 * D];
+        double bestv = __builtin_inf();
+        bool cfl = false;
+        for (int c = 0; c < nc; c++) {
+            double u[DU], cf[NCFa];
+#pragma unroll
+            for (int i = 0; i < DU; i++) u[i] = cr.get_u(i, c);
+            cf[0] = 0.0;
+#pragma unroll
+            for (int i = 0; i < Model::NCF; i++) cf[i] = cr.get_cf(i, c);
+            double b[D], sg[D];
+            Model::drift(A.prm, nd, x, u, cf, b);
+            Model::sigma(A.prm, x, u, sg);
+            double stage = stage0;
+            if constexpr (stage_usep<Model>()) stage = stage0 + cr.get_cf(0, c);
+            else if constexpr (Model::STAGE_UDEP) stage = Model::stage(A.prm, x, u);
+            double Q = Q0, PV = PV0;
+            constexpr unsigned UCh = Model::UCONST_MASK;
+#pragma unroll
+            for (int m = 0; m < D; m++) {
+                if ((UM >> m) & 1u) {
+                    double pm, pp;
+                    if ((UCh >> m) & 1u) {
+                        pm = cr.get_rpm(CandRegs<Model>::ucslot(m), c);
+                        pp = cr.get_rpp(CandRegs<Model>::ucslot(m), c);
+                    } else {
+                        const double half = t2l[m] * (sg[m] * sg[m]) / 2.0;
+                        const double tb = tl[m] * b[m];
+                        pm = (b[m] < -1e-14) ? half - tb : half;
+                        pp = (b[m] > 1e-14) ? half + tb : half;
+                    }
+                    if constexpr (UCh != UM) {
+                        Q += pm;
+                        Q += pp;
+                    }
+                    PV = fma(pm, V[2 * m], PV);
+                    PV = fma(pp, V[2 * m + 1], PV);
+                }
+            }
+            if constexpr (UCh == UM) Q = Q0 + cr.get_qab(c);
+            const double ctg = Vs + hdh2 * (PV - Q * Vs);
+            const double val = stage * hdt + hdisc * ctg;
+            const bool take = forced ? (c == fu) : (val < bestv); // +inf loses to the first candidate
+            cfl |= (Q * hdh2 > 1.0) & (forced ? (c == fu) : true);
+            bestv = take ? val : bestv;
+            ui = take ? c : ui;
+        }
+        if (cfl & (ab == 0)) st |= C3SC_STATUS_CFL;
+        best = (ui >= 0) ? bestv : 0.0;
+        best = (ab != 0) ? absorbed_cost : best;
+        ui = (ab != 0) ? -1 : ui;
+        return best;
+    }
     if (A.discount == 0.0) {
         // Undiscounted problems (beta = 0, exp(-beta dt) = 1): value_c = (h2*stage_c + PV_c)/Q_c + residue, so
         // the scan compares the candidates as fractions num_c/Q_c by cross-multiplication and divides ONCE for

@@ -326,7 +326,7 @@ __global__ void __launch_bounds__(256) k_rollout(const KArgs A, const SimK S, co
         }
         if (!boxed) {
             int ui;
-            (void)node_backup<Model, 1, 1, CandLds<Model>, true, NoPre, model_game<Model>()>(A, ro, xin, tv, cr, V, ab, ui, st);
+            (void)node_backup<Model, 1, 1, CandLds<Model>, true, NoPre, model_game<Model>(), model_horizon<Model>()>(A, ro, xin, tv, cr, V, ab, ui, st);
             const int uc = ui < 0 ? 0 : (model_game<Model>() ? game_pair_to_list(A, ui) : ui); // game: the saddle pair's list position
 #pragma unroll
             for (int k = 0; k < DU; k++) u[k] = (ui >= 0) ? ro[A.cands_off + uc * DU + k] : 0.0; // obstacle: u = 0
@@ -369,8 +369,11 @@ __global__ void __launch_bounds__(256) k_rollout(const KArgs A, const SimK S, co
             for (int m = 0; m < D; m++) S.traj[((size_t)i * nrow + (s + 1) / se) * D + m] = x[m];
     }
     if (S.s1 == S.nsteps) { // the final state: its exit test and the value there
-        exit_test(S.nsteps, exp(-beta * ((double)S.nsteps * dt)));
-        if (S.vend) {
+        const double dend = exp(-beta * ((double)S.nsteps * dt));
+        exit_test(S.nsteps, dend);
+        // horizon mode: this launch carries the cores of V_nsteps, and a trajectory still alive at the end pays
+        // the discounted interpolant there, so that the mean of J estimates V_0(x_0)
+        if (S.vend || model_horizon<Model>()) {
             double xin[D], V[2 * D + 1];
             int ab;
             if (S.wrap) wrap_periodic<D>(A, ro, x, xin);
@@ -378,7 +381,8 @@ __global__ void __launch_bounds__(256) k_rollout(const KArgs A, const SimK S, co
 #pragma unroll
                 for (int m = 0; m < D; m++) xin[m] = x[m];
             offgrid_stencil<D, RP>(A, ro, xin, S.constelm, V, ab);
-            S.vend[i] = V[2 * D];
+            if (S.vend) S.vend[i] = V[2 * D];
+            if constexpr (model_horizon<Model>()) J = (ex < 0) ? J + dend * V[2 * D] : J;
         }
     }
 #pragma unroll

@@ -108,6 +108,7 @@ RtcEntries rtc_entries();
 hipError_t rtc_launch(const KernelEntry &e, const KArgs &A, const LaunchIO &io);
 bool rtc_model_known(int model); // an id c3sc_hip_model_compile returned
 bool rtc_model_info(int model, int &du, bool &game); // its control dimension and whether it has game kernels (false: unknown id)
+bool rtc_model_horizon(int model); // it was compiled with the finite-horizon kernels (c3sc_hip_model_compile_fh, horizon = 1)
 inline hipError_t launch_entry(const KernelEntry &e, const KArgs &A, const LaunchIO &io) { return e.rtc ? rtc_launch(e, A, io) : e.fn(A, io); }
 #endif
 

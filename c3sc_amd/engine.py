@@ -36,6 +36,7 @@ EXPORTS = [
     "c3sc_hip_integrate", "c3sc_hip_integrate_host",
     "c3sc_hip_model_compile", "c3sc_hip_model_code_object", "c3sc_hip_model_log",
     "c3sc_hip_set_game", "c3sc_hip_model_compile_ex", "c3sc_hip_model_code_object_ex",
+    "c3sc_hip_model_compile_fh", "c3sc_hip_model_code_object_fh", "c3sc_hip_set_horizon_step", "c3sc_hip_upload_value_stack",
 ]
 
 class SimArgs(C.Structure):
@@ -70,6 +71,11 @@ class ModelSpec(C.Structure):
 class ModelSpecEx(C.Structure):
     """struct c3sc_hip_model_spec_ex (include/c3sc_hip.h): the spec plus the game flag"""
     _fields_ = [("base", ModelSpec), ("game", C.c_int)]
+
+
+class ModelSpecFh(C.Structure):
+    """struct c3sc_hip_model_spec_fh (include/c3sc_hip.h): the _ex spec plus the horizon flag"""
+    _fields_ = [("ex", ModelSpecEx), ("horizon", C.c_int)]
 
 
 MODEL_USER = 1000  # C3SC_MODEL_USER: first id of the run-time compiled models
@@ -139,6 +145,10 @@ def load_library():
         L.c3sc_hip_model_compile_ex.argtypes = [C.POINTER(ModelSpecEx), c_int_p]
         L.c3sc_hip_model_code_object_ex.argtypes = [C.POINTER(ModelSpecEx), C.c_void_p, c_size_p]
         L.c3sc_hip_set_game.argtypes = [C.c_void_p, C.c_int, C.c_int, c_double_p, C.c_int, c_double_p, C.c_int]
+        L.c3sc_hip_model_compile_fh.argtypes = [C.POINTER(ModelSpecFh), c_int_p]
+        L.c3sc_hip_model_code_object_fh.argtypes = [C.POINTER(ModelSpecFh), C.c_void_p, c_size_p]
+        L.c3sc_hip_set_horizon_step.argtypes = [C.c_void_p, C.c_double]
+        L.c3sc_hip_upload_value_stack.argtypes = [C.c_void_p, C.c_int, c_size_p, C.POINTER(c_double_p)]
         _LIB = L
     return _LIB
 
@@ -168,15 +178,19 @@ def _model_fail(rc, what):
 
 
 def compile_model(source: str, d: int, du: int, ranks=(4, 8), box: bool = False, udep_mask: int = 0, uconst_mask: int = 0,
-                  stage_udep: bool = True, name: Optional[str] = None, game: bool = False) -> int:
+                  stage_udep: bool = True, name: Optional[str] = None, game: bool = False, horizon: bool = False) -> int:
     """Compile a device model from source (c3sc_hip_model_compile, include/c3sc_hip.h states the source contract) and return
     its model id (>= MODEL_USER), usable wherever a built-in model id is.  No GPU is needed.  Raises C3scHipError with the
     compiler's log on failure; the error code is args[1].  game=True (c3sc_hip_model_compile_ex) adds the game kernels that
-    BellmanEngine.set_game needs: the control vector is then (u, w) of the two players."""
+    BellmanEngine.set_game needs: the control vector is then (u, w) of the two players.  horizon=True
+    (c3sc_hip_model_compile_fh) adds the finite-horizon kernels that BellmanEngine.set_horizon_step needs."""
     L = load_library()
     spec = _model_spec(source, d, du, tuple(ranks), box, udep_mask, uconst_mask, stage_udep, name)
     mid = C.c_int(0)
-    if game:
+    if horizon:
+        fh = ModelSpecFh(ModelSpecEx(spec, 1 if game else 0), 1)
+        rc = L.c3sc_hip_model_compile_fh(C.byref(fh), C.byref(mid))
+    elif game:
         ex = ModelSpecEx(spec, 1)
         rc = L.c3sc_hip_model_compile_ex(C.byref(ex), C.byref(mid))
     else:
@@ -187,7 +201,7 @@ def compile_model(source: str, d: int, du: int, ranks=(4, 8), box: bool = False,
 
 
 def code_object(source: str, d: int, du: int, ranks=(4, 8), box: bool = False, udep_mask: int = 0, uconst_mask: int = 0,
-                stage_udep: bool = True, name: Optional[str] = None, game: bool = False) -> bytes:
+                stage_udep: bool = True, name: Optional[str] = None, game: bool = False, horizon: bool = False) -> bytes:
     """The gfx950 code object of this spec (c3sc_hip_model_code_object): the loaded one if compile_model already compiled the
     spec, otherwise what compile_model would build now (its id and default name are in the kernel names), compiled and not
     registered."""
@@ -197,7 +211,10 @@ def code_object(source: str, d: int, du: int, ranks=(4, 8), box: bool = False, u
     for _ in range(2):
         buf = C.create_string_buffer(cap)
         size = C.c_size_t(cap)
-        if game:
+        if horizon:
+            fh = ModelSpecFh(ModelSpecEx(spec, 1 if game else 0), 1)
+            rc = L.c3sc_hip_model_code_object_fh(C.byref(fh), buf, C.byref(size))
+        elif game:
             rc = L.c3sc_hip_model_code_object_ex(C.byref(ModelSpecEx(spec, 1)), buf, C.byref(size))
         else:
             rc = L.c3sc_hip_model_code_object(C.byref(spec), buf, C.byref(size))
@@ -303,6 +320,24 @@ class BellmanEngine:
 
     def clear_game(self):
         self._chk(self.L.c3sc_hip_set_game(self.h, 0, 0, None, 0, None, 0), "set_game")
+
+    def set_horizon_step(self, dt: float):
+        """Finite-horizon mode (c3sc_hip_set_horizon_step): the Bellman calls apply Kushner's explicit scheme with the fixed step
+        dt, one stage back from the uploaded value; dt = 0 ends it.  The model must be compiled with horizon=True."""
+        self._chk(self.L.c3sc_hip_set_horizon_step(self.h, C.c_double(dt)), "set_horizon_step")
+        self.horizon_dt = float(dt)
+
+    def upload_value_stack(self, ranks, cores):
+        """V_0 .. V_N for simulate in horizon mode (c3sc_hip_upload_value_stack): ranks[s] is stage s's rank list (d + 1 entries),
+        cores[s] its d cores in upload_value's layout.  An empty list frees the stack."""
+        ns = len(ranks)
+        if ns == 0:
+            self._chk(self.L.c3sc_hip_upload_value_stack(self.h, 0, None, None), "upload_value_stack")
+            return
+        rk = np.ascontiguousarray(np.asarray(ranks).reshape(ns, -1), dtype=np.uintp)
+        cs = [_f64(c) for stage in cores for c in stage]
+        self._chk(self.L.c3sc_hip_upload_value_stack(self.h, C.c_int(ns), rk.ctypes.data_as(c_size_p), _ptr_array(cs)),
+                  "upload_value_stack")
 
     def set_variant(self, variant: int):
         self._chk(self.L.c3sc_hip_set_variant(self.h, C.c_int(variant)), "set_variant")
@@ -427,7 +462,9 @@ class BellmanEngine:
                  stream_ptr: Optional[int] = None):
         """Device API (c3sc_hip_simulate): x0_t float64 CUDA tensor (n, d).  Returns a dict of CUDA tensors: cost (n,),
         exit (int64, -1 = never), vend (n,), xfinal (n, d) and, with save_every > 0, traj (n, nsteps//save_every + 1, d)
-        and u (n, ceil(nsteps/save_every), du).  noise_t: float64 (n, nsteps, d) standard normals, else Philox(seed)."""
+        and u (n, ceil(nsteps/save_every), du).  noise_t: float64 (n, nsteps, d) standard normals, else Philox(seed).
+        In horizon mode (set_horizon_step, upload_value_stack) dt must be the horizon step, step k's controller uses V_{k+1},
+        and cost includes the discounted terminal value V_nsteps(x_nsteps) of the trajectories still alive."""
         import torch
 
         assert x0_t.is_cuda and x0_t.dtype == torch.float64 and x0_t.is_contiguous() and x0_t.shape[1] == self.d

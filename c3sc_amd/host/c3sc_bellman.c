@@ -375,6 +375,7 @@ struct DPparam {
     double prm[C3SC_MAX_PARAMS];
     int nprm;
     int model_checked;
+    double hz_dt; /* finite-horizon step delta (c3control_set_horizon_step); 0: the infinite-horizon operator */
 };
 
 struct DPparam *dp_param_create(size_t dx, size_t du, size_t dw, double discount)
@@ -426,6 +427,25 @@ void control_params_destroy(struct ControlParams *c) { free(c); }
 
 struct Memory { void *shared; size_t private; }; /* bellman.c:59-63 */
 
+/* the explicit finite-horizon backup of one candidate (node_backup's HORIZON branch): the upwind rates of
+ * assemble_rates un-normalised, Q = sum p_i, PV = sum p_i V_i, and g delta + e^{-beta delta} (V_self + (delta / h^2) (PV - Q V_self)).
+ * No division: Q = 0 is a legal "stay" candidate */
+static double horizon_rhs(size_t dx, double h2, const double *tv, double delta, double beta, const double *drift, const double *diff,
+                          double stage, const double *costs)
+{
+    double Q = 0.0, PV = 0.0;
+    for (size_t m = 0; m < dx; m++) {
+        const double t = tv[2 * m], t2 = tv[2 * m + 1], s = diff[m * dx + m];
+        const double half = t2 * (s * s) / 2.0, tb = t * drift[m];
+        const double pm = drift[m] < -1e-14 ? half - tb : half, pp = drift[m] > 1e-14 ? half + tb : half;
+        Q += pm;
+        Q += pp;
+        PV += pm * costs[2 * m] + pp * costs[2 * m + 1];
+    }
+    const double vs = costs[2 * dx];
+    return stage * delta + exp(-beta * delta) * (vs + delta / h2 * (PV - Q * vs));
+}
+
 double bellman_control(size_t du, const double *u, double *grad_u, void *args)
 { /* bellman.c:367-480: objective of one control at one node; reads the node's costs/absorbed from the workspace */
     struct Memory *mem = args;
@@ -445,6 +465,14 @@ double bellman_control(size_t du, const double *u, double *grad_u, void *args)
     double *costs = workspace_get_costs(w, node);
     double stage;
     int res;
+    if (dp->hz_dt > 0.0) { /* horizon mode: the explicit scheme; only candidate lists (the box minimiser has no horizon form) */
+        if (grad_u != NULL) DIE("bellman_control: horizon mode has no gradient (control-box) form");
+        res = drift_eval(dp->drift, p->time, x, u, drift, NULL); assert(res == 0);
+        res = diff_eval(dp->diff, p->time, x, u, diff, NULL); assert(res == 0);
+        res = dp->stagecost(p->time, x, u, &stage, NULL); assert(res == 0);
+        (void)res;
+        return horizon_rhs(dx, p->mca->h2, p->mca->t, dp->hz_dt, dp->discount, drift, diff, stage, costs);
+    }
     if (grad_u != NULL) {
         double *gdrift = workspace_get_grad_drift(w, node), *gdiff = workspace_get_grad_diff(w, node);
         double *gprob = workspace_get_grad_prob(w, node), *gdt = workspace_get_grad_dt(w, node);
@@ -555,6 +583,9 @@ static struct c3sc_hip_ctx *sync_device_ctx(struct ControlParams *cp, struct c3s
     if (gorder >= 0 && dp->model == 0) DIE("bellman_vi: games need a device model compiled with game kernels (c3sc_hip_model_compile_ex)");
     sig = fnv(sig, &gorder, sizeof(int));
     sig = fnv(sig, &gnu, sizeof(size_t));
+    if (dp->hz_dt > 0.0 && (!brute || gorder >= 0 || dp->model == 0))
+        DIE("bellman_vi: horizon mode needs a device model compiled with horizon kernels (c3sc_hip_model_compile_fh) and a plain candidate list");
+    sig = fnv(sig, &dp->hz_dt, sizeof(double));
     if (brute) sig = fnv(sig, c3opt_get_brute_vals(cp->opt), c3opt_get_nbrute(cp->opt) * odu * sizeof(double));
     else {
         const size_t g = c3opt_get_box_grid(cp->opt), pl = c3opt_get_box_polish(cp->opt);
@@ -577,6 +608,7 @@ static struct c3sc_hip_ctx *sync_device_ctx(struct ControlParams *cp, struct c3s
         else
             hipok(ctx, c3sc_hip_set_control_box(ctx, (int)odu, c3opt_get_lb(cp->opt), c3opt_get_ub(cp->opt), (int)c3opt_get_box_grid(cp->opt),
                                                 (int)c3opt_get_box_polish(cp->opt)), "c3sc_hip_set_control_box");
+        hipok(ctx, c3sc_hip_set_horizon_step(ctx, dp->hz_dt), "c3sc_hip_set_horizon_step");
         g_ctx[sl].cfg_set = 1;
         g_ctx[sl].cfg_sig = sig;
         g_ctx[sl].version = 0; /* set_grid invalidates the resident value function */
@@ -689,10 +721,12 @@ static double now_s(void) { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &
 /* transition_assemble's "stationary node" outcome (nodeutil.c:365-367; bellman.c:452 asserts on it) comes back as a
  * device flag.  The public per-fiber entry points read it after every call; the index-based batch entry points of the
  * solver loops read it once per sweep (c3control_end_vi / end_pi_step) -- a status read is a device round trip. */
+static unsigned g_status_seen; /* every status bit the reads below cleared (c3control_fh_solve looks for C3SC_STATUS_CFL) */
 static void die_if_stationary(struct c3sc_hip_ctx *ctx)
 {
     unsigned st = 0;
     hipok(ctx, c3sc_hip_get_status(ctx, &st, 1), "c3sc_hip_get_status");
+    g_status_seen |= st;
     if (st & C3SC_STATUS_STATIONARY) DIE("transition_assemble: stationary node (Q < 1e-14); the reference asserts here (bellman.c:452)");
 }
 
@@ -907,10 +941,18 @@ static void refuse_game_pi(const struct c3Opt *opt, const char *who)
         DIE("%s: policy iteration is not offered for games (c3opt_set_brute_force_game); use value iteration", who);
 }
 
+/* nor in horizon mode: a finite-horizon problem has no stationary policy to iterate on */
+static void refuse_horizon_pi(const struct DPparam *dp, const char *who)
+{
+    if (dp != NULL && dp->hz_dt > 0.0)
+        DIE("%s: policy iteration is not offered in horizon mode (c3control_set_horizon_step); use c3control_fh_solve", who);
+}
+
 static int pi_core(struct PIparam *pi, size_t F, size_t k0, const int32_t *idx, const double *x_in, double *out, int fast)
 {
     struct ControlParams *cp = pi->cp;
     refuse_game_pi(cp->opt, "bellman_pi");
+    refuse_horizon_pi(cp->dp, "bellman_pi");
     struct MCAparam *mca = cp->mca;
     struct DPparam *dp = cp->dp;
     const size_t dx = mca->dx, N = mca->ngrid[k0];
@@ -1223,6 +1265,7 @@ struct PIparam *c3control_begin_pi(struct C3Control *c, struct ValueF *policy)
 void c3control_begin_pi_step(struct C3Control *c, struct PIparam *pi, struct ValueF *vf, struct c3Opt *opt)
 { /* c3control_step_pi before valuef_interp (bellman.c:2236-2249) */
     refuse_game_pi(opt, "c3control_step_pi");
+    refuse_horizon_pi(c->dp, "c3control_step_pi");
     c->cp_active = control_params_create(c->dx, c->dw, c->dp, c->mca, c->work, opt);
     pi_param_add_cp(pi, c->cp_active);
     pi_param_add_value(pi, vf);
@@ -1474,10 +1517,43 @@ struct ValueF *c3control_vi_solve(struct C3Control *c, size_t maxiter, double ab
     return start;
 }
 
+void c3control_set_horizon_step(struct C3Control *c, double delta)
+{
+    if (!(delta >= 0.0) || !isfinite(delta)) DIE("c3control_set_horizon_step: delta must be >= 0 and finite (0 ends horizon mode)");
+    c->dp->hz_dt = delta;
+    c->dp->model_checked = 0; /* the first-fiber check runs again, against the operator now in force */
+}
+
+double c3control_get_horizon_step(const struct C3Control *c) { return c->dp->hz_dt; }
+
+struct ValueF **c3control_fh_solve(struct C3Control *c, size_t nstages, double delta, struct ValueF *terminal,
+                                   struct ApproxArgs *apargs, struct c3Opt *opt, int verbose)
+{ /* V_N = terminal, V_n = one explicit step back from V_{n+1} (c3control_step_vi in horizon mode) */
+    if (nstages < 1 || terminal == NULL || !(delta > 0.0)) DIE("c3control_fh_solve: nstages >= 1, a terminal value and delta > 0");
+    c3control_set_horizon_step(c, delta);
+    workspace_reset_vi_htable(c->work);
+    struct ValueF **V = xcalloc(nstages + 1, sizeof(struct ValueF *));
+    V[nstages] = valuef_copy(terminal);
+    for (size_t s = nstages; s-- > 0;) {
+        g_status_seen = 0;
+        V[s] = c3control_step_vi(c, V[s + 1], apargs, opt, verbose - 1, NULL);
+        if (g_status_seen & C3SC_STATUS_CFL) {
+            fprintf(stderr, "c3control_fh_solve: stage %zu raised C3SC_STATUS_CFL (a candidate with Q delta > h^2: negative self-loop "
+                            "probability); reduce delta\n", s);
+            for (size_t i = s; i <= nstages; i++) valuef_destroy(V[i]);
+            free(V);
+            return NULL;
+        }
+        if (verbose > 0) printf("\t Finite horizon: stage %zu of %zu, norm %3.5E\n", s, nstages, valuef_norm(V[s]));
+    }
+    return V;
+}
+
 struct ValueF *c3control_pi_solve(struct C3Control *c, size_t maxiter, double abs_conv_tol, struct ValueF *policy,
                                   struct ApproxArgs *apargs, struct c3Opt *opt, int verbose, struct Diag **diag)
 { /* bellman.c:2343-2407 */
     refuse_game_pi(opt, "c3control_pi_solve");
+    refuse_horizon_pi(c->dp, "c3control_pi_solve");
     struct ValueF *start = valuef_copy(policy);
     struct PIparam *poli = c3control_begin_pi(c, policy);
     double stot = 1.0;
@@ -1554,6 +1630,9 @@ int c3control_policy_eval(struct C3Control *c, double t, const double *x, double
     int res = mca_get_neighbor_node_costs(c->dx, x, c->bound, c->policy_sim, c->ngrid, c->xgrid, absorbed, costs);
     assert(res == 0);
     (void)res;
+    /* the explicit scheme weighs the node's own value by the self-loop 1 - Q delta / h^2 (the infinite-horizon operator's weight
+     * there is a rounding residue, and the stencil leaves that entry as it was): the interpolant at x, as the device rollouts use */
+    if (c->dp->hz_dt > 0.0 && *absorbed == 0) costs[2 * c->dx] = valuef_eval(c->policy_sim, x);
     if (c->prevpol == NULL) c->prevpol = xcalloc(c->du, sizeof(double));
     for (size_t i = 0; i < c->du; i++) u[i] = c->prevpol[i];
     control_params_add_time_and_states(cp, t, 1, x);

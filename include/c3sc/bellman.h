@@ -177,6 +177,18 @@ struct ValueF *c3control_step_vi(struct C3Control *, struct ValueF *vf, struct A
                                  size_t *nevals);                                           /* bellman.c:2177-2212 */
 struct ValueF *c3control_step_pi(struct C3Control *, struct ValueF *vf, struct PIparam *, struct ApproxArgs *,
                                  struct c3Opt *, int verbose, size_t *niter_evals);         /* bellman.c:2214-2262 */
+/* new: finite-horizon problems.  c3control_set_horizon_step(c, delta) switches the Bellman operator to Kushner's
+ * explicit scheme with the fixed step delta (0 switches back): V_n(x) = min_u [ g delta + e^{-beta delta} (V_self + (delta / h^2)
+ * (PV - Q V_self)) ] over the stencil of V_{n+1}.  It holds for the host scan (bellman_optimal, c3control_policy_eval /
+ * c3control_controller), the first-fiber check and the device context (which needs a model compiled with
+ * c3sc_hip_model_compile_fh, horizon = 1, and a candidate list).  Policy iteration stops with a message in horizon mode.
+ * c3control_fh_solve returns V_0 .. V_nstages (nstages + 1 value functions, the caller frees each and the array): V_nstages is a
+ * copy of terminal, V_n = c3control_step_vi(V_{n+1}) in horizon mode.  It leaves horizon mode on with delta.  A stage that raises
+ * C3SC_STATUS_CFL (Q delta > h^2: a negative self-loop) stops the solve: a message, and NULL. */
+void c3control_set_horizon_step(struct C3Control *, double delta);
+double c3control_get_horizon_step(const struct C3Control *);
+struct ValueF **c3control_fh_solve(struct C3Control *, size_t nstages, double delta, struct ValueF *terminal, struct ApproxArgs *,
+                                   struct c3Opt *, int verbose);
 struct ValueF *c3control_vi_solve(struct C3Control *, size_t maxiter, double abs_conv_tol, struct ValueF *vo,
                                   struct ApproxArgs *, struct c3Opt *, int verbose, struct Diag **diag); /* :2282-2340 */
 struct ValueF *c3control_pi_solve(struct C3Control *, size_t maxiter, double abs_conv_tol, struct ValueF *policy,

@@ -68,8 +68,10 @@ enum {
 
 /* status bits accumulated by the kernels (c3sc_hip_get_status) */
 enum {
-    C3SC_STATUS_STATIONARY = 1u /* transition_assemble would have returned 1 (Q < 1e-14, nodeutil.c:365);
+    C3SC_STATUS_STATIONARY = 1u, /* transition_assemble would have returned 1 (Q < 1e-14, nodeutil.c:365);
                                    the reference asserts (bellman.c:452); the candidate is skipped here */
+    C3SC_STATUS_CFL = 2u         /* horizon mode (c3sc_hip_set_horizon_step): a candidate with Q delta > h^2, i.e. a negative
+                                   self-loop probability 1 - Q delta / h^2; it still took part in the scan */
 };
 
 /* kernel variants (c3sc_hip_set_variant); 0 lets the library choose.  Set the variant BEFORE uploading the value: the padded
@@ -486,6 +488,37 @@ typedef struct c3sc_hip_model_spec_ex {
 } c3sc_hip_model_spec_ex;
 int c3sc_hip_model_compile_ex(const c3sc_hip_model_spec_ex *spec, int *model_id);
 int c3sc_hip_model_code_object_ex(const c3sc_hip_model_spec_ex *spec, void *buf, size_t *size);
+
+/* Finite-horizon problems: a deadline T = N delta, a terminal cost V_N and a value V_n per stage.  In horizon
+ * mode the Bellman operator is Kushner's explicit scheme with the fixed step delta (one stage back, V_{n+1} -> V_n):
+ *     V_n(x) = min_u [ g(x,u) delta + e^{-beta delta} ( V_self + (delta / h^2) (PV - Q V_self) ) ]
+ * with the upwind rates p_i of the infinite-horizon operator, Q = sum p_i, PV = sum p_i V_i and V_self the node's own value, all
+ * of V_{n+1} (the uploaded value).  The transition probabilities are delta p_i / h^2 and the self-loop 1 - Q delta / h^2.  There
+ * is no division: a candidate with Q = 0 ("stay") is not skipped.  A candidate with Q delta > h^2 (negative self-loop) still takes
+ * part and raises C3SC_STATUS_CFL.  Scan order and ties, absorbed and obstacle nodes and the forced path (policy evaluation) are
+ * the infinite-horizon operator's.
+ * The horizon kernels exist only in run-time compiled models built with c3sc_hip_model_compile_fh and horizon = 1 (the forms of
+ * the per-wave and rollout kernels at every requested rank).  horizon = 1 with ex.game = 1 or ex.base.box = 1 returns
+ * C3SC_ERR_UNSUPPORTED; horizon = 0 is exactly c3sc_hip_model_compile_ex. */
+typedef struct c3sc_hip_model_spec_fh {
+    c3sc_hip_model_spec_ex ex;
+    int horizon;
+} c3sc_hip_model_spec_fh;
+int c3sc_hip_model_compile_fh(const c3sc_hip_model_spec_fh *spec, int *model_id);
+int c3sc_hip_model_code_object_fh(const c3sc_hip_model_spec_fh *spec, void *buf, size_t *size);
+/* horizon mode on with the step dt > 0, off with dt = 0.  C3SC_ERR_UNSUPPORTED for built-in and TABLE models, a model compiled
+ * without horizon kernels and a context in game mode.  Honoured by bellman_fibers(_all|_host), policy_fibers(_all|_host) (on the
+ * fiber-per-wave kernel: AUTO picks it, a forced pair or quad variant is refused) and the cross calls that launch through them.
+ * Refused (C3SC_ERR_UNSUPPORTED): the box calls, cross_iteration_pi and integrate.  set_mca after it keeps delta and recomputes
+ * the wave-uniform constants. */
+int c3sc_hip_set_horizon_step(c3sc_hip_ctx *ctx, double dt);
+/* V_0 .. V_{nstack-1} on the device for c3sc_hip_simulate in horizon mode: ranks is [nstack][d + 1] (each row as
+ * c3sc_hip_upload_value's), cores is [nstack][d] host pointers in c3sc_hip_upload_value's layout.  Stages may differ in rank;
+ * each is padded to its own instantiation.  nstack = 0 frees the stack.  The uploaded value (upload_value) is untouched.
+ * c3sc_hip_simulate in horizon mode with a stack needs dt == delta (to 1e-12 relative) and nsteps <= nstack - 1; the controller
+ * of step k uses V_{k+1}; a trajectory still alive after nsteps adds e^{-beta nsteps delta} V_nsteps(x_nsteps) to d_cost (so the
+ * mean of J estimates V_0(x_0)), and d_vend is V_nsteps(x_nsteps).  The noise keying is the infinite-horizon rollouts'. */
+int c3sc_hip_upload_value_stack(c3sc_hip_ctx *ctx, int nstack, const size_t *ranks, const double *const *cores);
 
 int c3sc_hip_sync(c3sc_hip_ctx *ctx, void *stream);
 int c3sc_hip_get_status(c3sc_hip_ctx *ctx, unsigned *flags, int clear);
