@@ -256,10 +256,6 @@ static int pick_rp(int d, int maxrank, int model, int variant)
 }
 
 static unsigned long long g_launches = 0; // Bellman / stencil kernel launches of this process (c3sc_hip_launch_count)
-static int ensure_scratch(c3sc_hip_ctx *c, size_t bytes);
-static int ensure_pinned(c3sc_hip_ctx *c, size_t bytes);
-static bool zero_copy_batch(size_t bytes);
-static size_t align256(size_t x);
 static int fill_args(c3sc_hip_ctx *c, int k, size_t F, KArgs &A, bool need_model);
 
 // horizon mode is served by the horizon kernels of the model set now (set_model may have replaced the model set_horizon_step
@@ -279,6 +275,101 @@ static int check_game_model(c3sc_hip_ctx *c, const char *what)
     if (c->game_gsz > 0 && !(c->model >= C3SC_MODEL_USER && rtc_model_info(c->model, du, game) && game && du == c->du))
         return fail(c, C3SC_ERR_UNSUPPORTED, what);
     return C3SC_OK;
+}
+
+static int ensure_scratch(c3sc_hip_ctx *c, size_t bytes)
+{
+    if (bytes <= c->scratch_bytes) return C3SC_OK;
+    if (c->scratch) HIPCHK(c, hipFree(c->scratch));
+    c->scratch = nullptr;
+    c->scratch_bytes = 0;
+    HIPCHK(c, hipMalloc(&c->scratch, bytes));
+    c->scratch_bytes = bytes;
+    return C3SC_OK;
+}
+
+static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// Small batches of the *_host entry points (a cross-approximation core step: ~100 fibers, 3 KB in, 33 KB out) skip
+// the staging copies: indices are placed in a pinned host block the device maps, the kernel reads them and writes its
+// rows there, and the call is launch + stream synchronise.  The two hipMemcpy calls they replace cost 25 us of a
+// 53 us call (tools/call_latency.py).  Large batches keep the copies: PCIe would bound the kernel.
+static constexpr size_t ZERO_COPY_MAX_BYTES = (size_t)1 << 20;
+static bool zero_copy_batch(size_t bytes)
+{
+    static const bool off = getenv("C3SC_NO_ZEROCOPY") != nullptr;
+    return !off && bytes <= ZERO_COPY_MAX_BYTES;
+}
+static int ensure_pinned(c3sc_hip_ctx *c, size_t bytes)
+{
+    if (bytes <= c->pinned_bytes) return C3SC_OK;
+    if (c->pinned) HIPCHK(c, hipHostFree(c->pinned));
+    c->pinned = c->pinned_dev = nullptr;
+    c->pinned_bytes = 0;
+    const size_t cap = bytes < ((size_t)256 << 10) ? ((size_t)256 << 10) : bytes;
+    HIPCHK(c, hipHostMalloc(&c->pinned, cap, hipHostMallocMapped | hipHostMallocPortable));
+    HIPCHK(c, hipHostGetDevicePointer(&c->pinned_dev, c->pinned, 0));
+    c->pinned_bytes = cap;
+    return C3SC_OK;
+}
+
+// The staging of every host-buffer (*_host) entry point.  A call lists its buffers as segments; stage_host lays them out one
+// after the other at 256-byte alignment in one block of the storage `kind` names, copies the IN segments there, runs `call`
+// with one device pointer per segment and copies the OUT segments back.  The device pointer is null where the host pointer is,
+// but the segment's space is laid out all the same: which outputs a caller wants does not change the block's size (a segment
+// that needs no space has 0 bytes).
+enum SegDir { SEG_IN, SEG_OUT };
+struct HostSeg { const void *host; size_t bytes; SegDir dir; }; // SEG_OUT: `host` is the caller's writable buffer
+enum Staging {
+    STAGE_MAPPED_OR_SCRATCH, // the pinned, device-mapped block for a batch zero_copy_batch admits, else c->scratch
+    STAGE_SCRATCH,           // c->scratch
+    STAGE_PER_CALL,          // a device block of this call alone, freed on every return (trajectory buffers can be large)
+};
+struct DevPtr { // a segment's device pointer, handed to the device call as whatever pointer type its parameter has
+    void *p;
+    template <class T> operator T *() const { return static_cast<T *>(p); }
+};
+
+template <size_t NS, class Call>
+static int stage_host(c3sc_hip_ctx *c, Staging kind, const char *what, const HostSeg (&segs)[NS], Call &&call)
+{
+    size_t off[NS + 1] = {0};
+    for (size_t i = 0; i < NS; i++) off[i + 1] = off[i] + align256(segs[i].bytes);
+    // the segments of one direction: plain memcpy on the mapped block (hb: its host address; the call reads and writes it in
+    // place), else blocking hipMemcpy to or from device memory, whose copies back wait for the call
+    auto copy = [&](SegDir dir, char *hb, const DevPtr *dev) -> int {
+        for (size_t i = 0; i < NS; i++) {
+            if (!dev[i].p || segs[i].dir != dir || segs[i].bytes == 0) continue;
+            void *h = const_cast<void *>(segs[i].host), *b = hb ? hb + off[i] : dev[i].p;
+            void *dst = dir == SEG_IN ? b : h, *src = dir == SEG_IN ? h : b;
+            if (hb) memcpy(dst, src, segs[i].bytes);
+            else if (hipError_t e = hipMemcpy(dst, src, segs[i].bytes, dir == SEG_IN ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost); e != hipSuccess) {
+                c->err = std::string(what) + ": hipMemcpy of buffer " + std::to_string(i) + (dir == SEG_IN ? " in: " : " out: ") + hipGetErrorString(e);
+                return C3SC_ERR_HIP;
+            }
+        }
+        return C3SC_OK;
+    };
+    auto run = [&](char *hb, char *db) -> int {
+        DevPtr dev[NS];
+        for (size_t i = 0; i < NS; i++) dev[i].p = segs[i].host ? db + off[i] : nullptr;
+        int rc = copy(SEG_IN, hb, dev);
+        if (rc == C3SC_OK) rc = call(dev);
+        if (rc != C3SC_OK) return rc;
+        if (hb) HIPCHK(c, hipStreamSynchronize(nullptr));
+        return copy(SEG_OUT, hb, dev);
+    };
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t total = off[NS];
+    int rc;
+    if (kind == STAGE_MAPPED_OR_SCRATCH && zero_copy_batch(total))
+        return (rc = ensure_pinned(c, total)) != C3SC_OK ? rc : run((char *)c->pinned, (char *)c->pinned_dev);
+    if (kind != STAGE_PER_CALL) return (rc = ensure_scratch(c, total)) != C3SC_OK ? rc : run(nullptr, (char *)c->scratch);
+    void *buf = nullptr; // STAGE_PER_CALL
+    HIPCHK(c, hipMalloc(&buf, total));
+    rc = run(nullptr, (char *)buf);
+    (void)hipFree(buf);
+    return rc;
 }
 
 extern "C" {
@@ -787,6 +878,19 @@ static void arm_memo(c3sc_hip_ctx *c, const KernelEntry *e, KArgs &A)
     c->memo.applied = true;
 }
 
+// the one launch of a call served by a single kernel entry: counted (c3sc_hip_launch_count), the cached status word dropped; with
+// `unsupported`, a launcher that does not serve the call (hipErrorNotSupported) is reported as C3SC_ERR_UNSUPPORTED with that text
+static int launch_one(c3sc_hip_ctx *c, const KernelEntry *e, const KArgs &A, const LaunchIO &io, const char *unsupported = nullptr)
+{
+    c->last_kernel = e->name;
+    g_launches++;
+    c->status_cache_valid = false;
+    const hipError_t he = launch_entry(*e, A, io);
+    if (he == hipErrorNotSupported && unsupported) return fail(c, C3SC_ERR_UNSUPPORTED, unsupported);
+    HIPCHK(c, he);
+    return C3SC_OK;
+}
+
 static int launch_bellman(c3sc_hip_ctx *c, int k, size_t F, const int32_t *d_idx, const int32_t *d_policy, double *d_out,
                           int32_t *d_uidx, int32_t *d_absorbed, void *stream)
 {
@@ -927,15 +1031,9 @@ static int launch_box(c3sc_hip_ctx *c, int k, size_t F, const int32_t *d_idx, co
     A.forced_u = d_policy_u;
     const KernelEntry *e = find_kernel(c->model, c->d, c->rp, A.N, C3SC_VARIANT_FIBER_PER_WAVE, k);
     if (!e || e->rp != c->rp) return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_box: no fiber-per-wave instantiation for (model, dim, rank, N)");
-    c->last_kernel = e->name;
     arm_memo(c, e, A);
     LaunchIO io{c->arena, d_idx, d_out, nullptr, d_absorbed, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream};
-    g_launches++;
-    c->status_cache_valid = false;
-    const hipError_t he = launch_entry(*e, A, io);
-    if (he == hipErrorNotSupported) return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_box: no box-minimiser instantiation for this model");
-    HIPCHK(c, he);
-    return C3SC_OK;
+    return launch_one(c, e, A, io, "bellman_fibers_box: no box-minimiser instantiation for this model");
 }
 
 int c3sc_hip_bellman_fibers_box(c3sc_hip_ctx *c, int k, size_t F, const int32_t *d_idx, double *d_out, double *d_uopt,
@@ -951,67 +1049,29 @@ int c3sc_hip_policy_fibers_box(c3sc_hip_ctx *c, int k, size_t F, const int32_t *
     return launch_box(c, k, F, d_idx, d_policy_u, d_out, nullptr, d_absorbed, stream);
 }
 
-static int box_host(c3sc_hip_ctx *c, int k, size_t F, const int32_t *h_idx, const double *h_policy_u, double *h_out, double *h_uopt,
-                    int32_t *h_absorbed)
-{
-    if (!c || c->d == 0 || k < 0 || k >= c->d || c->box_du == 0) return fail(c, C3SC_ERR_ARG, "bellman_fibers_box_host: bad arguments");
-    if (F == 0) return C3SC_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t N = c->ngrid[k], du = c->box_du;
-    const size_t b_idx = align256(F * c->d * sizeof(int32_t)), b_out = align256(F * N * sizeof(double)),
-                 b_u = align256(F * N * du * sizeof(double)), b_i = align256(F * N * sizeof(int32_t));
-    int rc;
-    if (zero_copy_batch(b_idx + b_out + b_u + b_i)) {
-        if ((rc = ensure_pinned(c, b_idx + b_out + b_u + b_i)) != C3SC_OK) return rc;
-        char *hb = (char *)c->pinned, *db = (char *)c->pinned_dev;
-        memcpy(hb, h_idx, F * c->d * sizeof(int32_t));
-        double *zu = (double *)(db + b_idx + b_out);
-        int32_t *zab = h_absorbed ? (int32_t *)(db + b_idx + b_out + b_u) : nullptr;
-        if (h_policy_u) {
-            memcpy(hb + b_idx + b_out, h_policy_u, F * N * du * sizeof(double));
-            rc = c3sc_hip_policy_fibers_box(c, k, F, (int32_t *)db, zu, (double *)(db + b_idx), zab, nullptr);
-        } else {
-            rc = c3sc_hip_bellman_fibers_box(c, k, F, (int32_t *)db, (double *)(db + b_idx), h_uopt ? zu : nullptr, zab, nullptr);
-        }
-        if (rc != C3SC_OK) return rc;
-        HIPCHK(c, hipStreamSynchronize(nullptr));
-        memcpy(h_out, hb + b_idx, F * N * sizeof(double));
-        if (h_uopt && !h_policy_u) memcpy(h_uopt, hb + b_idx + b_out, F * N * du * sizeof(double));
-        if (h_absorbed) memcpy(h_absorbed, hb + b_idx + b_out + b_u, F * N * sizeof(int32_t));
-        return C3SC_OK;
-    }
-    rc = ensure_scratch(c, b_idx + b_out + b_u + b_i);
-    if (rc != C3SC_OK) return rc;
-    char *base = (char *)c->scratch;
-    int32_t *d_idx = (int32_t *)base;
-    double *d_out = (double *)(base + b_idx);
-    double *d_u = (double *)(base + b_idx + b_out);
-    int32_t *d_ab = (int32_t *)(base + b_idx + b_out + b_u);
-    HIPCHK(c, hipMemcpy(d_idx, h_idx, F * c->d * sizeof(int32_t), hipMemcpyHostToDevice));
-    if (h_policy_u) {
-        HIPCHK(c, hipMemcpy(d_u, h_policy_u, F * N * du * sizeof(double), hipMemcpyHostToDevice));
-        rc = c3sc_hip_policy_fibers_box(c, k, F, d_idx, d_u, d_out, h_absorbed ? d_ab : nullptr, nullptr);
-    } else {
-        rc = c3sc_hip_bellman_fibers_box(c, k, F, d_idx, d_out, h_uopt ? d_u : nullptr, h_absorbed ? d_ab : nullptr, nullptr);
-    }
-    if (rc != C3SC_OK) return rc;
-    HIPCHK(c, hipMemcpy(h_out, d_out, F * N * sizeof(double), hipMemcpyDeviceToHost));
-    if (h_uopt && !h_policy_u) HIPCHK(c, hipMemcpy(h_uopt, d_u, F * N * du * sizeof(double), hipMemcpyDeviceToHost));
-    if (h_absorbed) HIPCHK(c, hipMemcpy(h_absorbed, d_ab, F * N * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return C3SC_OK;
-}
-
 int c3sc_hip_bellman_fibers_box_host(c3sc_hip_ctx *c, int k, size_t F, const int32_t *h_idx, double *h_out, double *h_uopt,
                                      int32_t *h_absorbed)
 {
-    return box_host(c, k, F, h_idx, nullptr, h_out, h_uopt, h_absorbed);
+    if (!c || c->d == 0 || k < 0 || k >= c->d || c->box_du == 0) return fail(c, C3SC_ERR_ARG, "bellman_fibers_box_host: bad arguments");
+    if (F == 0) return C3SC_OK;
+    const size_t FN = F * c->ngrid[k];
+    return stage_host(c, STAGE_MAPPED_OR_SCRATCH, "bellman_fibers_box_host",
+                      {{h_idx, F * c->d * sizeof(int32_t), SEG_IN}, {h_out, FN * sizeof(double), SEG_OUT},
+                       {h_uopt, FN * c->box_du * sizeof(double), SEG_OUT}, {h_absorbed, FN * sizeof(int32_t), SEG_OUT}},
+                      [&](const DevPtr *d) { return c3sc_hip_bellman_fibers_box(c, k, F, d[0], d[1], d[2], d[3], nullptr); });
 }
 
 int c3sc_hip_policy_fibers_box_host(c3sc_hip_ctx *c, int k, size_t F, const int32_t *h_idx, const double *h_policy_u, double *h_out,
                                     int32_t *h_absorbed)
 {
     if (F != 0 && !h_policy_u) return fail(c, C3SC_ERR_ARG, "policy_fibers_box_host: null policy");
-    return box_host(c, k, F, h_idx, h_policy_u, h_out, nullptr, h_absorbed);
+    if (!c || c->d == 0 || k < 0 || k >= c->d || c->box_du == 0) return fail(c, C3SC_ERR_ARG, "policy_fibers_box_host: bad arguments");
+    if (F == 0) return C3SC_OK;
+    const size_t FN = F * c->ngrid[k];
+    return stage_host(c, STAGE_MAPPED_OR_SCRATCH, "policy_fibers_box_host",
+                      {{h_idx, F * c->d * sizeof(int32_t), SEG_IN}, {h_out, FN * sizeof(double), SEG_OUT},
+                       {h_policy_u, FN * c->box_du * sizeof(double), SEG_IN}, {h_absorbed, FN * sizeof(int32_t), SEG_OUT}},
+                      [&](const DevPtr *d) { return c3sc_hip_policy_fibers_box(c, k, F, d[0], d[2], d[1], d[3], nullptr); });
 }
 
 int c3sc_hip_policy_fibers(c3sc_hip_ctx *c, int k, size_t F, const int32_t *d_idx, const int32_t *d_policy, double *d_out,
@@ -1038,12 +1098,8 @@ static int launch_tables(c3sc_hip_ctx *c, int k, size_t F, const int32_t *d_idx,
     A.forced = d_policy;
     const KernelEntry *e = find_kernel(C3SC_MODEL_TABLE, c->d, c->rp, A.N, C3SC_VARIANT_AUTO, k);
     if (!e || e->rp != c->rp) return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_tables: no kernel instantiation for (dim, rank, N)");
-    c->last_kernel = e->name;
     LaunchIO io{c->arena, d_idx, d_out, d_uidx, d_absorbed, nullptr, nullptr, d_tables, d_costs2, (hipStream_t)stream};
-    g_launches++;
-    c->status_cache_valid = false;
-    HIPCHK(c, launch_entry(*e, A, io));
-    return C3SC_OK;
+    return launch_one(c, e, A, io);
 }
 
 int c3sc_hip_bellman_fibers_tables(c3sc_hip_ctx *c, int k, size_t F, const int32_t *d_idx, const double *d_tables,
@@ -1059,52 +1115,31 @@ int c3sc_hip_policy_fibers_tables(c3sc_hip_ctx *c, int k, size_t F, const int32_
     return launch_tables(c, k, F, d_idx, d_tables, d_costs2, d_policy, d_out, nullptr, d_absorbed, stream);
 }
 
-static int tables_host(c3sc_hip_ctx *c, int k, size_t F, const int32_t *h_idx, const double *h_tables, const double *h_costs2,
-                       const int32_t *h_policy, double *h_out, int32_t *h_uidx, int32_t *h_absorbed)
-{
-    if (!c || c->d == 0 || k < 0 || k >= c->d || c->ncand == 0) return fail(c, C3SC_ERR_ARG, "bellman_fibers_tables_host: bad arguments");
-    if (F == 0) return C3SC_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t N = c->ngrid[k], S = 2 * c->d + 1;
-    const size_t b_idx = align256(F * c->d * sizeof(int32_t)), b_out = align256(F * N * sizeof(double)),
-                 b_i = align256(F * N * sizeof(int32_t)), b_t = align256(F * N * c->ncand * S * sizeof(double)),
-                 b_c = align256(F * N * 2 * sizeof(double));
-    int rc = ensure_scratch(c, b_idx + b_out + 2 * b_i + b_t + b_c);
-    if (rc != C3SC_OK) return rc;
-    char *base = (char *)c->scratch;
-    int32_t *d_idx = (int32_t *)base;
-    double *d_out = (double *)(base + b_idx);
-    int32_t *d_ui = (int32_t *)(base + b_idx + b_out);
-    int32_t *d_ab = (int32_t *)(base + b_idx + b_out + b_i);
-    double *d_t = (double *)(base + b_idx + b_out + 2 * b_i);
-    double *d_c = (double *)(base + b_idx + b_out + 2 * b_i + b_t);
-    HIPCHK(c, hipMemcpy(d_idx, h_idx, F * c->d * sizeof(int32_t), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(d_t, h_tables, F * N * c->ncand * S * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(d_c, h_costs2, F * N * 2 * sizeof(double), hipMemcpyHostToDevice));
-    if (h_policy) { // the uidx buffer carries the policy in
-        HIPCHK(c, hipMemcpy(d_ui, h_policy, F * N * sizeof(int32_t), hipMemcpyHostToDevice));
-        rc = c3sc_hip_policy_fibers_tables(c, k, F, d_idx, d_t, d_c, d_ui, d_out, h_absorbed ? d_ab : nullptr, nullptr);
-    } else {
-        rc = c3sc_hip_bellman_fibers_tables(c, k, F, d_idx, d_t, d_c, d_out, h_uidx ? d_ui : nullptr, h_absorbed ? d_ab : nullptr, nullptr);
-    }
-    if (rc != C3SC_OK) return rc;
-    HIPCHK(c, hipMemcpy(h_out, d_out, F * N * sizeof(double), hipMemcpyDeviceToHost));
-    if (h_uidx && !h_policy) HIPCHK(c, hipMemcpy(h_uidx, d_ui, F * N * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (h_absorbed) HIPCHK(c, hipMemcpy(h_absorbed, d_ab, F * N * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return C3SC_OK;
-}
-
 int c3sc_hip_bellman_fibers_tables_host(c3sc_hip_ctx *c, int k, size_t F, const int32_t *h_idx, const double *h_tables,
                                         const double *h_costs2, double *h_out, int32_t *h_uidx, int32_t *h_absorbed)
 {
-    return tables_host(c, k, F, h_idx, h_tables, h_costs2, nullptr, h_out, h_uidx, h_absorbed);
+    if (!c || c->d == 0 || k < 0 || k >= c->d || c->ncand == 0) return fail(c, C3SC_ERR_ARG, "bellman_fibers_tables_host: bad arguments");
+    if (F == 0) return C3SC_OK;
+    const size_t FN = F * c->ngrid[k], S = 2 * c->d + 1;
+    return stage_host(c, STAGE_SCRATCH, "bellman_fibers_tables_host",
+                      {{h_idx, F * c->d * sizeof(int32_t), SEG_IN}, {h_out, FN * sizeof(double), SEG_OUT}, {h_uidx, FN * sizeof(int32_t), SEG_OUT},
+                       {h_absorbed, FN * sizeof(int32_t), SEG_OUT}, {h_tables, FN * c->ncand * S * sizeof(double), SEG_IN},
+                       {h_costs2, FN * 2 * sizeof(double), SEG_IN}},
+                      [&](const DevPtr *d) { return c3sc_hip_bellman_fibers_tables(c, k, F, d[0], d[4], d[5], d[1], d[2], d[3], nullptr); });
 }
 
 int c3sc_hip_policy_fibers_tables_host(c3sc_hip_ctx *c, int k, size_t F, const int32_t *h_idx, const double *h_tables,
                                        const double *h_costs2, const int32_t *h_policy, double *h_out, int32_t *h_absorbed)
 {
     if (F != 0 && !h_policy) return fail(c, C3SC_ERR_ARG, "policy_fibers_tables_host: null policy");
-    return tables_host(c, k, F, h_idx, h_tables, h_costs2, h_policy, h_out, nullptr, h_absorbed);
+    if (!c || c->d == 0 || k < 0 || k >= c->d || c->ncand == 0) return fail(c, C3SC_ERR_ARG, "policy_fibers_tables_host: bad arguments");
+    if (F == 0) return C3SC_OK;
+    const size_t FN = F * c->ngrid[k], S = 2 * c->d + 1;
+    return stage_host(c, STAGE_SCRATCH, "policy_fibers_tables_host",
+                      {{h_idx, F * c->d * sizeof(int32_t), SEG_IN}, {h_out, FN * sizeof(double), SEG_OUT}, {h_policy, FN * sizeof(int32_t), SEG_IN},
+                       {h_absorbed, FN * sizeof(int32_t), SEG_OUT}, {h_tables, FN * c->ncand * S * sizeof(double), SEG_IN},
+                       {h_costs2, FN * 2 * sizeof(double), SEG_IN}},
+                      [&](const DevPtr *d) { return c3sc_hip_policy_fibers_tables(c, k, F, d[0], d[4], d[5], d[2], d[1], d[3], nullptr); });
 }
 
 int c3sc_hip_stencil_fibers(c3sc_hip_ctx *c, int k, size_t F, const int32_t *d_idx, double *d_costs, int32_t *d_absorbed,
@@ -1123,48 +1158,8 @@ int c3sc_hip_stencil_fibers_nb(c3sc_hip_ctx *c, int k, size_t F, const int32_t *
     if (!d_idx || !d_costs) return fail(c, C3SC_ERR_ARG, "stencil_fibers: null buffer");
     const KernelEntry *e = find_kernel(0, c->d, c->rp, A.N, C3SC_VARIANT_AUTO, k);
     if (!e || e->rp != c->rp) return fail(c, C3SC_ERR_UNSUPPORTED, "stencil_fibers: no kernel instantiation for (dim, rank, N)");
-    c->last_kernel = e->name;
     LaunchIO io{c->arena, d_idx, d_costs, nullptr, d_absorbed, d_nb_fixed, d_nb_vary, nullptr, nullptr, (hipStream_t)stream};
-    g_launches++;
-    c->status_cache_valid = false;
-    HIPCHK(c, launch_entry(*e, A, io));
-    return C3SC_OK;
-}
-
-static int ensure_scratch(c3sc_hip_ctx *c, size_t bytes)
-{
-    if (bytes <= c->scratch_bytes) return C3SC_OK;
-    if (c->scratch) HIPCHK(c, hipFree(c->scratch));
-    c->scratch = nullptr;
-    c->scratch_bytes = 0;
-    HIPCHK(c, hipMalloc(&c->scratch, bytes));
-    c->scratch_bytes = bytes;
-    return C3SC_OK;
-}
-
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// Small batches of the *_host entry points (a cross-approximation core step: ~100 fibers, 3 KB in, 33 KB out) skip
-// the staging copies: indices are placed in a pinned host block the device maps, the kernel reads them and writes its
-// rows there, and the call is launch + stream synchronise.  The two hipMemcpy calls they replace cost 25 us of a
-// 53 us call (tools/call_latency.py).  Large batches keep the copies: PCIe would bound the kernel.
-static constexpr size_t ZERO_COPY_MAX_BYTES = (size_t)1 << 20;
-static bool zero_copy_batch(size_t bytes)
-{
-    static const bool off = getenv("C3SC_NO_ZEROCOPY") != nullptr;
-    return !off && bytes <= ZERO_COPY_MAX_BYTES;
-}
-static int ensure_pinned(c3sc_hip_ctx *c, size_t bytes)
-{
-    if (bytes <= c->pinned_bytes) return C3SC_OK;
-    if (c->pinned) HIPCHK(c, hipHostFree(c->pinned));
-    c->pinned = c->pinned_dev = nullptr;
-    c->pinned_bytes = 0;
-    const size_t cap = bytes < ((size_t)256 << 10) ? ((size_t)256 << 10) : bytes;
-    HIPCHK(c, hipHostMalloc(&c->pinned, cap, hipHostMallocMapped | hipHostMallocPortable));
-    HIPCHK(c, hipHostGetDevicePointer(&c->pinned_dev, c->pinned, 0));
-    c->pinned_bytes = cap;
-    return C3SC_OK;
+    return launch_one(c, e, A, io);
 }
 
 int c3sc_hip_bellman_fibers_host(c3sc_hip_ctx *c, int k, size_t F, const int32_t *h_idx, double *h_out, int32_t *h_uidx,
@@ -1172,38 +1167,11 @@ int c3sc_hip_bellman_fibers_host(c3sc_hip_ctx *c, int k, size_t F, const int32_t
 {
     if (!c || c->d == 0 || k < 0 || k >= c->d) return fail(c, C3SC_ERR_ARG, "bellman_fibers_host: bad arguments");
     if (F == 0) return C3SC_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t N = c->ngrid[k];
-    const size_t b_idx = align256(F * c->d * sizeof(int32_t)), b_out = align256(F * N * sizeof(double)),
-                 b_i = align256(F * N * sizeof(int32_t));
-    int rc;
-    if (zero_copy_batch(b_idx + b_out + 2 * b_i)) {
-        if ((rc = ensure_pinned(c, b_idx + b_out + 2 * b_i)) != C3SC_OK) return rc;
-        char *hb = (char *)c->pinned, *db = (char *)c->pinned_dev;
-        memcpy(hb, h_idx, F * c->d * sizeof(int32_t));
-        rc = c3sc_hip_bellman_fibers(c, k, F, (int32_t *)db, (double *)(db + b_idx), h_uidx ? (int32_t *)(db + b_idx + b_out) : nullptr,
-                                     h_absorbed ? (int32_t *)(db + b_idx + b_out + b_i) : nullptr, nullptr);
-        if (rc != C3SC_OK) return rc;
-        HIPCHK(c, hipStreamSynchronize(nullptr));
-        memcpy(h_out, hb + b_idx, F * N * sizeof(double));
-        if (h_uidx) memcpy(h_uidx, hb + b_idx + b_out, F * N * sizeof(int32_t));
-        if (h_absorbed) memcpy(h_absorbed, hb + b_idx + b_out + b_i, F * N * sizeof(int32_t));
-        return C3SC_OK;
-    }
-    rc = ensure_scratch(c, b_idx + b_out + 2 * b_i);
-    if (rc != C3SC_OK) return rc;
-    char *base = (char *)c->scratch;
-    int32_t *d_idx = (int32_t *)base;
-    double *d_out = (double *)(base + b_idx);
-    int32_t *d_ui = (int32_t *)(base + b_idx + b_out);
-    int32_t *d_ab = (int32_t *)(base + b_idx + b_out + b_i);
-    HIPCHK(c, hipMemcpy(d_idx, h_idx, F * c->d * sizeof(int32_t), hipMemcpyHostToDevice));
-    rc = c3sc_hip_bellman_fibers(c, k, F, d_idx, d_out, h_uidx ? d_ui : nullptr, h_absorbed ? d_ab : nullptr, nullptr);
-    if (rc != C3SC_OK) return rc;
-    HIPCHK(c, hipMemcpy(h_out, d_out, F * N * sizeof(double), hipMemcpyDeviceToHost));
-    if (h_uidx) HIPCHK(c, hipMemcpy(h_uidx, d_ui, F * N * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (h_absorbed) HIPCHK(c, hipMemcpy(h_absorbed, d_ab, F * N * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return C3SC_OK;
+    const size_t FN = F * c->ngrid[k];
+    return stage_host(c, STAGE_MAPPED_OR_SCRATCH, "bellman_fibers_host",
+                      {{h_idx, F * c->d * sizeof(int32_t), SEG_IN}, {h_out, FN * sizeof(double), SEG_OUT},
+                       {h_uidx, FN * sizeof(int32_t), SEG_OUT}, {h_absorbed, FN * sizeof(int32_t), SEG_OUT}},
+                      [&](const DevPtr *d) { return c3sc_hip_bellman_fibers(c, k, F, d[0], d[1], d[2], d[3], nullptr); });
 }
 
 int c3sc_hip_policy_fibers_host(c3sc_hip_ctx *c, int k, size_t F, const int32_t *h_idx, const int32_t *h_policy, double *h_out,
@@ -1211,38 +1179,11 @@ int c3sc_hip_policy_fibers_host(c3sc_hip_ctx *c, int k, size_t F, const int32_t 
 {
     if (!c || c->d == 0 || k < 0 || k >= c->d || (F != 0 && !h_policy)) return fail(c, C3SC_ERR_ARG, "policy_fibers_host: bad arguments");
     if (F == 0) return C3SC_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t N = c->ngrid[k];
-    const size_t b_idx = align256(F * c->d * sizeof(int32_t)), b_out = align256(F * N * sizeof(double)),
-                 b_i = align256(F * N * sizeof(int32_t));
-    int rc;
-    if (zero_copy_batch(b_idx + b_out + 2 * b_i)) {
-        if ((rc = ensure_pinned(c, b_idx + b_out + 2 * b_i)) != C3SC_OK) return rc;
-        char *hb = (char *)c->pinned, *db = (char *)c->pinned_dev;
-        memcpy(hb, h_idx, F * c->d * sizeof(int32_t));
-        memcpy(hb + b_idx + b_out, h_policy, F * N * sizeof(int32_t));
-        rc = c3sc_hip_policy_fibers(c, k, F, (int32_t *)db, (int32_t *)(db + b_idx + b_out), (double *)(db + b_idx),
-                                    h_absorbed ? (int32_t *)(db + b_idx + b_out + b_i) : nullptr, nullptr);
-        if (rc != C3SC_OK) return rc;
-        HIPCHK(c, hipStreamSynchronize(nullptr));
-        memcpy(h_out, hb + b_idx, F * N * sizeof(double));
-        if (h_absorbed) memcpy(h_absorbed, hb + b_idx + b_out + b_i, F * N * sizeof(int32_t));
-        return C3SC_OK;
-    }
-    rc = ensure_scratch(c, b_idx + b_out + 2 * b_i);
-    if (rc != C3SC_OK) return rc;
-    char *base = (char *)c->scratch;
-    int32_t *d_idx = (int32_t *)base;
-    double *d_out = (double *)(base + b_idx);
-    int32_t *d_pol = (int32_t *)(base + b_idx + b_out);
-    int32_t *d_ab = (int32_t *)(base + b_idx + b_out + b_i);
-    HIPCHK(c, hipMemcpy(d_idx, h_idx, F * c->d * sizeof(int32_t), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(d_pol, h_policy, F * N * sizeof(int32_t), hipMemcpyHostToDevice));
-    rc = c3sc_hip_policy_fibers(c, k, F, d_idx, d_pol, d_out, h_absorbed ? d_ab : nullptr, nullptr);
-    if (rc != C3SC_OK) return rc;
-    HIPCHK(c, hipMemcpy(h_out, d_out, F * N * sizeof(double), hipMemcpyDeviceToHost));
-    if (h_absorbed) HIPCHK(c, hipMemcpy(h_absorbed, d_ab, F * N * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return C3SC_OK;
+    const size_t FN = F * c->ngrid[k];
+    return stage_host(c, STAGE_MAPPED_OR_SCRATCH, "policy_fibers_host",
+                      {{h_idx, F * c->d * sizeof(int32_t), SEG_IN}, {h_out, FN * sizeof(double), SEG_OUT},
+                       {h_policy, FN * sizeof(int32_t), SEG_IN}, {h_absorbed, FN * sizeof(int32_t), SEG_OUT}},
+                      [&](const DevPtr *d) { return c3sc_hip_policy_fibers(c, k, F, d[0], d[2], d[1], d[3], nullptr); });
 }
 
 int c3sc_hip_stencil_fibers_host(c3sc_hip_ctx *c, int k, size_t F, const int32_t *h_idx, double *h_costs, int32_t *h_absorbed)
@@ -1255,28 +1196,12 @@ int c3sc_hip_stencil_fibers_nb_host(c3sc_hip_ctx *c, int k, size_t F, const int3
 {
     if (!c || c->d == 0 || k < 0 || k >= c->d) return fail(c, C3SC_ERR_ARG, "stencil_fibers_host: bad arguments");
     if (F == 0) return C3SC_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t N = c->ngrid[k], S = 2 * c->d + 1;
-    const size_t b_idx = align256(F * c->d * sizeof(int32_t)), b_out = align256(F * N * S * sizeof(double)),
-                 b_i = align256(F * N * sizeof(int32_t)), b_nf = align256(F * 2 * (c->d - 1) * sizeof(int32_t)),
-                 b_nv = align256(F * N * 2 * sizeof(int32_t));
-    int rc = ensure_scratch(c, b_idx + b_out + b_i + b_nf + b_nv);
-    if (rc != C3SC_OK) return rc;
-    char *base = (char *)c->scratch;
-    int32_t *d_idx = (int32_t *)base;
-    double *d_out = (double *)(base + b_idx);
-    int32_t *d_ab = (int32_t *)(base + b_idx + b_out);
-    int32_t *d_nf = (int32_t *)(base + b_idx + b_out + b_i);
-    int32_t *d_nv = (int32_t *)(base + b_idx + b_out + b_i + b_nf);
-    HIPCHK(c, hipMemcpy(d_idx, h_idx, F * c->d * sizeof(int32_t), hipMemcpyHostToDevice));
-    if (h_nb_fixed) HIPCHK(c, hipMemcpy(d_nf, h_nb_fixed, F * 2 * (c->d - 1) * sizeof(int32_t), hipMemcpyHostToDevice));
-    if (h_nb_vary) HIPCHK(c, hipMemcpy(d_nv, h_nb_vary, F * N * 2 * sizeof(int32_t), hipMemcpyHostToDevice));
-    rc = c3sc_hip_stencil_fibers_nb(c, k, F, d_idx, h_nb_fixed ? d_nf : nullptr, h_nb_vary ? d_nv : nullptr, d_out,
-                                    h_absorbed ? d_ab : nullptr, nullptr);
-    if (rc != C3SC_OK) return rc;
-    HIPCHK(c, hipMemcpy(h_costs, d_out, F * N * S * sizeof(double), hipMemcpyDeviceToHost));
-    if (h_absorbed) HIPCHK(c, hipMemcpy(h_absorbed, d_ab, F * N * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return C3SC_OK;
+    const size_t FN = F * c->ngrid[k], S = 2 * c->d + 1;
+    return stage_host(c, STAGE_SCRATCH, "stencil_fibers_host",
+                      {{h_idx, F * c->d * sizeof(int32_t), SEG_IN}, {h_costs, FN * S * sizeof(double), SEG_OUT},
+                       {h_absorbed, FN * sizeof(int32_t), SEG_OUT}, {h_nb_fixed, F * 2 * (c->d - 1) * sizeof(int32_t), SEG_IN},
+                       {h_nb_vary, FN * 2 * sizeof(int32_t), SEG_IN}},
+                      [&](const DevPtr *d) { return c3sc_hip_stencil_fibers_nb(c, k, F, d[0], d[3], d[4], d[1], d[2], nullptr); });
 }
 
 int c3sc_hip_sync(c3sc_hip_ctx *c, void *stream)
@@ -1348,11 +1273,7 @@ int c3sc_hip_stencil_points(c3sc_hip_ctx *c, size_t n, const double *d_x, double
     S.out = d_out;
     S.absorbed = d_absorbed;
     LaunchIO io{c->arena, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream, &S};
-    c->last_kernel = e->name;
-    g_launches++;
-    c->status_cache_valid = false;
-    HIPCHK(c, launch_entry(*e, A, io));
-    return C3SC_OK;
+    return launch_one(c, e, A, io);
 }
 
 int c3sc_hip_simulate(c3sc_hip_ctx *c, const c3sc_hip_sim_args *a, void *stream)
@@ -1472,41 +1393,19 @@ int c3sc_hip_simulate_host(c3sc_hip_ctx *c, const c3sc_hip_sim_args *h)
     if (h->n > SIM_MAX_TRAJ || h->nsteps > ((size_t)1 << 30)) return fail(c, C3SC_ERR_ARG, "simulate_host: sizes too large");
     if (h->save_every == 0 && (h->d_traj || h->d_u)) return fail(c, C3SC_ERR_ARG, "simulate: d_traj / d_u need save_every > 0");
     if (c->d == 0) return fail(c, C3SC_ERR_ARG, "simulate_host: set_grid first");
-    const size_t n = h->n, d = (size_t)c->d, du = (size_t)(h->box ? c->box_du : c->du);
+    const size_t n = h->n, d = (size_t)c->d, du = (size_t)(h->box ? c->box_du : c->du), D = sizeof(double);
     const size_t se = h->save_every, nrow = se ? h->nsteps / se + 1 : 0, nurow = se ? (h->nsteps + se - 1) / se : 0;
-    const size_t nnoise = h->d_noise ? n * h->nsteps * d : 0;
-    // staging buffer: [x0 | noise | traj | u | cost | exit | vend | xfinal]
-    size_t off[9];
-    const size_t sz[8] = {n * d, nnoise, h->d_traj ? n * nrow * d : 0, h->d_u ? n * nurow * du : 0, n, n, n, n * d};
-    off[0] = 0;
-    for (int i = 0; i < 8; i++) off[i + 1] = off[i] + ((sz[i] + 31) & ~(size_t)31);
-    HIPCHK(c, hipSetDevice(c->device));
-    double *buf = nullptr;
-    HIPCHK(c, hipMalloc((void **)&buf, off[8] * sizeof(double)));
-    c3sc_hip_sim_args a = *h;
-    a.d_x0 = buf + off[0];
-    a.d_noise = h->d_noise ? buf + off[1] : nullptr;
-    a.d_traj = h->d_traj ? buf + off[2] : nullptr;
-    a.d_u = h->d_u ? buf + off[3] : nullptr;
-    a.d_cost = buf + off[4];
-    a.d_exit = (int64_t *)(buf + off[5]);
-    a.d_vend = buf + off[6];
-    a.d_xfinal = buf + off[7];
-    int rc = C3SC_OK;
-    hipError_t e = hipMemcpy((void *)a.d_x0, h->d_x0, sz[0] * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess && nnoise) e = hipMemcpy((void *)a.d_noise, h->d_noise, nnoise * sizeof(double), hipMemcpyHostToDevice);
-    if (e != hipSuccess) rc = fail(c, C3SC_ERR_HIP, hipGetErrorString(e));
-    if (rc == C3SC_OK) rc = c3sc_hip_simulate(c, &a, nullptr);
-    struct { void *dst; const void *src; size_t bytes; } back[6] = {
-        {h->d_traj, a.d_traj, sz[2] * sizeof(double)}, {h->d_u, a.d_u, sz[3] * sizeof(double)}, {h->d_cost, a.d_cost, n * sizeof(double)},
-        {h->d_exit, a.d_exit, n * sizeof(int64_t)}, {h->d_vend, a.d_vend, n * sizeof(double)}, {h->d_xfinal, a.d_xfinal, n * d * sizeof(double)}};
-    for (int i = 0; i < 6 && rc == C3SC_OK; i++)
-        if (back[i].dst && back[i].bytes) {
-            e = hipMemcpy(back[i].dst, back[i].src, back[i].bytes, hipMemcpyDeviceToHost);
-            if (e != hipSuccess) rc = fail(c, C3SC_ERR_HIP, hipGetErrorString(e));
-        }
-    (void)hipFree(buf);
-    return rc;
+    return stage_host(c, STAGE_PER_CALL, "simulate_host",
+                      {{h->d_x0, n * d * D, SEG_IN}, {h->d_noise, h->d_noise ? n * h->nsteps * d * D : 0, SEG_IN},
+                       {h->d_traj, h->d_traj ? n * nrow * d * D : 0, SEG_OUT}, {h->d_u, h->d_u ? n * nurow * du * D : 0, SEG_OUT},
+                       {h->d_cost, n * D, SEG_OUT}, {h->d_exit, n * sizeof(int64_t), SEG_OUT}, {h->d_vend, n * D, SEG_OUT},
+                       {h->d_xfinal, n * d * D, SEG_OUT}},
+                      [&](const DevPtr *b) {
+                          c3sc_hip_sim_args a = *h;
+                          a.d_x0 = b[0]; a.d_noise = b[1]; a.d_traj = b[2]; a.d_u = b[3];
+                          a.d_cost = b[4]; a.d_exit = b[5]; a.d_vend = b[6]; a.d_xfinal = b[7];
+                          return c3sc_hip_simulate(c, &a, nullptr);
+                      });
 }
 
 // ------------------------------------------------------------------ closed-loop integration (kernel_rollout_ode.hpp)
@@ -1644,40 +1543,19 @@ int c3sc_hip_integrate_host(c3sc_hip_ctx *c, const c3sc_hip_ode_args *h)
     if (h->n > SIM_MAX_TRAJ || h->nout > ((size_t)1 << 30)) return fail(c, C3SC_ERR_ARG, "integrate_host: sizes too large");
     if (h->save_every == 0 && (h->d_traj || h->d_u)) return fail(c, C3SC_ERR_ARG, "integrate: d_traj / d_u need save_every > 0");
     if (c->d == 0) return fail(c, C3SC_ERR_ARG, "integrate_host: set_grid first");
-    const size_t n = h->n, d = (size_t)c->d, du = (size_t)(h->box ? c->box_du : c->du);
+    const size_t n = h->n, d = (size_t)c->d, du = (size_t)(h->box ? c->box_du : c->du), D = sizeof(double);
     const size_t se = h->save_every, nrow = se ? h->nout / se + 1 : 0, nurow = se ? (h->nout + se - 1) / se : 0;
-    // staging buffer: [x0 | traj | u | cost | stop_step | stop_reason | vend | xfinal]
-    size_t off[9];
-    const size_t sz[8] = {n * d, h->d_traj ? n * nrow * d : 0, h->d_u ? n * nurow * du : 0, n, n, n, n, n * d};
-    off[0] = 0;
-    for (int i = 0; i < 8; i++) off[i + 1] = off[i] + ((sz[i] + 31) & ~(size_t)31);
-    HIPCHK(c, hipSetDevice(c->device));
-    double *buf = nullptr;
-    HIPCHK(c, hipMalloc((void **)&buf, off[8] * sizeof(double)));
-    c3sc_hip_ode_args a = *h;
-    a.d_x0 = buf + off[0];
-    a.d_traj = h->d_traj ? buf + off[1] : nullptr;
-    a.d_u = h->d_u ? buf + off[2] : nullptr;
-    a.d_cost = buf + off[3];
-    a.d_stop_step = (int64_t *)(buf + off[4]);
-    a.d_stop_reason = (int32_t *)(buf + off[5]);
-    a.d_vend = buf + off[6];
-    a.d_xfinal = buf + off[7];
-    int rc = C3SC_OK;
-    hipError_t e = hipMemcpy((void *)a.d_x0, h->d_x0, sz[0] * sizeof(double), hipMemcpyHostToDevice);
-    if (e != hipSuccess) rc = fail(c, C3SC_ERR_HIP, hipGetErrorString(e));
-    if (rc == C3SC_OK) rc = c3sc_hip_integrate(c, &a, nullptr);
-    struct { void *dst; const void *src; size_t bytes; } back[7] = {
-        {h->d_traj, a.d_traj, sz[1] * sizeof(double)}, {h->d_u, a.d_u, sz[2] * sizeof(double)}, {h->d_cost, a.d_cost, n * sizeof(double)},
-        {h->d_stop_step, a.d_stop_step, n * sizeof(int64_t)}, {h->d_stop_reason, a.d_stop_reason, n * sizeof(int32_t)},
-        {h->d_vend, a.d_vend, n * sizeof(double)}, {h->d_xfinal, a.d_xfinal, n * d * sizeof(double)}};
-    for (int i = 0; i < 7 && rc == C3SC_OK; i++)
-        if (back[i].dst && back[i].bytes) {
-            e = hipMemcpy(back[i].dst, back[i].src, back[i].bytes, hipMemcpyDeviceToHost);
-            if (e != hipSuccess) rc = fail(c, C3SC_ERR_HIP, hipGetErrorString(e));
-        }
-    (void)hipFree(buf);
-    return rc;
+    return stage_host(c, STAGE_PER_CALL, "integrate_host",
+                      {{h->d_x0, n * d * D, SEG_IN}, {h->d_traj, h->d_traj ? n * nrow * d * D : 0, SEG_OUT},
+                       {h->d_u, h->d_u ? n * nurow * du * D : 0, SEG_OUT}, {h->d_cost, n * D, SEG_OUT},
+                       {h->d_stop_step, n * sizeof(int64_t), SEG_OUT}, {h->d_stop_reason, n * sizeof(int32_t), SEG_OUT},
+                       {h->d_vend, n * D, SEG_OUT}, {h->d_xfinal, n * d * D, SEG_OUT}},
+                      [&](const DevPtr *b) {
+                          c3sc_hip_ode_args a = *h;
+                          a.d_x0 = b[0]; a.d_traj = b[1]; a.d_u = b[2]; a.d_cost = b[3];
+                          a.d_stop_step = b[4]; a.d_stop_reason = b[5]; a.d_vend = b[6]; a.d_xfinal = b[7];
+                          return c3sc_hip_integrate(c, &a, nullptr);
+                      });
 }
 
 int c3sc_hip_normals(uint64_t seed, uint64_t traj0, size_t ntraj, uint64_t step0, size_t nsteps, int dw, double *out)

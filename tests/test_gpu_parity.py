@@ -544,8 +544,9 @@ def test_c_abi_error_behaviour():
 
 @pytest.mark.gpu
 def test_host_entry_zero_copy_and_staged_paths_agree():
-    """c3sc_hip_bellman_fibers_host serves batches up to 1 MiB from a pinned device-mapped block and larger ones through
-    device scratch: the same fibers must come back bit for bit (values, argmin, absorbed flags) either way."""
+    """c3sc_hip_bellman_fibers_host, c3sc_hip_policy_fibers_host and the two box calls serve batches up to 1 MiB from a pinned
+    device-mapped block and larger ones through device scratch: the same fibers must come back bit for bit (values, argmin or
+    minimiser, absorbed flags) either way."""
     w = wl.c4_car7d().scaled(ngrid=(11,) * 7, rank=10)
     cores = wl.synth_cores(w)
     eng = _engine(w, cores, 0)
@@ -555,7 +556,25 @@ def test_host_entry_zero_copy_and_staged_paths_agree():
         o1, u1, a1 = eng.bellman_fibers_host(k, small)
         o2, u2, a2 = eng.bellman_fibers_host(k, big)
         assert np.array_equal(o1, o2[:100]) and np.array_equal(u1, u2[:100]) and np.array_equal(a1, a2[:100])
+        pol = np.random.default_rng(k).integers(0, len(w.cands), size=u2.shape).astype(np.int32)  # same sizes as above
+        p1, pa1 = eng.policy_fibers_host(k, small, pol[:100])
+        p2, pa2 = eng.policy_fibers_host(k, big, pol)
+        assert np.array_equal(p1, p2[:100]) and np.array_equal(pa1, pa2[:100])
     assert eng.status() == 0
+    # the box pair on a model compiled with the box minimiser (car7d has none)
+    wb = wl.WORKLOADS["perch7d"]().scaled(ngrid=(6, 5, 7, 6, 5, 6, 5), rank=4)
+    engb = _engine(wb, wl.synth_cores(wb), 0)
+    engb.set_control_box([-2.0 * np.pi], [2.0 * np.pi], grid=33, polish=2)
+    for k in (0, 3, 6):
+        big = wl.synth_fibers(wb, k, 12000)  # 12000 x (28 + 20 N) B > 1 MiB at N >= 5: staged
+        small = big[:100].copy()
+        b1, uo1, ba1 = engb.bellman_fibers_box_host(k, small)
+        b2, uo2, ba2 = engb.bellman_fibers_box_host(k, big)
+        assert np.array_equal(b1, b2[:100]) and np.array_equal(uo1, uo2[:100]) and np.array_equal(ba1, ba2[:100])
+        q1, qa1 = engb.policy_fibers_box_host(k, small, uo2[:100])
+        q2, qa2 = engb.policy_fibers_box_host(k, big, uo2)
+        assert np.array_equal(q1, q2[:100]) and np.array_equal(qa1, qa2[:100])
+    assert engb.status() == 0
 
 
 @pytest.mark.gpu
