@@ -120,6 +120,7 @@ def load_library():
         L.c3sc_hip_stencil_fibers_nb_host.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
                                                       C.c_void_p, C.c_void_p]
         L.c3sc_hip_bellman_fibers_tables_host.argtypes = [C.c_void_p, C.c_int, C.c_size_t] + [C.c_void_p] * 6
+        L.c3sc_hip_policy_fibers_tables_host.argtypes = [C.c_void_p, C.c_int, C.c_size_t] + [C.c_void_p] * 6
         L.c3sc_hip_launch_count.restype = C.c_ulonglong
         L.c3sc_hip_sync.argtypes = [C.c_void_p, C.c_void_p]
         L.c3sc_hip_timer_start.argtypes = [C.c_void_p, C.c_void_p]
@@ -607,6 +608,22 @@ class BellmanEngine:
                                                              costs2.ctypes.data, out.ctypes.data, ui.ctypes.data,
                                                              ab.ctypes.data), "bellman_fibers_tables_host")
         return out, ui, ab
+
+    def policy_fibers_tables_host(self, k: int, idx: np.ndarray, tables: np.ndarray, costs2: np.ndarray, policy: np.ndarray):
+        """Policy evaluation on the universal path (c3sc_hip_policy_fibers_tables_host): apply candidate policy[f, j] of the
+        tables at every node.  Returns (values (F, N), absorbed (F, N))."""
+        idx = np.ascontiguousarray(idx, dtype=np.int32)
+        tables = _f64(tables)
+        costs2 = _f64(costs2)
+        policy = np.ascontiguousarray(policy, dtype=np.int32)
+        F, N = idx.shape[0], self.ngrid[k]
+        assert policy.shape == (F, N)
+        out = np.empty((F, N))
+        ab = np.empty((F, N), dtype=np.int32)
+        self._chk(self.L.c3sc_hip_policy_fibers_tables_host(self.h, k, F, idx.ctypes.data, tables.ctypes.data, costs2.ctypes.data,
+                                                            policy.ctypes.data, out.ctypes.data, ab.ctypes.data),
+                  "policy_fibers_tables_host")
+        return out, ab
 
     def stencil_fibers_host(self, k: int, idx: np.ndarray, nb_fixed=None, nb_vary=None):
         idx = np.ascontiguousarray(idx, dtype=np.int32)

@@ -1,7 +1,8 @@
 """GPU parity tests proper: the HIP path (through the C-ABI) against the CPU oracle on the same
 seeded inputs.  Bar: absorbed flags / indices bit-exact; values within REL_TOL relative to the
 magnitude of the value function (north_star: 1e-6 L-inf after N iterations; we hold single
-backups to 1e-12)."""
+backups to 1e-12).
+The registered kernels one by one, by name: tests/fiber_kernel_cases.py (the case table) and tests/test_gpu_fiber_kernels.py."""
 import numpy as np
 import pytest
 
@@ -488,7 +489,9 @@ def test_edge_cases_empty_batch_max_rank_max_nodes(oracle):
 
 def test_large_core_not_staged_in_lds(oracle):
     """Rank 20 on a 100-node dimension (the reference's own regression size, tprob_test.c:2284,2310): N x RP^2 doubles
-    exceed the CU's LDS, the per-wave kernel then reads each node's matrix from L2 instead of staging the core."""
+    exceed the CU's LDS, the per-wave kernel then reads each node's matrix from L2 instead of staging the core.  Only a middle
+    dimension holds N x RP^2 doubles (an end dimension, so both dimensions of a 2-D problem, holds N x RP and is always staged):
+    the unstaged instantiation is the one the last grid reaches, 101 nodes x 257 doubles on dimension 1 of a 3-D problem."""
     w = wl.c1_lqg2d().scaled(ngrid=(100, 100), rank=20)
     cores = wl.synth_cores(w)
     P = oracle.Problem(w, cores)
@@ -505,6 +508,12 @@ def test_large_core_not_staged_in_lds(oracle):
     eng3 = _engine(w3, cores3)
     for k in (0, 1, 2):
         _check(eng3, P3, w3, k, wl.synth_fibers(w3, k, 9))
+    w4 = wl.c2_dubins().scaled(ngrid=(33, 101, 35), rank=16)
+    cores4 = wl.synth_cores(w4)
+    P4 = oracle.Problem(w4, cores4)
+    eng4 = _engine(w4, cores4)
+    _check(eng4, P4, w4, 1, wl.synth_fibers(w4, 1, 9))
+    assert eng4.last_kernel() == "k_fiber_per_wave<Dubins3D,16,2>"
 
 
 @pytest.mark.gpu

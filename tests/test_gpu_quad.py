@@ -1,6 +1,7 @@
 """The fiber-quad kernel (kernel_fiber_quad.hpp: 16 fibers per wavefront, rank quarters in lane groups, f64 MFMA for the
 varying-core products, in-register transposing reductions) against the CPU oracle: every varying dimension, ragged tiles,
-faces, periodic wrap, obstacles, policy evaluation; values to 1e-12 of the value scale, flags bit-exact."""
+faces, periodic wrap, obstacles, policy evaluation; values to 1e-12 of the value scale, flags bit-exact.
+Every registered quad / duo instantiation by name: tests/fiber_kernel_cases.py and tests/test_gpu_fiber_kernels.py."""
 import numpy as np
 import pytest
 
