@@ -22,7 +22,8 @@ tiles for the pair / quad / duo families; rows 0, 1, 2 are the all-zero, all N-1
 
 tests/test_fiber_kernel_cases.py holds the table to the registry (registered == table + UNREACHABLE) and to a restatement of the
 selection logic and of the launchers' LDS arithmetic, and pins the reference below to the oracle; tests/test_gpu_fiber_kernels.py
-runs every row on a device.
+runs every row on a device, at the discount of its example and at the discounts of the regimes defined below (one per scan body of
+node_backup), and the LqgNd / Chain rows on inputs with stationary candidates.
 
 LDS arithmetic behind the tagged rows (doubles; the limit is 160 KiB = 20480 doubles; CW = doubles per candidate row):
   per-wave, staged:  4 (4 RP + 2 D RP + 64 NPL) + N_k ((k is an end ? RP : RP^2) | 1) + ncand CW
@@ -57,9 +58,13 @@ REL_TOL = 1e-12
 # 2d + 1 stencil nodes with probabilities p_i >= 0, sum_i p_i <= 1 (and exp(..) <= 1), so the value errors enter with weight at
 # most one: <= d r u max Vabs, plus 2d + 3 roundings of the sum itself, each relative to a partial sum bounded by
 # max(|ref|, max Vabs).  With d <= 10, r <= 20 that is (200 + 23) u = 2.5e-14 of the scale per side, 5e-14 between two double
-# implementations that order the sums differently: a factor 20 below REL_TOL.  The measured errors are in DESIGN.md (4.8, coverage of
-# the Bellman fiber kernels).
-EPS_BOUND = (10 * 20 + 2 * 10 + 3) * 2.0 ** -53
+# implementations that order the sums differently: a factor 20 below REL_TOL.  The discount factor adds its own term when beta is
+# the regime's and not the example's: the device forms exp(x), x = -beta dt, by a polynomial (exp_tiny: truncation below
+# 2^-56; exp_small: degree 7 below 2^-7) or by the device libm, the oracle by the host libm, each within an ulp or two of exp(x),
+# i.e. 4 u between them; x itself carries the two roundings of dt = h2 / Q and of the product, 2 u |x|, which exp turns into
+# 2 u |x| e^x <= 2 u / e < u of the factor.  The factor multiplies the cost-to-go, which the scale bounds, so the term is 5 u of the
+# scale.  The measured errors are in DESIGN.md (4.8, coverage of the Bellman fiber kernels).
+EPS_BOUND = (10 * 20 + 2 * 10 + 3 + 5) * 2.0 ** -53
 
 PER_WAVE, PAIR, QUAD = 1, 3, 4  # C3SC_VARIANT_*
 Case = namedtuple("Case", "family key rp tag name ngrid ranks variant nfib ks kernels opts")
@@ -94,7 +99,11 @@ MAX_CANDS = 6  # a row's candidate list: this many rows of the workload's own li
 def workload(case):
     w = _base(case.name).scaled(ngrid=case.ngrid)
     w.ranks = tuple(case.ranks)
-    n = min(w.ncand, case.opts.get("ncand", MAX_CANDS))
+    want = case.opts.get("ncand", MAX_CANDS)
+    if want > w.ncand and case.opts.get("spread"):  # a list longer than the model's own: evenly spaced inside its control range
+        lo, hi = w.cands.min(axis=0), w.cands.max(axis=0)
+        return with_cands(w, lo + (hi - lo) * np.linspace(0.0, 1.0, want)[:, None])
+    n = min(w.ncand, want)
     if n < w.ncand:
         w = with_cands(w, w.cands[np.unique(np.round(np.linspace(0, w.ncand - 1, n)).astype(int))])
     return w
@@ -334,3 +343,264 @@ def box_grid(lb, ub, G):
             rem //= G
             out[c, i] = ub[i] if gi == G - 1 else lb[i] + gi * dl[i]
     return out
+
+
+# ------------------------------------------------------------------------------------------------------- discount regimes
+# node_backup (c3sc_amd/csrc/kernel_common.hpp) compiles several candidate scans into every kernel and picks one per node, by wave
+# votes on the run-time discount beta:
+#   beta == 0                            the fraction scan (cross-multiplied comparison, one division for the winner)
+#   SPLIT kernels (per-wave, pair)       q0ok = no lane with Q0 < 1e-14;  x0 = beta h2 / Q0 per lane
+#     q0ok, every x0 < 2^-10             E0        exp_tiny (degree 4)
+#     q0ok, every x0 < 2^-7              E1        exp_small (degree 7)
+#     q0ok otherwise                     E2        exp_discount: exp_small where every lane's beta dt_c < 2^-7, else libm exp
+#     not q0ok                           E2+CHECK  the same with the stationary test
+#   !SPLIT kernels (quad, duo)           E3        one body with the stationary test; the same three forms chosen inside, all_tiny and
+#                                                  all_small without q0ok (a lane with Q0 = 0 fails both votes)
+# Q0 is the sum of the upwind rates of the dimensions outside the model's control-dependent set, restated here from models.hpp
+# (tests/test_fiber_kernel_cases.py holds the table to every UDEP_MASK line); Chain<DIM> and LqgNd<DIM> are formulas in DIM.
+UDEP = {"Dubins3D": (2,), "Scar4D": (2, 3), "Car7D": (5, 6), "Rossler3D": (1,), "Tprob3D": (0, 1, 2), "Perch7D": (3, 4, 5, 6),
+        "Skid5D": (3, 4), "Cothrust6D": (3, 4, 5), "TableModel": (), "NoModel": (),
+        "LqgNd": lambda dim: tuple(range(1, dim, 2)),  # odd dimensions are driven by a control
+        "Chain": lambda dim: (dim - 1,)}
+
+
+def udep(mtype):
+    """the control-dependent dimensions of a model type string such as "Car7D" or "LqgNd<6>" """
+    base, _, arg = mtype.partition("<")
+    v = UDEP[base]
+    return tuple(v(int(arg.rstrip(">")))) if callable(v) else v
+
+
+REGIMES = ("zero", "tiny", "small", "libm", "mixed", "vote")
+SPLIT = {"fpw": True, "fpp": True, "fq": False, "fqd": False}  # node_backup's SPLIT argument in the family's kernel
+# the bodies a SPLIT setting compiles: name, or name + "+CHECK" where the stationary test is compiled in and a stationary lane
+# (SPLIT) or candidate (fraction) is in the batch.  The fraction scan and E3 always carry the test.
+BODIES = {True: ("fraction", "E0", "E1", "E2-poly", "E2-libm", "E2-poly+CHECK", "E2-libm+CHECK"),
+          False: ("fraction", "E3-tiny", "E3-small", "E3-poly", "E3-libm")}
+# body -> (families, why no row of theirs reaches it).  Empty: every family reaches every body its SPLIT setting compiles.
+UNREACHABLE_BODIES = {}
+
+NodePieces = namedtuple("NodePieces", "dt r0 prob stage h2")
+
+
+def node_pieces(oracle, w, k, idx, mtype=None):
+    """Per node of every fiber (absorbed nodes included: their lanes take part in the wave votes) and per candidate, from the
+    oracle's pieces: orc_model_drift / _diff_diag / _stage and transition_assemble.
+      dt[f, j, c]   = h2 / Q_c, nan where transition_assemble returns 1 (Q_c < 1e-14: a stationary candidate)
+      r0[f, j]      = h2 / Q0 from transition_assemble on the drift and diffusion with the control-dependent dimensions zeroed,
+                      inf where that returns 1 (Q0 < 1e-14)
+      prob[f, j, c] = the 2d + 1 transition probabilities, stage[f, j, c] the stage cost"""
+    import ctypes as C
+
+    L, dp = oracle.lib(), oracle.dp
+    mtype = mtype or MODEL_OF[w.name]
+    P = oracle.Problem(w)
+    h2, tv = P.h2(), P.tvec()
+    xg = w.xgrid()
+    d, N, S, F = w.dx, w.ngrid[k], 2 * w.dx + 1, len(idx)
+    keep = np.array([m not in udep(mtype) for m in range(d)], dtype=np.float64)
+    prm = np.zeros(8)
+    prm[:len(w.params)] = w.params
+    cands = np.ascontiguousarray(w.cands, dtype=np.float64)
+    dt = np.full((F, N, w.ncand), np.nan)
+    r0 = np.full((F, N), np.inf)
+    prob = np.full((F, N, w.ncand, S), np.nan)
+    stage = np.zeros((F, N, w.ncand))
+    x, b, sg, b0, diff, p1, st, dtv = np.zeros(d), np.zeros(d), np.zeros(d), np.zeros(d), np.zeros(d * d), np.zeros(S), C.c_double(0), C.c_double(0)
+    diag = diff[::d + 1]  # a view of the diagonal
+    args = (C.c_size_t(d), C.c_size_t(w.du), C.c_size_t(d), C.c_double(h2), dp(tv))
+    pprm, px, pb, psg, pb0, pdiff, pp1, pst, pdt = dp(prm), dp(x), dp(b), dp(sg), dp(b0), dp(diff), dp(p1), C.byref(st), C.byref(dtv)
+    for f, row in enumerate(idx):
+        for m in range(d):
+            x[m] = xg[m][row[m]]
+        for j in range(N):
+            x[k] = xg[k][j]
+            for c in range(w.ncand):
+                pu = dp(cands[c])
+                L.orc_model_drift(w.model, pprm, px, pu, pb)
+                L.orc_model_diff_diag(w.model, pprm, px, pu, psg)
+                L.orc_model_stage(w.model, pprm, px, pu, pst)
+                stage[f, j, c] = st.value
+                diag[:] = sg
+                if L.orc_transition_assemble(*args, pb, None, pdiff, None, pp1, None, pdt, None, None) == 0:
+                    dt[f, j, c] = dtv.value
+                    prob[f, j, c] = p1
+                if c == 0:  # the control-independent share: the same call on the other dimensions alone
+                    b0[:] = b * keep
+                    diag[:] = sg * keep
+                    if L.orc_transition_assemble(*args, pb0, None, pdiff, None, pp1, None, pdt, None, None) == 0:
+                        r0[f, j] = dtv.value
+    return NodePieces(dt, r0, prob, stage, h2)
+
+
+_PIECES = {}
+
+
+def row_pieces(oracle, case, w=None, fib=None):
+    """{k: (dt, r0)} of a row's batches (memoised per row, candidate list and batch: the regimes of a row share them)"""
+    w = w or workload(case)
+    fib = fib or fibers
+    key = (case_id(case), w.ngrid, w.params, w.cands.tobytes(), fib.__name__)
+    if key not in _PIECES:
+        mtype = MODEL_OF[case.name]
+        out = {}
+        for k in case.ks:
+            p = node_pieces(oracle, w, k, fib(w, k, case.nfib), mtype)
+            out[k] = (p.dt, p.r0)
+        _PIECES[key] = out
+    return _PIECES[key]
+
+
+def regime_betas(oracle, case, w=None, fib=None):
+    """The discounts of a row, from the oracle's own dt and r0 over all of the row's k (never a literal).  R is r0 where
+    it is finite and the node's largest dt where it is not; the factors of two keep every vote clear of rounding.
+      zero   0                     the fraction scan
+      tiny   2^-11 / max R         beta r0 <= 2^-11 < 2^-10 on every lane: all_tiny wherever q0ok holds
+      small  2^-8 / max R          beta r0 <= 2^-8 < 2^-7 on every lane: all_small; = 2^-8 > 2^-10 on the maximising node
+      libm   2^-6 / min dt         beta dt_c >= 2^-6 > 2^-7 for every candidate of every lane (and r0 >= dt_c): exp() runs
+      mixed  2^-7 / median dt      the batch straddles 2^-7
+      vote   2^-7 / sqrt(max R m)  m = min over the candidates of the largest dt_c of the batch (m <= max R: a candidate only adds
+                                   rates).  Where m < max R the lane of the largest r0 fails all_small while the candidate that
+                                   attains m passes the per-candidate vote in every wave: exp_discount's polynomial arm"""
+    pc = row_pieces(oracle, case, w, fib)
+    dts = np.concatenate([dt[np.isfinite(dt)] for dt, _ in pc.values()])
+    R = np.concatenate([np.where(np.isfinite(r0), r0, np.nanmax(np.where(np.isfinite(dt), dt, -np.inf), axis=-1)).ravel()
+                        for dt, r0 in pc.values()])
+    assert np.isfinite(R).all() and (dts > 0).all()
+    m = min(max(np.nanmax(dt[..., c]) for dt, _ in pc.values()) for c in range(next(iter(pc.values()))[0].shape[-1]))
+    assert m <= R.max()
+    return {"zero": 0.0, "tiny": 2.0 ** -11 / R.max(), "small": 2.0 ** -8 / R.max(), "libm": 2.0 ** -6 / dts.min(),
+            "mixed": 2.0 ** -7 / float(np.median(dts)), "vote": 2.0 ** -7 / float(np.sqrt(R.max() * m))}
+
+
+def bodies_of(split, dt, r0, beta):
+    """The set of scan bodies a batch with these dt[f, j, c] and r0[f, j] reaches at discount beta, from batch-wide inequalities
+    alone (which lanes share a wave is not modelled).  A body is listed when some wave must take it whatever its lanes are:
+      the wave that holds a lane with r0 = inf takes the CHECK body (SPLIT) / fails all_tiny and all_small (E3);
+      where every lane of the batch passes a vote, every wave passes it; the wave that holds the lane with the largest r0 fails
+      every vote that lane fails; a candidate whose beta dt_c is below 2^-7 on every lane of the batch passes the per-candidate
+      vote in every wave, one that is at or above it on every lane fails it in every wave.
+    Bodies that only some arrangement of lanes would reach are left out."""
+    valid = np.isfinite(dt)
+    if beta == 0.0:
+        return {"fraction"}
+    fin = np.isfinite(r0)
+    x0 = beta * np.where(fin, r0, np.inf)
+    xc = beta * np.where(valid, dt, np.nan)
+    cmax = np.nanmax(np.where(valid, xc, -np.inf).reshape(-1, dt.shape[-1]), axis=0)  # per candidate, over the batch
+    cmin = np.nanmin(np.where(valid, xc, np.inf).reshape(-1, dt.shape[-1]), axis=0)
+    vote = set()  # what exp_discount does in a wave that reaches it
+    if (cmax < 2.0 ** -7).any():
+        vote.add("poly")
+    if (cmin >= 2.0 ** -7).any():
+        vote.add("libm")
+    out = set()
+    if split:
+        if not fin.all():
+            out |= {f"E2-{v}+CHECK" for v in vote}
+        if fin.all():  # every wave has q0ok
+            if (x0 < 2.0 ** -10).all():
+                out.add("E0")
+            elif (x0 < 2.0 ** -7).all():
+                out.add("E1")  # the wave of the largest r0; others may take E0
+            else:
+                out |= {f"E2-{v}" for v in vote}  # the wave of the largest r0
+        return out
+    if (x0 < 2.0 ** -10).all():
+        out.add("E3-tiny")
+    elif (x0 < 2.0 ** -7).all():
+        out.add("E3-small")
+    else:
+        out |= {f"E3-{v}" for v in vote}
+    return out
+
+
+def scan_bodies(oracle, case, k, beta, w=None, fib=None):
+    dt, r0 = row_pieces(oracle, case, w, fib)[k]
+    return bodies_of(SPLIT[case.family], dt, r0, beta)
+
+
+# ------------------------------------------------------------------------------------------- the skip-and-flag path
+# The oracle fails a whole fiber on a stationary candidate (rc 101), so Q[f, j, c] is built from its pieces: the stencil of
+# P.stencil_fibers, node_pieces above and bellmanrhs; an invalid candidate is nan.  Inputs: LqgNd and Chain with the diffusion
+# switched off (sigma = 0 in both parameters), on a grid with a node at 0 on every axis that is another equation's drift, and a
+# candidate list that holds u = 0: there every rate vanishes.  Rossler3D cannot: its third equation's drift 0.1 + x2 (x0 - 14) and
+# its first, -x1 - x2, vanish together only off the grid nodes of its box, and its diffusion parameters are shared with them.
+STATIONARY_ROWS = (("fpw", "LqgNd<2>", 4, ""), ("fpw", "LqgNd<4>", 4, ""), ("fpw", "LqgNd<6>", 8, ""), ("fpw", "Chain<2>", 4, ""),
+                   ("fpw", "Chain<4>", 4, ""), ("fpp", "LqgNd<2>", 4, ""), ("fpp", "LqgNd<6>", 4, ""), ("fpp", "LqgNd<6>", 8, ""),
+                   ("fq", "LqgNd<6>", 8, ""))
+
+
+STATIONARY_REGIMES = ("zero", "tiny", "libm")  # tiny: the polynomial arm of the CHECK body on the pair kernels too
+
+
+def stationary_cases():
+    return [c for c in CASES if (c.family, c.key, c.rp, c.tag) in STATIONARY_ROWS]
+
+
+def stationary_workload(case):
+    """the row's workload without diffusion, every N made odd (a node at 0: the boxes are symmetric), u = 0 as the candidate list's
+    third entry"""
+    w = workload(case)
+    ngrid = tuple(n | 1 for n in w.ngrid)
+    cands = w.cands[(w.cands != 0.0).any(axis=1)]  # u = 0 sits at position 2, once
+    cands = np.insert(cands, 2, 0.0, axis=0) if len(cands) < w.ncand else np.concatenate([cands[:2], cands[:1] * 0.0, cands[3:]])
+    assert len({tuple(c) for c in cands}) == len(cands)
+    params = (w.params[0], 0.0, 0.0) + tuple(w.params[3:])
+    w2 = wl.Workload(w.name, w.model, params, w.dx, w.du, w.lb, w.ub, ngrid, w.ranks, w.discount, w.bc, [], cands)
+    for g, n in zip(w2.xgrid(), ngrid):
+        assert g[n // 2] == 0.0
+    return w2
+
+
+def fibers_through(w, k, F):
+    """F fibers along k, every fixed index at the centre node on a third of them (rows 0, 3, 6, ..: the stationary nodes lie there)"""
+    idx = fibers(w, k, F)
+    idx[::3] = np.array(w.ngrid) // 2
+    idx[:, k] = 0
+    return idx
+
+
+def fibers_clear(w, k, F):
+    """F fibers along k with no fixed index at its centre node"""
+    idx = fibers(w, k, F)
+    mid = np.array(w.ngrid) // 2
+    idx = np.where(idx == mid, idx + 1, idx).astype(idx.dtype)
+    idx[:, k] = 0
+    return idx
+
+
+def zero_axes(mtype):
+    """the coordinates that must vanish for u = 0 to be stationary without diffusion: another equation's drift"""
+    d = int(mtype.partition("<")[2].rstrip(">"))
+    return tuple(range(1, d, 2)) if mtype.startswith("LqgNd") else tuple(range(1, d))
+
+
+def q_pieces(oracle, w, cs, k, idx, mtype):
+    """(Q[f, j, c], flags, status): bellmanrhs on the oracle's stencil and node_pieces; nan where the candidate is stationary;
+    absorbed nodes carry the model's cost in every column.  status: a live node has an invalid candidate."""
+    import ctypes as C
+
+    L, dp = oracle.lib(), oracle.dp
+    P = oracle.Problem(w, cs)
+    V, ab = P.stencil_fibers(k, idx)
+    p = node_pieces(oracle, w, k, idx, mtype)
+    F, N, U = p.dt.shape
+    Q = np.full((F, N, U), np.nan)
+    xg = w.xgrid()
+    prm = np.zeros(8)
+    prm[:len(w.params)] = w.params
+    d = w.dx
+    for f in range(F):
+        for j in range(N):
+            if ab[f, j] != 0:
+                x = np.array([xg[m][j] if m == k else xg[m][idx[f][m]] for m in range(d)])
+                v = C.c_double(0)
+                (L.orc_model_boundcost if ab[f, j] == 1 else L.orc_model_obscost)(w.model, dp(prm), dp(x), C.byref(v))
+                Q[f, j] = v.value
+                continue
+            for c in range(U):
+                if np.isfinite(p.dt[f, j, c]):
+                    Q[f, j, c], _ = oracle.bellmanrhs(d, w.du, p.stage[f, j, c], w.discount, p.prob[f, j, c], p.dt[f, j, c], V[f, j])
+    live = ab == 0
+    return Q, ab, bool((np.isnan(Q).any(axis=-1) & live).any())

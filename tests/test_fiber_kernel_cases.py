@@ -384,3 +384,156 @@ def test_q_table_is_the_oracles_backup(oracle, case, signed):
         assert np.abs(at - qmin)[live].max() <= 1e-14 * scale
         if signed:
             assert T.vabs(oracle, w, cs, k, idx) > 0.0
+
+
+# ------------------------------------------------------------------------------------------------ discount regimes
+def test_udep_table_matches_models_hpp():
+    """T.UDEP restates every UDEP_MASK line of models.hpp; Chain<DIM> and LqgNd<DIM> as formulas, compared at every registered DIM"""
+    src = re.sub(r"//.*", "", open(os.path.join(CSRC, "models.hpp")).read())
+    found, name, templ, prev = {}, None, False, ""
+    for line in src.splitlines():
+        m = re.match(r"struct\s+(\w+)\s*\{", line)  # a top-level struct (nested ones are indented)
+        if m:
+            name, templ = m.group(1), bool(re.match(r"template\s*<int DIM>", prev))
+        m = re.search(r"UDEP_MASK\s*=\s*([^;,]+)[;,]", line)
+        if m:
+            assert name and name not in found, line
+            found[name] = (templ, re.sub(r"(0x[0-9A-Fa-f]+|\d+)u\b", r"\1", m.group(1)).strip())
+        prev = line if line.strip() else prev
+    assert len(re.findall(r"UDEP_MASK\s*=", src)) == len(found)
+    assert set(found) == set(T.UDEP), set(found) ^ set(T.UDEP)
+    dims = {"LqgNd": (2, 4, 6), "Chain": (2, 4, 10), "TableModel": (2, 3, 4, 6, 7, 10), "NoModel": (2, 3, 4, 5, 6, 7, 10)}
+    for name, (templ, expr) in found.items():
+        for dim in dims.get(name, (None,)):
+            assert templ == (dim is not None), name
+            mask = eval(expr, {"__builtins__": {}}, {"DIM": dim})
+            want = T.udep(name if dim is None else f"{name}<{dim}>")
+            assert mask == sum(1 << m for m in want), (name, dim, hex(mask), want)
+    for c in T.CASES:  # every row's model has an entry
+        if c.family not in ("table", "stencil"):
+            T.udep(c.key)
+
+
+def test_bodies_of_on_hand_made_batches():
+    """the batch-wide inequalities one by one"""
+    dt = np.array([[[1.0, 0.5], [0.25, 0.125]]])
+    r0 = np.array([[2.0, 0.5]])
+    B = lambda split, beta, r=r0, t=dt: T.bodies_of(split, t, r, beta)
+    assert B(True, 0.0) == B(False, 0.0) == {"fraction"}
+    assert B(True, 2.0 ** -12) == {"E0"} and B(False, 2.0 ** -12) == {"E3-tiny"}
+    assert B(True, 2.0 ** -11) == {"E1"} and B(False, 2.0 ** -9) == {"E3-small"}  # 2^-11 x 2 = 2^-10 fails all_tiny
+    assert B(True, 2.0 ** -8) == {"E2-poly"}  # the lane with r0 = 2 fails all_small; every dt <= 1 passes the candidate vote
+    assert B(True, 2.0 ** -7) == {"E2-poly"} and B(False, 2.0 ** -7) == {"E3-poly"}  # candidate 1 passes everywhere, candidate 0 is split
+    assert B(True, 2.0 ** -4) == {"E2-libm"} and B(False, 2.0 ** -4) == {"E3-libm"}
+    rinf = np.array([[np.inf, 0.5]])
+    assert B(True, 2.0 ** -12, rinf) == {"E2-poly+CHECK"} and B(True, 2.0 ** -4, rinf) == {"E2-libm+CHECK"}
+    assert B(False, 2.0 ** -12, rinf) == {"E3-poly"}  # a lane with Q0 = 0 fails all_tiny and all_small
+    dtn = dt.copy()
+    dtn[0, 0, 0] = np.nan  # an invalid candidate takes no part in the inequalities
+    assert B(True, 2.0 ** -4, rinf, dtn) == {"E2-libm+CHECK"}
+
+
+LIST_ROWS = [c for c in T.CASES if c.family in T.LIST_FAMILIES]
+
+
+@pytest.mark.parametrize("case", LIST_ROWS, ids=T.case_id)
+def test_regime_implies_body(oracle, case):
+    """the named regime implies the named body, for every k of the row, from the oracle's dt and r0"""
+    beta = T.regime_betas(oracle, case)
+    assert set(beta) == set(T.REGIMES)
+    split = T.SPLIT[case.family]
+    pc = T.row_pieces(oracle, case)
+    any_inf = any(np.isinf(r0).any() for _, r0 in pc.values())
+    all_inf = all(np.isinf(r0).all() for _, r0 in pc.values())
+    assert any_inf == all_inf == (case.key == "Tprob3D")  # a row's own batch has no stationary lane, Tprob3D's nothing else
+    B = {r: {k: T.scan_bodies(oracle, case, k, beta[r]) for k in case.ks} for r in T.REGIMES}
+    union = {r: set().union(*B[r].values()) for r in T.REGIMES}
+    for k in case.ks:
+        dt, r0 = pc[k]
+        assert np.isfinite(dt).all()
+        assert B["zero"][k] == {"fraction"}
+        if not split:
+            assert B["tiny"][k] == {"E3-tiny"} and B["libm"][k] == {"E3-libm"} and B["small"][k] <= {"E3-tiny", "E3-small"}
+        elif all_inf:
+            assert B["tiny"][k] == B["small"][k] == {"E2-poly+CHECK"} and B["libm"][k] == {"E2-libm+CHECK"}
+        else:
+            assert B["tiny"][k] == {"E0"} and B["libm"][k] == {"E2-libm"} and B["small"][k] <= {"E0", "E1"}
+        assert B["small"][k]
+    # the k that holds the row's largest r0 fails all_tiny in `small`
+    assert ("E3-small" if not split else "E2-poly+CHECK" if all_inf else "E1") in union["small"]
+    dts = np.concatenate([dt.ravel() for dt, _ in pc.values()])
+    assert beta["mixed"] * dts.min() < 2.0 ** -7 <= beta["mixed"] * dts.max()  # the batch straddles the threshold
+    assert 0.0 < beta["tiny"] < beta["small"] < beta["libm"]
+
+
+def _stationary_bodies(oracle, case):
+    w = T.stationary_workload(case)
+    beta = T.regime_betas(oracle, case, w, T.fibers_through)
+    return {r: set().union(*[T.scan_bodies(oracle, case, k, beta[r], w, T.fibers_through) for k in case.ks]) for r in T.STATIONARY_REGIMES}
+
+
+def test_every_family_reaches_every_body(oracle):
+    """over the table and the regimes, every family reaches every body its SPLIT setting compiles, up to UNREACHABLE_BODIES; the
+    CHECK bodies are reached by rows other than Tprob3D's (the stationary inputs)"""
+    reached = {f: set() for f in T.LIST_FAMILIES}
+    check_rows = set()
+    for case in LIST_ROWS:
+        beta = T.regime_betas(oracle, case)
+        for r in T.REGIMES:
+            for k in case.ks:
+                b = T.scan_bodies(oracle, case, k, beta[r])
+                reached[case.family] |= b
+                if any(x.endswith("+CHECK") for x in b):
+                    check_rows.add(case.key)
+    for case in T.stationary_cases():
+        for r, b in _stationary_bodies(oracle, case).items():
+            reached[case.family] |= b
+            if any(x.endswith("+CHECK") for x in b):
+                check_rows.add(T.case_id(case))
+    for fam, got in reached.items():
+        want = set(T.BODIES[T.SPLIT[fam]])
+        assert got <= want
+        missing = want - got - {b for b, (fams, why) in T.UNREACHABLE_BODIES.items() if fam in fams}
+        assert not missing, (fam, sorted(missing))
+    for b, (fams, why) in T.UNREACHABLE_BODIES.items():
+        assert isinstance(why, str) and why.strip()
+        for fam in fams:
+            assert b in T.BODIES[T.SPLIT[fam]] and b not in reached[fam], (b, fam)  # a stale entry
+    assert check_rows - {"Tprob3D"}, check_rows
+    assert {c.family for c in T.stationary_cases()} == {"fpw", "fpp", "fq"} and len(T.stationary_cases()) == len(T.STATIONARY_ROWS)
+
+
+@pytest.mark.parametrize("case", T.stationary_cases(), ids=T.case_id)
+def test_stationary_reference_is_pinned_to_q_table(oracle, case):
+    """Q built from the oracle's pieces (T.q_pieces) equals T.q_table to 1e-14 of the batch scale on a batch without a stationary
+    node, flags included; on the batch through the centre nodes it has invalid candidates exactly where every coordinate of
+    T.zero_axes vanishes, only at u = 0, the oracle fails those fibers with 101, and every node keeps a valid candidate"""
+    import ctypes as C
+
+    w = T.stationary_workload(case)
+    cs = T.cores(case, w)
+    mtype = T.MODEL_OF[case.name]
+    za = T.zero_axes(mtype)
+    xg = w.xgrid()
+    assert (w.cands[2] == 0.0).all()
+    for k in case.ks:
+        n = min(case.nfib, 12)
+        if any(m != k for m in za):
+            idx = T.fibers_clear(w, k, n)
+            Q, ab, bad = T.q_pieces(oracle, w, cs, k, idx, mtype)
+            Qt, flags = T.q_table(oracle, w, cs, k, idx)
+            assert not bad and not np.isnan(Q).any()
+            assert np.array_equal(flags[0], ab)
+            assert np.abs(Q - Qt).max() <= 1e-14 * np.abs(Qt).max()
+        idx = T.fibers_through(w, k, n)
+        Q, ab, bad = T.q_pieces(oracle, w, cs, k, idx, mtype)
+        x = np.stack([np.broadcast_to(xg[m][:, None] if m == k else xg[m][idx[:, m]][None, :], (w.ngrid[k], n)).T for m in range(w.dx)], -1)
+        want = (x[..., list(za)] == 0.0).all(axis=-1) & (ab == 0)
+        assert want.any() and bad
+        assert np.array_equal(np.isnan(Q[..., 2]), want)
+        assert not np.isnan(np.delete(Q, 2, axis=-1)).any()
+        P = oracle.Problem(w, cs)
+        o, u = np.zeros((1, w.ngrid[k])), np.zeros((1, w.ngrid[k]), dtype=np.int32)
+        f = int(np.argmax(want.any(axis=1)))
+        row = np.ascontiguousarray(idx[f:f + 1], dtype=np.int32)
+        assert P.L.orc_bellman_fibers(P.h, C.c_size_t(k), C.c_size_t(1), oracle.ip(row), oracle.dp(o), oracle.ip(u), None) == 101

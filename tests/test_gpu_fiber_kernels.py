@@ -8,8 +8,17 @@ one oracle run per candidate (fiber_kernel_cases.q_table), which makes the FORCE
 argmin checkable without ties.  Flags are bit-exact; values to REL_TOL = 1e-12 of the scale fiber_kernel_cases derives; no node is
 left out of a comparison.
 
+The discount is a run-time argument and node_backup picks one of several compiled scans per node by it, so every list row also
+runs at six discounts computed from the oracle's own dt and h2 / Q0 of its batches (fiber_kernel_cases.regime_betas: zero, tiny,
+small, libm, mixed, vote -- the fraction scan, exp_tiny, exp_small, libm exp, a batch that straddles 2^-7, exp_discount's
+polynomial arm), the table rows at three and the box rows at two; the pair and duo rows with 4, 5 and 7 candidates (remainders
+against the three candidates per trip of the pair kernel's fraction scan); the LqgNd and Chain rows without diffusion through the
+nodes where u = 0 is stationary, against the minimum over the valid candidates built from the oracle's pieces.  Same bar.
+
 Every test prints its row's worst relative error (pytest -s); the worst per family and data class, and the file's run time, are
 recorded in DESIGN.md (4.8, coverage of the Bellman fiber kernels)."""
+import dataclasses
+
 import numpy as np
 import pytest
 
@@ -38,8 +47,8 @@ def _rows(*families):
     return [c for c in T.CASES if c.family in families]
 
 
-def _report(case, signed, worst):
-    print(f"{T.case_id(case)} {'signed' if signed else 'synth'}: worst relative error {worst:.2e}")
+def _report(case, signed, worst, label=""):
+    print(f"{T.case_id(case)}{' ' + label if label else ''} {'signed' if signed else 'synth'}: worst relative error {worst:.2e}")
 
 
 @pytest.mark.parametrize("signed", DATA, ids=DATA_IDS)
@@ -49,7 +58,12 @@ def test_list_kernels_vs_oracle(oracle, case, signed):
     where Q[node, ui] is within the tolerance of the minimum, status 0 and the row's kernel name for every k.  FORCED form on the
     same rows: a seeded random policy through policy_fibers_host against the gather from Q, equal flags, the same kernel name,
     identical bits on a repeat."""
-    w = T.workload(case)
+    _check_list(oracle, case, signed, T.workload(case))
+
+
+def _check_list(oracle, case, signed, w, label=""):
+    """the checks of test_list_kernels_vs_oracle on the workload w (the row's own, or the row's at another discount or with
+    another candidate list)"""
     cs = T.cores(case, w, signed)
     P = oracle.Problem(w, cs)
     eng = _engine(case, w, cs)
@@ -87,7 +101,8 @@ def test_list_kernels_vs_oracle(oracle, case, signed):
         assert err <= T.REL_TOL, f"{T.case_id(case)} k={k}: FORCED form, relative error {err:.3e} (scale {fscale:.3e})"
         again, ab3 = eng.policy_fibers_host(k, idx, pol)
         assert np.array_equal(again, got) and np.array_equal(ab3, ab2)
-    _report(case, signed, worst)
+    eng.close()
+    _report(case, signed, worst, label)
 
 
 @pytest.mark.parametrize("signed", DATA, ids=DATA_IDS)
@@ -95,7 +110,10 @@ def test_list_kernels_vs_oracle(oracle, case, signed):
 def test_table_kernels_vs_oracle(oracle, case, signed):
     """TableModel<D> at every registered (D, RP, NPL): (drift, sigma, stage) tables and costs from the oracle's model callbacks; the
     minimising call against Q.min and the policy call (BellmanEngine.policy_fibers_tables_host) against the gather from Q"""
-    w = T.workload(case)
+    _check_table(oracle, case, signed, T.workload(case))
+
+
+def _check_table(oracle, case, signed, w, label=""):
     cs = T.cores(case, w, signed)
     P = oracle.Problem(w, cs)
     eng = _engine(case, w, cs)
@@ -131,7 +149,8 @@ def test_table_kernels_vs_oracle(oracle, case, signed):
         assert err <= T.REL_TOL, f"{T.case_id(case)} k={k}: policy call, relative error {err:.3e}"
         again, _ = eng.policy_fibers_tables_host(k, idx, tables, costs2, pol)
         assert np.array_equal(again, got)
-    _report(case, signed, worst)
+    eng.close()
+    _report(case, signed, worst, label)
 
 
 @pytest.mark.parametrize("signed", DATA, ids=DATA_IDS)
@@ -164,9 +183,12 @@ def test_box_kernels_vs_oracle(oracle, case, signed):
     the result on live nodes does not exceed the oracle's scan over that same grid of controls by more than the tolerance; the
     returned controls, evaluated as an explicit candidate list through the list kernel's FORCED form on the same cores (held to
     the oracle by test_list_kernels_vs_oracle), reproduce the box output; absorbed nodes equal the oracle's"""
+    _check_box(oracle, case, signed, T.workload(case))
+
+
+def _check_box(oracle, case, signed, w, label=""):
     from c3sc_amd.engine import BellmanEngine
 
-    w = T.workload(case)
     cs = T.cores(case, w, signed)
     lb, ub, G = np.array(case.opts["lb"]), np.array(case.opts["ub"]), case.opts["grid"]
     eng = _engine(case, w, cs)
@@ -204,4 +226,99 @@ def test_box_kernels_vs_oracle(oracle, case, signed):
         worst = max(worst, err)
         assert err <= T.REL_TOL, f"{T.case_id(case)} k={k}: list kernel on the returned controls, relative error {err:.3e}"
         eng2.close()
-    _report(case, signed, worst)
+    eng.close()
+    _report(case, signed, worst, label)
+
+
+# ------------------------------------------------------------------------------------------------------- discount regimes
+def _at(oracle, case, regime, w=None):
+    """the row's workload at the regime's discount (fiber_kernel_cases.regime_betas: from the oracle's dt and r0 of the row's own
+    batches, over all of its k)"""
+    w = w or T.workload(case)
+    return dataclasses.replace(w, discount=T.regime_betas(oracle, case, w)[regime])
+
+
+@pytest.mark.parametrize("signed", DATA, ids=DATA_IDS)
+@pytest.mark.parametrize("case", _rows(*T.LIST_FAMILIES), ids=T.case_id)
+@pytest.mark.parametrize("regime", T.REGIMES)
+def test_list_kernels_in_every_regime(oracle, case, signed, regime):
+    """every check of test_list_kernels_vs_oracle with the discount of each regime, q_table built with the same discount: the
+    fraction scan, exp_tiny, exp_small, libm exp, the straddling batch and exp_discount's polynomial arm
+    (tests/test_fiber_kernel_cases.py holds regime -> body on the CPU)"""
+    _check_list(oracle, case, signed, _at(oracle, case, regime), regime)
+
+
+@pytest.mark.parametrize("signed", DATA, ids=DATA_IDS)
+@pytest.mark.parametrize("case", _rows("table"), ids=T.case_id)
+@pytest.mark.parametrize("regime", ("zero", "libm", "mixed"))
+def test_table_kernels_in_every_regime(oracle, case, signed, regime):
+    """node_backup_tables has one discounted form (libm exp) and the undiscounted one"""
+    _check_table(oracle, case, signed, _at(oracle, case, regime), regime)
+
+
+@pytest.mark.parametrize("signed", DATA, ids=DATA_IDS)
+@pytest.mark.parametrize("case", _rows("fpw_box"), ids=T.case_id)
+@pytest.mark.parametrize("regime", ("zero", "libm"))
+def test_box_kernels_in_every_regime(oracle, case, signed, regime):
+    """node_backup_box: the factor is 1 at beta = 0, else exp_discount.  The discount is the one of the row's candidate list, which
+    spans the same box"""
+    _check_box(oracle, case, signed, _at(oracle, case, regime), regime)
+
+
+TAIL_ROWS = [(c, r) for c in _rows("fpp") for r in ("zero",)] + [(c, r) for c in _rows("fqd") for r in ("zero", "libm")]
+
+
+@pytest.mark.parametrize("signed", DATA, ids=DATA_IDS)
+@pytest.mark.parametrize("ncand", (4, 5, 7))
+@pytest.mark.parametrize("case,regime", TAIL_ROWS, ids=lambda v: T.case_id(v) if isinstance(v, tuple) else v)
+def test_candidate_count_tails(oracle, case, regime, ncand, signed):
+    """candidate counts 4, 5 and 7: remainders 1, 2 and 1 against the pair kernel's three candidates per trip of the fraction
+    scan (the tail trip clamps the candidate index), and one list longer than the table's six.  The pair rows undiscounted (the
+    discounted pair scan takes one candidate per trip), the duo rows undiscounted and in the libm regime.  A list longer than
+    the model's own is spread evenly inside its control range."""
+    case = case._replace(opts=dict(case.opts, ncand=ncand, spread=True))
+    w = T.workload(case)
+    assert w.ncand == ncand and ncand % 3 != 0
+    _check_list(oracle, case, signed, _at(oracle, case, regime, w), f"{regime} ncand={ncand}")
+
+
+# ------------------------------------------------------------------------------------------- the skip-and-flag path
+@pytest.mark.parametrize("signed", DATA, ids=DATA_IDS)
+@pytest.mark.parametrize("case", T.stationary_cases(), ids=T.case_id)
+@pytest.mark.parametrize("regime", T.STATIONARY_REGIMES)
+def test_stationary_candidates_are_skipped_and_flagged(oracle, case, signed, regime):
+    """LqgNd / Chain without diffusion, u = 0 in the list, fibers through the nodes where it is stationary: the value is the
+    minimum over the valid candidates (fiber_kernel_cases.q_pieces: the oracle's pieces, nan where transition_assemble
+    returns 1), the argmin is a valid candidate that attains it, C3SC_STATUS_STATIONARY is set; on a batch that avoids those
+    nodes the same engine leaves it clear and matches the same reference"""
+    w0 = T.stationary_workload(case)
+    w = dataclasses.replace(w0, discount=T.regime_betas(oracle, case, w0, T.fibers_through)[regime])
+    cs = T.cores(case, w, signed)
+    mtype = T.MODEL_OF[case.name]
+    eng = _engine(case, w, cs)
+    worst = 0.0
+    for k in case.ks:
+        for fib in (T.fibers_clear, T.fibers_through):
+            if fib is T.fibers_clear and not any(m != k for m in T.zero_axes(mtype)):
+                continue  # every fiber along k crosses the stationary node (the only coordinate that must vanish varies)
+            idx = fib(w, k, case.nfib)
+            Q, ref_ab, bad = T.q_pieces(oracle, w, cs, k, idx, mtype)
+            assert bad == (fib is T.fibers_through)
+            qmin = np.nanmin(Q, axis=-1)
+            scale = T.scale_of(oracle, w, cs, k, idx, qmin, signed)
+            out, ui, ab = eng.bellman_fibers_host(k, idx)
+            st = eng.status()
+            assert (st & 1) == int(bad) and (st & ~1) == 0, (k, fib.__name__, st)
+            assert eng.last_kernel() == case.kernels[k], (k, eng.last_kernel())
+            np.testing.assert_array_equal(ab, ref_ab)
+            live = ref_ab == 0
+            assert live.any()
+            err = _rel(out, qmin, scale)
+            worst = max(worst, err)
+            assert err <= T.REL_TOL, f"{T.case_id(case)} k={k} {fib.__name__}: relative error {err:.3e} (scale {scale:.3e})"
+            assert (ui[live] >= 0).all() and (ui[live] < w.ncand).all()
+            at = np.take_along_axis(Q, np.clip(ui, 0, w.ncand - 1)[..., None], axis=-1)[..., 0]
+            assert np.isfinite(at[live]).all(), f"{T.case_id(case)} k={k}: an argmin on a stationary candidate"
+            assert (at[live] - qmin[live]).max() <= T.REL_TOL * scale
+    eng.close()
+    _report(case, signed, worst, regime)
