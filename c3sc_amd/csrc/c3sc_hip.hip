@@ -1276,18 +1276,100 @@ int c3sc_hip_stencil_points(c3sc_hip_ctx *c, size_t n, const double *d_x, double
     return launch_one(c, e, A, io);
 }
 
-int c3sc_hip_simulate(c3sc_hip_ctx *c, const c3sc_hip_sim_args *a, void *stream)
+// ---- the front end c3sc_hip_simulate and c3sc_hip_integrate share.  who = "simulate" / "integrate" opens every message; Args is
+// c3sc_hip_sim_args / c3sc_hip_ode_args (the fields read here have the same names in both).  The callers keep the order of their
+// checks: it decides which error a bad call gets.
+extern "C++" { // templates
+static int failw(c3sc_hip_ctx *c, int code, const char *who, const char *msg) { return fail(c, code, (std::string(who) + msg).c_str()); }
+
+// what the context must hold before a closed loop of either kind
+template <class Args>
+static int closed_loop_setup(c3sc_hip_ctx *c, const char *who, const Args *a)
 {
     if (!c) return C3SC_ERR_ARG;
-    if (!a) return fail(c, C3SC_ERR_ARG, "simulate: null argument struct");
-    if (c->model == C3SC_MODEL_TABLE) return fail(c, C3SC_ERR_UNSUPPORTED, "simulate: the TABLE model has no device dynamics");
-    if (!c->have_mca || c->model == 0) return fail(c, C3SC_ERR_ARG, "simulate: mca and model must be set");
-    if (a->box ? c->box_du == 0 : c->ncand == 0)
-        return fail(c, C3SC_ERR_ARG, a->box ? "simulate: set_control_box first" : "simulate: set_controls first");
+    if (!a) return failw(c, C3SC_ERR_ARG, who, ": null argument struct");
+    if (c->model == C3SC_MODEL_TABLE) return failw(c, C3SC_ERR_UNSUPPORTED, who, ": the TABLE model has no device dynamics");
+    if (!c->have_mca || c->model == 0) return failw(c, C3SC_ERR_ARG, who, ": mca and model must be set");
+    if (a->box ? c->box_du == 0 : c->ncand == 0) return failw(c, C3SC_ERR_ARG, who, a->box ? ": set_control_box first" : ": set_controls first");
     if (a->box && model_ncf(c->model) != 0 && c->model != C3SC_MODEL_COTHRUST6D)
-        return fail(c, C3SC_ERR_UNSUPPORTED, "simulate: this model needs transcendental functions of the control in a box");
-    if (a->box && c->game_gsz > 0) return fail(c, C3SC_ERR_UNSUPPORTED, "simulate: games have no control-box form");
-    if (check_game_model(c, "simulate: game mode needs a model compiled with game kernels") != C3SC_OK) return C3SC_ERR_UNSUPPORTED;
+        return failw(c, C3SC_ERR_UNSUPPORTED, who, ": this model needs transcendental functions of the control in a box");
+    if (a->box && c->game_gsz > 0) return failw(c, C3SC_ERR_UNSUPPORTED, who, ": games have no control-box form");
+    if (check_game_model(c, (std::string(who) + ": game mode needs a model compiled with game kernels").c_str()) != C3SC_OK) return C3SC_ERR_UNSUPPORTED;
+    return C3SC_OK;
+}
+
+// the batch size and the rows saved of nouter steps; many / late: the caller's texts for too many trajectories and for a
+// save_every beyond its step count
+template <class Args>
+static int closed_loop_sizes(c3sc_hip_ctx *c, const char *who, const Args *a, size_t nouter, const char *many, const char *late)
+{
+    if (a->n > SIM_MAX_TRAJ) return fail(c, C3SC_ERR_ARG, many);
+    if (a->save_every == 0 && (a->d_traj || a->d_u)) return failw(c, C3SC_ERR_ARG, who, ": d_traj / d_u need save_every > 0");
+    if (a->save_every > nouter && a->save_every > 1 && (a->d_traj || a->d_u)) return fail(c, C3SC_ERR_ARG, late);
+    return C3SC_OK;
+}
+
+// the state between launches (x | cost | what the kernel adds), grow-only
+static int closed_loop_state(c3sc_hip_ctx *c, size_t bytes)
+{
+    if (bytes <= c->sim_state_bytes) return C3SC_OK;
+    if (c->sim_state) HIPCHK(c, hipFree(c->sim_state));
+    c->sim_state = nullptr;
+    c->sim_state_bytes = 0;
+    HIPCHK(c, hipMalloc(&c->sim_state, bytes));
+    c->sim_state_bytes = bytes;
+    return C3SC_OK;
+}
+
+static void closed_loop_box(const c3sc_hip_ctx *c, int box, KArgs &A)
+{
+    A.cmode = box ? 1 : 0;
+    A.ugrid = c->box_grid;
+    A.upolish = c->box_polish;
+    for (int i = 0; i < c->box_du; i++) { A.ulb[i] = c->box_lb[i]; A.uub[i] = c->box_ub[i]; }
+}
+
+static int copy_back(c3sc_hip_ctx *c, void *dst, const void *src, size_t bytes, void *stream)
+{
+    if (dst) HIPCHK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return C3SC_OK;
+}
+
+// final states, costs and the step each trajectory ended at (-1: none), from the state block to the caller's buffers
+template <class Args>
+static int closed_loop_results(c3sc_hip_ctx *c, const Args *a, int64_t *d_step, void *stream)
+{
+    const size_t n = a->n, d = (size_t)c->d;
+    const double *st_x = (const double *)c->sim_state, *st_cost = st_x + n * d;
+    int rc = copy_back(c, a->d_xfinal, st_x, n * d * sizeof(double), stream);
+    if (rc == C3SC_OK) rc = copy_back(c, a->d_cost, st_cost, n * sizeof(double), stream);
+    if (rc == C3SC_OK) rc = copy_back(c, d_step, st_cost + n, n * sizeof(int64_t), stream);
+    return rc;
+}
+
+// the host-buffer variants: the checks before staging, and the buffer shapes (rows of d_traj and d_u per trajectory)
+struct HostShape {
+    size_t n, d, du, nrow, nurow;
+};
+
+template <class Args>
+static int closed_loop_host_shape(c3sc_hip_ctx *c, const char *who, const Args *h, size_t nouter, HostShape &sh)
+{
+    if (!h->d_x0) return failw(c, C3SC_ERR_ARG, who, "_host: null x0");
+    if (h->n > SIM_MAX_TRAJ || nouter > ((size_t)1 << 30)) return failw(c, C3SC_ERR_ARG, who, "_host: sizes too large");
+    if (h->save_every == 0 && (h->d_traj || h->d_u)) return failw(c, C3SC_ERR_ARG, who, ": d_traj / d_u need save_every > 0");
+    if (c->d == 0) return failw(c, C3SC_ERR_ARG, who, "_host: set_grid first");
+    const size_t se = h->save_every;
+    sh = {h->n, (size_t)c->d, (size_t)(h->box ? c->box_du : c->du), se ? nouter / se + 1 : 0, se ? (nouter + se - 1) / se : 0};
+    return C3SC_OK;
+}
+} // extern "C++"
+
+int c3sc_hip_simulate(c3sc_hip_ctx *c, const c3sc_hip_sim_args *a, void *stream)
+{
+    const char *who = "simulate";
+    int rc = closed_loop_setup(c, who, a);
+    if (rc != C3SC_OK) return rc;
     const bool hz = c->hz_dt > 0.0; // horizon mode: one launch per step, step k's controller on the cores of V_{k+1}
     if (hz) {
         if (check_horizon_model(c, "simulate: horizon mode needs a model compiled with horizon kernels") != C3SC_OK) return C3SC_ERR_UNSUPPORTED;
@@ -1298,7 +1380,7 @@ int c3sc_hip_simulate(c3sc_hip_ctx *c, const c3sc_hip_sim_args *a, void *stream)
         if (a->nsteps + 1 > (size_t)c->hz_nstack) return fail(c, C3SC_ERR_ARG, "simulate: nsteps exceeds the value stack (nstack - 1 stages)");
     }
     KArgs A;
-    int rc = fill_args(c, 0, 0, A, false);
+    rc = fill_args(c, 0, 0, A, false);
     if (rc != C3SC_OK) return rc;
     if (hz) {
         if (c->hz_stack_static != c->static_doubles)
@@ -1311,10 +1393,9 @@ int c3sc_hip_simulate(c3sc_hip_ctx *c, const c3sc_hip_sim_args *a, void *stream)
     if (rc != C3SC_OK) return rc;
     if (!(a->dt > 0.0) || !std::isfinite(a->dt)) return fail(c, C3SC_ERR_ARG, "simulate: dt must be positive and finite");
     if (a->nsteps > (size_t)1 << 30) return fail(c, C3SC_ERR_ARG, "simulate: nsteps too large");
-    if (a->n > SIM_MAX_TRAJ) return fail(c, C3SC_ERR_ARG, "simulate: more than 2^31 trajectories in one call (split the batch, traj_offset)");
-    if (a->save_every == 0 && (a->d_traj || a->d_u)) return fail(c, C3SC_ERR_ARG, "simulate: d_traj / d_u need save_every > 0");
-    if (a->save_every > a->nsteps && a->save_every > 1 && (a->d_traj || a->d_u))
-        return fail(c, C3SC_ERR_ARG, "simulate: save_every larger than nsteps");
+    rc = closed_loop_sizes(c, who, a, a->nsteps, "simulate: more than 2^31 trajectories in one call (split the batch, traj_offset)",
+                           "simulate: save_every larger than nsteps");
+    if (rc != C3SC_OK) return rc;
     if (a->steps_per_launch < 0) return fail(c, C3SC_ERR_ARG, "simulate: steps_per_launch < 0");
     const KernelEntry *e = find_sim_kernel(VARIANT_ROLLOUT, c->model, c->d, hz ? c->hz_rp[a->nsteps] : c->rp);
     if (!e) return fail(c, C3SC_ERR_UNSUPPORTED, "simulate: no rollout instantiation for this model at this padded rank");
@@ -1322,20 +1403,9 @@ int c3sc_hip_simulate(c3sc_hip_ctx *c, const c3sc_hip_sim_args *a, void *stream)
     if (!a->d_x0) return fail(c, C3SC_ERR_ARG, "simulate: null d_x0");
     const int d = c->d;
     const size_t n = a->n;
-    const size_t bytes = n * (size_t)(d + 2) * sizeof(double);
-    if (bytes > c->sim_state_bytes) {
-        if (c->sim_state) HIPCHK(c, hipFree(c->sim_state));
-        c->sim_state = nullptr;
-        c->sim_state_bytes = 0;
-        HIPCHK(c, hipMalloc(&c->sim_state, bytes));
-        c->sim_state_bytes = bytes;
-    }
-    double *st_x = (double *)c->sim_state, *st_cost = st_x + n * d;
-    long long *st_exit = (long long *)(st_cost + n);
-    A.cmode = a->box ? 1 : 0;
-    A.ugrid = c->box_grid;
-    A.upolish = c->box_polish;
-    for (int i = 0; i < c->box_du; i++) { A.ulb[i] = c->box_lb[i]; A.uub[i] = c->box_ub[i]; }
+    rc = closed_loop_state(c, n * (size_t)(d + 2) * sizeof(double)); // x | cost | exit_step
+    if (rc != C3SC_OK) return rc;
+    closed_loop_box(c, a->box, A);
     SimK S;
     std::memset(&S, 0, sizeof(S));
     S.n = (long)n;
@@ -1349,15 +1419,13 @@ int c3sc_hip_simulate(c3sc_hip_ctx *c, const c3sc_hip_sim_args *a, void *stream)
     S.sqdt = std::sqrt(a->dt);
     S.x0 = a->d_x0;
     S.noise = a->d_noise;
-    S.x = st_x;
-    S.cost = st_cost;
-    S.exit_step = st_exit;
+    S.x = (double *)c->sim_state;
+    S.cost = S.x + n * d;
+    S.exit_step = (long long *)(S.cost + n);
     S.traj = a->d_traj;
     S.u = a->d_u;
     S.vend = a->d_vend;
     const int chunk = hz ? 1 : (a->steps_per_launch > 0 ? a->steps_per_launch : 64);
-    c->last_kernel = e->name;
-    c->status_cache_valid = false;
     if (hz) HIPCHK(c, hipMemcpyAsync(c->hz_stack, c->arena, c->static_doubles * sizeof(double), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     int s0 = 0;
     do { // at least one launch: nsteps = 0 still tests x_0 and evaluates V_end
@@ -1371,17 +1439,11 @@ int c3sc_hip_simulate(c3sc_hip_ctx *c, const c3sc_hip_sim_args *a, void *stream)
             ro = c->hz_stack;
         }
         LaunchIO io{ro, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream, &S};
-        g_launches++;
-        const hipError_t he = launch_entry(*ek, A, io);
-        if (he == hipErrorNotSupported) return fail(c, C3SC_ERR_UNSUPPORTED, "simulate: this rollout kernel has no box minimiser");
-        HIPCHK(c, he);
+        rc = launch_one(c, ek, A, io, "simulate: this rollout kernel has no box minimiser");
+        if (rc != C3SC_OK) return rc;
         s0 = S.s1;
     } while (s0 < (int)a->nsteps);
-    hipStream_t sm = (hipStream_t)stream;
-    if (a->d_xfinal) HIPCHK(c, hipMemcpyAsync(a->d_xfinal, st_x, n * d * sizeof(double), hipMemcpyDeviceToDevice, sm));
-    if (a->d_cost) HIPCHK(c, hipMemcpyAsync(a->d_cost, st_cost, n * sizeof(double), hipMemcpyDeviceToDevice, sm));
-    if (a->d_exit) HIPCHK(c, hipMemcpyAsync(a->d_exit, st_exit, n * sizeof(int64_t), hipMemcpyDeviceToDevice, sm));
-    return C3SC_OK;
+    return closed_loop_results(c, a, a->d_exit, stream);
 }
 
 int c3sc_hip_simulate_host(c3sc_hip_ctx *c, const c3sc_hip_sim_args *h)
@@ -1389,15 +1451,13 @@ int c3sc_hip_simulate_host(c3sc_hip_ctx *c, const c3sc_hip_sim_args *h)
     if (!c) return C3SC_ERR_ARG;
     if (!h) return fail(c, C3SC_ERR_ARG, "simulate_host: null argument struct");
     if (h->n == 0) return c3sc_hip_simulate(c, h, nullptr);
-    if (!h->d_x0) return fail(c, C3SC_ERR_ARG, "simulate_host: null x0");
-    if (h->n > SIM_MAX_TRAJ || h->nsteps > ((size_t)1 << 30)) return fail(c, C3SC_ERR_ARG, "simulate_host: sizes too large");
-    if (h->save_every == 0 && (h->d_traj || h->d_u)) return fail(c, C3SC_ERR_ARG, "simulate: d_traj / d_u need save_every > 0");
-    if (c->d == 0) return fail(c, C3SC_ERR_ARG, "simulate_host: set_grid first");
-    const size_t n = h->n, d = (size_t)c->d, du = (size_t)(h->box ? c->box_du : c->du), D = sizeof(double);
-    const size_t se = h->save_every, nrow = se ? h->nsteps / se + 1 : 0, nurow = se ? (h->nsteps + se - 1) / se : 0;
+    HostShape sh;
+    const int rc = closed_loop_host_shape(c, "simulate", h, h->nsteps, sh);
+    if (rc != C3SC_OK) return rc;
+    const size_t n = sh.n, d = sh.d, D = sizeof(double);
     return stage_host(c, STAGE_PER_CALL, "simulate_host",
                       {{h->d_x0, n * d * D, SEG_IN}, {h->d_noise, h->d_noise ? n * h->nsteps * d * D : 0, SEG_IN},
-                       {h->d_traj, h->d_traj ? n * nrow * d * D : 0, SEG_OUT}, {h->d_u, h->d_u ? n * nurow * du * D : 0, SEG_OUT},
+                       {h->d_traj, h->d_traj ? n * sh.nrow * d * D : 0, SEG_OUT}, {h->d_u, h->d_u ? n * sh.nurow * sh.du * D : 0, SEG_OUT},
                        {h->d_cost, n * D, SEG_OUT}, {h->d_exit, n * sizeof(int64_t), SEG_OUT}, {h->d_vend, n * D, SEG_OUT},
                        {h->d_xfinal, n * d * D, SEG_OUT}},
                       [&](const DevPtr *b) {
@@ -1431,19 +1491,12 @@ static bool ode_box_ok(const double *b, int d)
 
 int c3sc_hip_integrate(c3sc_hip_ctx *c, const c3sc_hip_ode_args *a, void *stream)
 {
-    if (!c) return C3SC_ERR_ARG;
-    if (!a) return fail(c, C3SC_ERR_ARG, "integrate: null argument struct");
-    if (c->model == C3SC_MODEL_TABLE) return fail(c, C3SC_ERR_UNSUPPORTED, "integrate: the TABLE model has no device dynamics");
-    if (!c->have_mca || c->model == 0) return fail(c, C3SC_ERR_ARG, "integrate: mca and model must be set");
-    if (a->box ? c->box_du == 0 : c->ncand == 0)
-        return fail(c, C3SC_ERR_ARG, a->box ? "integrate: set_control_box first" : "integrate: set_controls first");
-    if (a->box && model_ncf(c->model) != 0 && c->model != C3SC_MODEL_COTHRUST6D)
-        return fail(c, C3SC_ERR_UNSUPPORTED, "integrate: this model needs transcendental functions of the control in a box");
-    if (a->box && c->game_gsz > 0) return fail(c, C3SC_ERR_UNSUPPORTED, "integrate: games have no control-box form");
-    if (check_game_model(c, "integrate: game mode needs a model compiled with game kernels") != C3SC_OK) return C3SC_ERR_UNSUPPORTED;
+    const char *who = "integrate";
+    int rc = closed_loop_setup(c, who, a);
+    if (rc != C3SC_OK) return rc;
     if (c->hz_dt > 0.0) return fail(c, C3SC_ERR_UNSUPPORTED, "integrate: deterministic closed loops are not offered in horizon mode");
     KArgs A;
-    int rc = fill_args(c, 0, 0, A, false);
+    rc = fill_args(c, 0, 0, A, false);
     if (rc != C3SC_OK) return rc;
     rc = check_bounds_set(c, "integrate: every dimension needs a boundary type");
     if (rc != C3SC_OK) return rc;
@@ -1456,10 +1509,9 @@ int c3sc_hip_integrate(c3sc_hip_ctx *c, const c3sc_hip_ode_args *a, void *stream
     const int nstage = a->method == C3SC_ODE_RK4 ? 4 : 1;
     if (a->nout > (size_t)1 << 30) return fail(c, C3SC_ERR_ARG, "integrate: nout too large");
     if ((size_t)nsub * a->nout * nstage > ODE_MAX_EVALS) return fail(c, C3SC_ERR_ARG, "integrate: more than 2^40 controller evaluations per trajectory");
-    if (a->n > SIM_MAX_TRAJ) return fail(c, C3SC_ERR_ARG, "integrate: more than 2^31 trajectories in one call (split the batch)");
-    if (a->save_every == 0 && (a->d_traj || a->d_u)) return fail(c, C3SC_ERR_ARG, "integrate: d_traj / d_u need save_every > 0");
-    if (a->save_every > a->nout && a->save_every > 1 && (a->d_traj || a->d_u))
-        return fail(c, C3SC_ERR_ARG, "integrate: save_every larger than nout");
+    rc = closed_loop_sizes(c, who, a, a->nout, "integrate: more than 2^31 trajectories in one call (split the batch)",
+                           "integrate: save_every larger than nout");
+    if (rc != C3SC_OK) return rc;
     if (a->evals_per_launch < 0) return fail(c, C3SC_ERR_ARG, "integrate: evals_per_launch < 0");
     if (!ode_box_ok(a->goal, c->d) || !ode_box_ok(a->keep, c->d))
         return fail(c, C3SC_ERR_ARG, "integrate: a stop box has lo > hi (or a NaN)");
@@ -1469,21 +1521,9 @@ int c3sc_hip_integrate(c3sc_hip_ctx *c, const c3sc_hip_ode_args *a, void *stream
     if (!a->d_x0) return fail(c, C3SC_ERR_ARG, "integrate: null d_x0");
     const int d = c->d;
     const size_t n = a->n;
-    const size_t bytes = n * (size_t)(d + 3) * sizeof(double); // x | cost | stop_step | stop_reason
-    if (bytes > c->sim_state_bytes) {
-        if (c->sim_state) HIPCHK(c, hipFree(c->sim_state));
-        c->sim_state = nullptr;
-        c->sim_state_bytes = 0;
-        HIPCHK(c, hipMalloc(&c->sim_state, bytes));
-        c->sim_state_bytes = bytes;
-    }
-    double *st_x = (double *)c->sim_state, *st_cost = st_x + n * d;
-    long long *st_stop = (long long *)(st_cost + n);
-    int32_t *st_why = (int32_t *)(st_stop + n);
-    A.cmode = a->box ? 1 : 0;
-    A.ugrid = c->box_grid;
-    A.upolish = c->box_polish;
-    for (int i = 0; i < c->box_du; i++) { A.ulb[i] = c->box_lb[i]; A.uub[i] = c->box_ub[i]; }
+    rc = closed_loop_state(c, n * (size_t)(d + 3) * sizeof(double)); // x | cost | stop_step | stop_reason
+    if (rc != C3SC_OK) return rc;
+    closed_loop_box(c, a->box, A);
     OdeK S;
     std::memset(&S, 0, sizeof(S));
     S.n = (long)n;
@@ -1504,34 +1544,27 @@ int c3sc_hip_integrate(c3sc_hip_ctx *c, const c3sc_hip_ode_args *a, void *stream
         S.keep_hi[m] = a->keep ? a->keep[d + m] : INFINITY;
     }
     S.x0 = a->d_x0;
-    S.x = st_x;
-    S.cost = st_cost;
-    S.stop_step = st_stop;
-    S.stop_reason = st_why;
+    S.x = (double *)c->sim_state;
+    S.cost = S.x + n * d;
+    S.stop_step = (long long *)(S.cost + n);
+    S.stop_reason = (int32_t *)(S.stop_step + n);
     S.traj = a->d_traj;
     S.u = a->d_u;
     S.vend = a->d_vend;
     const long long ktot = nsub * (long long)a->nout;
     const long long chunk = std::max<long long>(1, (a->evals_per_launch > 0 ? a->evals_per_launch : 256) / nstage);
-    c->last_kernel = e->name;
-    c->status_cache_valid = false;
     long long k0 = 0;
     do { // at least one launch: nout = 0 still tests x_0 and evaluates V_end
         S.k0 = k0;
         S.k1 = std::min(k0 + chunk, ktot);
         LaunchIO io{c->arena, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream, &S};
-        g_launches++;
-        const hipError_t he = launch_entry(*e, A, io);
-        if (he == hipErrorNotSupported) return fail(c, C3SC_ERR_UNSUPPORTED, "integrate: this integrate kernel has no box minimiser");
-        HIPCHK(c, he);
+        rc = launch_one(c, e, A, io, "integrate: this integrate kernel has no box minimiser");
+        if (rc != C3SC_OK) return rc;
         k0 = S.k1;
     } while (k0 < ktot);
-    hipStream_t sm = (hipStream_t)stream;
-    if (a->d_xfinal) HIPCHK(c, hipMemcpyAsync(a->d_xfinal, st_x, n * d * sizeof(double), hipMemcpyDeviceToDevice, sm));
-    if (a->d_cost) HIPCHK(c, hipMemcpyAsync(a->d_cost, st_cost, n * sizeof(double), hipMemcpyDeviceToDevice, sm));
-    if (a->d_stop_step) HIPCHK(c, hipMemcpyAsync(a->d_stop_step, st_stop, n * sizeof(int64_t), hipMemcpyDeviceToDevice, sm));
-    if (a->d_stop_reason) HIPCHK(c, hipMemcpyAsync(a->d_stop_reason, st_why, n * sizeof(int32_t), hipMemcpyDeviceToDevice, sm));
-    return C3SC_OK;
+    rc = closed_loop_results(c, a, a->d_stop_step, stream);
+    if (rc != C3SC_OK) return rc;
+    return copy_back(c, a->d_stop_reason, S.stop_reason, n * sizeof(int32_t), stream);
 }
 
 int c3sc_hip_integrate_host(c3sc_hip_ctx *c, const c3sc_hip_ode_args *h)
@@ -1539,15 +1572,13 @@ int c3sc_hip_integrate_host(c3sc_hip_ctx *c, const c3sc_hip_ode_args *h)
     if (!c) return C3SC_ERR_ARG;
     if (!h) return fail(c, C3SC_ERR_ARG, "integrate_host: null argument struct");
     if (h->n == 0) return c3sc_hip_integrate(c, h, nullptr);
-    if (!h->d_x0) return fail(c, C3SC_ERR_ARG, "integrate_host: null x0");
-    if (h->n > SIM_MAX_TRAJ || h->nout > ((size_t)1 << 30)) return fail(c, C3SC_ERR_ARG, "integrate_host: sizes too large");
-    if (h->save_every == 0 && (h->d_traj || h->d_u)) return fail(c, C3SC_ERR_ARG, "integrate: d_traj / d_u need save_every > 0");
-    if (c->d == 0) return fail(c, C3SC_ERR_ARG, "integrate_host: set_grid first");
-    const size_t n = h->n, d = (size_t)c->d, du = (size_t)(h->box ? c->box_du : c->du), D = sizeof(double);
-    const size_t se = h->save_every, nrow = se ? h->nout / se + 1 : 0, nurow = se ? (h->nout + se - 1) / se : 0;
+    HostShape sh;
+    const int rc = closed_loop_host_shape(c, "integrate", h, h->nout, sh);
+    if (rc != C3SC_OK) return rc;
+    const size_t n = sh.n, d = sh.d, D = sizeof(double);
     return stage_host(c, STAGE_PER_CALL, "integrate_host",
-                      {{h->d_x0, n * d * D, SEG_IN}, {h->d_traj, h->d_traj ? n * nrow * d * D : 0, SEG_OUT},
-                       {h->d_u, h->d_u ? n * nurow * du * D : 0, SEG_OUT}, {h->d_cost, n * D, SEG_OUT},
+                      {{h->d_x0, n * d * D, SEG_IN}, {h->d_traj, h->d_traj ? n * sh.nrow * d * D : 0, SEG_OUT},
+                       {h->d_u, h->d_u ? n * sh.nurow * sh.du * D : 0, SEG_OUT}, {h->d_cost, n * D, SEG_OUT},
                        {h->d_stop_step, n * sizeof(int64_t), SEG_OUT}, {h->d_stop_reason, n * sizeof(int32_t), SEG_OUT},
                        {h->d_vend, n * D, SEG_OUT}, {h->d_xfinal, n * d * D, SEG_OUT}},
                       [&](const DevPtr *b) {

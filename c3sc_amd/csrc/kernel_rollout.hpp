@@ -11,6 +11,10 @@
 // lanes repeat the last trajectory and store the same bits to the same addresses); the device libm (cos / sin / tan of the
 // models' tables at an off-grid state) and the box minimiser do branch per lane.  That is harmless because nothing here is
 // lane-distributed: the candidate table lives in LDS (CandLds, wave-uniform addresses), not in VGPR lanes read by v_readlane.
+// The candidate-table fill, the wrap of the final state and the launcher are shared with the deterministic integrator,
+// k_rollout_ode (kernel_rollout_ode.hpp).  The controller block is not: k_rollout keeps it in its step loop and k_rollout_ode has
+// ode_policy, the same statements as a function.  Calling that function from k_rollout changes the register allocation of the
+// instantiations that spill (car7d at ranks 16 and 20, cothrust6d at 20).
 // tests/test_rollout_isa.py checks the ISA (global loads only; no scratch at the benchmark's ranks).
 #pragma once
 #ifndef __HIPCC_RTC__
@@ -245,13 +249,12 @@ __global__ void __launch_bounds__(256) k_stencil_points(const KArgs A, const Sim
     if (S.absorbed) S.absorbed[i] = ab;
 }
 
-// BOX: the instantiation also serves the control-box minimiser (A.cmode == 1, a wave-uniform switch)
-template <int MID, class Model, int RP, bool BOX>
-__global__ void __launch_bounds__(256) k_rollout(const KArgs A, const SimK S, const double *__restrict__ ro)
+// ---- the blocks k_rollout and k_rollout_ode (kernel_rollout_ode.hpp) share
+
+// the candidate table of the list minimiser in dynamic LDS (the box minimiser, A.cmode == 1, reads none)
+template <class Model>
+__device__ inline void rollout_cands(const KArgs &A, const double *__restrict__ ro, double *smem, CandLds<Model> &cr)
 {
-    constexpr int D = Model::D, DU = Model::DU, NT = Model::NTAB > 0 ? Model::NTAB : 1, NCFa = Model::NCF > 0 ? Model::NCF : 1;
-    extern __shared__ double smem[];
-    CandLds<Model> cr;
     cr.tb = smem;
     if (A.cmode == 0) {
         for (int c0 = 0; c0 < A.ncand; c0 += 64) { // every wave writes the same rows
@@ -261,6 +264,27 @@ __global__ void __launch_bounds__(256) k_rollout(const KArgs A, const SimK S, co
         }
         __syncthreads();
     }
+}
+
+// the state the value function is read at for V_end: x, wrapped into the periodic dimensions when the call asks for it
+template <int D>
+__device__ inline void rollout_input(const KArgs &A, const double *__restrict__ ro, int wrap, const double (&x)[D], double (&xin)[D])
+{
+    if (wrap) wrap_periodic<D>(A, ro, x, xin);
+    else
+#pragma unroll
+        for (int m = 0; m < D; m++) xin[m] = x[m];
+}
+
+// state in, controller, Euler-Maruyama step, exit test, state out
+// BOX: the instantiation also serves the control-box minimiser (A.cmode == 1, a wave-uniform switch)
+template <int MID, class Model, int RP, bool BOX>
+__global__ void __launch_bounds__(256) k_rollout(const KArgs A, const SimK S, const double *__restrict__ ro)
+{
+    constexpr int D = Model::D, DU = Model::DU, NT = Model::NTAB > 0 ? Model::NTAB : 1, NCFa = Model::NCF > 0 ? Model::NCF : 1;
+    extern __shared__ double smem[];
+    CandLds<Model> cr;
+    rollout_cands<Model>(A, ro, smem, cr);
     const long i = min((long)blockIdx.x * blockDim.x + threadIdx.x, S.n - 1); // tail lanes repeat the last trajectory
     const int se = S.save_every;
     const long nrow = se > 0 ? S.nsteps / se + 1 : 0, nurow = se > 0 ? (S.nsteps + se - 1) / se : 0;
@@ -376,10 +400,7 @@ __global__ void __launch_bounds__(256) k_rollout(const KArgs A, const SimK S, co
         if (S.vend || model_horizon<Model>()) {
             double xin[D], V[2 * D + 1];
             int ab;
-            if (S.wrap) wrap_periodic<D>(A, ro, x, xin);
-            else
-#pragma unroll
-                for (int m = 0; m < D; m++) xin[m] = x[m];
+            rollout_input<D>(A, ro, S.wrap, x, xin);
             offgrid_stencil<D, RP>(A, ro, xin, S.constelm, V, ab);
             if (S.vend) S.vend[i] = V[2 * D];
             if constexpr (model_horizon<Model>()) J = (ex < 0) ? J + dend * V[2 * D] : J;
@@ -399,18 +420,18 @@ __global__ void __launch_bounds__(256) k_rollout(const KArgs A, const SimK S, co
 inline size_t rollout_shmem(int cmode, size_t cand_doubles) { return (cmode == 0 ? cand_doubles : 1) * sizeof(double); }
 inline unsigned rollout_grid(long n) { return (unsigned)((n + 255) / 256); }
 
-template <int MID, class Model, int RP, bool BOX>
-hipError_t launch_rollout(const KArgs &A, const LaunchIO &io)
+// the launcher of k_rollout (K = SimK) and k_rollout_ode (K = OdeK): KERN is the kernel, so each has its own LaunchCache
+template <class Model, bool BOX, class K, auto KERN>
+hipError_t launch_closed_loop(const KArgs &A, const LaunchIO &io)
 {
     if (A.cmode == 1 && !BOX) return hipErrorNotSupported;
-    const SimK &S = *(const SimK *)io.sim;
+    const K &S = *(const K *)io.sim;
     const size_t shmem = rollout_shmem(A.cmode, (size_t)CandLds<Model>::doubles(A.ncand));
-    auto kern = k_rollout<MID, Model, RP, BOX>;
     static LaunchCache cache;
     int blocks_per_cu = 1, num_cu = 256;
-    hipError_t e = cache.prepare((const void *)kern, 256, shmem, blocks_per_cu, num_cu);
+    hipError_t e = cache.prepare((const void *)KERN, 256, shmem, blocks_per_cu, num_cu);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(rollout_grid(S.n)), dim3(256), shmem, io.stream, A, S, io.ro);
+    hipLaunchKernelGGL(KERN, dim3(rollout_grid(S.n)), dim3(256), shmem, io.stream, A, S, io.ro);
     return hipGetLastError();
 }
 
@@ -430,7 +451,8 @@ hipError_t launch_stencil_points(const KArgs &A, const LaunchIO &io)
 // one rollout kernel per (model, padded rank); BOX = 1 where the model's Bellman kernels serve the control box too
 #define C3SC_REG_ROLLOUT(MODEL_ID, RP, BOX, ...)                                                               \
     static Registrar C3SC_CAT(reg_roll_, __COUNTER__)(KernelEntry{                                            \
-        MODEL_ID, __VA_ARGS__::D, RP, 0, VARIANT_ROLLOUT, 0, -1, &launch_rollout<MODEL_ID, __VA_ARGS__, RP, BOX>, \
+        MODEL_ID, __VA_ARGS__::D, RP, 0, VARIANT_ROLLOUT, 0, -1,                                               \
+        &launch_closed_loop<__VA_ARGS__, BOX, SimK, k_rollout<MODEL_ID, __VA_ARGS__, RP, BOX>>,                   \
         "k_rollout<" #__VA_ARGS__ "," #RP ">"});
 #define C3SC_REG_STENCIL_POINTS(DIM, RP)                                                                       \
     static Registrar C3SC_CAT(reg_stp_, __COUNTER__)(KernelEntry{                                             \

@@ -7,9 +7,12 @@
 // tested at every outer step.  A launch covers a range of substeps; state, cost and stop fields go to device memory between
 // launches, and every lane follows the same substep schedule, so the results do not depend on how a call is cut.
 //
-// The controller block is k_rollout's (off-grid stencil at the possibly wrapped state, node_backup over the candidates in LDS
-// or node_backup_box, u = 0 inside an obstacle), and the lane-uniformity rules are the same: frozen lanes and
-// workgroup tail lanes are selects, nothing is lane-distributed.  The stage loop is rolled, so the controller is emitted once.
+// The controller block is k_rollout's, restated here as the function ode_policy (off-grid stencil at the possibly wrapped state,
+// node_backup over the candidates in LDS or node_backup_box, u = 0 inside an obstacle); k_rollout keeps its own copy inline,
+// because calling ode_policy from it changes the register allocation of its spilling instantiations.  The candidate-table fill,
+// the wrap of the final state and the launcher are kernel_rollout.hpp's.  The lane-uniformity rules are the same:
+// frozen lanes and workgroup tail lanes are selects, nothing is lane-distributed.  The stage loop is rolled, so the controller is
+// emitted once.
 #pragma once
 #include "kernel_rollout.hpp"
 
@@ -86,21 +89,14 @@ __device__ inline void ode_policy(const KArgs &A, const double *__restrict__ ro,
         for (int t = 0; t < NT; t++) tvy[t] = tv[t];
 }
 
+// state in, controller at every stage state, RK4 / forward-Euler substep, stops, state out
 template <int MID, class Model, int RP, bool BOX>
 __global__ void __launch_bounds__(256) k_rollout_ode(const KArgs A, const OdeK S, const double *__restrict__ ro)
 {
     constexpr int D = Model::D, DU = Model::DU, NT = Model::NTAB > 0 ? Model::NTAB : 1, NCFa = Model::NCF > 0 ? Model::NCF : 1;
     extern __shared__ double smem[];
     CandLds<Model> cr;
-    cr.tb = smem;
-    if (A.cmode == 0) {
-        for (int c0 = 0; c0 < A.ncand; c0 += 64) { // every wave writes the same rows
-            CandRegs<Model> cr0;
-            cr0.load(A, ro, c0);
-            cr.fill(smem, cr0, A.ncand, c0);
-        }
-        __syncthreads();
-    }
+    rollout_cands<Model>(A, ro, smem, cr);
     const long i = min((long)blockIdx.x * blockDim.x + threadIdx.x, S.n - 1); // tail lanes repeat the last trajectory
     const int se = S.save_every, nsub = S.nsub;
     const long nrow = se > 0 ? S.nout / se + 1 : 0, nurow = se > 0 ? (S.nout + se - 1) / se : 0;
@@ -200,10 +196,7 @@ __global__ void __launch_bounds__(256) k_rollout_ode(const KArgs A, const OdeK S
         if (S.vend) {
             double xin[D], V[2 * D + 1];
             int ab;
-            if (S.wrap) wrap_periodic<D>(A, ro, x, xin);
-            else
-#pragma unroll
-                for (int m = 0; m < D; m++) xin[m] = x[m];
+            rollout_input<D>(A, ro, S.wrap, x, xin);
             offgrid_stencil<D, RP>(A, ro, xin, S.constelm, V, ab);
             S.vend[i] = V[2 * D];
         }
@@ -217,25 +210,11 @@ __global__ void __launch_bounds__(256) k_rollout_ode(const KArgs A, const OdeK S
 }
 
 #ifndef __HIPCC_RTC__
-template <int MID, class Model, int RP, bool BOX>
-hipError_t launch_rollout_ode(const KArgs &A, const LaunchIO &io)
-{
-    if (A.cmode == 1 && !BOX) return hipErrorNotSupported;
-    const OdeK &S = *(const OdeK *)io.sim;
-    const size_t shmem = rollout_shmem(A.cmode, (size_t)CandLds<Model>::doubles(A.ncand));
-    auto kern = k_rollout_ode<MID, Model, RP, BOX>;
-    static LaunchCache cache;
-    int blocks_per_cu = 1, num_cu = 256;
-    hipError_t e = cache.prepare((const void *)kern, 256, shmem, blocks_per_cu, num_cu);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(rollout_grid(S.n)), dim3(256), shmem, io.stream, A, S, io.ro);
-    return hipGetLastError();
-}
-
 // one integrate kernel per (model, padded rank); BOX = 1 where the model's Bellman kernels serve the control box too
 #define C3SC_REG_ROLLOUT_ODE(MODEL_ID, RP, BOX, ...)                                                                   \
     static Registrar C3SC_CAT(reg_rode_, __COUNTER__)(KernelEntry{                                                    \
-        MODEL_ID, __VA_ARGS__::D, RP, 0, VARIANT_ROLLOUT_ODE, 0, -1, &launch_rollout_ode<MODEL_ID, __VA_ARGS__, RP, BOX>, \
+        MODEL_ID, __VA_ARGS__::D, RP, 0, VARIANT_ROLLOUT_ODE, 0, -1,                                                   \
+        &launch_closed_loop<__VA_ARGS__, BOX, OdeK, k_rollout_ode<MODEL_ID, __VA_ARGS__, RP, BOX>>,                       \
         "k_rollout_ode<" #__VA_ARGS__ "," #RP ">"});
 #endif
 

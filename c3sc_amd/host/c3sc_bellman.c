@@ -1657,10 +1657,34 @@ int c3control_controller(double t, const double *x, double *u, void *args)
     return out;
 }
 
-static int sim_batch_reject(const char *msg)
+static int reject(const char *who, const char *msg)
 {
-    fprintf(stderr, "c3control_simulate_batch: %s\n", msg);
+    fprintf(stderr, "%s: %s\n", who, msg);
     return C3SC_ERR_ARG;
+}
+
+/* What c3control_simulate_batch and c3control_integrate_batch share, in two steps because the callers' own checks run between
+   them and nothing may touch the device before the last rejection.  First: the control can run closed loops on the device. */
+static int batch_policy_check(const char *who, const struct C3Control *c, int wrap_periodic)
+{
+    if (c == NULL) return reject(who, "null control");
+    if (c->dp->model == 0) return reject(who, "no device model (c3control_set_device_model): host callbacks cannot run on the device");
+    if (c->policy_sim == NULL || c->opt_sim == NULL) return reject(who, "no implicit policy (c3control_add_policy_sim)");
+    if (c->transform_sim != NULL && !wrap_periodic)
+        return reject(who, "a state transform is a host callback the device cannot call; pass wrap_periodic = 1 if it only wraps periodic angles");
+    return 0;
+}
+
+/* Then: the minimiser's dimensions, and the device context synced to policy_sim and opt_sim.  *box: opt_sim is a control box. */
+static int batch_device_ctx(const char *who, struct C3Control *c, struct c3sc_hip_ctx **ctx, int *box)
+{
+    *box = !c3opt_is_bruteforce(c->opt_sim);
+    if (*box && c3opt_get_d(c->opt_sim) > C3SC_MAX_DU) return reject(who, "the box minimiser handles up to C3SC_MAX_DU controls");
+    if (c3opt_get_d(c->opt_sim) != c->du) return reject(who, "opt_sim's dimension differs from the control dimension");
+    struct ControlParams *cp = control_params_create(c->dx, c->dw, c->dp, c->mca, c->work, c->opt_sim);
+    *ctx = sync_device_ctx(cp, workspace_get_hip_ctx(c->work), c->policy_sim);
+    control_params_destroy(cp);
+    return 0;
 }
 
 int c3control_simulate_batch(struct C3Control *c, size_t ntraj, const double *x0, double dt, size_t nsteps, uint64_t seed,
@@ -1669,23 +1693,19 @@ int c3control_simulate_batch(struct C3Control *c, size_t ntraj, const double *x0
 { /* new: ntraj closed loops of the implicit policy on the device (c3sc_hip_simulate_host): the policy_sim value function, the
      opt_sim minimiser (candidate list or control box) and the device model; prevpol is neither read nor written (both
      minimisers ignore the starting point) */
-    if (c == NULL) return sim_batch_reject("null control");
-    if (c->dp->model == 0) return sim_batch_reject("no device model (c3control_set_device_model): host callbacks cannot run on the device");
-    if (c->policy_sim == NULL || c->opt_sim == NULL) return sim_batch_reject("no implicit policy (c3control_add_policy_sim)");
-    if (c->transform_sim != NULL && !wrap_periodic)
-        return sim_batch_reject("a state transform is a host callback the device cannot call; pass wrap_periodic = 1 if it only wraps periodic angles");
-    if (c->dw != c->dx) return sim_batch_reject("the device models have dw = dx (diagonal diffusion)");
+    const char *who = "c3control_simulate_batch";
+    int rc = batch_policy_check(who, c, wrap_periodic);
+    if (rc != 0) return rc;
+    if (c->dw != c->dx) return reject(who, "the device models have dw = dx (diagonal diffusion)");
     if (ntraj == 0) return 0;
-    if (x0 == NULL) return sim_batch_reject("null x0");
-    if (!(dt > 0.0) || !isfinite(dt)) return sim_batch_reject("dt must be positive and finite");
-    if ((traj != NULL || utraj != NULL) && save_every == 0) return sim_batch_reject("traj / utraj need save_every > 0");
-    if (ntraj > ((size_t)1 << 31) || nsteps > ((size_t)1 << 30)) return sim_batch_reject("more than 2^31 trajectories or 2^30 steps");
-    const int brute = c3opt_is_bruteforce(c->opt_sim);
-    if (!brute && c3opt_get_d(c->opt_sim) > C3SC_MAX_DU) return sim_batch_reject("the box minimiser handles up to C3SC_MAX_DU controls");
-    if (c3opt_get_d(c->opt_sim) != c->du) return sim_batch_reject("opt_sim's dimension differs from the control dimension");
-    struct ControlParams *cp = control_params_create(c->dx, c->dw, c->dp, c->mca, c->work, c->opt_sim);
-    struct c3sc_hip_ctx *ctx = sync_device_ctx(cp, workspace_get_hip_ctx(c->work), c->policy_sim);
-    control_params_destroy(cp);
+    if (x0 == NULL) return reject(who, "null x0");
+    if (!(dt > 0.0) || !isfinite(dt)) return reject(who, "dt must be positive and finite");
+    if ((traj != NULL || utraj != NULL) && save_every == 0) return reject(who, "traj / utraj need save_every > 0");
+    if (ntraj > ((size_t)1 << 31) || nsteps > ((size_t)1 << 30)) return reject(who, "more than 2^31 trajectories or 2^30 steps");
+    struct c3sc_hip_ctx *ctx;
+    int box;
+    rc = batch_device_ctx(who, c, &ctx, &box);
+    if (rc != 0) return rc;
     c3sc_hip_sim_args a;
     memset(&a, 0, sizeof(a));
     a.n = ntraj;
@@ -1695,15 +1715,15 @@ int c3control_simulate_batch(struct C3Control *c, size_t ntraj, const double *x0
     a.seed = seed;
     a.d_noise = noise;
     a.wrap_periodic = wrap_periodic;
-    a.box = !brute;
+    a.box = box;
     a.save_every = save_every;
     a.d_traj = traj;
     a.d_u = utraj;
     a.d_cost = cost;
     a.d_exit = (int64_t *)exit_step;
     a.d_vend = vend;
-    const int rc = c3sc_hip_simulate_host(ctx, &a);
-    if (rc != C3SC_OK) fprintf(stderr, "c3control_simulate_batch: %s (code %d)\n", c3sc_hip_last_error(ctx), rc);
+    rc = c3sc_hip_simulate_host(ctx, &a);
+    if (rc != C3SC_OK) fprintf(stderr, "%s: %s (code %d)\n", who, c3sc_hip_last_error(ctx), rc);
     return rc;
 }
 
@@ -1716,30 +1736,24 @@ static int ode_method(const char *name)
     return -1;
 }
 
-static int integrate_reject(const char *who, const char *msg)
-{
-    fprintf(stderr, "%s: %s\n", who, msg);
-    return C3SC_ERR_ARG;
-}
-
 /* the checks c3control_integrate and c3control_integrate_batch share; *nsub out */
 static int integrate_check(const char *who, size_t dx, const char *method, double dt_int, double dt_out, size_t nout,
                            const double *goal, const double *keep, size_t *nsub)
 {
-    if (ode_method(method) < 0) return integrate_reject(who, "method must be \"forward-euler\" or \"rk4\"");
-    if (!(dt_out > 0.0) || !isfinite(dt_out)) return integrate_reject(who, "dt_out must be positive and finite");
-    if (!(dt_int >= 0.0) || !isfinite(dt_int)) return integrate_reject(who, "dt_int must be >= 0 and finite");
+    if (ode_method(method) < 0) return reject(who, "method must be \"forward-euler\" or \"rk4\"");
+    if (!(dt_out > 0.0) || !isfinite(dt_out)) return reject(who, "dt_out must be positive and finite");
+    if (!(dt_int >= 0.0) || !isfinite(dt_int)) return reject(who, "dt_int must be >= 0 and finite");
     *nsub = 1;
     if (dt_int > 0.0) {
         const double r = dt_out / dt_int, q = nearbyint(r);
         if (!(q >= 1.0) || !(fabs(r - q) <= 1e-9 * q) || q > (double)(1 << 30))
-            return integrate_reject(who, "dt_out / dt_int is not an integer (to 1e-9 relative)");
+            return reject(who, "dt_out / dt_int is not an integer (to 1e-9 relative)");
         *nsub = (size_t)q;
     }
-    if (nout > ((size_t)1 << 30)) return integrate_reject(who, "nout too large");
+    if (nout > ((size_t)1 << 30)) return reject(who, "nout too large");
     for (size_t m = 0; m < dx; m++) {
-        if (goal != NULL && !(goal[m] <= goal[dx + m])) return integrate_reject(who, "the goal box has lo > hi");
-        if (keep != NULL && !(keep[m] <= keep[dx + m])) return integrate_reject(who, "the keep-in box has lo > hi");
+        if (goal != NULL && !(goal[m] <= goal[dx + m])) return reject(who, "the goal box has lo > hi");
+        if (keep != NULL && !(keep[m] <= keep[dx + m])) return reject(who, "the keep-in box has lo > hi");
     }
     return 0;
 }
@@ -1750,10 +1764,10 @@ int c3control_integrate(struct C3Control *c, const char *method, double dt_int, 
 { /* new: the examples' cdyn tail (integrator_create_controlled + trajectory_step + the goal test, e.g. dubinscar.c:379-412)
      for one trajectory, over the user's callbacks and c3control_controller; the host twin of c3sc_hip_integrate */
     const char *who = "c3control_integrate";
-    if (c == NULL || x0 == NULL) return integrate_reject(who, "null control or x0");
-    if (c->policy_sim == NULL || c->opt_sim == NULL) return integrate_reject(who, "no implicit policy (c3control_add_policy_sim)");
+    if (c == NULL || x0 == NULL) return reject(who, "null control or x0");
+    if (c->policy_sim == NULL || c->opt_sim == NULL) return reject(who, "no implicit policy (c3control_add_policy_sim)");
     if (c->dp->drift == NULL || c->dp->stagecost == NULL || c->dp->boundcost == NULL || c->dp->obscost == NULL)
-        return integrate_reject(who, "the host callbacks (drift, stagecost, boundcost, obscost) are needed");
+        return reject(who, "the host callbacks (drift, stagecost, boundcost, obscost) are needed");
     size_t nsub;
     int rc = integrate_check(who, c->dx, method, dt_int, dt_out, nout, goal, keep, &nsub);
     if (rc != 0) return rc;
@@ -1830,24 +1844,19 @@ int c3control_integrate_batch(struct C3Control *c, size_t ntraj, const double *x
 { /* new: ntraj closed loops of c3control_integrate on the device (c3sc_hip_integrate_host): the policy_sim value function, the
      opt_sim minimiser and the device model, as c3control_simulate_batch */
     const char *who = "c3control_integrate_batch";
-    if (c == NULL) return integrate_reject(who, "null control");
-    if (c->dp->model == 0) return integrate_reject(who, "no device model (c3control_set_device_model): host callbacks cannot run on the device");
-    if (c->policy_sim == NULL || c->opt_sim == NULL) return integrate_reject(who, "no implicit policy (c3control_add_policy_sim)");
-    if (c->transform_sim != NULL && !wrap_periodic)
-        return integrate_reject(who, "a state transform is a host callback the device cannot call; pass wrap_periodic = 1 if it only wraps periodic angles");
+    int rc = batch_policy_check(who, c, wrap_periodic);
+    if (rc != 0) return rc;
     size_t nsub;
-    int rc = integrate_check(who, c->dx, method, dt_int, dt_out, nout, goal, keep, &nsub);
+    rc = integrate_check(who, c->dx, method, dt_int, dt_out, nout, goal, keep, &nsub);
     if (rc != 0) return rc;
     if (ntraj == 0) return 0;
-    if (x0 == NULL) return integrate_reject(who, "null x0");
-    if ((traj != NULL || utraj != NULL) && save_every == 0) return integrate_reject(who, "traj / utraj need save_every > 0");
-    if (ntraj > ((size_t)1 << 31)) return integrate_reject(who, "more than 2^31 trajectories");
-    const int brute = c3opt_is_bruteforce(c->opt_sim);
-    if (!brute && c3opt_get_d(c->opt_sim) > C3SC_MAX_DU) return integrate_reject(who, "the box minimiser handles up to C3SC_MAX_DU controls");
-    if (c3opt_get_d(c->opt_sim) != c->du) return integrate_reject(who, "opt_sim's dimension differs from the control dimension");
-    struct ControlParams *cp = control_params_create(c->dx, c->dw, c->dp, c->mca, c->work, c->opt_sim);
-    struct c3sc_hip_ctx *ctx = sync_device_ctx(cp, workspace_get_hip_ctx(c->work), c->policy_sim);
-    control_params_destroy(cp);
+    if (x0 == NULL) return reject(who, "null x0");
+    if ((traj != NULL || utraj != NULL) && save_every == 0) return reject(who, "traj / utraj need save_every > 0");
+    if (ntraj > ((size_t)1 << 31)) return reject(who, "more than 2^31 trajectories");
+    struct c3sc_hip_ctx *ctx;
+    int box;
+    rc = batch_device_ctx(who, c, &ctx, &box);
+    if (rc != 0) return rc;
     int32_t *why = stop_reason ? xcalloc(ntraj, sizeof(int32_t)) : NULL;
     c3sc_hip_ode_args a;
     memset(&a, 0, sizeof(a));
@@ -1858,7 +1867,7 @@ int c3control_integrate_batch(struct C3Control *c, size_t ntraj, const double *x
     a.nout = nout;
     a.method = ode_method(method);
     a.wrap_periodic = wrap_periodic;
-    a.box = !brute;
+    a.box = box;
     a.goal = goal;
     a.keep = keep;
     a.save_every = save_every;
