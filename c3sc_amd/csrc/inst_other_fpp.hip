@@ -7,6 +7,10 @@ namespace c3sc {
     C3SC_REG_FPP1(C3SC_MODEL_DUBINS3D, RP, 0, Dubins3D)  \
     C3SC_REG_FPP1(C3SC_MODEL_DUBINS3D, RP, 1, Dubins3D)  \
     C3SC_REG_FPP1(C3SC_MODEL_DUBINS3D, RP, 2, Dubins3D)
+// K = 0: x and y both drift with theta alone; y is the only other uncontrolled dimension and merges into one vector right of K,
+// theta keeps its pair: 3 vectors.  K = 2: both drifts read the varying dimension, nothing merges: 4.
+static_assert(PairPark<Dubins3D, 0>::merged() == 0x2u && PairMap<Dubins3D, 0>::nv() == 3, "dubins3d: slot map of K = 0");
+static_assert(PairPark<Dubins3D, 2>::merged() == 0x0u && PairMap<Dubins3D, 2>::nv() == 4, "dubins3d: slot map of K = 2");
 REG3P(4)
 REG3P(6)
 REG3P(8)

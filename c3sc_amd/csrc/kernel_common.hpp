@@ -553,14 +553,22 @@ __device__ inline double rcp_newton(double q)
 // (nodeutil.c:267-406) + bellmanrhs (bellman.c:88-112).  V[2m], V[2m+1] = value at the (-,+)
 // neighbour in dim m, V[2D] = value at the node.  The candidate scan keeps the first minimum
 // (strict '<'), as the brute-force c3opt is assumed to.
-// precomputed rates of control-independent dimensions (NoPre: none).  MASK: the dimensions whose (p-, p+) come from pm(m) / pp(m)
-// instead of being formed from the node's drift -- the fiber-pair kernel keeps those that do not depend on the varying
-// dimension per fiber (PairPark)
+// precomputed rates of control-independent dimensions (NoPre: none) -- the fiber-pair kernel keeps those that do not depend on
+// the varying dimension per fiber (PairPark).  MASK: the MERGED dimensions: their terms are skipped one by one and enter as a
+// whole, Q0 += q() (the sum of their rates) and PV0 += pv() (their rate-weighted neighbour values, already summed: the stencil
+// value of such a dimension is used linearly only).  RATES (optional member): the dimensions whose (p-, p+) come from pm(m) /
+// pp(m) instead of being formed from the node's drift; their stencil values are read as usual.
 struct NoPre {
     static constexpr unsigned MASK = 0u;
     __device__ inline double pm(int) const { return 0.0; }
     __device__ inline double pp(int) const { return 0.0; }
 };
+template <class Pre>
+__host__ __device__ constexpr unsigned pre_rates()
+{
+    if constexpr (requires { Pre::RATES; }) return Pre::RATES;
+    else return 0u;
+}
 
 // upwind rates of one dimension (nodeutil.c:289-309): p-+ = t2 sigma^2 / 2 + t max(-+b, 0) with the +-1e-14 dead zone
 __device__ __forceinline__ void upwind_rates(double t, double t2, double b, double sg, double &pm, double &pp)
@@ -640,15 +648,19 @@ __device__ inline double node_backup(const KArgs &A, const double *__restrict__ 
         else if constexpr (stage_usep<Model>()) stage0 = Model::stage_x(A.prm, x); // + the candidate's stage_u below
 #pragma unroll
         for (int m = 0; m < D; m++) {
-            if (!((UM >> m) & 1u)) {
+            if (!((UM >> m) & 1u) && !((Pre::MASK >> m) & 1u)) {
                 double pm, pp;
-                if ((Pre::MASK >> m) & 1u) { pm = pre.pm(m); pp = pre.pp(m); } // a constant of the fiber, formed once with upwind_rates
+                if ((pre_rates<Pre>() >> m) & 1u) { pm = pre.pm(m); pp = pre.pp(m); } // a constant of the fiber, formed once with upwind_rates
                 else upwind_rates(A.t[2 * m], A.t[2 * m + 1], b[m], s[m], pm, pp);
                 Q0 += pm;
                 Q0 += pp;
                 PV0 = fma(pm, V[2 * m], PV0);
                 PV0 = fma(pp, V[2 * m + 1], PV0);
             }
+        }
+        if constexpr (Pre::MASK != 0u) { // the merged dimensions, once: V[2m], V[2m+1] of those are not read
+            Q0 += pre.q();
+            PV0 += pre.pv();
         }
     }
     double best = 0.0;

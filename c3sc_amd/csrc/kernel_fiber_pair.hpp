@@ -11,6 +11,10 @@
 // LDS and take turns running the control minimisation (wave 0: even nodes, wave 1: odd nodes, delayed
 // by one node pair so the dim-k neighbours are known).  One s_barrier pair per two nodes.
 //
+// Merged rates (PairPark::merged, PairMap): a control-independent dimension whose rates are constants of the fiber does not
+// keep its two vectors -- they are summed rate-weighted into one vector per side of K, so car7d carries 5 to 11 vectors per
+// launch instead of 12.
+//
 // Folding (once per 64-fiber tile): each wave folds the neighbour vectors of half of the dims (full
 // length, 6 x r doubles in registers) through the fixed cores staged in LDS -- exactly as the
 // fiber-per-lane kernel does -- and the halves are swapped through LDS afterwards.
@@ -108,36 +112,17 @@ __device__ inline void stage_core_image(double *sK, const double *img, int n_dou
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-// which wave folds the neighbour pair of dim m (m != K): alternate by distance from K so the O(distance)
-// propagation work is balanced
+// which wave folds the neighbour pair of dim m (m != K) where nothing is merged (PairMap::owner): alternate by distance from K
+// so the O(distance) propagation work is balanced
 template <int K>
 __host__ __device__ constexpr int pair_owner(int m) { return m < K ? ((K - 1 - m) & 1) : ((m - K) & 1); }
-
-template <int D, int K, int H>
-__host__ __device__ constexpr int own_left_before(int m)
-{ // number of left dims < m owned by H
-    int c = 0;
-    for (int q = 0; q < m && q < K; q++) c += (pair_owner<K>(q) == H);
-    return c;
-}
-template <int D, int K, int H>
-__host__ __device__ constexpr int own_right_after(int m)
-{ // number of right dims > m owned by H
-    int c = 0;
-    for (int q = D - 1; q > m && q > K; q--) c += (pair_owner<K>(q) == H);
-    return c;
-}
-
-// dims-neighbour vector index (skips K): (m, s) -> 0 .. 2(D-1)-1
-template <int K>
-__host__ __device__ constexpr int gvec(int m, int s) { return (m < K ? 2 * m : 2 * (m - 1)) + s; }
 
 // What a fiber parks in LDS for the moment its nodes are finalised (rows of 64 lanes behind the exchange rows).  Without
 // dependency information (Model::HAS_DEPS absent): every fixed coordinate and every table value.  With it: the upwind rates of
 // the control-independent dimensions whose drift does not read the varying dimension are constants of the fiber -- formed once
 // (upwind_rates, the node loop's own arithmetic) and parked INSTEAD of the coordinates / table values only they needed; the node
-// then reads two doubles per such dimension where it formed a drift, two compares, four selects and three flops (car7d: 3.7 of
-// the 5 control-independent dimensions on average over K).
+// then reads the sum of those rates (and one rate-weighted total of their neighbour values, PairMap) where it formed a drift, two
+// compares, four selects and three flops per such dimension (car7d: 3.7 of the 5 control-independent dimensions on average over K).
 template <class Model, int K>
 struct PairPark {
     static constexpr int D = Model::D, NTAB = Model::NTAB;
@@ -193,21 +178,150 @@ struct PairPark {
         return r;
     }
     __host__ __device__ static constexpr int nt() { return row_t(NTAB) - nx(); }
+    // ... of which every one but K is MERGED: its stencil values enter a node only as pm V- + pp V+, with (pm, pp) constants of
+    // the fiber, so its two neighbour vectors are folded rate-weighted into one vector per side of K (PairMap) and the node
+    // reads one total PVc and one Qc = sum (pm + pp) for all of them.  K's own rates (its stencil values are the node values
+    // of the fiber itself) stay a parked pair.
+    __host__ __device__ static constexpr unsigned merged() { return constd() & ~(1u << K); }
+    __host__ __device__ static constexpr unsigned rates() { return constd() & (1u << K); }
     __host__ __device__ static constexpr int row_pm(int m)
     {
         int r = nx() + nt();
-        for (int q = 0; q < m; q++) r += 2 * ((constd() >> q) & 1u);
+        for (int q = 0; q < m; q++) r += 2 * ((rates() >> q) & 1u);
         return r;
     }
-    __host__ __device__ static constexpr int rows() { return row_pm(D); }
+    __host__ __device__ static constexpr int row_q() { return row_pm(D); }
+    __host__ __device__ static constexpr int rows() { return row_q() + (merged() != 0u); }
+};
+
+// Slot map of the folded vectors.  Items: the +- pair of every non-merged dimension m != K (item m), the merged vector U_L of
+// the merged dimensions left of K (item D) and U_R of those right of it (item D + 1).  Node-loop order (Wh, the exchange rows):
+// [U_L] pairs of m < K ascending | [U_R] pairs of m > K ascending; the first nvl() are dotted with c = G_K[j] R, the others
+// with a = L G_K[j].
+//   U_L = sum_{m merged, m < K} (pm_m w_m^- + pp_m w_m^+): carried through the later cores as ONE vector, U <- U G_m[i_m], plus
+//   pm (L G_m[i_m - 1]) + pp (L G_m[i_m + 1]) where m is itself merged; U_R likewise from the right.
+template <class Model, int K>
+struct PairMap {
+    typedef PairPark<Model, K> PK;
+    static constexpr int D = Model::D, NIT = D + 2, UL = D, UR = D + 1;
+    __host__ __device__ static constexpr bool mg(int m) { return (PK::merged() >> m) & 1u; }
+    __host__ __device__ static constexpr int first_l()
+    { // the merged dimension at which U_L is created (the smallest), -1: none
+        for (int m = 0; m < K; m++)
+            if (mg(m)) return m;
+        return -1;
+    }
+    __host__ __device__ static constexpr int first_r()
+    { // ... U_R (the largest)
+        for (int m = D - 1; m > K; m--)
+            if (mg(m)) return m;
+        return -1;
+    }
+    __host__ __device__ static constexpr bool valid(int it)
+    {
+        return it == UL ? first_l() >= 0 : (it == UR ? first_r() >= 0 : (it != K && !mg(it)));
+    }
+    __host__ __device__ static constexpr int count(int it) { return !valid(it) ? 0 : (it < D ? 2 : 1); }
+    __host__ __device__ static constexpr int nvl()
+    {
+        int c = count(UL);
+        for (int m = 0; m < K; m++) c += count(m);
+        return c;
+    }
+    __host__ __device__ static constexpr int nvr()
+    {
+        int c = count(UR);
+        for (int m = K + 1; m < D; m++) c += count(m);
+        return c;
+    }
+    __host__ __device__ static constexpr int nv() { return nvl() + nvr(); }
+    __host__ __device__ static constexpr int gslot(int it)
+    { // first node-loop slot of an item
+        if (it == UL) return 0;
+        if (it == UR) return nvl();
+        int c = it < K ? count(UL) : nvl() + count(UR);
+        for (int m = it < K ? 0 : K + 1; m < it; m++) c += count(m);
+        return c;
+    }
+    // fold work of an item in vector-matrix products (edge cores combine rows: free)
+    __host__ __device__ static constexpr int cost(int it)
+    {
+        if (!valid(it)) return 0;
+        if (it == UL) {
+            int c = K - 1 - first_l();
+            for (int m = 1; m < K; m++) c += 2 * mg(m);
+            return c;
+        }
+        if (it == UR) {
+            int c = first_r() - K - 1;
+            for (int m = K + 1; m < D - 1; m++) c += 2 * mg(m);
+            return c;
+        }
+        return it < K ? (it > 0 ? 2 : 0) + 2 * (K - 1 - it) : (it < D - 1 ? 2 : 0) + 2 * (it - K - 1);
+    }
+    // Which wave folds an item.  Nothing merged: pair_owner (alternate by distance from K).  Otherwise that is no longer balanced
+    // -- a side that collapsed to one carried vector costs a fraction of its pairs -- and the items are dealt by their cost
+    // count, the most expensive first, each to the wave with less work so far.
+    __host__ __device__ static constexpr int owner(int it)
+    {
+        if (PK::merged() == 0u) return pair_owner<K>(it);
+        int load[2] = {0, 0}, own[NIT] = {};
+        bool done[NIT] = {};
+        for (int n = 0; n < NIT; n++) {
+            int best = -1;
+            for (int q = 0; q < NIT; q++)
+                if (valid(q) && !done[q] && (best < 0 || cost(q) > cost(best))) best = q;
+            if (best < 0) break;
+            const int h = load[1] < load[0] ? 1 : 0;
+            own[best] = h;
+            load[h] += cost(best);
+            done[best] = true;
+        }
+        return own[it];
+    }
+    // the item a left (right) core step m creates: the pair of m, or U at its first merged dimension; -1: none
+    __host__ __device__ static constexpr int created(int m)
+    {
+        if (m == K) return -1;
+        if (!mg(m)) return m;
+        return m < K ? (m == first_l() ? UL : -1) : (m == first_r() ? UR : -1);
+    }
+    // own vectors of wave H that exist before the left step m (created at dimensions < m), resp. before the right step m (> m):
+    // a wave keeps its vectors in creation order, left ones first
+    template <int H>
+    __host__ __device__ static constexpr int left_before(int m)
+    {
+        int c = 0;
+        for (int q = 0; q < m && q < K; q++)
+            if (created(q) >= 0 && owner(created(q)) == H) c += count(created(q));
+        return c;
+    }
+    template <int H>
+    __host__ __device__ static constexpr int right_after(int m)
+    {
+        int c = 0;
+        for (int q = D - 1; q > m && q > K; q--)
+            if (created(q) >= 0 && owner(created(q)) == H) c += count(created(q));
+        return c;
+    }
+    template <int H>
+    __host__ __device__ static constexpr int lslot(int it)
+    { // slot of an item in its owner's W
+        if (it == UL) return left_before<H>(first_l());
+        if (it == UR) return left_before<H>(K) + right_after<H>(first_r());
+        return it < K ? left_before<H>(it) : left_before<H>(K) + right_after<H>(it);
+    }
 };
 
 // the parked rates as node_backup's Pre
 template <class Model, int K>
 struct PairPre {
-    static constexpr unsigned MASK = PairPark<Model, K>::constd();
+    static constexpr unsigned MASK = PairPark<Model, K>::merged(), RATES = PairPark<Model, K>::rates();
     const double *PX;
     int lane;
+    double pvc; // the merged slots' totals of this node
+    __device__ inline double q() const { return PX[PairPark<Model, K>::row_q() * 64 + lane]; }
+    __device__ inline double pv() const { return pvc; }
     __device__ inline double pm(int m) const { return PX[PairPark<Model, K>::row_pm(m) * 64 + lane]; }
     __device__ inline double pp(int m) const { return PX[(PairPark<Model, K>::row_pm(m) + 1) * 64 + lane]; }
 };
@@ -228,9 +342,12 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
     constexpr int D = Model::D;
     constexpr int S = 2 * D + 1;
     constexpr int RH = RP / 2;
-    constexpr int NV = 2 * (D - 1);                      // neighbour vectors in total
-    constexpr int NOL = 2 * own_left_before<D, K, H>(K); // own left vectors (slots [0, NOL))
-    constexpr int NOR = 2 * own_right_after<D, K, H>(K); // own right vectors (slots [NOL, NOL+NOR))
+    typedef PairPark<Model, K> PK;
+    typedef PairMap<Model, K> PM;
+    constexpr int NV = PM::nv();                            // folded vectors in total: 2(D-1) when nothing is merged
+    constexpr int NVL = PM::nvl();                          // ... of which left of K (dotted with c)
+    constexpr int NOL = PM::template left_before<H>(K);     // own left vectors (slots [0, NOL))
+    constexpr int NOR = PM::template right_after<H>(K);     // own right vectors (slots [NOL, NOL+NOR))
     constexpr int NOWN = (NOL + NOR) > 0 ? (NOL + NOR) : 1;
     constexpr int NP = NV + 1; // partial sums per node: NV neighbour values + the node value
     constexpr bool DIRECT = fpp_direct<Model, RP>();
@@ -276,6 +393,27 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
         double tv[Model::NTAB > 0 ? Model::NTAB : 1]; // model tables: constant along the fiber unless indexed by dim K
         table_values<Model>(A, ro, fi, tv);
 
+        // (p-, p+) of the fiber-constant dimensions, before the fold: the merged vectors are weighted with them
+        double rpm[D], rpp[D];
+#pragma unroll
+        for (int m = 0; m < D; m++) { rpm[m] = 0.0; rpp[m] = 0.0; }
+        if constexpr (PK::constd() != 0) {
+            // x[K] and the K-indexed tables are node 0's here (fi[K] = 0): the rates kept do not read them
+            typename Model::Node nd0;
+            Model::prep(A.prm, x, tv, nd0);
+            double u0[Model::DU], cf0[Model::NCF > 0 ? Model::NCF : 1], b0[D], s0[D];
+#pragma unroll
+            for (int i = 0; i < Model::DU; i++) u0[i] = cr.get_u(i, 0);
+            cf0[0] = 0.0;
+#pragma unroll
+            for (int i = 0; i < Model::NCF; i++) cf0[i] = cr.get_cf(i, 0);
+            Model::drift(A.prm, nd0, x, u0, cf0, b0);
+            Model::sigma(A.prm, x, u0, s0);
+#pragma unroll
+            for (int m = 0; m < D; m++)
+                if ((PK::constd() >> m) & 1u) upwind_rates(A.t[2 * m], A.t[2 * m + 1], b0[m], s0[m], rpm[m], rpp[m]);
+        }
+
         double L[RP], R[RP], W[NOWN][RP];
 #pragma unroll
         for (int a = 0; a < RP; a++) { L[a] = (a == 0) ? 1.0 : 0.0; R[a] = (a == 0) ? 1.0 : 0.0; }
@@ -298,7 +436,9 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
 #pragma unroll
                 for (int b = 0; b < RP; b++) {
                     L[b] = src[fi[0] * str + b];
-                    if constexpr (pair_owner<K>(0) == H) {
+                    if constexpr (PM::mg(0)) { // an edge core: U_L starts as the weighted rows
+                        if constexpr (PM::owner(PM::UL) == H) W[0][b] = fma(rpp[0], src[nbp[0] * str + b], rpm[0] * src[nbm[0] * str + b]);
+                    } else if constexpr (PM::owner(0) == H) {
                         W[0][b] = src[nbm[0] * str + b];
                         W[1][b] = src[nbp[0] * str + b];
                     }
@@ -307,7 +447,9 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
             auto left_step = [&](auto mc) __attribute__((always_inline)) {
                 constexpr int m = decltype(mc)::value;
                 constexpr int str = DIRECT ? RP * RP : fpl_lds_stride(RP * RP);
-                constexpr int before = 2 * own_left_before<D, K, H>(m); // own vectors created so far
+                constexpr int before = PM::template left_before<H>(m); // own vectors created so far
+                constexpr bool PAIR = !PM::mg(m) && PM::owner(m) == H, ACC = PM::mg(m) && PM::owner(PM::UL) == H;
+                double nw[RP]; // a merged dimension's share of U_L
                 const double *src = sK;
                 FPP_STAMP(1)
                 if constexpr (DIRECT) src = ro + A.core_off[m];
@@ -318,7 +460,7 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
                 }
                 FPP_STAMP(7)
                 const double *G = src + fi[m] * str;
-                if constexpr (pair_owner<K>(m) == H) { // the new pair first: it needs the prefix BEFORE this core
+                if constexpr (PAIR || ACC) { // the new pair first: it needs the prefix BEFORE this core
                     double t0[1][RP], t1[1][RP];
 #pragma unroll
                     for (int a = 0; a < RP; a++) { t0[0][a] = L[a]; t1[0][a] = L[a]; }
@@ -330,7 +472,10 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
                         vecmat_lds<RP, 1>(src + nbp[m] * str, t1);
                     }
 #pragma unroll
-                    for (int a = 0; a < RP; a++) { W[before][a] = t0[0][a]; W[before + 1][a] = t1[0][a]; }
+                    for (int a = 0; a < RP; a++) {
+                        if constexpr (PAIR) { W[before][a] = t0[0][a]; W[before + 1][a] = t1[0][a]; }
+                        else nw[a] = fma(rpp[m], t1[0][a], rpm[m] * t0[0][a]);
+                    }
                 }
                 if constexpr (DIRECT) {
                     double tl[1][RP];
@@ -342,6 +487,11 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
                     apply_range_glb<RP, NOWN, 0, before, true>(G, W);
                 } else
                     apply_core_and<RP, NOWN, 0, before, true>(G, W, L);
+                if constexpr (ACC) { // U_L: created here, or carried through this core above and added to
+                    constexpr int su = PM::template lslot<H>(PM::UL);
+#pragma unroll
+                    for (int a = 0; a < RP; a++) W[su][a] = (m == PM::first_l()) ? nw[a] : W[su][a] + nw[a];
+                }
             };
             [&]<int... Ms>(std::integer_sequence<int, Ms...>) { (left_step(std::integral_constant<int, Ms + 1>{}), ...); }
             (std::make_integer_sequence<int, (K > 1 ? K - 1 : 0)>{});
@@ -363,7 +513,10 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
 #pragma unroll
                 for (int a = 0; a < RP; a++) {
                     R[a] = src[fi[D - 1] * str + a];
-                    if constexpr (pair_owner<K>(D - 1) == H) {
+                    if constexpr (PM::mg(D - 1)) {
+                        if constexpr (PM::owner(PM::UR) == H)
+                            W[NOL][a] = fma(rpp[D - 1], src[nbp[D - 1] * str + a], rpm[D - 1] * src[nbm[D - 1] * str + a]);
+                    } else if constexpr (PM::owner(D - 1) == H) {
                         W[NOL][a] = src[nbm[D - 1] * str + a];
                         W[NOL + 1][a] = src[nbp[D - 1] * str + a];
                     }
@@ -372,7 +525,9 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
             auto right_step = [&](auto mc) __attribute__((always_inline)) {
                 constexpr int m = decltype(mc)::value; // D-2 down to K+1
                 constexpr int str = DIRECT ? RP * RP : fpl_lds_stride(RP * RP);
-                constexpr int after = 2 * own_right_after<D, K, H>(m);
+                constexpr int after = PM::template right_after<H>(m);
+                constexpr bool PAIR = !PM::mg(m) && PM::owner(m) == H, ACC = PM::mg(m) && PM::owner(PM::UR) == H;
+                double nw[RP];
                 const double *src = sK;
                 FPP_STAMP(1)
                 if constexpr (DIRECT) src = ro + A.core_off[m];
@@ -383,7 +538,7 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
                 }
                 FPP_STAMP(7)
                 const double *G = src + fi[m] * str;
-                if constexpr (pair_owner<K>(m) == H) {
+                if constexpr (PAIR || ACC) {
                     double t0[1][RP], t1[1][RP];
 #pragma unroll
                     for (int a = 0; a < RP; a++) { t0[0][a] = R[a]; t1[0][a] = R[a]; }
@@ -395,7 +550,10 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
                         matvec_lds<RP, 1>(src + nbp[m] * str, t1);
                     }
 #pragma unroll
-                    for (int a = 0; a < RP; a++) { W[NOL + after][a] = t0[0][a]; W[NOL + after + 1][a] = t1[0][a]; }
+                    for (int a = 0; a < RP; a++) {
+                        if constexpr (PAIR) { W[NOL + after][a] = t0[0][a]; W[NOL + after + 1][a] = t1[0][a]; }
+                        else nw[a] = fma(rpp[m], t1[0][a], rpm[m] * t0[0][a]);
+                    }
                 }
                 if constexpr (DIRECT) {
                     double tr[1][RP];
@@ -407,6 +565,11 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
                     apply_range_glb<RP, NOWN, NOL, after, false>(G, W);
                 } else
                     apply_core_and<RP, NOWN, NOL, after, false>(G, W, R);
+                if constexpr (ACC) {
+                    constexpr int su = PM::template lslot<H>(PM::UR);
+#pragma unroll
+                    for (int a = 0; a < RP; a++) W[su][a] = (m == PM::first_r()) ? nw[a] : W[su][a] + nw[a];
+                }
             };
             [&]<int... Ms>(std::integer_sequence<int, Ms...>) { (right_step(std::integral_constant<int, D - 2 - Ms>{}), ...); }
             (std::make_integer_sequence<int, (D - 2 - K > 0 ? D - 2 - K : 0)>{});
@@ -419,13 +582,13 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
         {
             double *X = sK; // [NV][RH][64]
             pair_barrier();
-            auto put_get_own = [&](auto mc) __attribute__((always_inline)) {
-                constexpr int m = decltype(mc)::value;
-                if constexpr (m != K && pair_owner<K>(m) == H) {
-                    constexpr int slot = (m < K) ? 2 * own_left_before<D, K, H>(m) : NOL + 2 * own_right_after<D, K, H>(m);
+            auto put_get_own = [&](auto ic) __attribute__((always_inline)) {
+                constexpr int it = decltype(ic)::value;
+                if constexpr (PM::valid(it) && PM::owner(it) == H) {
+                    constexpr int slot = PM::template lslot<H>(it);
 #pragma unroll
-                    for (int s = 0; s < 2; s++) {
-                        const int g = gvec<K>(m, s);
+                    for (int s = 0; s < PM::count(it); s++) {
+                        const int g = PM::gslot(it) + s;
 #pragma unroll
                         for (int i = 0; i < RH; i++) {
                             X[(g * RH + i) * 64 + lane] = W[slot + s][(1 - H) * RH + i];
@@ -435,21 +598,21 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
                 }
             };
             [&]<int... Ms>(std::integer_sequence<int, Ms...>) { (put_get_own(std::integral_constant<int, Ms>{}), ...); }
-            (std::make_integer_sequence<int, D>{});
+            (std::make_integer_sequence<int, PM::NIT>{});
             pair_barrier();
-            auto get_other = [&](auto mc) __attribute__((always_inline)) {
-                constexpr int m = decltype(mc)::value;
-                if constexpr (m != K && pair_owner<K>(m) != H) {
+            auto get_other = [&](auto ic) __attribute__((always_inline)) {
+                constexpr int it = decltype(ic)::value;
+                if constexpr (PM::valid(it) && PM::owner(it) != H) {
 #pragma unroll
-                    for (int s = 0; s < 2; s++) {
-                        const int g = gvec<K>(m, s);
+                    for (int s = 0; s < PM::count(it); s++) {
+                        const int g = PM::gslot(it) + s;
 #pragma unroll
                         for (int i = 0; i < RH; i++) Wh[g][i] = X[(g * RH + i) * 64 + lane];
                     }
                 }
             };
             [&]<int... Ms>(std::integer_sequence<int, Ms...>) { (get_other(std::integral_constant<int, Ms>{}), ...); }
-            (std::make_integer_sequence<int, D>{});
+            (std::make_integer_sequence<int, PM::NIT>{});
             pair_barrier();
         }
         // L and R move to LDS (rows of 64 lanes): both waves hold the same values, wave 0 stores L, wave 1 R.
@@ -464,7 +627,6 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
             // the fiber's coordinates and table values are only needed when a node is finalised: parked in LDS
             // (wave 0 writes; both waves hold the same numbers) they do not occupy VGPRs during the partial sums
             if constexpr (H == 0) {
-                typedef PairPark<Model, K> PK;
                 static_assert(PK::rows() <= NP, "parking rows exceed the reserved block");
                 double *PXw = sK + (2 * RP + 2 * (NP + 1) + NP) * 64;
 #pragma unroll
@@ -473,26 +635,18 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
 #pragma unroll
                 for (int t = 0; t < Model::NTAB; t++)
                     if (PK::need_t(t)) PXw[PK::row_t(t) * 64 + lane] = tv[t];
-                if constexpr (PK::constd() != 0) {
-                    // x[K] and the K-indexed tables are node 0's here (fi[K] = 0): the rates kept do not read them
-                    typename Model::Node nd0;
-                    Model::prep(A.prm, x, tv, nd0);
-                    double u0[Model::DU], cf0[Model::NCF > 0 ? Model::NCF : 1], b0[D], s0[D];
 #pragma unroll
-                    for (int i = 0; i < Model::DU; i++) u0[i] = cr.get_u(i, 0);
-                    cf0[0] = 0.0;
-#pragma unroll
-                    for (int i = 0; i < Model::NCF; i++) cf0[i] = cr.get_cf(i, 0);
-                    Model::drift(A.prm, nd0, x, u0, cf0, b0);
-                    Model::sigma(A.prm, x, u0, s0);
+                for (int m = 0; m < D; m++)
+                    if ((PK::rates() >> m) & 1u) {
+                        PXw[PK::row_pm(m) * 64 + lane] = rpm[m];
+                        PXw[(PK::row_pm(m) + 1) * 64 + lane] = rpp[m];
+                    }
+                if constexpr (PK::merged() != 0u) { // Qc: the merged dimensions' share of Q = sum p
+                    double qc = 0.0;
 #pragma unroll
                     for (int m = 0; m < D; m++)
-                        if ((PK::constd() >> m) & 1u) {
-                            double pm, pp;
-                            upwind_rates(A.t[2 * m], A.t[2 * m + 1], b0[m], s0[m], pm, pp);
-                            PXw[PK::row_pm(m) * 64 + lane] = pm;
-                            PXw[(PK::row_pm(m) + 1) * 64 + lane] = pp;
-                        }
+                        if (PM::mg(m)) { qc += rpm[m]; qc += rpp[m]; }
+                    PXw[PK::row_q() * 64 + lane] = qc;
                 }
             }
             pair_barrier();
@@ -555,9 +709,9 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
                 for (int i = 0; i < RH; i++) v = fma(sL[(H * RH + i) * 64 + lane], ch[i], v);
                 pv = v;
 #pragma unroll
-                for (int g = 0; g < 2 * K; g++) sink(g, dot_reg<RH>(Wh[g], ch));
+                for (int g = 0; g < NVL; g++) sink(g, dot_reg<RH>(Wh[g], ch));
 #pragma unroll
-                for (int g = 2 * K; g < NV; g++) sink(g, dot_reg<RH>(ah, Wh[g]));
+                for (int g = NVL; g < NV; g++) sink(g, dot_reg<RH>(ah, Wh[g]));
             }
             sink(NV, pv);
             return pv;
@@ -633,16 +787,16 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
         auto dots_quarter = [&](int q, const double (&ch)[RH], const double (&ah)[RH], auto &&sink) __attribute__((always_inline)) {
 #pragma unroll
             for (int g = 0; g < NV; g++)
-                if (g * 4 / NV == q) sink(g, (g < 2 * K) ? dot_reg<RH>(Wh[g], ch) : dot_reg<RH>(ah, Wh[g]));
+                if (g * 4 / NV == q) sink(g, (g < NVL) ? dot_reg<RH>(Wh[g], ch) : dot_reg<RH>(ah, Wh[g]));
         };
         auto dots_part = [&](const double (&ch)[RH], const double (&ah)[RH], auto &&sink) __attribute__((always_inline)) -> double {
             double v = 0.0;
 #pragma unroll
             for (int i = 0; i < RH; i++) v = fma(sL[(H * RH + i) * 64 + lane], ch[i], v);
 #pragma unroll
-            for (int g = 0; g < 2 * K; g++) sink(g, dot_reg<RH>(Wh[g], ch));
+            for (int g = 0; g < NVL; g++) sink(g, dot_reg<RH>(Wh[g], ch));
 #pragma unroll
-            for (int g = 2 * K; g < NV; g++) sink(g, dot_reg<RH>(ah, Wh[g]));
+            for (int g = NVL; g < NV; g++) sink(g, dot_reg<RH>(ah, Wh[g]));
             sink(NV, v);
             return v;
         };
@@ -652,15 +806,19 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
         double *B2 = B1 + (NP + 1) * 64;  // wave 1 own       : P_1(j1)[NP]
         double *PX = B2 + NP * 64;        // parked per-fiber constants: x[m] (m != K) rows 0..D-1, model tables after
 
-        // finalise one node from its assembled stencil (NV neighbour values in gvec order, node value last)
+        // finalise one node from its assembled stencil (NV totals in PairMap order, node value last)
         auto finalize = [&](int jn, const double (&Vt)[NP], double vlo, double vhi) __attribute__((always_inline)) {
             double V[S];
 #pragma unroll
             for (int m = 0; m < D; m++) {
                 if (m == K) { V[2 * m] = vlo; V[2 * m + 1] = vhi; }
-                else { V[2 * m] = Vt[gvec<K>(m, 0)]; V[2 * m + 1] = Vt[gvec<K>(m, 1)]; }
+                else if (PM::mg(m)) { V[2 * m] = 0.0; V[2 * m + 1] = 0.0; } // not formed: it enters through PVc
+                else { V[2 * m] = Vt[PM::gslot(m)]; V[2 * m + 1] = Vt[PM::gslot(m) + 1]; }
             }
             V[2 * D] = Vt[NV];
+            double pvc = 0.0; // sum over the merged dimensions of pm V- + pp V+
+            if constexpr (PM::valid(PM::UL)) pvc += Vt[PM::gslot(PM::UL)];
+            if constexpr (PM::valid(PM::UR)) pvc += Vt[PM::gslot(PM::UR)];
             double x[D], tv[Model::NTAB > 0 ? Model::NTAB : 1];
             tv[0] = 0.0;
 #pragma unroll
@@ -679,7 +837,7 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
             // FORCED (policy evaluation) is a separate instantiation: as a run-time flag it costs the minimising kernel 4 %
             int fu = -1;
             if constexpr (FORCED) fu = A.forced[(size_t)f * N + jn];
-            const PairPre<Model, K> pre{PX, lane};
+            const PairPre<Model, K> pre{PX, lane, pvc};
             const double val = node_backup<Model, FPP_CG, FPP_CGD, CandLds<Model>, true, PairPre<Model, K>>(A, ro, x, tv, cr, V, ab, ui, st, FORCED, fu, pre);
             FPP_STAMP(9) // control scan
             // lanes past the last fiber duplicate fiber F-1 and store the same numbers to the same place: no

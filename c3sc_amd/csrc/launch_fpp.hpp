@@ -9,7 +9,7 @@ template <class Model, int RP, int K, bool FORCED>
 hipError_t launch_fpp_impl(const KArgs &A, const LaunchIO &io)
 {
     constexpr int D = Model::D;
-    constexpr int NV = 2 * (D - 1), NP = NV + 1, RH = RP / 2;
+    constexpr int NV = PairMap<Model, K>::nv(), NP = NV + 1, RH = RP / 2; // the kernel's own count of folded vectors
     if (A.ncand > 64) return hipErrorNotSupported; // one lane per candidate fills the table: the per-wave kernel walks longer lists
     // LDS: max(largest staged fixed core, half-swap buffer, per-node exchange buffers)
     size_t doubles = (size_t)NV * RH * 64;
