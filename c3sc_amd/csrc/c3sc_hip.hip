@@ -50,10 +50,18 @@ __global__ void k_pad_core(const double *__restrict__ src, double *__restrict__ 
 // fiber-pair kernel copies its fixed cores into LDS by LDS-DMA (global_load_lds, 16 bytes per lane), which writes
 // lane-linearly and cannot pad, so the padding (elems | 1 doubles per node there, elems + 2 for the fiber-quad kernels) is
 // laid down here.  blockIdx.y = job.
+// Two more jobs of the same launch build the fiber-pair kernel's product tables (kernel_fiber_pair.hpp: fpp_edge_tables), one row
+// of RP doubles per index pair (a, b) of a side's two outer cores:
+//   tab 1: row[beta]  = sum_alpha G_0[a][alpha] G_1[b][alpha + beta RP]          (src = G_0, src2 = G_1,     nodes2 = N_1)
+//   tab 2: row[alpha] = sum_beta  G_{d-2}[a][alpha + beta RP] G_{d-1}[b][beta]   (src = G_{d-2}, src2 = G_{d-1}, nodes2 = N_{d-1})
+// Each entry is ONE fma chain from 0.0 with the summed index ascending -- the order of vecmat_lds / matvec_lds (fold_lds.hpp), so a
+// row is bit for bit the vector the kernel used to fold from the two cores.  Built from the padded cores: padding stays exact zero.
 struct ImgJobs {
     int n;
-    long src[3 * MAXD], dst[3 * MAXD];
-    int nodes[3 * MAXD], per[3 * MAXD], stride[3 * MAXD];
+    long src[3 * MAXD + 2], dst[3 * MAXD + 2];
+    int nodes[3 * MAXD + 2], per[3 * MAXD + 2], stride[3 * MAXD + 2];
+    int tab[3 * MAXD + 2], nodes2[3 * MAXD + 2]; // tab: 0 image, 1 / 2 product table (per = RP)
+    long src2[3 * MAXD + 2];
 };
 __global__ void k_core_images(double *__restrict__ arena, const ImgJobs J)
 {
@@ -61,6 +69,25 @@ __global__ void k_core_images(double *__restrict__ arena, const ImgJobs J)
     const double *core = arena + J.src[jb];
     double *img = arena + J.dst[jb];
     const int per = J.per[jb], stride = J.stride[jb];
+    if (J.tab[jb] != 0) {
+        const double *core2 = arena + J.src2[jb];
+        const int RP = per, n2 = J.nodes2[jb];
+        const bool left = J.tab[jb] == 1;
+        const long total = (long)J.nodes[jb] * n2 * RP;
+        for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
+            const long row = e / RP;
+            const int c = (int)(e - row * RP), a = (int)(row / n2), b = (int)(row - (long)a * n2);
+            // left: the edge core is the row vector G_0[a] and c the column of G_1[b]; right: the edge core is the column vector
+            // G_{d-1}[b] and c the row of G_{d-2}[a]
+            const double *vec = left ? core + (size_t)a * RP : core2 + (size_t)b * RP;
+            const double *mat = left ? core2 + (size_t)b * RP * RP + (size_t)c * RP : core + (size_t)a * RP * RP + c;
+            const int ms = left ? 1 : RP;
+            double t = 0.0;
+            for (int s = 0; s < RP; s++) t = fma(vec[s], mat[(size_t)s * ms], t);
+            img[e] = t;
+        }
+        return;
+    }
     const long total = (long)J.nodes[jb] * stride;
     for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
         const int j = (int)(e / stride), w = (int)(e - (long)j * stride);
@@ -637,7 +664,20 @@ static int prepare_value(c3sc_hip_ctx *c, const size_t *ranks, size_t *cores_dou
     for (int m = 0; m < d; m++) { // LDS images for the fiber-pair kernel's LDS-DMA staging (+2: its last 16-byte piece may overhang)
         const size_t per = (m == 0 || m == d - 1) ? rp : (size_t)rp * rp;
         img_off[m] = (long)off;
-        off += ((size_t)c->ngrid[m] * (per | 1) + 2 + 15) & ~(size_t)15;
+        off += (size_t)pair_img_doubles(c->ngrid[m], (int)per);
+    }
+    // product tables of each side's two outer cores for the staged fiber-pair kernels (kernel_common.hpp: pair_tabL_off), right
+    // behind the last image: made only when such a kernel of this (dimension, padded rank) exists -- of ANY model: the model may
+    // be set after the upload, and a pair kernel must never run without its tables
+    long tabL_off = 0, tabR_off = 0;
+    bool have_pair = false;
+    for (const auto &e : kernel_registry())
+        if (e.variant == C3SC_VARIANT_FIBER_PAIR && e.d == d && e.rp == rp) have_pair = true;
+    if (d >= 4 && have_pair) {
+        tabL_off = (long)off;
+        off += (size_t)pair_tab_doubles(c->ngrid[0], c->ngrid[1], rp);
+        tabR_off = (long)off;
+        off += (size_t)pair_tab_doubles(c->ngrid[d - 2], c->ngrid[d - 1], rp);
     }
     long qimgL_off[MAXD] = {0}, qimgR_off[MAXD] = {0};
     if (rp % 4 == 0 && have_quad) { // LDS images for the duo kernel's double-buffered LDS-DMA staging
@@ -659,6 +699,8 @@ static int prepare_value(c3sc_hip_ctx *c, const size_t *ranks, size_t *cores_dou
     if (stat != c->static_doubles) c->static_dirty = true;
     c->static_doubles = stat;
     for (int m = 0; m < d; m++) { c->core_off[m] = core_off[m]; c->coreT_off[m] = coreT_off[m]; c->aop_off[m] = aop_off[m]; c->img_off[m] = img_off[m]; c->qimgL_off[m] = qimgL_off[m]; c->qimgR_off[m] = qimgR_off[m]; }
+    c->tabL_off = tabL_off;
+    c->tabR_off = tabR_off;
     for (int m = 0; m <= d; m++) c->ranks[m] = ranks[m];
     c->rp = rp;
     *cores_doubles = primary_end - stat;
@@ -680,6 +722,7 @@ static int make_quad_aux(c3sc_hip_ctx *c, void *stream)
     long maxtotal = 1;
     auto add = [&](long src, long dst, int nodes, int per, int stride) {
         J.src[J.n] = src; J.dst[J.n] = dst; J.nodes[J.n] = nodes; J.per[J.n] = per; J.stride[J.n] = stride;
+        J.tab[J.n] = 0; J.nodes2[J.n] = 0; J.src2[J.n] = 0;
         J.n++;
         maxtotal = std::max(maxtotal, (long)nodes * stride);
     };
@@ -689,6 +732,13 @@ static int make_quad_aux(c3sc_hip_ctx *c, void *stream)
         if (c->qimgL_off[m]) add(c->core_off[m], c->qimgL_off[m], c->ngrid[m], per, per + 2);
         if (c->qimgR_off[m]) add((m == c->d - 1) ? c->core_off[m] : c->coreT_off[m], c->qimgR_off[m], c->ngrid[m], per, per + 2);
     }
+    auto add_tab = [&](int tab, long dst, int ma, int mb) { // one thread per table entry, grid-stride like the images
+        add(c->core_off[ma], dst, c->ngrid[ma], c->rp, c->rp);
+        J.tab[J.n - 1] = tab; J.nodes2[J.n - 1] = c->ngrid[mb]; J.src2[J.n - 1] = c->core_off[mb];
+        maxtotal = std::max(maxtotal, (long)c->ngrid[ma] * c->ngrid[mb] * c->rp);
+    };
+    if (c->tabL_off) add_tab(1, c->tabL_off, 0, 1);
+    if (c->tabR_off) add_tab(2, c->tabR_off, c->d - 2, c->d - 1);
     hipLaunchKernelGGL(k_core_images, dim3((unsigned)std::min<long>((maxtotal + 255) / 256, 64), (unsigned)J.n), dim3(256), 0, (hipStream_t)stream,
                        c->arena, J);
     HIPCHK(c, hipGetLastError());
@@ -839,6 +889,8 @@ static int fill_args(c3sc_hip_ctx *c, int k, size_t F, KArgs &A, bool need_model
         A.quad_imgR_off[m] = c->qimgR_off[m];
     }
     A.img_base = c->arena;
+    if (c->tabL_off && (c->tabL_off != pair_tabL_off(A, c->rp) || c->tabR_off != pair_tabR_off(A, c->rp)))
+        return fail(c, C3SC_ERR_ARG, "launch: the pair kernel's product tables are not where the kernel looks for them");
     A.cends = c->cends;
     A.memo_keys = nullptr; // only the launch paths that found a fiber-per-wave kernel switch the memo epilogue on
     A.skip = c->skip_flag;

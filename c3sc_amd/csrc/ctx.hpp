@@ -58,6 +58,7 @@ struct c3sc_hip_ctx {
     long coreT_off[c3sc::MAXD] = {0}, aop_off[c3sc::MAXD] = {0}; // fiber-quad copies of the middle cores (0 = none)
     long img_off[c3sc::MAXD] = {0};                        // fiber-pair LDS images of all cores (padded node stride)
     long qimgL_off[c3sc::MAXD] = {0}, qimgR_off[c3sc::MAXD] = {0}; // fiber-quad-duo LDS images (node stride elems + 2)
+    long tabL_off = 0, tabR_off = 0;                       // fiber-pair product tables of the two outer cores of each side (0 = none)
     int obs_off = 0, cands_off = 0, tab_off[4] = {0, 0, 0, 0}, cfeat_off = 0;
     unsigned *d_status = nullptr;
     // the status word as of the last c3sc_hip_cross_fetch, valid until the next launch through this context: the solver reads the

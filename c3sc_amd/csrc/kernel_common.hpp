@@ -87,6 +87,19 @@ struct KArgs {
                                // images through it (see stage_core_image on why it must not be derived from `ro`)
 };
 
+// Product tables of the staged fiber-pair kernels at d >= 4 (kernel_fiber_pair.hpp: fpp_edge_tables), built once per upload by
+// k_core_images: rows of RP doubles,
+//   tabL[(a N_1 + b) RP + beta]      = sum_alpha G_0[a][alpha] G_1[b][alpha, beta]
+//   tabR[(a N_{d-1} + b) RP + alpha] = sum_beta  G_{d-2}[a][alpha, beta] G_{d-1}[b][beta].
+// KArgs carries no offsets for them -- its size is fixed (see game_gsz) and it has no alignment hole left: the two tables FOLLOW
+// THE LAST PAIR IMAGE in the arena, tabL then tabR, every block rounded up to 16 doubles, and the host's layout (prepare_value) and
+// the kernel both take the offsets from the functions below.
+__host__ __device__ constexpr long arena_block(long doubles) { return (doubles + 15) & ~15L; }
+__host__ __device__ constexpr long pair_img_doubles(int nodes, int per) { return arena_block((long)nodes * (per | 1) + 2); } // +2: the last 16-byte piece may overhang
+__host__ __device__ constexpr long pair_tab_doubles(int na, int nb, int rp) { return arena_block((long)na * nb * rp); }
+__host__ __device__ inline long pair_tabL_off(const KArgs &A, int rp) { return A.pair_img_off[A.d - 1] + pair_img_doubles(A.ngrid[A.d - 1], rp); }
+__host__ __device__ inline long pair_tabR_off(const KArgs &A, int rp) { return pair_tabL_off(A, rp) + pair_tab_doubles(A.ngrid[0], A.ngrid[1], rp); }
+
 // Pair index iu * nw + iw of the game candidate at list position p, and back (MINMAX: groups are u, the list is the pair order)
 __device__ inline int game_list_to_pair(const KArgs &A, int p)
 {

@@ -42,6 +42,9 @@
 #ifndef FPP_DIRECT_MAXD
 #define FPP_DIRECT_MAXD 3
 #endif
+#ifndef FPP_EDGE_TABLES
+#define FPP_EDGE_TABLES 1 // the two outer cores of each side enter through their product table (fpp_edge_tables); 0: a diagnostic build folds them
+#endif
 
 namespace c3sc {
 
@@ -52,6 +55,29 @@ constexpr int FPP_THREADS = 128;
 // workgroups at two wavefronts per SIMD -- without it the exchange rows are the LDS footprint (21 KB: three to four).
 template <class Model, int RP>
 __host__ __device__ constexpr bool fpp_direct() { return Model::D <= FPP_DIRECT_MAXD && RP <= 8; }
+
+// Edge tables.  The first matrix level of a side -- L = G_0[i_0] G_1[i_1] with its four neighbour vectors G_0[i_0 +- 1] G_1[i_1],
+// G_0[i_0] G_1[i_1 +- 1], and the same from the right with G_{d-2}, G_{d-1} -- is one function of an index pair, T(a, b), and the
+// cores change once per upload, not per fiber: the host builds T over all N_0 N_1 (N_{d-2} N_{d-1}) pairs at the upload
+// (k_core_images; kernel_common.hpp: pair_tabL_off / pair_tabR_off; 2 x 134 KB for car7d: L2-resident) and a tile gathers up to five rows of
+// RP doubles per side instead of staging two cores and pushing its vectors through one of them.  Where a side consists of the
+// edge core alone (K = 1, K = d-2) its rows are read straight from the arena.  Only the staged kernels from d = 4 on: a
+// 3-D problem has no side with two cores.
+template <class Model, int RP>
+__host__ __device__ constexpr bool fpp_edge_tables() { return FPP_EDGE_TABLES && !fpp_direct<Model, RP>() && Model::D >= 4; }
+
+// one table row (16-byte aligned: even RP, 16-double aligned table) as 16-byte loads
+template <int RP>
+__device__ __forceinline__ void load_row16(const double *__restrict__ p, double (&r)[RP])
+{
+    typedef double v2d __attribute__((ext_vector_type(2)));
+#pragma unroll
+    for (int i = 0; i < RP / 2; i++) {
+        const v2d v = *reinterpret_cast<const v2d *>(p + 2 * i);
+        r[2 * i] = v.x;
+        r[2 * i + 1] = v.y;
+    }
+}
 
 // apply the staged matrix G to W[FIRST .. FIRST+COUNT) AND to one extra vector E in the same passes: every pass
 // re-reads the 100-element matrix of the lane's node from LDS, and LDS (gathered rows, ~2x bank conflicts) is the
@@ -200,10 +226,20 @@ struct PairPark {
 // with a = L G_K[j].
 //   U_L = sum_{m merged, m < K} (pm_m w_m^- + pp_m w_m^+): carried through the later cores as ONE vector, U <- U G_m[i_m], plus
 //   pm (L G_m[i_m - 1]) + pp (L G_m[i_m + 1]) where m is itself merged; U_R likewise from the right.
-template <class Model, int K>
+// TAB (fpp_edge_tables): the product tables absorb each side's first matrix level -- the fold plan (plan()) and the cost count
+// follow it; the slots, NV and the exchange layout do not depend on it.
+struct FoldPlan {
+    int lfirst, rfirst; // the staged left steps are the cores lfirst .. K-1, the right ones rfirst .. K+1 (descending)
+    bool ledge, redge;  // a side's edge core is staged on its own (else: absorbed by a table, read from the arena, or no such side)
+    int staged;         // staging rounds per tile
+    int products;       // vector-matrix products per tile, both wavefronts, L / R carried once
+};
+template <class Model, int K, bool TAB = false>
 struct PairMap {
     typedef PairPark<Model, K> PK;
     static constexpr int D = Model::D, NIT = D + 2, UL = D, UR = D + 1;
+    __host__ __device__ static constexpr bool ltab() { return TAB && K >= 2; }     // cores 0, 1 enter through tabL
+    __host__ __device__ static constexpr bool rtab() { return TAB && K <= D - 3; } // cores d-2, d-1 through tabR
     __host__ __device__ static constexpr bool mg(int m) { return (PK::merged() >> m) & 1u; }
     __host__ __device__ static constexpr int first_l()
     { // the merged dimension at which U_L is created (the smallest), -1: none
@@ -243,21 +279,34 @@ struct PairMap {
         for (int m = it < K ? 0 : K + 1; m < it; m++) c += count(m);
         return c;
     }
-    // fold work of an item in vector-matrix products (edge cores combine rows: free)
+    // fold work of an item in vector-matrix products (edge cores combine rows, the tables' levels are gathered rows: free)
     __host__ __device__ static constexpr int cost(int it)
     {
         if (!valid(it)) return 0;
+        constexpr int lf = ltab() ? 2 : 1, rf = rtab() ? D - 3 : D - 2; // plan().lfirst, .rfirst
         if (it == UL) {
-            int c = K - 1 - first_l();
-            for (int m = 1; m < K; m++) c += 2 * mg(m);
+            int c = K - 1 - first_l() - (ltab() && first_l() == 0);
+            for (int m = lf; m < K; m++) c += 2 * mg(m);
             return c;
         }
         if (it == UR) {
-            int c = first_r() - K - 1;
-            for (int m = K + 1; m < D - 1; m++) c += 2 * mg(m);
+            int c = first_r() - K - 1 - (rtab() && first_r() == D - 1);
+            for (int m = K + 1; m <= rf; m++) c += 2 * mg(m);
             return c;
         }
-        return it < K ? (it > 0 ? 2 : 0) + 2 * (K - 1 - it) : (it < D - 1 ? 2 : 0) + 2 * (it - K - 1);
+        if (it < K) return (ltab() && it <= 1) ? 2 * (K - 2) : (it > 0 ? 2 : 0) + 2 * (K - 1 - it);
+        return (rtab() && it >= D - 2) ? 2 * (D - 3 - K) : (it < D - 1 ? 2 : 0) + 2 * (it - K - 1);
+    }
+    // What the fold of a tile does: the kernel takes its step ranges from here, the tests its counts.
+    __host__ __device__ static constexpr FoldPlan plan()
+    {
+        // an edge core on its own is staged too unless the tables are on (then it is read from the arena)
+        FoldPlan p{ltab() ? 2 : 1, rtab() ? D - 3 : D - 2, K > 0 && !TAB, K < D - 1 && !TAB, 0, 0};
+        const int ls = K - p.lfirst > 0 ? K - p.lfirst : 0, rs = p.rfirst - K > 0 ? p.rfirst - K : 0;
+        p.staged = ls + rs + p.ledge + p.redge;
+        p.products = ls + rs; // L and R through every staged middle core
+        for (int it = 0; it < NIT; it++) p.products += cost(it);
+        return p;
     }
     // Which wave folds an item.  Nothing merged: pair_owner (alternate by distance from K).  Otherwise that is no longer balanced
     // -- a side that collapsed to one carried vector costs a fraction of its pairs -- and the items are dealt by their cost
@@ -343,7 +392,9 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
     constexpr int S = 2 * D + 1;
     constexpr int RH = RP / 2;
     typedef PairPark<Model, K> PK;
-    typedef PairMap<Model, K> PM;
+    constexpr bool ET = fpp_edge_tables<Model, RP>();
+    typedef PairMap<Model, K, ET> PM;
+    constexpr FoldPlan PL = PM::plan();
     constexpr int NV = PM::nv();                            // folded vectors in total: 2(D-1) when nothing is merged
     constexpr int NVL = PM::nvl();                          // ... of which left of K (dotted with c)
     constexpr int NOL = PM::template left_before<H>(K);     // own left vectors (slots [0, NOL))
@@ -422,11 +473,52 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
         FPP_STAMP(0) // tile setup
         if (!(C3SC_STAMPS_ON && (A.dbg & 1))) {
         if constexpr (K > 0) {
-            {
-                constexpr int str = DIRECT ? RP : fpl_lds_stride(RP);
+            // rows of tabL: T(a, b) = G_0[a] G_1[b].  All loads of the side are issued here, ahead of the first staging round,
+            // and combined (left_combine) behind it: their L2 round trip runs under the staging wait.
+            constexpr bool OWN0 = PM::ltab() && (PM::mg(0) ? PM::owner(PM::UL) == H : PM::owner(0) == H);
+            constexpr bool OWN1 = PM::ltab() && (PM::mg(1) ? PM::owner(PM::UL) == H : PM::owner(1) == H);
+            double t0m[OWN0 ? RP : 1], t0p[OWN0 ? RP : 1], t1m[OWN1 ? RP : 1], t1p[OWN1 ? RP : 1];
+            if constexpr (PM::ltab()) {
+                const double *T = ro + pair_tabL_off(A, RP);
+                const int n1 = A.ngrid[1];
+                load_row16<RP>(T + ((long)fi[0] * n1 + fi[1]) * RP, L);
+                if constexpr (OWN0) {
+                    load_row16<RP>(T + ((long)nbm[0] * n1 + fi[1]) * RP, t0m);
+                    load_row16<RP>(T + ((long)nbp[0] * n1 + fi[1]) * RP, t0p);
+                }
+                if constexpr (OWN1) {
+                    load_row16<RP>(T + ((long)fi[0] * n1 + nbm[1]) * RP, t1m);
+                    load_row16<RP>(T + ((long)fi[0] * n1 + nbp[1]) * RP, t1p);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            auto left_combine = [&]() __attribute__((always_inline)) { // what the edge block and left_step<1> leave in W
+                if constexpr (OWN0) {
+#pragma unroll
+                    for (int b = 0; b < RP; b++) {
+                        if constexpr (PM::mg(0)) W[0][b] = fma(rpp[0], t0p[b], rpm[0] * t0m[b]);
+                        else { W[0][b] = t0m[b]; W[1][b] = t0p[b]; }
+                    }
+                }
+                if constexpr (OWN1) {
+                    constexpr int before = PM::template left_before<H>(1);
+#pragma unroll
+                    for (int b = 0; b < RP; b++) {
+                        if constexpr (PM::mg(1)) {
+                            constexpr int su = PM::template lslot<H>(PM::UL);
+                            const double nw = fma(rpp[1], t1p[b], rpm[1] * t1m[b]);
+                            W[su][b] = (1 == PM::first_l()) ? nw : W[su][b] + nw;
+                        } else { W[before][b] = t1m[b]; W[before + 1][b] = t1p[b]; }
+                    }
+                }
+            };
+            if constexpr (PM::ltab() && K == PL.lfirst) left_combine(); // no staged core on this side
+            if constexpr (!PM::ltab()) {
+                constexpr bool GLB = DIRECT || !PL.ledge; // tables on, K = 1: the lone edge core straight from the arena
+                constexpr int str = GLB ? RP : fpl_lds_stride(RP);
                 const double *src = sK;
                 FPP_STAMP(1)
-                if constexpr (DIRECT) src = ro + A.core_off[0];
+                if constexpr (GLB) src = ro + A.core_off[0];
                 else {
                     pair_barrier();
                     stage_core_image<H>(sK, A.img_base + A.pair_img_off[0], A.ngrid[0] * str);
@@ -458,6 +550,7 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
                     stage_core_image<H>(sK, A.img_base + A.pair_img_off[m], A.ngrid[m] * str);
                     pair_barrier();
                 }
+                if constexpr (PM::ltab() && m == PL.lfirst) left_combine();
                 FPP_STAMP(7)
                 const double *G = src + fi[m] * str;
                 if constexpr (PAIR || ACC) { // the new pair first: it needs the prefix BEFORE this core
@@ -493,17 +586,57 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
                     for (int a = 0; a < RP; a++) W[su][a] = (m == PM::first_l()) ? nw[a] : W[su][a] + nw[a];
                 }
             };
-            [&]<int... Ms>(std::integer_sequence<int, Ms...>) { (left_step(std::integral_constant<int, Ms + 1>{}), ...); }
-            (std::make_integer_sequence<int, (K > 1 ? K - 1 : 0)>{});
+            [&]<int... Ms>(std::integer_sequence<int, Ms...>) { (left_step(std::integral_constant<int, Ms + PL.lfirst>{}), ...); }
+            (std::make_integer_sequence<int, (K > PL.lfirst ? K - PL.lfirst : 0)>{});
         }
 
         // ------------------------------------------------------------ fold the suffix side
         if constexpr (K < D - 1) {
-            {
-                constexpr int str = DIRECT ? RP : fpl_lds_stride(RP);
+            // rows of tabR: T(a, b) = G_{d-2}[a] G_{d-1}[b], as on the left
+            constexpr bool OWN0 = PM::rtab() && (PM::mg(D - 1) ? PM::owner(PM::UR) == H : PM::owner(D - 1) == H);
+            constexpr bool OWN1 = PM::rtab() && (PM::mg(D - 2) ? PM::owner(PM::UR) == H : PM::owner(D - 2) == H);
+            double t0m[OWN0 ? RP : 1], t0p[OWN0 ? RP : 1], t1m[OWN1 ? RP : 1], t1p[OWN1 ? RP : 1];
+            if constexpr (PM::rtab()) {
+                const double *T = ro + pair_tabR_off(A, RP);
+                const int n1 = A.ngrid[D - 1];
+                load_row16<RP>(T + ((long)fi[D - 2] * n1 + fi[D - 1]) * RP, R);
+                if constexpr (OWN0) {
+                    load_row16<RP>(T + ((long)fi[D - 2] * n1 + nbm[D - 1]) * RP, t0m);
+                    load_row16<RP>(T + ((long)fi[D - 2] * n1 + nbp[D - 1]) * RP, t0p);
+                }
+                if constexpr (OWN1) {
+                    load_row16<RP>(T + ((long)nbm[D - 2] * n1 + fi[D - 1]) * RP, t1m);
+                    load_row16<RP>(T + ((long)nbp[D - 2] * n1 + fi[D - 1]) * RP, t1p);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            auto right_combine = [&]() __attribute__((always_inline)) { // what the edge block and right_step<D-2> leave in W
+                if constexpr (OWN0) {
+#pragma unroll
+                    for (int a = 0; a < RP; a++) {
+                        if constexpr (PM::mg(D - 1)) W[NOL][a] = fma(rpp[D - 1], t0p[a], rpm[D - 1] * t0m[a]);
+                        else { W[NOL][a] = t0m[a]; W[NOL + 1][a] = t0p[a]; }
+                    }
+                }
+                if constexpr (OWN1) {
+                    constexpr int after = PM::template right_after<H>(D - 2);
+#pragma unroll
+                    for (int a = 0; a < RP; a++) {
+                        if constexpr (PM::mg(D - 2)) {
+                            constexpr int su = PM::template lslot<H>(PM::UR);
+                            const double nw = fma(rpp[D - 2], t1p[a], rpm[D - 2] * t1m[a]);
+                            W[su][a] = (D - 2 == PM::first_r()) ? nw : W[su][a] + nw;
+                        } else { W[NOL + after][a] = t1m[a]; W[NOL + after + 1][a] = t1p[a]; }
+                    }
+                }
+            };
+            if constexpr (PM::rtab() && K == PL.rfirst) right_combine(); // no staged core on this side
+            if constexpr (!PM::rtab()) {
+                constexpr bool GLB = DIRECT || !PL.redge; // tables on, K = d-2: the lone edge core straight from the arena
+                constexpr int str = GLB ? RP : fpl_lds_stride(RP);
                 const double *src = sK;
                 FPP_STAMP(1)
-                if constexpr (DIRECT) src = ro + A.core_off[D - 1];
+                if constexpr (GLB) src = ro + A.core_off[D - 1];
                 else {
                     pair_barrier();
                     stage_core_image<H>(sK, A.img_base + A.pair_img_off[D - 1], A.ngrid[D - 1] * str);
@@ -536,6 +669,7 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
                     stage_core_image<H>(sK, A.img_base + A.pair_img_off[m], A.ngrid[m] * str);
                     pair_barrier();
                 }
+                if constexpr (PM::rtab() && m == PL.rfirst) right_combine();
                 FPP_STAMP(7)
                 const double *G = src + fi[m] * str;
                 if constexpr (PAIR || ACC) {
@@ -571,8 +705,8 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
                     for (int a = 0; a < RP; a++) W[su][a] = (m == PM::first_r()) ? nw[a] : W[su][a] + nw[a];
                 }
             };
-            [&]<int... Ms>(std::integer_sequence<int, Ms...>) { (right_step(std::integral_constant<int, D - 2 - Ms>{}), ...); }
-            (std::make_integer_sequence<int, (D - 2 - K > 0 ? D - 2 - K : 0)>{});
+            [&]<int... Ms>(std::integer_sequence<int, Ms...>) { (right_step(std::integral_constant<int, PL.rfirst - Ms>{}), ...); }
+            (std::make_integer_sequence<int, (PL.rfirst - K > 0 ? PL.rfirst - K : 0)>{});
         }
 
         } // dbg & 1
