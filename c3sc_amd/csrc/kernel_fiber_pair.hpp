@@ -46,6 +46,13 @@
 #define FPP_EDGE_TABLES 1 // the two outer cores of each side enter through their product table (fpp_edge_tables); 0: a diagnostic build folds them
 #endif
 
+#ifndef FPP_NODE_SPLIT
+#define FPP_NODE_SPLIT 1 // one node per wavefront at full rank where few vectors remain (fpp_node_split); 0: a diagnostic build splits the rank everywhere
+#endif
+#ifndef FPP_NODE_SPLIT_VGPRS
+#define FPP_NODE_SPLIT_VGPRS 140 // what the full-length vectors of a lane may take: 7 vectors at rank 10, the half-length cost of 12 + merging
+#endif
+
 namespace c3sc {
 
 constexpr int FPP_THREADS = 128;
@@ -361,6 +368,30 @@ struct PairMap {
         return it < K ? left_before<H>(it) : left_before<H>(K) + right_after<H>(it);
     }
 };
+
+// Node split.  The rank is split over the two wavefronts because 2(d-1) full-length vectors do not fit a lane; where merging left
+// few enough of them that they do (car7d at rank 10: K = 0, 1, 4, 5, 6 carry 5 / 6 / 7 / 5 / 5 = 100-140 VGPRs, what the half-length
+// ones cost before merging), the split only makes work: every node's NV + 1 partial sums cross through LDS, each wavefront
+// fetches 3/4 of G_K[j] for both nodes of a pair, both re-read L and R for both nodes, and there are two barriers per pair.  There
+// wavefront h owns the nodes j = h (mod 2) outright: all vectors at full length, the full c, a and NV + 1 dots, one set of scalar
+// loads for both products, and only v[j] crosses (one barrier per pair).  Staged instantiations with something merged only;
+// everything else compiles as before.
+// The opt-out list: instantiations (dimension count, padded rank, K) that measured no faster, or whose node loop gained scratch
+// reloads, under the node split.
+//   d = 7, rank 10, K = 4 (car7d, 7 vectors): the node loop of wavefront 0 reloads five registers from scratch per node (60 B per
+//   lane against none in the rank split) -- taken off before it was timed
+//   padded ranks below 10: the rank split leaves those kernels at 130-170 VGPRs, the full-length vectors take 180-230 and with
+//   them the third wavefront per SIMD (car7d and lqg6d at rank 4), and lqg6d at rank 8 gains scratch at K = 2, 3 -- none of them
+//   has been timed, so they stay as they are
+__host__ __device__ constexpr bool fpp_node_split_optout(int d, int rp, int k) { return rp < 10 || (d == 7 && rp == 10 && k == 4); }
+template <class Model, int RP, int K>
+__host__ __device__ constexpr bool fpp_node_split()
+{
+    if constexpr (!FPP_NODE_SPLIT || fpp_direct<Model, RP>()) return false;
+    else
+        return PairPark<Model, K>::merged() != 0u && PairMap<Model, K>::nv() * RP * 2 <= FPP_NODE_SPLIT_VGPRS &&
+               !fpp_node_split_optout(Model::D, RP, K);
+}
 
 // the parked rates as node_backup's Pre
 template <class Model, int K>
@@ -712,8 +743,51 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
         } // dbg & 1
         FPP_STAMP(1) // folding
         // ------------------------------------------------------------ swap halves: Wh[g][i] = component H*RH + i of vector g
-        double Wh[NV][RH];
-        {
+        constexpr bool NS = fpp_node_split<Model, RP, K>();
+        double Wh[NS ? 1 : NV][RH];
+        double Wf[NS ? NV : 1][RP]; // node split: every vector at full length in both wavefronts
+        if constexpr (NS) {
+            // hand-over of whole vectors, one half of the components at a time: each wavefront writes the vectors it folded and
+            // reads the ones its partner folded, so NV * RH rows are in flight -- the half swap's buffer
+            double *X = sK; // [NV][RH][64]
+            auto put_get_own = [&](auto ic, auto pc) __attribute__((always_inline)) {
+                constexpr int it = decltype(ic)::value, P = decltype(pc)::value;
+                if constexpr (PM::valid(it) && PM::owner(it) == H) {
+                    constexpr int slot = PM::template lslot<H>(it);
+#pragma unroll
+                    for (int s = 0; s < PM::count(it); s++) {
+                        const int g = PM::gslot(it) + s;
+#pragma unroll
+                        for (int i = 0; i < RH; i++) {
+                            X[(g * RH + i) * 64 + lane] = W[slot + s][P * RH + i];
+                            Wf[g][P * RH + i] = W[slot + s][P * RH + i];
+                        }
+                    }
+                }
+            };
+            auto get_other = [&](auto ic, auto pc) __attribute__((always_inline)) {
+                constexpr int it = decltype(ic)::value, P = decltype(pc)::value;
+                if constexpr (PM::valid(it) && PM::owner(it) != H) {
+#pragma unroll
+                    for (int s = 0; s < PM::count(it); s++) {
+                        const int g = PM::gslot(it) + s;
+#pragma unroll
+                        for (int i = 0; i < RH; i++) Wf[g][P * RH + i] = X[(g * RH + i) * 64 + lane];
+                    }
+                }
+            };
+            auto half = [&](auto pc) __attribute__((always_inline)) {
+                pair_barrier();
+                [&]<int... Ms>(std::integer_sequence<int, Ms...>) { (put_get_own(std::integral_constant<int, Ms>{}, pc), ...); }
+                (std::make_integer_sequence<int, PM::NIT>{});
+                pair_barrier();
+                [&]<int... Ms>(std::integer_sequence<int, Ms...>) { (get_other(std::integral_constant<int, Ms>{}, pc), ...); }
+                (std::make_integer_sequence<int, PM::NIT>{});
+            };
+            half(std::integral_constant<int, 0>{});
+            half(std::integral_constant<int, 1>{});
+            pair_barrier();
+        } else {
             double *X = sK; // [NV][RH][64]
             pair_barrier();
             auto put_get_own = [&](auto ic) __attribute__((always_inline)) {
@@ -981,6 +1055,136 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
             if (absorbed) absorbed[(size_t)f * N + jn] = ab;
         };
 
+        if constexpr (NS) {
+        // ------------------------------------------------------------ node split: wavefront H owns the nodes j = H (mod 2)
+        // the whole stencil of node j: Vt[g] = dot g in PairMap order, Vt[NV] = v[j].  Element e = p RP + q of G_K[j] enters both
+        // products, c[q] += G[e] R[p] and a[p] += L[q] G[e] (the summed index ascending in each, as in the rank split), so the
+        // matrix is fetched once: four batches of scalar loads, each issued back to back and waited for once.
+        auto stencil = [&](int j, double (&Vt)[NP]) __attribute__((always_inline)) {
+            double v = 0.0;
+            if constexpr (K == 0) { // G_0[j] is a 1 x r row: a = row, no left vectors
+                double a[RP];
+#pragma unroll
+                for (int i = 0; i < RP; i++) a[i] = Gk[(size_t)j * RP + i];
+#pragma unroll
+                for (int i = 0; i < RP; i++) v = fma(a[i], sR[i * 64 + lane], v);
+#pragma unroll
+                for (int g = 0; g < NV; g++) Vt[g] = dot_reg<RP>(a, Wf[g]);
+            } else if constexpr (K == D - 1) { // G_{d-1}[j] is an r x 1 column: c = column, no right vectors
+                double c[RP];
+#pragma unroll
+                for (int i = 0; i < RP; i++) c[i] = Gk[(size_t)j * RP + i];
+#pragma unroll
+                for (int i = 0; i < RP; i++) v = fma(sL[i * 64 + lane], c[i], v);
+#pragma unroll
+                for (int g = 0; g < NV; g++) Vt[g] = dot_reg<RP>(Wf[g], c);
+            } else {
+                const double *G0 = Gk + (size_t)j * RP * RP;
+                constexpr int NE = RP * RP, NB = (NE + 3) / 4; // elements per batch (25 doubles = 50 SGPRs at rank 10)
+                double c[RP], a[RP], lv[RP];
+#pragma unroll
+                for (int i = 0; i < RP; i++) lv[i] = sL[i * 64 + lane];
+#pragma unroll
+                for (int i = 0; i < RP; i++) { c[i] = 0.0; a[i] = 0.0; }
+#pragma unroll
+                for (int b0 = 0; b0 < NE; b0 += NB) {
+                    double g[NB];
+#pragma unroll
+                    for (int e = 0; e < NB; e++) g[e] = (b0 + e < NE) ? G0[b0 + e] : 0.0;
+                    double rv[RP]; // R: only the rows this batch touches (three at rank 10), read under the same wait
+#pragma unroll
+                    for (int p = 0; p < RP; p++) rv[p] = (p >= b0 / RP && p * RP < b0 + NB) ? sR[p * 64 + lane] : 0.0;
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int e = 0; e < NB; e++) asm volatile("" : "+s"(g[e]));
+#pragma unroll
+                    for (int e = 0; e < NB; e++) {
+                        if (b0 + e < NE) {
+                            const int p = (b0 + e) / RP, q = (b0 + e) % RP;
+                            c[q] = fma(g[e], rv[p], c[q]);
+                            a[p] = fma(lv[q], g[e], a[p]);
+                        }
+                    }
+                    // the products are not ordered against the next batch's loads by themselves: left floating they all sink
+                    // behind the last batch and the 200 SGPRs of the matrix are parked in VGPR lanes meanwhile
+#pragma unroll
+                    for (int i = 0; i < RP; i++) asm volatile("" : "+v"(c[i]), "+v"(a[i]));
+                }
+#pragma unroll
+                for (int i = 0; i < RP; i++) v = fma(sL[i * 64 + lane], c[i], v);
+#pragma unroll
+                for (int g = 0; g < NVL; g++) Vt[g] = dot_reg<RP>(Wf[g], c);
+#pragma unroll
+                for (int g = NVL; g < NV; g++) Vt[g] = dot_reg<RP>(a, Wf[g]);
+            }
+            Vt[NV] = v;
+        };
+        // Only v[j] crosses: wavefront h writes row 2h + (t & 1) of the exchange block before the barrier of iteration t and its
+        // partner reads it behind that barrier; the row is written again two iterations (two barriers) later.
+        double *VX = B0;
+        double vwrap = 0.0; // value of node N-2 (left neighbour of node 0 under a periodic boundary): both wavefronts compute it
+        if (bck == C3SC_PERIODIC) {
+            double Vw[NP];
+            stencil(N - 2, Vw);
+            vwrap = Vw[NV];
+        }
+        double vone = 0.0;             // v[1]
+        double v_m2 = 0.0, v_m1 = 0.0; // v[2t-2], v[2t-1]
+        double Vd[NP];                 // wave 1: stencil of node 2t-1 waiting for v[2t]
+#pragma unroll
+        for (int g = 0; g < NP; g++) Vd[g] = 0.0;
+        const int T = N / 2 + 1;
+        for (int t = 0; t < T; t++) {
+            const int j0 = 2 * t, j1 = 2 * t + 1;
+            const bool has0 = j0 < N, has1 = j1 < N;
+            double *vx = VX + (t & 1) * 64;
+            double v0 = 0.0, v1 = 0.0; // v[j0], v[j1]
+            double Pn[NP];
+#pragma unroll
+            for (int g = 0; g < NP; g++) Pn[g] = 0.0;
+            if constexpr (H == 0) {
+                if (has0) {
+                    stencil(j0, Pn);
+                    v0 = Pn[NV];
+                    vx[lane] = v0;
+                }
+                FPP_STAMP(3) // stencil
+                pair_barrier();
+                FPP_STAMP(4) // the barrier
+                if (has1) v1 = vx[2 * 64 + lane];
+                if (has0) {
+                    double vlo, vhi;
+                    dimk_values(j0, N, bck, v_m1, v0, v1, vwrap, (j0 == 0 ? v1 : vone), vlo, vhi);
+                    finalize(j0, Pn, vlo, vhi);
+                }
+            } else {
+                if (has1) {
+                    stencil(j1, Pn);
+                    v1 = Pn[NV];
+                    vx[2 * 64 + lane] = v1;
+                }
+                FPP_STAMP(3)
+                pair_barrier();
+                FPP_STAMP(4)
+                if (has0) v0 = vx[lane];
+                if (t >= 1) { // node 2t-1
+                    const int jn = j0 - 1;
+                    double vlo, vhi;
+                    dimk_values(jn, N, bck, v_m2, Vd[NV], v0, vwrap, (jn == 1 ? Vd[NV] : vone), vlo, vhi);
+                    finalize(jn, Vd, vlo, vhi);
+                }
+                if (has1) {
+#pragma unroll
+                    for (int g = 0; g < NP; g++) Vd[g] = Pn[g];
+                }
+            }
+            if (t == 0) vone = v1;
+            v_m2 = v0;
+            v_m1 = v1;
+            FPP_STAMP(5) // finalize
+        }
+        pair_barrier(); // the parked rows and L, R are read until the last node is finalised; the next tile overwrites them
+        } else {
         // value of node N-2 (left neighbour of node 0 under a periodic boundary)
         double vwrap = 0.0;
         if (bck == C3SC_PERIODIC) {
@@ -1086,6 +1290,7 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
             pair_barrier();
             FPP_STAMP(6) // barrier 2
         }
+        } // rank split
     }
     if (C3SC_STAMPS_ON && (A.dbg & 128) && lane == 0) {
         const size_t w = ((size_t)blockIdx.x * 2 + H) * 12;

@@ -5,16 +5,30 @@
 
 namespace c3sc {
 
+// LDS doubles a tile needs apart from its staged cores: max(vector exchange after the fold, node-loop rows).
+//   rank split: half-swap buffer [NV][RH] rows; L, R rows + three partial-sum blocks + the parked rows (<= NP)
+//   node split: the hand-over moves one half of the components at a time through the same [NV][RH] rows; L, R rows + four rows of
+//               node values + the parked rows, which stay where the rank split has them
+template <class Model, int RP, int K>
+__host__ __device__ constexpr size_t fpp_tile_doubles(bool node_split)
+{
+    constexpr int NV = PairMap<Model, K>::nv(), NP = NV + 1, RH = RP / 2; // the kernel's own count of folded vectors
+    const size_t swap = (size_t)NV * RH * 64;
+    const size_t parked = (size_t)(2 * RP + (NP + 1) * 2 + NP) * 64; // where the parked rows start (PX in the kernel)
+    const size_t rows = node_split ? parked + (size_t)PairPark<Model, K>::rows() * 64 : parked + (size_t)NP * 64;
+    return swap > rows ? swap : rows;
+}
+
 template <class Model, int RP, int K, bool FORCED>
 hipError_t launch_fpp_impl(const KArgs &A, const LaunchIO &io)
 {
     constexpr int D = Model::D;
-    constexpr int NV = PairMap<Model, K>::nv(), NP = NV + 1, RH = RP / 2; // the kernel's own count of folded vectors
     if (A.ncand > 64) return hipErrorNotSupported; // one lane per candidate fills the table: the per-wave kernel walks longer lists
-    // LDS: max(largest staged fixed core, half-swap buffer, per-node exchange buffers)
-    size_t doubles = (size_t)NV * RH * 64;
-    const size_t exch = (size_t)(2 * RP + (NP + 1) * 2 + 2 * NP) * 64; // L, R rows + exchange rows
-    if (exch > doubles) doubles = exch;
+    // LDS: max(largest staged fixed core, vector exchange, node-loop rows)
+    constexpr bool NS = fpp_node_split<Model, RP, K>();
+    static_assert(fpp_tile_doubles<Model, RP, K>(NS) <= fpp_tile_doubles<Model, RP, K>(false), "the node split must not need more LDS than the rank split");
+    static_assert(!NS || 4 * fpp_tile_doubles<Model, RP, K>(NS) * sizeof(double) <= 160 * 1024, "four node-split workgroups per CU must fit the LDS");
+    size_t doubles = fpp_tile_doubles<Model, RP, K>(false); // the rank-split figure in both forms: the footprint does not move
     for (int m = 0; m < D; m++) {
         if (m == K || fpp_direct<Model, RP>()) continue; // no staged core when the fold reads the cores directly
         const int elems = (m == 0 || m == D - 1) ? RP : RP * RP;
