@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/c3sc_hip.h"
+#include "fiber_partition.hpp"
 #include "kernel_common.hpp"
 #include "kernel_rollout.hpp"
 #include "kernel_rollout_ode.hpp"
@@ -445,6 +446,8 @@ void c3sc_hip_ctx_destroy(c3sc_hip_ctx *c)
     if (c->d_dbg) (void)hipFree(c->d_dbg);
     if (c->scratch) (void)hipFree(c->scratch);
     if (c->sim_state) (void)hipFree(c->sim_state);
+    for (void *p : c->part)
+        if (p) (void)hipFree(p);
     if (c->pinned) (void)hipHostFree(c->pinned);
     c3sc_hip_cross_free(c);
     for (int i = 0; i < c3sc_hip_ctx::NSIDE; i++) {
@@ -943,8 +946,56 @@ static int launch_one(c3sc_hip_ctx *c, const KernelEntry *e, const KArgs &A, con
     return C3SC_OK;
 }
 
+// Smallest batch the fiber-pair launches partition (fiber_partition.hpp).  C3SC_FIBER_PARTITION, read at every launch, replaces
+// it: 0 switches the pass off, n > 0 runs it from n fibers on.  The three partition launches cost about 10 us in front of every
+// pair launch whatever the batch, what the absorbed tiles save grows with it: car7d loses 5 % at 2^17 fibers per launch
+// (1.469 -> 1.543 ms per step), gains 3.3 % at 2^20 and breaks even near 2^18 by those two figures.
+constexpr long FIBER_PARTITION_MIN = 524288;
+static long fiber_partition_min()
+{
+    const char *e = getenv("C3SC_FIBER_PARTITION");
+    if (!e || !*e) return FIBER_PARTITION_MIN;
+    const long v = atol(e);
+    return v > 0 ? v : -1;
+}
+
+// Live fibers first (fiber_partition.hpp) for a fiber-pair launch of a batch that can hold absorbed fibers: some fixed dimension
+// is absorbing.  Enqueued on the launch's stream into the scratch block `slot`; io.perm stays null where the pass does not run.
+// `launched` reports the pass's kernel launches; the pair launcher's own early refusal (launch_fpp_impl: more than 64 candidates) is
+// anticipated here, so that nothing is enqueued in front of a launcher that declines.
+static int partition_fibers(c3sc_hip_ctx *c, const KernelEntry *e, const KArgs &A, LaunchIO &io, int slot, int &launched)
+{
+    io.perm = nullptr;
+    io.nlive = nullptr;
+    launched = 0;
+    if (e->variant != C3SC_VARIANT_FIBER_PAIR || e->rtc || A.ncand > 64) return C3SC_OK;
+    bool faces = false;
+    for (int m = 0; m < A.d; m++) faces = faces || (m != A.k && A.bctype[m] == C3SC_ABSORB);
+    const long fmin = fiber_partition_min();
+    if (!faces || fmin < 0 || A.F < fmin || A.F > 0x40000000L) return C3SC_OK; // perm and nlive are int32
+    const size_t need = fpart_bytes(A.F);
+    if (need > c->part_bytes[slot]) {
+        if (c->part[slot]) HIPCHK(c, hipFree(c->part[slot])); // synchronises the device: the launches that read the block are done
+        c->part[slot] = nullptr;
+        c->part_bytes[slot] = 0;
+        HIPCHK(c, hipMalloc(&c->part[slot], need));
+        c->part_bytes[slot] = need;
+    }
+    const PartScratch ps = fpart_carve(c->part[slot], A.F);
+    PartArgs P;
+    P.d = A.d;
+    P.k = A.k;
+    P.F = A.F;
+    for (int m = 0; m < MAXD; m++) { P.ngrid[m] = A.ngrid[m]; P.bctype[m] = A.bctype[m]; }
+    HIPCHK(c, fpart_launch(P, io.idx, ps, io.stream));
+    launched = 3;
+    io.perm = ps.perm;
+    io.nlive = ps.nlive;
+    return C3SC_OK;
+}
+
 static int launch_bellman(c3sc_hip_ctx *c, int k, size_t F, const int32_t *d_idx, const int32_t *d_policy, double *d_out,
-                          int32_t *d_uidx, int32_t *d_absorbed, void *stream)
+                          int32_t *d_uidx, int32_t *d_absorbed, void *stream, int part_slot = 0)
 {
     KArgs A;
     int rc = fill_args(c, k, F, A, true);
@@ -973,6 +1024,7 @@ static int launch_bellman(c3sc_hip_ctx *c, int k, size_t F, const int32_t *d_idx
     // rank 16, the one-buffer quad kernel behind it N <= 75, the per-wave kernel behind that only stages the varying core).
     std::vector<const KernelEntry *> declined;
     hipError_t he = hipSuccess;
+    int part_launches = 0; // of the entry that served the call
     for (;;) {
         const KernelEntry *e = find_kernel(c->model, c->d, c->rp, A.N, variant, k, F, &declined);
         if (!e || e->rp != c->rp) {
@@ -983,13 +1035,15 @@ static int launch_bellman(c3sc_hip_ctx *c, int k, size_t F, const int32_t *d_idx
         }
         c->last_kernel = e->name;
         arm_memo(c, e, A);
+        rc = partition_fibers(c, e, A, io, part_slot, part_launches);
+        if (rc != C3SC_OK) return rc;
         he = launch_entry(*e, A, io);
         if (he != hipErrorOutOfMemory && he != hipErrorNotSupported) break;
         c->memo.applied = false;
         if (getenv("C3SC_VERBOSE")) fprintf(stderr, "c3sc: %s declined (%s), trying the next instantiation\n", e->name, hipGetErrorName(he));
         declined.push_back(e);
     }
-    g_launches++;
+    g_launches += 1 + part_launches;
     c->status_cache_valid = false;
     HIPCHK(c, he);
     return C3SC_OK;
@@ -1038,7 +1092,7 @@ static int launch_bellman_all(c3sc_hip_ctx *c, int nk, const int *ks, const size
     for (int s = 0; s < nk && rc == C3SC_OK; s++) {
         const int lane = overlap ? s % (c3sc_hip_ctx::NSIDE + 1) : 0; // 0: the caller's stream
         rc = launch_bellman(c, ks[s], F[s], d_idx[s], d_policy ? d_policy[s] : nullptr, d_out[s], d_uidx ? d_uidx[s] : nullptr,
-                            d_absorbed ? d_absorbed[s] : nullptr, lane == 0 ? stream : (void *)c->side[lane - 1]);
+                            d_absorbed ? d_absorbed[s] : nullptr, lane == 0 ? stream : (void *)c->side[lane - 1], lane);
     }
     if (overlap) // join even after a failed launch: what was enqueued on the side streams must not outlive the call's ordering
         for (int i = 0; i < c3sc_hip_ctx::NSIDE; i++) {

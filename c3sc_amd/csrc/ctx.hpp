@@ -74,6 +74,12 @@ struct c3sc_hip_ctx {
     static constexpr int NSIDE = 2;
     hipStream_t side[NSIDE] = {nullptr, nullptr};
     hipEvent_t fork_ev = nullptr, join_ev[NSIDE] = {nullptr, nullptr};
+    // fiber-pair launches: scratch of the live-first partition of a batch (fiber_partition.hpp), grow-only, one block per stream
+    // of c3sc_hip_bellman_fibers_all (0: the caller's stream, which also serves the single-launch entry points).  A block is read
+    // by the pair kernel it was filled for, so the launches of one context that partition are ordered by the caller: one stream
+    // at a time (c3sc_hip.h, c3sc_hip_bellman_fibers).  Growing a block frees the old one, which synchronises the device.
+    void *part[NSIDE + 1] = {nullptr, nullptr, nullptr};
+    size_t part_bytes[NSIDE + 1] = {0, 0, 0};
     // scratch for the *_host convenience calls
     void *scratch = nullptr;
     size_t scratch_bytes = 0;

@@ -413,10 +413,11 @@ struct PairPre {
         tlast = now__;                                                    \
     }
 
-template <class Model, int RP, int K, int H, bool FORCED>
+template <class Model, int RP, int K, int H, bool FORCED, bool PART>
 __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArgs &A, const double *__restrict__ ro,
                                                                      const int32_t *__restrict__ idx, double *__restrict__ outv,
                                                                      int32_t *__restrict__ uidx, int32_t *__restrict__ absorbed,
+                                                                     const int32_t *__restrict__ perm, const int32_t *__restrict__ nlive_p,
                                                                      double *sK, unsigned &st)
 {
     constexpr int D = Model::D;
@@ -437,6 +438,14 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
     const int lane = threadIdx.x & 63;
     const int N = A.N;
     const long ntiles = (A.F + 63) / 64;
+    // Absorbed tiles.  With a permutation of the batch (fiber_partition.hpp: live fibers first) lane l of tile t takes fiber
+    // perm[64 t + l], and every tile from ceil(nlive / 64) on holds only fibers with a fixed index on an absorbing face: each of
+    // their nodes is absorbed (finalize: ab = 1) and its value is Model::boundcost, except the two end nodes of a reflecting or
+    // periodic K under the literal end-point rule (vary_neighbors, keep_ends = 0).  Wave-uniform: one scalar load, the same
+    // value in both wavefronts, so both pass the same barriers.  PART = false (k_fiber_pair: launches without a partition) compiles
+    // none of it.
+    int first_dead = 0x7fffffff;
+    if constexpr (PART) first_dead = __builtin_amdgcn_readfirstlane((int)(((long)*nlive_p + 63) >> 6));
     unsigned long long seg[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, tlast = clock64();
     // candidate and node tables: computed lane-distributed once, then kept in LDS behind the exchange rows and read
     // with wave-uniform addresses -- 16 VGPRs less in the node loop than keeping them in lanes, and no dependence on
@@ -458,7 +467,29 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
         FPP_STAMP(7)
         const long f_raw = tile * 64 + lane;
         const bool live = f_raw < A.F;
-        const long f = live ? f_raw : A.F - 1;
+        const long f_pos = live ? f_raw : A.F - 1;
+        long f = f_pos;
+        if constexpr (PART) f = (long)perm[f_pos];
+        const bool dead_tile = PART && tile >= (long)first_dead;
+
+        if constexpr (PART) if (dead_tile) {
+            // the nodes whose value is boundcost whatever the stencil holds: all of them where K absorbs or the ends are
+            // consistent -- the tile is done, nothing is staged or folded --, else the interior ones; the wavefronts split them
+            // by parity as in the node loop.  x as finalize forms it (PairPark: a coordinate no node reads is not kept).  The
+            // block stands in front of the tile set-up and reads its own coordinates: nothing of a live tile is live across it.
+            const bool whole = A.bctype[K] == C3SC_ABSORB || A.cends != 0;
+            const int jb = whole ? 0 : 1, je = whole ? N : N - 1;
+            double xb[D];
+#pragma unroll
+            for (int m = 0; m < D; m++) xb[m] = (m != K && PK::need_x(m)) ? ro[A.xg_off[m] + idx[f * D + m]] : 0.0;
+            for (int j = jb + ((jb ^ H) & 1); j < je; j += 2) {
+                xb[K] = nr.x_at(j);
+                outv[(size_t)f * N + j] = Model::boundcost(A.prm, xb);
+                if (uidx) uidx[(size_t)f * N + j] = -1;
+                if (absorbed) absorbed[(size_t)f * N + j] = 1;
+            }
+            if (whole) continue;
+        }
 
         int fi[D], nbm[D], nbp[D];
         bool fiber_abs = false;
@@ -1120,7 +1151,9 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
             Vt[NV] = v;
         };
         // Only v[j] crosses: wavefront h writes row 2h + (t & 1) of the exchange block before the barrier of iteration t and its
-        // partner reads it behind that barrier; the row is written again two iterations (two barriers) later.
+        // partner reads it behind that barrier; the row is written again two EXECUTED trips (two barriers) later -- the trips an
+        // absorbed tile leaves out (end of the loop) are cut so that the parity of t still alternates from one executed trip to
+        // the next.
         double *VX = B0;
         double vwrap = 0.0; // value of node N-2 (left neighbour of node 0 under a periodic boundary): both wavefronts compute it
         if (bck == C3SC_PERIODIC) {
@@ -1182,6 +1215,11 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
             v_m2 = v0;
             v_m1 = v1;
             FPP_STAMP(5) // finalize
+            // an absorbed tile under literal ends: the ends need the node pairs (0, 1) and (N-2, N-1) only, i.e. the trips 0,
+            // T-2 and T-1; the interior nodes those trips finalise are absorbed and get boundcost once more.  The trip behind
+            // trip 0 must be an odd one (it writes the other exchange rows: trip 0's are still being read, one barrier back):
+            // T-2 where T is odd, T-3 where it is even.
+            if (PART && dead_tile && t == 0 && T > 4) t = ((T - 3) | 1) - 1;
         }
         pair_barrier(); // the parked rows and L, R are read until the last node is finalised; the next tile overwrites them
         } else {
@@ -1289,6 +1327,9 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
             FPP_STAMP(5) // LDS reads + finalize
             pair_barrier();
             FPP_STAMP(6) // barrier 2
+            // an absorbed tile under literal ends: the trips 0, T-2, T-1 as in the node split; with two barriers per trip and
+            // no row toggled by t, any trip may follow trip 0
+            if (PART && dead_tile && t == 0 && T > 3) t = T - 3;
         }
         } // rank split
     }
@@ -1318,8 +1359,24 @@ __global__ void __launch_bounds__(FPP_THREADS, (fpp_waves_per_simd<Model, RP>())
     extern __shared__ double sKp[];
     unsigned st = 0;
     const int h = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    if (h == 0) fiber_pair_body<Model, RP, K, 0, FORCED>(A, ro, idx, outv, uidx, absorbed, sKp, st);
-    else fiber_pair_body<Model, RP, K, 1, FORCED>(A, ro, idx, outv, uidx, absorbed, sKp, st);
+    if (h == 0) fiber_pair_body<Model, RP, K, 0, FORCED, false>(A, ro, idx, outv, uidx, absorbed, nullptr, nullptr, sKp, st);
+    else fiber_pair_body<Model, RP, K, 1, FORCED, false>(A, ro, idx, outv, uidx, absorbed, nullptr, nullptr, sKp, st);
+    if (st) atomicOr(A.status, st);
+}
+
+// the same kernel behind a partition of its batch (fiber_partition.hpp): tiles read their fibers through perm, tiles of absorbed
+// fibers leave the work out.  A kernel of its own, so that every launch without a partition runs the code it ran before.
+template <class Model, int RP, int K, bool FORCED>
+__global__ void __launch_bounds__(FPP_THREADS, (fpp_waves_per_simd<Model, RP>()))
+    k_fiber_pair_part(const KArgs A, const double *__restrict__ ro, const int32_t *__restrict__ idx, double *__restrict__ outv,
+                      int32_t *__restrict__ uidx, int32_t *__restrict__ absorbed, const int32_t *__restrict__ perm,
+                      const int32_t *__restrict__ nlive_p)
+{
+    extern __shared__ double sKp[];
+    unsigned st = 0;
+    const int h = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (h == 0) fiber_pair_body<Model, RP, K, 0, FORCED, true>(A, ro, idx, outv, uidx, absorbed, perm, nlive_p, sKp, st);
+    else fiber_pair_body<Model, RP, K, 1, FORCED, true>(A, ro, idx, outv, uidx, absorbed, perm, nlive_p, sKp, st);
     if (st) atomicOr(A.status, st);
 }
 

@@ -19,7 +19,7 @@ __host__ __device__ constexpr size_t fpp_tile_doubles(bool node_split)
     return swap > rows ? swap : rows;
 }
 
-template <class Model, int RP, int K, bool FORCED>
+template <class Model, int RP, int K, bool FORCED, bool PART>
 hipError_t launch_fpp_impl(const KArgs &A, const LaunchIO &io)
 {
     constexpr int D = Model::D;
@@ -40,10 +40,10 @@ hipError_t launch_fpp_impl(const KArgs &A, const LaunchIO &io)
     B.tbl_off = (int)doubles;
     doubles += (size_t)CandLds<Model>::doubles(A.ncand) + (size_t)NodeLds<Model, K>::doubles(A.N);
     const size_t shmem = doubles * sizeof(double);
-    auto kern = k_fiber_pair<Model, RP, K, FORCED>;
+    const void *kern = PART ? (const void *)k_fiber_pair_part<Model, RP, K, FORCED> : (const void *)k_fiber_pair<Model, RP, K, FORCED>;
     static LaunchCache cache;
     int blocks_per_cu = 1, num_cu = 256;
-    hipError_t e = cache.prepare((const void *)kern, FPP_THREADS, shmem, blocks_per_cu, num_cu);
+    hipError_t e = cache.prepare(kern, FPP_THREADS, shmem, blocks_per_cu, num_cu);
     if (e != hipSuccess) return e;
     const long ntiles = (A.F + 63) / 64;
     const long cap = (long)num_cu * blocks_per_cu;
@@ -56,14 +56,20 @@ hipError_t launch_fpp_impl(const KArgs &A, const LaunchIO &io)
     int grid = (int)(ntiles < cap ? ntiles : cap);
     if (ntiles >= 8 * cap && ntiles < 0x7fffffffL) grid = (int)ntiles;
     if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(FPP_THREADS), shmem, io.stream, B, io.ro, io.idx, io.out, io.uidx, io.absorbed);
+    if constexpr (PART)
+        hipLaunchKernelGGL((k_fiber_pair_part<Model, RP, K, FORCED>), dim3(grid), dim3(FPP_THREADS), shmem, io.stream, B, io.ro, io.idx, io.out,
+                           io.uidx, io.absorbed, io.perm, io.nlive);
+    else
+        hipLaunchKernelGGL((k_fiber_pair<Model, RP, K, FORCED>), dim3(grid), dim3(FPP_THREADS), shmem, io.stream, B, io.ro, io.idx, io.out, io.uidx,
+                           io.absorbed);
     return hipGetLastError();
 }
 
 template <class Model, int RP, int K>
 hipError_t launch_fpp(const KArgs &A, const LaunchIO &io)
 {
-    return A.forced ? launch_fpp_impl<Model, RP, K, true>(A, io) : launch_fpp_impl<Model, RP, K, false>(A, io);
+    if (io.perm) return A.forced ? launch_fpp_impl<Model, RP, K, true, true>(A, io) : launch_fpp_impl<Model, RP, K, false, true>(A, io);
+    return A.forced ? launch_fpp_impl<Model, RP, K, true, false>(A, io) : launch_fpp_impl<Model, RP, K, false, false>(A, io);
 }
 
 #define C3SC_REG_FPP1(MODEL_ID, RP, K, ...)                                                                   \

@@ -24,6 +24,10 @@ struct LaunchIO {
     const double *tcost; // TableModel only: [F][N][2] (boundcost, obscost)
     hipStream_t stream;
     const void *sim = nullptr; // rollout / off-grid stencil kernels only: their SimK argument block (kernel_rollout.hpp)
+    // fiber-pair kernels only (fiber_partition.hpp): the batch order live fibers first, and the device-side count of live ones;
+    // null = batch order
+    const int32_t *perm = nullptr;
+    const int32_t *nlive = nullptr;
 };
 #endif
 

@@ -132,7 +132,10 @@ int c3sc_hip_set_variant(c3sc_hip_ctx *ctx, int variant);
  *   d_out      double [F*N_k]     device, out[f*N_k + j] like the callback's out[]
  *   d_uidx     int32 [F*N_k] or NULL: winning candidate index, -1 for absorbed nodes
  *   d_absorbed int32 [F*N_k] or NULL: absorbed[] of process_fibers_neighbor (0 / 1 / -1)
- * Asynchronous on `stream`. */
+ * Asynchronous on `stream`.  Large fiber-pair batches with an absorbing fixed dimension are partitioned on the device first
+ * (live fibers first; C3SC_FIBER_PARTITION=0 in the environment switches that off, n > 0 sets the smallest such batch) into
+ * scratch the context owns: the Bellman launches of ONE context must be ordered with respect to each other (one stream, or
+ * events between streams); c3sc_hip_bellman_fibers_all orders its own. */
 int c3sc_hip_bellman_fibers(c3sc_hip_ctx *ctx, int k, size_t F, const int32_t *d_idx, double *d_out,
                             int32_t *d_uidx, int32_t *d_absorbed, void *stream);
 /* The same for SEVERAL varying dimensions of one batch -- a sweep over independent fiber batches (SURVEY.md 8d's roofline batch, a
