@@ -1756,13 +1756,21 @@ int c3sc_hip_cross_confirm(c3sc_hip_ctx *c, int *confirmed, void *stream)
     }
     HIPCHK(c, hipGetLastError());
     // the flag and, in the same wait, everything a successful confirmation is followed by (c3sc_hip_cross_fetch then copies from
-    // the pinned block); after a mismatch the block is stale and the counters it brought wait in `pending`
+    // the pinned block); after a mismatch the block is stale and the counters it brought wait in `pending` -- the nodes stored
+    // ([0]: a speculative attempt's fibers) and the memo's state ([3]), but not the deficiency flag and the swaps of the confirm-mode
+    // steps: they factored matrices of index sets that do not stand, and the sequential iteration that follows counts its own
+    // (the flag arrived as 2 and every swap twice in the next fetch)
     int *hflag = (int *)(x->stage + x->sets_bytes + x->cores_bytes + 4 * sizeof(unsigned long long) + sizeof(unsigned) + 4);
     *hflag = 1;
+    const unsigned long long flag_before = x->pending[1], swaps_before = x->pending[2];
     const int rc = stage_download(c, mismatch, hflag, sizeof(int), st);
     if (rc != C3SC_OK) return rc;
     *confirmed = *hflag == 0;
-    if (!*confirmed) x->stage_fresh = false;
+    if (!*confirmed) {
+        x->stage_fresh = false;
+        x->pending[1] = flag_before;
+        x->pending[2] = swaps_before;
+    }
     return C3SC_OK;
 }
 
@@ -1818,6 +1826,7 @@ static int stage_download(c3sc_hip_ctx *c, const void *extra, void *extra_host, 
     HIPCHK(c, hipStreamSynchronize(st));
     const unsigned long long *cnt = (const unsigned long long *)(x->stage + nb);
     for (int i = 0; i < 4; i++) x->pending[i] += cnt[i];
+    x->pending[1] = x->pending[1] ? 1 : 0; // a flag, not a count
     c->status_cache = *hstat;
     c->status_cache_valid = true; // until the next launch through this context
     x->stage_fresh = true;
