@@ -131,6 +131,8 @@ def load_library():
         L.c3sc_hip_cross_iteration.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.c3sc_hip_cross_confirm.argtypes = [C.c_void_p, c_int_p, C.c_void_p]
         L.c3sc_hip_cross_options.argtypes = [C.c_void_p, C.c_int, C.c_double]
+        L.c3sc_hip_cross_iteration_pi.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]
+        L.c3sc_hip_cross_grow_memo.argtypes = [C.c_void_p]
         L.c3sc_hip_cross_fetch.argtypes = [C.c_void_p, C.POINTER(c_double_p), C.POINTER(c_i32_p), C.POINTER(c_i32_p),
                                            C.POINTER(C.c_ulonglong), C.c_void_p]
         L.c3sc_hip_set_interp.argtypes = [C.c_void_p, C.c_int]

@@ -351,6 +351,11 @@ int c3sc_hip_normals(uint64_t seed, uint64_t traj0, size_t ntraj, uint64_t step0
  * one-workgroup pivoted factorisation + maxvol that writes the interpolatory core and the next index set.
  *   ranks[d+1]; I[k]: ranks[k] tuples over dims 0..k-1 (int32, row-major); J[k]: ranks[k+1] tuples over dims k+1..d-1
  *   new_sweep != 0 starts a new memo epoch (workspace_increment_vi_iter, bellman.c:2199)
+ *   Every set-up -- and ONLY a set-up -- starts a new generation of cached step values: a core step that finds the fiber list it
+ *   already holds, with values of the current generation, keeps them and launches nothing.  c3sc_hip_upload_value[_device] does
+ *   NOT start one.  So whenever the value function changes between two iterations (ctx's own, or policy_ctx's for
+ *   c3sc_hip_cross_iteration_pi, or the policy tag), call c3sc_hip_cross_setup in between -- new_sweep = 0 keeps the memo epoch and
+ *   its entries -- or a step whose list did not change returns the values (the policy) of the OLD function.
  *   box: 0 = candidate list (set_controls), 1 = control box (set_control_box)
  *   fetch waits for the stream and returns the cores of the last half sweep in the layout G_k[a + r_k (j + N_k b)], both
  *   families of index sets, and info[4] = {nodes stored in the memo since the last fetch (the reference's nnode_evals),

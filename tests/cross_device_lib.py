@@ -2,6 +2,7 @@
 the CPU simulation of their cases in test_cross_reference.py): the dispatch class of every step of an iteration, seeded index
 tuples, and one BellmanEngine context driven through the c3sc_hip_cross_* entry points."""
 import ctypes as C
+import time
 
 import numpy as np
 
@@ -61,14 +62,17 @@ def _ptrs(arrs, ctype, ptype):
 
 
 class DeviceCross:
-    """One BellmanEngine context driven through c3sc_hip_cross_* (null stream)."""
+    """One BellmanEngine context driven through c3sc_hip_cross_* (null stream).  consistent_ends=False keeps the reference's
+    literal end-point rule; variant forces a kernel family (C3SC_VARIANT_*), set before the value is uploaded."""
 
-    def __init__(self, w, cores):
+    def __init__(self, w, cores, consistent_ends=True, variant=None):
         from c3sc_amd.engine import BellmanEngine
 
         self.eng = BellmanEngine(0)
+        if variant is not None:
+            self.eng.set_variant(variant)
         self.eng.configure(w, cores)
-        self.eng.set_consistent_ends(True)
+        self.eng.set_consistent_ends(consistent_ends)
         self.L, self.h, self.w = self.eng.L, self.eng.h, w
 
     def err(self):
@@ -78,12 +82,40 @@ class DeviceCross:
     def setup(self, ranks, I, J, new_sweep=1):
         self.ranks = [int(r) for r in ranks]
         rk = np.ascontiguousarray(ranks, dtype=np.uintp)
-        return self.L.c3sc_hip_cross_setup(self.h, rk.ctypes.data_as(C.POINTER(C.c_size_t)), _ptrs(I, np.int32, c_i32_p),
-                                           _ptrs(J, np.int32, c_i32_p), new_sweep)
+        self._setup_args = (rk.ctypes.data_as(C.POINTER(C.c_size_t)), _ptrs(I, np.int32, c_i32_p), _ptrs(J, np.int32, c_i32_p), new_sweep)
+        self._setup_keep = rk
+        return self.L.c3sc_hip_cross_setup(self.h, *self._setup_args)
+
+    def setup_repeat(self, n, new_sweep=1):
+        """the last set-up again, n times, without an iteration in between (n new memo epochs); returns the seconds it took"""
+        args = self._setup_args[:-1] + (new_sweep,)
+        t0 = time.perf_counter()
+        for i in range(n):
+            rc = self.L.c3sc_hip_cross_setup(self.h, *args)
+            assert rc == 0, f"cross_setup {i} of {n}: code {rc}: {self.err()}"
+        return time.perf_counter() - t0
+
+    def upload_value(self, cores):
+        """Another value function for the context.  It does NOT start a new generation of cached step values: call setup (with
+        new_sweep=0 to stay in the memo epoch) before the next iteration, or a step that finds its list unchanged keeps the values
+        it holds (c3sc_hip.h above c3sc_hip_cross_setup)."""
+        self.eng.upload_value(self.w.ranks, cores)
+
+    def grow_memo(self):
+        rc = self.L.c3sc_hip_cross_grow_memo(self.h)
+        assert rc == 0, f"cross_grow_memo: code {rc}: {self.err()}"
+
+    def last_kernel(self):
+        return self.eng.last_kernel()
 
     def iteration(self):
         rc = self.L.c3sc_hip_cross_iteration(self.h, 0, None)
         assert rc == 0, f"cross_iteration: code {rc}: {self.err()}"
+
+    def iteration_pi(self, policy_engine, tag):
+        """c3sc_hip_cross_iteration_pi with the greedy policy of policy_engine's value function (a DeviceCross or a BellmanEngine);
+        returns the code: the caller asserts it."""
+        return self.L.c3sc_hip_cross_iteration_pi(self.h, policy_engine.h, C.c_longlong(tag), None)
 
     def confirm(self):
         ok = C.c_int(-1)

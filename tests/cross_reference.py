@@ -331,10 +331,13 @@ def fiber_index_list(d, k, Ik, Jk):
     return idx
 
 
-def simulate_iteration(problem, ranks, J_in, swap_tol=0.05, restatement=False, I_in=None):
+def simulate_iteration(problem, ranks, J_in, swap_tol=0.05, restatement=False, I_in=None, ratios=None):
     """One cross iteration in numpy in the layouts above: (cores, I, J).  The 'device' of the iteration-level self-tests, and a
     way to see on the CPU whether a case's matrices are well conditioned.  Every step is maxvol_rows, or with restatement=True
-    lu_maxvol_reference with the warm rows of the previous sets (I_in: the left sets before the iteration, or None)."""
+    lu_maxvol_reference with the warm rows of the previous sets (I_in: the left sets before the iteration, or None); a list
+    given as `ratios` then receives every step's pivot ratio (what the deficiency flag is made of).  The fiber lists are asked
+    of `problem` in the device's order of core steps, so a problem that keeps a memo (cross_memo_model.MemoProblem) sees the
+    nodes in the order the device's memo does."""
     w = problem.w
     d, N = w.dx, list(w.ngrid)
     r = [int(v) for v in ranks]
@@ -346,6 +349,8 @@ def simulate_iteration(problem, ranks, J_in, swap_tol=0.05, restatement=False, I
         if not restatement:
             return maxvol_rows(A, swap_tol)
         f = lu_maxvol_reference(A, swap_tol, warm_rows(old_set, prefix_set, Nk, side, A.shape[0]))
+        if ratios is not None:
+            ratios.append(f.ratio)
         return f.rows, f.B
 
     for k in range(d - 1):
