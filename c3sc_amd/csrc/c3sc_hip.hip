@@ -950,6 +950,10 @@ static int launch_one(c3sc_hip_ctx *c, const KernelEntry *e, const KArgs &A, con
 // it: 0 switches the pass off, n > 0 runs it from n fibers on.  The three partition launches cost about 10 us in front of every
 // pair launch whatever the batch, what the absorbed tiles save grows with it: car7d loses 5 % at 2^17 fibers per launch
 // (1.469 -> 1.543 ms per step), gains 3.3 % at 2^20 and breaks even near 2^18 by those two figures.
+// The grouping by the fold's key levels rides in the same three launches (FPART_MIN_PER_BIN in fiber_partition.hpp: two keys from
+// 128 fibers per key on).  Traced, the pass takes 53 us per launch at 2^20 fibers (42 us before the grouping; the 10 us above was
+// an inference).  car7d at the threshold, 2^19 fibers (312 per key): 4.969-4.980 -> 4.789-4.827 ms per step; at 2^20 (624 per key)
+// 9.320-9.365 -> 8.870-8.895 (profiles/r07_car7d_grouped_fold.txt).
 constexpr long FIBER_PARTITION_MIN = 524288;
 static long fiber_partition_min()
 {
@@ -963,6 +967,17 @@ static long fiber_partition_min()
 // is absorbing.  Enqueued on the launch's stream into the scratch block `slot`; io.perm stays null where the pass does not run.
 // `launched` reports the pass's kernel launches; the pair launcher's own early refusal (launch_fpp_impl: more than 64 candidates) is
 // anticipated here, so that nothing is enqueued in front of a launcher that declines.
+// C3SC_FIBER_GROUP, read at every launch like C3SC_FIBER_PARTITION: 0 leaves the partition at live fibers first (no grouping by
+// the fold's key levels), n > 0 replaces FPART_MIN_PER_BIN, the fewest fibers per bin a key level is grouped by (1: every batch
+// the bin cap allows -- a setting for the tests, which group batches of a few hundred fibers)
+static long fiber_group_floor()
+{
+    const char *e = getenv("C3SC_FIBER_GROUP");
+    if (!e || !*e) return FPART_MIN_PER_BIN;
+    const long v = atol(e);
+    return v > 0 ? v : -1;
+}
+
 static int partition_fibers(c3sc_hip_ctx *c, const KernelEntry *e, const KArgs &A, LaunchIO &io, int slot, int &launched)
 {
     io.perm = nullptr;
@@ -973,20 +988,23 @@ static int partition_fibers(c3sc_hip_ctx *c, const KernelEntry *e, const KArgs &
     for (int m = 0; m < A.d; m++) faces = faces || (m != A.k && A.bctype[m] == C3SC_ABSORB);
     const long fmin = fiber_partition_min();
     if (!faces || fmin < 0 || A.F < fmin || A.F > 0x40000000L) return C3SC_OK; // perm and nlive are int32
-    const size_t need = fpart_bytes(A.F);
-    if (need > c->part_bytes[slot]) {
-        if (c->part[slot]) HIPCHK(c, hipFree(c->part[slot])); // synchronises the device: the launches that read the block are done
-        c->part[slot] = nullptr;
-        c->part_bytes[slot] = 0;
-        HIPCHK(c, hipMalloc(&c->part[slot], need));
-        c->part_bytes[slot] = need;
-    }
-    const PartScratch ps = fpart_carve(c->part[slot], A.F);
     PartArgs P;
     P.d = A.d;
     P.k = A.k;
     P.F = A.F;
     for (int m = 0; m < MAXD; m++) { P.ngrid[m] = A.ngrid[m]; P.bctype[m] = A.bctype[m]; }
+    fpart_plan(P, fpp_group_levels(A.d, e->rp, A.k), fiber_group_floor()); // the keys of the grouped fold, where the kernel has one
+    const size_t need = fpart_bytes(A.F, P.nbins);
+    if (need > c->part_bytes[slot]) {
+        if (c->part[slot]) HIPCHK(c, hipFree(c->part[slot])); // synchronises the device: the launches that read the block are done
+        c->part[slot] = nullptr;
+        c->part_bytes[slot] = 0;
+        c->part_last[slot] = {}; // c3sc_hip_last_partition must not read the freed block
+        HIPCHK(c, hipMalloc(&c->part[slot], need));
+        c->part_bytes[slot] = need;
+    }
+    const PartScratch ps = fpart_carve(c->part[slot], A.F, P.nbins);
+    c->part_last[slot] = {ps.perm, ps.nlive, A.F, io.stream};
     HIPCHK(c, fpart_launch(P, io.idx, ps, io.stream));
     launched = 3;
     io.perm = ps.perm;
@@ -1706,6 +1724,24 @@ int c3sc_hip_normals(uint64_t seed, uint64_t traj0, size_t ntraj, uint64_t step0
 }
 
 unsigned long long c3sc_hip_launch_count(void) { return g_launches; }
+
+int c3sc_hip_last_partition(c3sc_hip_ctx *c, int slot, int32_t *perm, size_t cap, size_t *F, int *nlive)
+{
+    if (!c) return C3SC_ERR_ARG;
+    if (slot < 0 || slot > c3sc_hip_ctx::NSIDE || !F || !nlive) return fail(c, C3SC_ERR_ARG, "last_partition: bad arguments");
+    const auto &lp = c->part_last[slot];
+    if (!lp.perm) return fail(c, C3SC_ERR_ARG, "last_partition: no partition has run on this slot");
+    *F = (size_t)lp.F;
+    HIPCHK(c, hipStreamSynchronize(lp.stream));
+    int32_t nl = 0;
+    HIPCHK(c, hipMemcpy(&nl, lp.nlive, sizeof(nl), hipMemcpyDeviceToHost));
+    *nlive = nl;
+    if (perm) {
+        if (cap < (size_t)lp.F) return fail(c, C3SC_ERR_ARG, "last_partition: perm holds fewer than F entries");
+        HIPCHK(c, hipMemcpy(perm, lp.perm, (size_t)lp.F * sizeof(int32_t), hipMemcpyDeviceToHost));
+    }
+    return C3SC_OK;
+}
 
 int c3sc_hip_debug_read(c3sc_hip_ctx *c, unsigned long long *out, size_t n)
 {

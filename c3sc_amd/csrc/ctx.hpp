@@ -80,6 +80,12 @@ struct c3sc_hip_ctx {
     // at a time (c3sc_hip.h, c3sc_hip_bellman_fibers).  Growing a block frees the old one, which synchronises the device.
     void *part[NSIDE + 1] = {nullptr, nullptr, nullptr};
     size_t part_bytes[NSIDE + 1] = {0, 0, 0};
+    // the last partition of each block, for c3sc_hip_last_partition (tests): valid until the block grows or the context goes
+    struct {
+        int32_t *perm = nullptr, *nlive = nullptr;
+        long F = 0;
+        hipStream_t stream = nullptr;
+    } part_last[NSIDE + 1];
     // scratch for the *_host convenience calls
     void *scratch = nullptr;
     size_t scratch_bytes = 0;

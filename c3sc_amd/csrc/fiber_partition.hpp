@@ -1,14 +1,20 @@
-// fiber_partition.hpp -- stable partition of a fiber batch for the fiber-pair kernel: live fibers first, absorbed ones last.
+// fiber_partition.hpp -- stable partition of a fiber batch for the fiber-pair kernel: live fibers first, absorbed ones last, and
+// the live ones grouped by the indices of the fold levels next to K.
 //
 // A fiber with a FIXED index on an absorbing face is absorbed at every node (fixed_neighbors returns true for that dimension):
 // its values are Model::boundcost, whatever the fold and the node loop compute.  k_fiber_pair maps one fiber to a lane, so it
-// can only leave that work out for 64 such fibers at a time: the batch is reordered so that they share tiles.
-//   perm[0 .. nlive)  the live fibers, in batch order
+// can only leave that work out for 64 such fibers at a time: the batch is reordered so that they share tiles.  In the same way a
+// tile whose 64 fibers share the index of a fold level applies ONE matrix at that level, from SGPRs instead of through a staged
+// core (kernel_fiber_pair.hpp: grouped fold), so the live fibers are ordered by the indices of up to two such levels
+// (kernel_common.hpp: fpp_key_levels; fpart_plan below says how many).
+//   perm[0 .. nlive)  the live fibers, keys (major index, minor index) ascending, batch order inside a key
 //   perm[nlive .. F)  the dead ones, in batch order
-// Three launches on the caller's stream, no host synchronisation: per-block counts (and one flag byte per fiber), an exclusive
-// scan of the counts by one workgroup, the scatter.  The order is a function of the batch alone -- no atomics: discounted models
-// choose the form of their discount factor by wave vote, so a fiber's bits may depend on its tile-mates, and tile-mates must not
-// change from run to run.
+// A stable counting sort over bins (key, then one bin for the dead) in three launches on the caller's stream, no host
+// synchronisation: per-block histograms (and one bin number per fiber); an exclusive scan of every bin over the blocks, 16 bins per
+// workgroup; the scatter, where a block sorts its (bin, position) words in LDS to rank each fiber among the block's own.  The
+// order is a function of the batch alone -- the histogram's LDS atomics only count, no atomic decides a position: discounted
+// models choose the form of their discount factor by wave vote, so a fiber's bits may depend on its tile-mates, and tile-mates
+// must not change from run to run.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -17,39 +23,76 @@
 namespace c3sc {
 
 constexpr int FPART_THREADS = 256, FPART_PER_THREAD = 4, FPART_BLOCK = FPART_THREADS * FPART_PER_THREAD;
+static_assert(FPART_BLOCK == 1024, "the scatter packs (bin, position in the block) into one word with 10 position bits");
+// Cap on the bins of one pass.  The counter scratch is blocks x bins x 4 B = 4 bins B per fiber: at the cap 8 B per fiber, under a
+// third of what the pass reads anyway (the index list of a 7-D batch: 28 B per fiber).  It is also what the scatter keeps in LDS
+// (8 bins per thread, two tables of 8 KB) and holds car7d's 41 x 41 + 1 bins.
+constexpr int FPART_BIN_PER_THREAD = 8, FPART_MAX_BINS = FPART_THREADS * FPART_BIN_PER_THREAD;
+// Floor on the mean number of live fibers per bin below which the minor key is dropped (and the major one where it alone falls
+// below it).  A bin of s fibers covers s / 64 tiles and one tile straddles each bin boundary, so about 1 - 64 / s of the tiles are
+// uniform: counted on the CPU with car7d's random fibers, 2^20 fibers (624 per bin) give 88.8-89.9 % of the tiles uniform in both
+// keys, 2^19 (312 per bin) 77.5-79.8 %.  Below 128 per bin most tiles straddle two bins.
+constexpr long FPART_MIN_PER_BIN = 128;
+constexpr int FPART_SCAN_BINS = 16; // bins per workgroup of the scan: one 64-byte piece of a histogram row
 
 struct PartArgs {
     int d, k;
     long F;
     int ngrid[MAXD];
     int bctype[MAXD];
+    int kmaj = -1, kmin = -1; // key dimensions, -1: none
+    int nmin = 1;             // bins per major index
+    int nbins = 2;            // keys + the dead bin (the last one)
 };
 
-// scratch of one partition, carved from a block of fpart_bytes(F) (the context keeps one block per stream a batch may run on)
+// How many key levels a launch groups by: two, one or none, from F and the grid alone.  floor: fibers per bin (< 0: no grouping).
+inline void fpart_plan(PartArgs &P, KeyLevels kl, long floor)
+{
+    P.kmaj = P.kmin = -1;
+    P.nmin = 1;
+    P.nbins = 2;
+    if (floor < 0 || kl.n < 1) return;
+    const long nmaj = P.ngrid[kl.major];
+    if (nmaj + 1 > FPART_MAX_BINS || P.F < floor * nmaj) return;
+    P.kmaj = kl.major;
+    P.nbins = (int)nmaj + 1;
+    if (kl.n < 2) return;
+    const long nkeys = nmaj * P.ngrid[kl.minor];
+    if (nkeys + 1 > FPART_MAX_BINS || P.F < floor * nkeys) return;
+    P.kmin = kl.minor;
+    P.nmin = P.ngrid[kl.minor];
+    P.nbins = (int)nkeys + 1;
+}
+
+// scratch of one partition, carved from a block of fpart_bytes(F, nbins) (the context keeps one block per stream a batch may run on)
 struct PartScratch {
     int32_t *perm = nullptr;   // [F]
-    int32_t *blocks = nullptr; // [nblocks] live count per block, then its exclusive prefix
+    int32_t *counts = nullptr; // [nblocks][nbins] fibers of a bin in a block, then those in the blocks before it
+    int32_t *totals = nullptr; // [nbins]
     int32_t *nlive = nullptr;  // [1]
-    uint8_t *flags = nullptr;  // [F] 1: dead
+    uint16_t *bins = nullptr;  // [F] bin of a fiber
 };
 
 __host__ __device__ constexpr size_t fpart_align(size_t b) { return (b + 255) & ~(size_t)255; }
 inline long fpart_blocks(long F) { return (F + FPART_BLOCK - 1) / FPART_BLOCK; }
-inline size_t fpart_bytes(long F)
+inline size_t fpart_bytes(long F, int nbins)
 {
-    return fpart_align((size_t)F * 4) + fpart_align((size_t)fpart_blocks(F) * 4) + fpart_align(4) + fpart_align((size_t)F);
+    return fpart_align((size_t)F * 4) + fpart_align((size_t)fpart_blocks(F) * nbins * 4) + fpart_align((size_t)nbins * 4) + fpart_align(4) +
+           fpart_align((size_t)F * 2);
 }
-inline PartScratch fpart_carve(void *base, long F)
+inline PartScratch fpart_carve(void *base, long F, int nbins)
 {
     PartScratch s;
     char *p = (char *)base;
     s.perm = (int32_t *)p;
     p += fpart_align((size_t)F * 4);
-    s.blocks = (int32_t *)p;
-    p += fpart_align((size_t)fpart_blocks(F) * 4);
+    s.counts = (int32_t *)p;
+    p += fpart_align((size_t)fpart_blocks(F) * nbins * 4);
+    s.totals = (int32_t *)p;
+    p += fpart_align((size_t)nbins * 4);
     s.nlive = (int32_t *)p;
     p += fpart_align(4);
-    s.flags = (uint8_t *)p;
+    s.bins = (uint16_t *)p;
     return s;
 }
 
@@ -89,73 +132,177 @@ __device__ inline int fpart_block_scan(int v, int &total)
     return before + inc - v;
 }
 
-__global__ void __launch_bounds__(FPART_THREADS) k_fpart_count(const PartArgs P, const int32_t *__restrict__ idx, uint8_t *__restrict__ flags,
-                                                               int32_t *__restrict__ blocks)
+__global__ void __launch_bounds__(FPART_THREADS) k_fpart_count(const PartArgs P, const int32_t *__restrict__ idx, uint16_t *__restrict__ bins,
+                                                               int32_t *__restrict__ counts)
 {
-    const long f0 = (long)blockIdx.x * FPART_BLOCK + (long)threadIdx.x * FPART_PER_THREAD;
-    int live = 0;
+    __shared__ int hist[FPART_MAX_BINS];
+    for (int b = threadIdx.x; b < P.nbins; b += FPART_THREADS) hist[b] = 0;
+    __syncthreads();
+    // a wave instruction takes 64 consecutive fibers (the histogram does not care about the order): 64 x d consecutive indices
+    const long f0 = (long)blockIdx.x * FPART_BLOCK + threadIdx.x;
 #pragma unroll
     for (int i = 0; i < FPART_PER_THREAD; i++) {
-        const long f = f0 + i;
+        const long f = f0 + (long)i * FPART_THREADS;
         if (f < P.F) {
-            const bool dead = fiber_dead(P, idx, f);
-            flags[f] = dead ? 1 : 0;
-            live += dead ? 0 : 1;
+            int bin = P.nbins - 1;
+            if (!fiber_dead(P, idx, f)) {
+                bin = P.kmaj >= 0 ? idx[f * P.d + P.kmaj] : 0;
+                if (P.kmin >= 0) bin = bin * P.nmin + idx[f * P.d + P.kmin];
+                bin = min(max(bin, 0), P.nbins - 2); // an index off the grid must not leave the histogram
+            }
+            bins[f] = (uint16_t)bin;
+            atomicAdd(&hist[bin], 1); // a count: its value does not depend on the order
         }
     }
-    int total;
-    (void)fpart_block_scan(live, total);
-    if (threadIdx.x == 0) blocks[blockIdx.x] = total;
+    __syncthreads();
+    int32_t *row = counts + (size_t)blockIdx.x * P.nbins;
+    for (int b = threadIdx.x; b < P.nbins; b += FPART_THREADS) row[b] = hist[b];
 }
 
-// one workgroup: blocks[b] <- live fibers in the blocks before b; *nlive <- all of them
-__global__ void __launch_bounds__(FPART_THREADS) k_fpart_scan(int32_t *__restrict__ blocks, long nblocks, int32_t *__restrict__ nlive)
+// workgroup g scans the bins [16 g, 16 g + 16) over the blocks: counts[b][bin] <- fibers of the bin in the blocks before b,
+// totals[bin] <- all of them.  Thread (s, c) takes bin c of the s-th 64th of the blocks: a row's 16 bins are one 64-byte read.  The
+// loads of a chunk are issued together (the pass is latency: 16 rows per thread at 2^20 fibers), then summed or rewritten.  Traced
+// at 2^20 fibers and 1682 bins: 12.8 us, against 16.9 us for the count and 23.6 us for the scatter, whose sort is the larger cost
+// (with 256 threads and one row in flight the scan took 29.7 us); keeping the first walk's partial sums is what is left here.
+constexpr int FPART_SCAN_THREADS = 1024, FPART_SCAN_CHUNK = 8;
+__global__ void __launch_bounds__(FPART_SCAN_THREADS) k_fpart_scan(int32_t *__restrict__ counts, long nblocks, int nbins, int32_t *__restrict__ totals)
 {
-    int carry = 0;
-    for (long b0 = 0; b0 < nblocks; b0 += FPART_THREADS) {
-        const long b = b0 + threadIdx.x;
-        const int v = b < nblocks ? blocks[b] : 0;
+    constexpr int NS = FPART_SCAN_THREADS / FPART_SCAN_BINS;
+    __shared__ int part[NS][FPART_SCAN_BINS];
+    const int c = threadIdx.x % FPART_SCAN_BINS, s = threadIdx.x / FPART_SCAN_BINS;
+    const int bin = blockIdx.x * FPART_SCAN_BINS + c;
+    const bool on = bin < nbins;
+    const long per = (nblocks + NS - 1) / NS, b0 = s * per < nblocks ? s * per : nblocks, b1 = b0 + per < nblocks ? b0 + per : nblocks;
+    int sum = 0;
+    if (on)
+        for (long b = b0; b < b1; b += FPART_SCAN_CHUNK) {
+            int v[FPART_SCAN_CHUNK];
+#pragma unroll
+            for (int q = 0; q < FPART_SCAN_CHUNK; q++) v[q] = b + q < b1 ? counts[(size_t)(b + q) * nbins + bin] : 0;
+#pragma unroll
+            for (int q = 0; q < FPART_SCAN_CHUNK; q++) sum += v[q];
+        }
+    part[s][c] = sum;
+    __syncthreads();
+    int run = 0, total = 0;
+    for (int q = 0; q < NS; q++) {
+        const int v = part[q][c];
+        if (q < s) run += v;
+        total += v;
+    }
+    if (on) {
+        for (long b = b0; b < b1; b += FPART_SCAN_CHUNK) {
+            int v[FPART_SCAN_CHUNK];
+#pragma unroll
+            for (int q = 0; q < FPART_SCAN_CHUNK; q++) v[q] = b + q < b1 ? counts[(size_t)(b + q) * nbins + bin] : 0;
+#pragma unroll
+            for (int q = 0; q < FPART_SCAN_CHUNK; q++) {
+                if (b + q < b1) counts[(size_t)(b + q) * nbins + bin] = run;
+                run += v[q];
+            }
+        }
+        if (s == 0) totals[bin] = total;
+    }
+}
+
+__global__ void __launch_bounds__(FPART_THREADS) k_fpart_scatter(long F, int nbins, const uint16_t *__restrict__ bins, const int32_t *__restrict__ counts,
+                                                                 const int32_t *__restrict__ totals, int32_t *__restrict__ nlive,
+                                                                 int32_t *__restrict__ perm)
+{
+    __shared__ int base[FPART_MAX_BINS];  // first position of a bin in perm: the prefix over the bin totals
+    __shared__ int start[FPART_MAX_BINS]; // where a bin's run starts in the sorted block
+    __shared__ unsigned srt[FPART_BLOCK]; // (bin << 10 | position in the block), sorted: stable by construction
+    const int tid = threadIdx.x;
+    {
+        int v[FPART_BIN_PER_THREAD], sum = 0;
+#pragma unroll
+        for (int i = 0; i < FPART_BIN_PER_THREAD; i++) {
+            const int b = tid * FPART_BIN_PER_THREAD + i;
+            v[i] = b < nbins ? totals[b] : 0;
+            sum += v[i];
+        }
         int total;
-        const int ex = fpart_block_scan(v, total);
-        if (b < nblocks) blocks[b] = carry + ex;
-        carry += total;
+        int ex = fpart_block_scan(sum, total);
+#pragma unroll
+        for (int i = 0; i < FPART_BIN_PER_THREAD; i++) {
+            base[tid * FPART_BIN_PER_THREAD + i] = ex;
+            ex += v[i];
+        }
     }
-    if (threadIdx.x == 0) *nlive = carry;
-}
-
-__global__ void __launch_bounds__(FPART_THREADS) k_fpart_scatter(long F, const uint8_t *__restrict__ flags, const int32_t *__restrict__ blocks,
-                                                                 const int32_t *__restrict__ nlive, int32_t *__restrict__ perm)
-{
-    const long fb = (long)blockIdx.x * FPART_BLOCK, f0 = fb + (long)threadIdx.x * FPART_PER_THREAD;
-    bool dead[FPART_PER_THREAD];
-    int live = 0;
+    const long fb = (long)blockIdx.x * FPART_BLOCK;
+    if (nbins == 2) { // live and dead only (no key level, or grouping off): the rank is a prefix count, nothing to sort
+        if (blockIdx.x == 0 && tid == 0) *nlive = base[1];
+        bool dead[FPART_PER_THREAD];
+        int live = 0;
+#pragma unroll
+        for (int i = 0; i < FPART_PER_THREAD; i++) {
+            const long f = fb + tid * FPART_PER_THREAD + i;
+            dead[i] = f < F ? bins[f] != 0 : true;
+            live += dead[i] ? 0 : 1;
+        }
+        int total;
+        const int ex = fpart_block_scan(live, total);
+        const int32_t *row = counts + (size_t)blockIdx.x * 2;
+        long lpos = (long)row[0] + ex, dpos = (long)base[1] + row[1] + (tid * FPART_PER_THREAD - ex);
+#pragma unroll
+        for (int i = 0; i < FPART_PER_THREAD; i++) {
+            const long f = fb + tid * FPART_PER_THREAD + i;
+            if (f < F) {
+                if (dead[i]) perm[dpos++] = (int32_t)f;
+                else perm[lpos++] = (int32_t)f;
+            }
+        }
+        return;
+    }
 #pragma unroll
     for (int i = 0; i < FPART_PER_THREAD; i++) {
-        dead[i] = (f0 + i < F) ? flags[f0 + i] != 0 : true;
-        live += dead[i] ? 0 : 1;
+        const int p = tid * FPART_PER_THREAD + i;
+        srt[p] = fb + p < F ? ((unsigned)bins[fb + p] << 10) | (unsigned)p : 0xffffffffu;
     }
-    int total;
-    const int ex = fpart_block_scan(live, total);
-    const long live_before = blocks[blockIdx.x];
-    long lpos = live_before + ex;                                                    // live fibers before f0
-    long dpos = (long)*nlive + (fb - live_before) + ((long)threadIdx.x * FPART_PER_THREAD - ex); // nlive + dead fibers before f0
+    // bitonic sort, ascending: two compare-exchanges per thread and step
+    for (int k = 2; k <= FPART_BLOCK; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            __syncthreads();
+#pragma unroll
+            for (int e = tid; e < FPART_BLOCK / 2; e += FPART_THREADS) {
+                const int lo = ((e & ~(j - 1)) << 1) | (e & (j - 1)), hi = lo | j;
+                const unsigned a = srt[lo], b = srt[hi];
+                const bool up = (lo & k) == 0;
+                if ((a > b) == up) {
+                    srt[lo] = b;
+                    srt[hi] = a;
+                }
+            }
+        }
+    __syncthreads();
+    if (blockIdx.x == 0 && tid == 0) *nlive = base[nbins - 1]; // the dead bin is the last one
+    unsigned w[FPART_PER_THREAD];
 #pragma unroll
     for (int i = 0; i < FPART_PER_THREAD; i++) {
-        if (f0 + i < F) {
-            if (dead[i]) perm[dpos++] = (int32_t)(f0 + i);
-            else perm[lpos++] = (int32_t)(f0 + i);
+        const int s = tid * FPART_PER_THREAD + i;
+        w[i] = srt[s];
+        if (w[i] != 0xffffffffu && (s == 0 || (srt[s - 1] >> 10) != (w[i] >> 10))) start[w[i] >> 10] = s;
+    }
+    __syncthreads();
+    const int32_t *row = counts + (size_t)blockIdx.x * nbins;
+#pragma unroll
+    for (int i = 0; i < FPART_PER_THREAD; i++) {
+        if (w[i] != 0xffffffffu) {
+            const int s = tid * FPART_PER_THREAD + i, bin = (int)(w[i] >> 10);
+            perm[(long)base[bin] + row[bin] + (s - start[bin])] = (int32_t)(fb + (w[i] & 1023u));
         }
     }
 }
 
-// enqueue the partition of idx[F][d] on `stream`; s has been carved for F
+// enqueue the partition of idx[F][d] on `stream`; s has been carved for (F, P.nbins)
 inline hipError_t fpart_launch(const PartArgs &P, const int32_t *idx, const PartScratch &s, hipStream_t stream)
 {
     const long nb = fpart_blocks(P.F);
-    hipLaunchKernelGGL(k_fpart_count, dim3((unsigned)nb), dim3(FPART_THREADS), 0, stream, P, idx, s.flags, s.blocks);
-    hipLaunchKernelGGL(k_fpart_scan, dim3(1), dim3(FPART_THREADS), 0, stream, s.blocks, nb, s.nlive);
-    hipLaunchKernelGGL(k_fpart_scatter, dim3((unsigned)nb), dim3(FPART_THREADS), 0, stream, P.F, (const uint8_t *)s.flags, (const int32_t *)s.blocks,
-                       (const int32_t *)s.nlive, s.perm);
+    hipLaunchKernelGGL(k_fpart_count, dim3((unsigned)nb), dim3(FPART_THREADS), 0, stream, P, idx, s.bins, s.counts);
+    hipLaunchKernelGGL(k_fpart_scan, dim3((unsigned)((P.nbins + FPART_SCAN_BINS - 1) / FPART_SCAN_BINS)), dim3(FPART_SCAN_THREADS), 0, stream, s.counts, nb,
+                       P.nbins, s.totals);
+    hipLaunchKernelGGL(k_fpart_scatter, dim3((unsigned)nb), dim3(FPART_THREADS), 0, stream, P.F, P.nbins, (const uint16_t *)s.bins,
+                       (const int32_t *)s.counts, (const int32_t *)s.totals, s.nlive, s.perm);
     return hipGetLastError();
 }
 

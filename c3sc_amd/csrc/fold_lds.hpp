@@ -120,6 +120,71 @@ __device__ inline void apply_core(const double *G, double (&W)[NW][RP])
     }
 }
 
+// ---- the same products with a WAVE-UNIFORM matrix: all 64 fibers of the tile share the level's index (kernel_fiber_pair.hpp:
+// grouped fold), so G is one matrix read from the cores in global memory on the scalar path -- no staged core, no LDS gather.
+// v <- v G (ROWVEC) or v <- G v for NV vectors.  The matrix comes in four batches of scalar loads (a quarter of it: 50 SGPRs at
+// rank 10), each issued back to back and waited for once, as in the node loop (stencil()); element e = a + b RP is walked in
+// storage order, so every output sums its index ascending from 0.0: the FMA chains of vecmat_lds / matvec_lds, bit for bit.
+template <int RP, int NV, bool ROWVEC>
+__device__ __forceinline__ void apply_uni(const double *__restrict__ G, double (&v)[NV][RP])
+{
+    constexpr int NE = RP * RP, NB = (NE + 3) / 4;
+    double t[NV][RP];
+#pragma unroll
+    for (int s = 0; s < NV; s++)
+#pragma unroll
+        for (int i = 0; i < RP; i++) t[s][i] = 0.0;
+#pragma unroll
+    for (int b0 = 0; b0 < NE; b0 += NB) {
+        double g[NB];
+#pragma unroll
+        for (int e = 0; e < NB; e++) g[e] = (b0 + e < NE) ? G[b0 + e] : 0.0;
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int e = 0; e < NB; e++) asm volatile("" : "+s"(g[e]));
+#pragma unroll
+        for (int e = 0; e < NB; e++) {
+            if (b0 + e < NE) {
+                const int a = (b0 + e) % RP, b = (b0 + e) / RP;
+#pragma unroll
+                for (int s = 0; s < NV; s++) {
+                    if constexpr (ROWVEC) t[s][b] = fma(v[s][a], g[e], t[s][b]);
+                    else t[s][a] = fma(g[e], v[s][b], t[s][a]);
+                }
+            }
+        }
+        // pinned behind each batch: left floating the products sink behind the last batch and the matrix is parked in VGPR lanes
+#pragma unroll
+        for (int s = 0; s < NV; s++)
+#pragma unroll
+            for (int i = 0; i < RP; i++) pin(t[s][i]);
+    }
+#pragma unroll
+    for (int s = 0; s < NV; s++)
+#pragma unroll
+        for (int i = 0; i < RP; i++) v[s][i] = t[s][i];
+}
+
+// W[FIRST .. FIRST+COUNT) through the uniform G in passes of at most NVMAX vectors
+template <int RP, int NW, int FIRST, int COUNT, bool ROWVEC, int NVMAX>
+__device__ __forceinline__ void apply_range_uni(const double *__restrict__ G, double (&W)[NW][RP])
+{
+    if constexpr (COUNT > 0) {
+        constexpr int NV = COUNT >= NVMAX ? NVMAX : COUNT;
+        double tmp[NV][RP];
+#pragma unroll
+        for (int s = 0; s < NV; s++)
+#pragma unroll
+            for (int a = 0; a < RP; a++) tmp[s][a] = W[FIRST + s][a];
+        apply_uni<RP, NV, ROWVEC>(G, tmp);
+#pragma unroll
+        for (int s = 0; s < NV; s++)
+#pragma unroll
+            for (int a = 0; a < RP; a++) W[FIRST + s][a] = tmp[s][a];
+        apply_range_uni<RP, NW, FIRST + NV, COUNT - NV, ROWVEC, NVMAX>(G, W);
+    }
+}
+
 template <int RP>
 __device__ inline double dot_reg(const double (&a)[RP], const double (&b)[RP])
 {

@@ -100,6 +100,46 @@ __host__ __device__ constexpr long pair_tab_doubles(int na, int nb, int rp) { re
 __host__ __device__ inline long pair_tabL_off(const KArgs &A, int rp) { return A.pair_img_off[A.d - 1] + pair_img_doubles(A.ngrid[A.d - 1], rp); }
 __host__ __device__ inline long pair_tabR_off(const KArgs &A, int rp) { return pair_tabL_off(A, rp) + pair_tab_doubles(A.ngrid[0], A.ngrid[1], rp); }
 
+// Key levels of the grouped fold (fiber_partition.hpp groups the live fibers of a partitioned fiber-pair batch by them,
+// kernel_fiber_pair.hpp folds a tile that shares one from SGPRs).  With `tab` (fpp_edge_tables) the staged matrix levels are the
+// cores lfirst .. k-1 on the left and k+1 .. rfirst on the right (PairMap::plan).  The nearest to k on each side; where a side
+// has none, the two nearest on the other; the nearer one is the major key (the left one on a tie).  n: how many there are.
+struct KeyLevels {
+    int n, major, minor;
+};
+__host__ __device__ constexpr KeyLevels fpp_key_levels(int d, int k, bool tab)
+{
+    const int lfirst = (tab && k >= 2) ? 2 : 1, rfirst = (tab && k <= d - 3) ? d - 3 : d - 2;
+    const int nl = k - lfirst > 0 ? k - lfirst : 0, nr = rfirst - k > 0 ? rfirst - k : 0;
+    if (nl > 0 && nr > 0) return {2, k - 1, k + 1};
+    if (nl > 0) return {nl > 1 ? 2 : 1, k - 1, nl > 1 ? k - 2 : -1};
+    if (nr > 0) return {nr > 1 ? 2 : 1, k + 1, nr > 1 ? k + 2 : -1};
+    return {0, -1, -1};
+}
+#ifndef FPP_DIRECT_MAXD
+#define FPP_DIRECT_MAXD 3 // kernel_fiber_pair.hpp: fpp_direct
+#endif
+#ifndef FPP_EDGE_TABLES
+#define FPP_EDGE_TABLES 1 // kernel_fiber_pair.hpp: fpp_edge_tables
+#endif
+#ifndef FPP_GROUP_FOLD
+#define FPP_GROUP_FOLD 1 // 0: a diagnostic build keeps the LDS fold everywhere (and the partition ungrouped)
+#endif
+// The opt-out list of the grouped fold: instantiations (dimension count, padded rank, K) that measured no faster with it, or
+// whose node loop gained scratch reloads.
+//   d = 7, rank 10, K = 1 (car7d): 1.370-1.377 ms per launch without it, 1.365-1.375 with it over five alternating runs at 2^20
+//   fibers -- inside the spread; its key levels carry 16 of 23 products (a count, not a share of the time) but it keeps a staging
+//   round, and the grouped instantiation spilled 83 VGPRs against 59 (profiles/r07_car7d_grouped_fold.txt, section 5)
+__host__ __device__ constexpr bool fpp_group_fold_optout(int d, int rp, int k) { return d == 7 && rp == 10 && k == 1; }
+// the key levels of the fiber-pair instantiation (d, padded rank, k), for the host's pre-pass and the kernel alike: none for the
+// direct-fold kernels (nothing is staged) and the opt-outs
+__host__ __device__ constexpr KeyLevels fpp_group_levels(int d, int rp, int k)
+{
+    const bool direct = d <= FPP_DIRECT_MAXD && rp <= 8;
+    if (!FPP_GROUP_FOLD || direct || fpp_group_fold_optout(d, rp, k)) return {0, -1, -1};
+    return fpp_key_levels(d, k, FPP_EDGE_TABLES && d >= 4);
+}
+
 // Pair index iu * nw + iw of the game candidate at list position p, and back (MINMAX: groups are u, the list is the pair order)
 __device__ inline int game_list_to_pair(const KArgs &A, int p)
 {

@@ -111,6 +111,42 @@ __device__ inline void apply_core_and(const double *G, double (&W)[NW][RP], doub
     apply_core<RP, NW, FIRST + N1, COUNT - N1, ROWVEC, FPP_NV>(G, W);
 }
 
+// apply_core_and with a wave-uniform matrix (fold_lds.hpp: apply_uni): the same vectors per pass, the same sums
+template <int RP, int NW, int FIRST, int COUNT, bool ROWVEC>
+__device__ __forceinline__ void apply_uni_and(const double *__restrict__ G, double (&W)[NW][RP], double (&E)[RP])
+{
+    constexpr int N1 = COUNT >= FPP_NV - 1 ? FPP_NV - 1 : COUNT;
+    double tmp[N1 + 1][RP];
+#pragma unroll
+    for (int a = 0; a < RP; a++) tmp[0][a] = E[a];
+#pragma unroll
+    for (int s = 0; s < N1; s++)
+#pragma unroll
+        for (int a = 0; a < RP; a++) tmp[s + 1][a] = W[FIRST + s][a];
+    apply_uni<RP, N1 + 1, ROWVEC>(G, tmp);
+#pragma unroll
+    for (int a = 0; a < RP; a++) E[a] = tmp[0][a];
+#pragma unroll
+    for (int s = 0; s < N1; s++)
+#pragma unroll
+        for (int a = 0; a < RP; a++) W[FIRST + s][a] = tmp[s + 1][a];
+    apply_range_uni<RP, NW, FIRST + N1, COUNT - N1, ROWVEC, FPP_NV>(G, W);
+}
+
+// One staged fold level: `body(uniform, index)` runs the level.  At a key level of the grouped fold (KEY) the tile is asked whether
+// its 64 lanes share the level's index v -- the first lane's value and a ballot of the lanes that differ: an SGPR condition and a
+// scalar branch, no lane-divergent control flow -- and a tile that does runs the uniform form with that index.
+template <bool KEY, class Body>
+__device__ __forceinline__ void fold_level(int v, Body &&body)
+{
+    if constexpr (KEY) {
+        const int u = __builtin_amdgcn_readfirstlane(v);
+        if (__ballot(v != u) == 0ull) body(std::true_type{}, u);
+        else body(std::false_type{}, 0);
+    } else
+        body(std::false_type{}, 0);
+}
+
 __device__ inline void pair_barrier()
 { // workgroup barrier + LDS visibility between the two wavefronts.  Only LDS traffic is exchanged, so only
   // lgkmcnt is drained: a workgroup-scope release fence would also wait (vmcnt(0)) for the scattered
@@ -315,6 +351,19 @@ struct PairMap {
         for (int it = 0; it < NIT; it++) p.products += cost(it);
         return p;
     }
+    // Grouped fold: the products of the staged level m, both wavefronts -- L or R, the new pair (or the merged share), and every
+    // vector created before it; those of the key levels (fpp_key_levels) run from SGPRs in a tile that shares the level's index,
+    // and the level's staging round is left out.  The sum over all staged levels is plan().products.
+    __host__ __device__ static constexpr int level_products(int m)
+    {
+        return 3 + (m < K ? left_before<0>(m) + left_before<1>(m) : right_after<0>(m) + right_after<1>(m));
+    }
+    __host__ __device__ static constexpr int uniform_rounds() { return fpp_key_levels(D, K, TAB).n; }
+    __host__ __device__ static constexpr int uniform_products()
+    {
+        constexpr KeyLevels kl = fpp_key_levels(D, K, TAB);
+        return (kl.n > 0 ? level_products(kl.major) : 0) + (kl.n > 1 ? level_products(kl.minor) : 0);
+    }
     // Which wave folds an item.  Nothing merged: pair_owner (alternate by distance from K).  Otherwise that is no longer balanced
     // -- a side that collapsed to one carried vector costs a fraction of its pairs -- and the items are dealt by their cost
     // count, the most expensive first, each to the wave with less work so far.
@@ -434,6 +483,16 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
     constexpr int NOWN = (NOL + NOR) > 0 ? (NOL + NOR) : 1;
     constexpr int NP = NV + 1; // partial sums per node: NV neighbour values + the node value
     constexpr bool DIRECT = fpp_direct<Model, RP>();
+    // Grouped fold (PART only: the pre-pass orders the live fibers by these levels' indices, fiber_partition.hpp).  At a key
+    // level both wavefronts ask whether the tile's 64 lanes share fi[m] -- the first lane's value and a ballot of the lanes that
+    // differ: an SGPR condition, a scalar branch, the same answer in both wavefronts (they read the same perm entries), so both
+    // pass the same barriers.  A tile that does takes the level's matrices from the arena on the scalar path and skips the
+    // staging round; each level decides on its own, a mixed one runs the staged code.  Skipping the round is safe for the LDS
+    // reuse around it: every read of sK by a wavefront precedes that wavefront's next barrier, and everything that writes sK
+    // (a later staging round, the half swap) starts behind a barrier of its own.
+    constexpr KeyLevels KL = fpp_group_levels(D, RP, K);
+    constexpr bool GROUP = PART && KL.n > 0;
+    static_assert(!GROUP || fpp_key_levels(D, K, ET).major == KL.major, "the key levels follow the kernel's own fold plan");
     static_assert(RP % 2 == 0, "rank-split kernel needs an even padded rank");
     const int lane = threadIdx.x & 63;
     const int N = A.N;
@@ -600,53 +659,63 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
             }
             auto left_step = [&](auto mc) __attribute__((always_inline)) {
                 constexpr int m = decltype(mc)::value;
-                constexpr int str = DIRECT ? RP * RP : fpl_lds_stride(RP * RP);
-                constexpr int before = PM::template left_before<H>(m); // own vectors created so far
-                constexpr bool PAIR = !PM::mg(m) && PM::owner(m) == H, ACC = PM::mg(m) && PM::owner(PM::UL) == H;
-                double nw[RP]; // a merged dimension's share of U_L
-                const double *src = sK;
-                FPP_STAMP(1)
-                if constexpr (DIRECT) src = ro + A.core_off[m];
-                else {
-                    pair_barrier();
-                    stage_core_image<H>(sK, A.img_base + A.pair_img_off[m], A.ngrid[m] * str);
-                    pair_barrier();
-                }
-                if constexpr (PM::ltab() && m == PL.lfirst) left_combine();
-                FPP_STAMP(7)
-                const double *G = src + fi[m] * str;
-                if constexpr (PAIR || ACC) { // the new pair first: it needs the prefix BEFORE this core
-                    double t0[1][RP], t1[1][RP];
+                // UNI: the tile shares fi[m] = iu -- one matrix per product, from the arena on the scalar path, nothing staged
+                auto body = [&](auto uc, int iu) __attribute__((always_inline)) {
+                    constexpr bool UNI = decltype(uc)::value;
+                    constexpr int str = (DIRECT || UNI) ? RP * RP : fpl_lds_stride(RP * RP);
+                    constexpr int before = PM::template left_before<H>(m); // own vectors created so far
+                    constexpr bool PAIR = !PM::mg(m) && PM::owner(m) == H, ACC = PM::mg(m) && PM::owner(PM::UL) == H;
+                    double nw[RP]; // a merged dimension's share of U_L
+                    const double *src = sK;
+                    FPP_STAMP(1)
+                    if constexpr (DIRECT || UNI) src = ro + A.core_off[m];
+                    else {
+                        pair_barrier();
+                        stage_core_image<H>(sK, A.img_base + A.pair_img_off[m], A.ngrid[m] * str);
+                        pair_barrier();
+                    }
+                    if constexpr (PM::ltab() && m == PL.lfirst) left_combine();
+                    FPP_STAMP(7)
+                    const double *G = src + (UNI ? iu : fi[m]) * str;
+                    if constexpr (PAIR || ACC) { // the new pair first: it needs the prefix BEFORE this core
+                        double t0[1][RP], t1[1][RP];
 #pragma unroll
-                    for (int a = 0; a < RP; a++) { t0[0][a] = L[a]; t1[0][a] = L[a]; }
+                        for (int a = 0; a < RP; a++) { t0[0][a] = L[a]; t1[0][a] = L[a]; }
+                        if constexpr (DIRECT) {
+                            apply_glb<RP, 1, true>(src + nbm[m] * str, t0);
+                            apply_glb<RP, 1, true>(src + nbp[m] * str, t1);
+                        } else if constexpr (UNI) { // functions of the shared index: uniform too
+                            apply_uni<RP, 1, true>(src + __builtin_amdgcn_readfirstlane(nbm[m]) * str, t0);
+                            apply_uni<RP, 1, true>(src + __builtin_amdgcn_readfirstlane(nbp[m]) * str, t1);
+                        } else {
+                            vecmat_lds<RP, 1>(src + nbm[m] * str, t0);
+                            vecmat_lds<RP, 1>(src + nbp[m] * str, t1);
+                        }
+#pragma unroll
+                        for (int a = 0; a < RP; a++) {
+                            if constexpr (PAIR) { W[before][a] = t0[0][a]; W[before + 1][a] = t1[0][a]; }
+                            else nw[a] = fma(rpp[m], t1[0][a], rpm[m] * t0[0][a]);
+                        }
+                    }
                     if constexpr (DIRECT) {
-                        apply_glb<RP, 1, true>(src + nbm[m] * str, t0);
-                        apply_glb<RP, 1, true>(src + nbp[m] * str, t1);
-                    } else {
-                        vecmat_lds<RP, 1>(src + nbm[m] * str, t0);
-                        vecmat_lds<RP, 1>(src + nbp[m] * str, t1);
+                        double tl[1][RP];
+#pragma unroll
+                        for (int a = 0; a < RP; a++) tl[0][a] = L[a];
+                        apply_glb<RP, 1, true>(G, tl);
+#pragma unroll
+                        for (int a = 0; a < RP; a++) L[a] = tl[0][a];
+                        apply_range_glb<RP, NOWN, 0, before, true>(G, W);
+                    } else if constexpr (UNI)
+                        apply_uni_and<RP, NOWN, 0, before, true>(G, W, L);
+                    else
+                        apply_core_and<RP, NOWN, 0, before, true>(G, W, L);
+                    if constexpr (ACC) { // U_L: created here, or carried through this core above and added to
+                        constexpr int su = PM::template lslot<H>(PM::UL);
+#pragma unroll
+                        for (int a = 0; a < RP; a++) W[su][a] = (m == PM::first_l()) ? nw[a] : W[su][a] + nw[a];
                     }
-#pragma unroll
-                    for (int a = 0; a < RP; a++) {
-                        if constexpr (PAIR) { W[before][a] = t0[0][a]; W[before + 1][a] = t1[0][a]; }
-                        else nw[a] = fma(rpp[m], t1[0][a], rpm[m] * t0[0][a]);
-                    }
-                }
-                if constexpr (DIRECT) {
-                    double tl[1][RP];
-#pragma unroll
-                    for (int a = 0; a < RP; a++) tl[0][a] = L[a];
-                    apply_glb<RP, 1, true>(G, tl);
-#pragma unroll
-                    for (int a = 0; a < RP; a++) L[a] = tl[0][a];
-                    apply_range_glb<RP, NOWN, 0, before, true>(G, W);
-                } else
-                    apply_core_and<RP, NOWN, 0, before, true>(G, W, L);
-                if constexpr (ACC) { // U_L: created here, or carried through this core above and added to
-                    constexpr int su = PM::template lslot<H>(PM::UL);
-#pragma unroll
-                    for (int a = 0; a < RP; a++) W[su][a] = (m == PM::first_l()) ? nw[a] : W[su][a] + nw[a];
-                }
+                };
+                fold_level<GROUP && (m == KL.major || (KL.n > 1 && m == KL.minor))>(fi[m], body);
             };
             [&]<int... Ms>(std::integer_sequence<int, Ms...>) { (left_step(std::integral_constant<int, Ms + PL.lfirst>{}), ...); }
             (std::make_integer_sequence<int, (K > PL.lfirst ? K - PL.lfirst : 0)>{});
@@ -719,53 +788,62 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
             }
             auto right_step = [&](auto mc) __attribute__((always_inline)) {
                 constexpr int m = decltype(mc)::value; // D-2 down to K+1
-                constexpr int str = DIRECT ? RP * RP : fpl_lds_stride(RP * RP);
-                constexpr int after = PM::template right_after<H>(m);
-                constexpr bool PAIR = !PM::mg(m) && PM::owner(m) == H, ACC = PM::mg(m) && PM::owner(PM::UR) == H;
-                double nw[RP];
-                const double *src = sK;
-                FPP_STAMP(1)
-                if constexpr (DIRECT) src = ro + A.core_off[m];
-                else {
-                    pair_barrier();
-                    stage_core_image<H>(sK, A.img_base + A.pair_img_off[m], A.ngrid[m] * str);
-                    pair_barrier();
-                }
-                if constexpr (PM::rtab() && m == PL.rfirst) right_combine();
-                FPP_STAMP(7)
-                const double *G = src + fi[m] * str;
-                if constexpr (PAIR || ACC) {
-                    double t0[1][RP], t1[1][RP];
+                auto body = [&](auto uc, int iu) __attribute__((always_inline)) { // UNI: as in left_step
+                    constexpr bool UNI = decltype(uc)::value;
+                    constexpr int str = (DIRECT || UNI) ? RP * RP : fpl_lds_stride(RP * RP);
+                    constexpr int after = PM::template right_after<H>(m);
+                    constexpr bool PAIR = !PM::mg(m) && PM::owner(m) == H, ACC = PM::mg(m) && PM::owner(PM::UR) == H;
+                    double nw[RP];
+                    const double *src = sK;
+                    FPP_STAMP(1)
+                    if constexpr (DIRECT || UNI) src = ro + A.core_off[m];
+                    else {
+                        pair_barrier();
+                        stage_core_image<H>(sK, A.img_base + A.pair_img_off[m], A.ngrid[m] * str);
+                        pair_barrier();
+                    }
+                    if constexpr (PM::rtab() && m == PL.rfirst) right_combine();
+                    FPP_STAMP(7)
+                    const double *G = src + (UNI ? iu : fi[m]) * str;
+                    if constexpr (PAIR || ACC) {
+                        double t0[1][RP], t1[1][RP];
 #pragma unroll
-                    for (int a = 0; a < RP; a++) { t0[0][a] = R[a]; t1[0][a] = R[a]; }
+                        for (int a = 0; a < RP; a++) { t0[0][a] = R[a]; t1[0][a] = R[a]; }
+                        if constexpr (DIRECT) {
+                            apply_glb<RP, 1, false>(src + nbm[m] * str, t0);
+                            apply_glb<RP, 1, false>(src + nbp[m] * str, t1);
+                        } else if constexpr (UNI) {
+                            apply_uni<RP, 1, false>(src + __builtin_amdgcn_readfirstlane(nbm[m]) * str, t0);
+                            apply_uni<RP, 1, false>(src + __builtin_amdgcn_readfirstlane(nbp[m]) * str, t1);
+                        } else {
+                            matvec_lds<RP, 1>(src + nbm[m] * str, t0);
+                            matvec_lds<RP, 1>(src + nbp[m] * str, t1);
+                        }
+#pragma unroll
+                        for (int a = 0; a < RP; a++) {
+                            if constexpr (PAIR) { W[NOL + after][a] = t0[0][a]; W[NOL + after + 1][a] = t1[0][a]; }
+                            else nw[a] = fma(rpp[m], t1[0][a], rpm[m] * t0[0][a]);
+                        }
+                    }
                     if constexpr (DIRECT) {
-                        apply_glb<RP, 1, false>(src + nbm[m] * str, t0);
-                        apply_glb<RP, 1, false>(src + nbp[m] * str, t1);
-                    } else {
-                        matvec_lds<RP, 1>(src + nbm[m] * str, t0);
-                        matvec_lds<RP, 1>(src + nbp[m] * str, t1);
+                        double tr[1][RP];
+#pragma unroll
+                        for (int a = 0; a < RP; a++) tr[0][a] = R[a];
+                        apply_glb<RP, 1, false>(G, tr);
+#pragma unroll
+                        for (int a = 0; a < RP; a++) R[a] = tr[0][a];
+                        apply_range_glb<RP, NOWN, NOL, after, false>(G, W);
+                    } else if constexpr (UNI)
+                        apply_uni_and<RP, NOWN, NOL, after, false>(G, W, R);
+                    else
+                        apply_core_and<RP, NOWN, NOL, after, false>(G, W, R);
+                    if constexpr (ACC) {
+                        constexpr int su = PM::template lslot<H>(PM::UR);
+#pragma unroll
+                        for (int a = 0; a < RP; a++) W[su][a] = (m == PM::first_r()) ? nw[a] : W[su][a] + nw[a];
                     }
-#pragma unroll
-                    for (int a = 0; a < RP; a++) {
-                        if constexpr (PAIR) { W[NOL + after][a] = t0[0][a]; W[NOL + after + 1][a] = t1[0][a]; }
-                        else nw[a] = fma(rpp[m], t1[0][a], rpm[m] * t0[0][a]);
-                    }
-                }
-                if constexpr (DIRECT) {
-                    double tr[1][RP];
-#pragma unroll
-                    for (int a = 0; a < RP; a++) tr[0][a] = R[a];
-                    apply_glb<RP, 1, false>(G, tr);
-#pragma unroll
-                    for (int a = 0; a < RP; a++) R[a] = tr[0][a];
-                    apply_range_glb<RP, NOWN, NOL, after, false>(G, W);
-                } else
-                    apply_core_and<RP, NOWN, NOL, after, false>(G, W, R);
-                if constexpr (ACC) {
-                    constexpr int su = PM::template lslot<H>(PM::UR);
-#pragma unroll
-                    for (int a = 0; a < RP; a++) W[su][a] = (m == PM::first_r()) ? nw[a] : W[su][a] + nw[a];
-                }
+                };
+                fold_level<GROUP && (m == KL.major || (KL.n > 1 && m == KL.minor))>(fi[m], body);
             };
             [&]<int... Ms>(std::integer_sequence<int, Ms...>) { (right_step(std::integral_constant<int, PL.rfirst - Ms>{}), ...); }
             (std::make_integer_sequence<int, (PL.rfirst - K > 0 ? PL.rfirst - K : 0)>{});

@@ -133,7 +133,11 @@ int c3sc_hip_set_variant(c3sc_hip_ctx *ctx, int variant);
  *   d_uidx     int32 [F*N_k] or NULL: winning candidate index, -1 for absorbed nodes
  *   d_absorbed int32 [F*N_k] or NULL: absorbed[] of process_fibers_neighbor (0 / 1 / -1)
  * Asynchronous on `stream`.  Large fiber-pair batches with an absorbing fixed dimension are partitioned on the device first
- * (live fibers first; C3SC_FIBER_PARTITION=0 in the environment switches that off, n > 0 sets the smallest such batch) into
+ * (live fibers first, grouped by the indices of the two fold levels next to k so that a tile's 64 fibers share those levels'
+ * matrices; C3SC_FIBER_PARTITION=0 in the environment switches the pass off, n > 0 sets the smallest such batch,
+ * C3SC_FIBER_GROUP=0 keeps the pass but leaves the live fibers in batch order, n > 0 sets the fewest fibers per key a level is
+ * grouped by -- meant for tests: 1 groups every batch, which costs a production batch more than it gains; the results do not
+ * depend on any of them) into
  * scratch the context owns: the Bellman launches of ONE context must be ordered with respect to each other (one stream, or
  * events between streams); c3sc_hip_bellman_fibers_all orders its own. */
 int c3sc_hip_bellman_fibers(c3sc_hip_ctx *ctx, int k, size_t F, const int32_t *d_idx, double *d_out,
@@ -539,6 +543,11 @@ int c3sc_hip_debug_read(c3sc_hip_ctx *ctx, unsigned long long *out, size_t n);
 /* diagnostics: Bellman / policy / stencil kernel launches made by this process so far (the reference calls its fiber
  * callback once per fiber, bellman.c:1295; here one launch serves a batch -- this counts them) */
 unsigned long long c3sc_hip_launch_count(void);
+/* tests: the last partition a fiber-pair launch ran in scratch block `slot` (0: the caller's stream and the single-launch entry
+ * points; 1, 2: the side streams of c3sc_hip_bellman_fibers_all).  Synchronises that launch's stream, then copies perm[F] (fiber
+ * of every tile position: live fibers first, grouped by the fold's key levels, dead ones last) into `perm` (cap entries; NULL: not
+ * wanted) and reports F and the number of live fibers.  An error if no partition has run on the slot. */
+int c3sc_hip_last_partition(c3sc_hip_ctx *ctx, int slot, int32_t *perm, size_t cap, size_t *F, int *nlive);
 
 /* device-side timing on `stream` with HIP events (used by bench.py's roofline leg) */
 int c3sc_hip_timer_start(c3sc_hip_ctx *ctx, void *stream);
