@@ -46,7 +46,7 @@ struct PartArgs {
 };
 
 // How many key levels a launch groups by: two, one or none, from F and the grid alone.  floor: fibers per bin (< 0: no grouping).
-inline void fpart_plan(PartArgs &P, KeyLevels kl, long floor)
+constexpr void fpart_plan(PartArgs &P, KeyLevels kl, long floor)
 {
     P.kmaj = P.kmin = -1;
     P.nmin = 1;
@@ -74,25 +74,33 @@ struct PartScratch {
 };
 
 __host__ __device__ constexpr size_t fpart_align(size_t b) { return (b + 255) & ~(size_t)255; }
-inline long fpart_blocks(long F) { return (F + FPART_BLOCK - 1) / FPART_BLOCK; }
-inline size_t fpart_bytes(long F, int nbins)
+constexpr long fpart_blocks(long F) { return (F + FPART_BLOCK - 1) / FPART_BLOCK; }
+// byte offsets of the regions in that block, in PartScratch's order; end: the size of the block
+struct PartOffsets {
+    size_t perm, counts, totals, nlive, bins, end;
+};
+constexpr PartOffsets fpart_offsets(long F, int nbins)
 {
-    return fpart_align((size_t)F * 4) + fpart_align((size_t)fpart_blocks(F) * nbins * 4) + fpart_align((size_t)nbins * 4) + fpart_align(4) +
-           fpart_align((size_t)F * 2);
+    PartOffsets o{};
+    o.perm = 0;
+    o.counts = o.perm + fpart_align((size_t)F * 4);
+    o.totals = o.counts + fpart_align((size_t)fpart_blocks(F) * nbins * 4);
+    o.nlive = o.totals + fpart_align((size_t)nbins * 4);
+    o.bins = o.nlive + fpart_align(4);
+    o.end = o.bins + fpart_align((size_t)F * 2);
+    return o;
 }
+constexpr size_t fpart_bytes(long F, int nbins) { return fpart_offsets(F, nbins).end; }
 inline PartScratch fpart_carve(void *base, long F, int nbins)
 {
+    const PartOffsets o = fpart_offsets(F, nbins);
     PartScratch s;
     char *p = (char *)base;
-    s.perm = (int32_t *)p;
-    p += fpart_align((size_t)F * 4);
-    s.counts = (int32_t *)p;
-    p += fpart_align((size_t)fpart_blocks(F) * nbins * 4);
-    s.totals = (int32_t *)p;
-    p += fpart_align((size_t)nbins * 4);
-    s.nlive = (int32_t *)p;
-    p += fpart_align(4);
-    s.bins = (uint16_t *)p;
+    s.perm = (int32_t *)(p + o.perm);
+    s.counts = (int32_t *)(p + o.counts);
+    s.totals = (int32_t *)(p + o.totals);
+    s.nlive = (int32_t *)(p + o.nlive);
+    s.bins = (uint16_t *)(p + o.bins);
     return s;
 }
 

@@ -25,6 +25,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import fiber_partition_ref as fp
 from c3sc_amd import workloads as wl
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -48,17 +49,9 @@ def key_levels(d, k, tab=True):
     return []
 
 
-OPTOUT = {("car7d", 10, 1)}  # kernel_common.hpp: fpp_group_fold_optout -- measured no faster: neither grouped nor folded from SGPRs
-
-
 def keys_in_use(w, k, F, floor=1):
     """fiber_partition.hpp: fpart_plan -- the key dimensions a batch of F fibers is grouped by"""
-    kl = [] if (w.name, max(w.ranks), k) in OPTOUT else key_levels(w.dx, k)
-    if not kl or F < floor * w.ngrid[kl[0]]:
-        return []
-    if len(kl) < 2 or F < floor * w.ngrid[kl[0]] * w.ngrid[kl[1]]:
-        return kl[:1]
-    return kl
+    return fp.plan(w, k, max(w.ranks), F, floor)[0]
 
 
 def _engine(w, cores, cends=0):
@@ -90,14 +83,6 @@ def _live_values(w, m):
     """indices of dimension m a live fiber may have, ascending: an absorbing dimension keeps off its faces"""
     n = w.ngrid[m]
     return list(range(1, n - 1)) if w.bc[m] == wl.BC_ABSORB else list(range(n))
-
-
-def _dead_mask(w, k, idx):
-    dead = np.zeros(idx.shape[0], dtype=bool)
-    for m in range(w.dx):
-        if m != k and w.bc[m] == wl.BC_ABSORB:
-            dead |= (idx[:, m] == 0) | (idx[:, m] == w.ngrid[m] - 1)
-    return dead
 
 
 def _live_rows(w, k, F, seed):
@@ -202,19 +187,7 @@ def _hold(out, ui, ab, ref, ref_ui, ref_ab, what):
 
 def _check_perm(w, k, idx, perm, nlive, keys):
     """the order fiber_partition.hpp promises, with `keys` the key dimensions in use (major first; empty: plain partition)"""
-    F = idx.shape[0]
-    assert perm.shape == (F,)
-    np.testing.assert_array_equal(np.sort(perm), np.arange(F))
-    dead = _dead_mask(w, k, idx)
-    assert nlive == int((~dead).sum())
-    assert not dead[perm[:nlive]].any() and dead[perm[nlive:]].all(), "live fibers first"
-    np.testing.assert_array_equal(perm[nlive:], np.flatnonzero(dead))  # dead fibers in batch order
-    key = np.zeros(F, dtype=np.int64)
-    for m in keys:
-        key = key * w.ngrid[m] + idx[:, m]
-    live = np.flatnonzero(~dead)
-    want = live[np.argsort(key[live], kind="stable")]  # keys ascending, batch order inside a key
-    np.testing.assert_array_equal(perm[:nlive], want)
+    fp.check_partition(w, k, idx, perm, nlive, keys)
 
 
 def _tile_structure(idx, perm, kl, ntiles):
