@@ -17,7 +17,9 @@
 //
 // Folding (once per 64-fiber tile): each wave folds the neighbour vectors of half of the dims (full
 // length, 6 x r doubles in registers) through the fixed cores staged in LDS -- exactly as the
-// fiber-per-lane kernel does -- and the halves are swapped through LDS afterwards.
+// fiber-per-lane kernel does -- and the halves are swapped through LDS afterwards.  What is mirrored about K is described once
+// (PairMap::Side) and the staged core steps of both sides are one routine (fold_step); the table rows and the lone edge core of
+// a side stand in fiber_pair_body once per side (moved into a callable they compile to the same instructions in another order).
 //
 // Budget: 128-thread workgroups, <= 256 VGPRs (2 waves per SIMD with 4 workgroups per CU), LDS = one
 // staged core (33 KB at N = 41, r = 10), reused as the exchange buffer during the node loop.
@@ -131,6 +133,13 @@ __device__ __forceinline__ void apply_uni_and(const double *__restrict__ G, doub
 #pragma unroll
         for (int a = 0; a < RP; a++) W[FIRST + s][a] = tmp[s + 1][a];
     apply_range_uni<RP, NW, FIRST + N1, COUNT - N1, ROWVEC, FPP_NV>(G, W);
+}
+
+// f(std::integral_constant<int, 0>{}), ..., f(std::integral_constant<int, N - 1>{}) in this order
+template <int N, class F>
+__device__ __forceinline__ void static_for(F &&f)
+{
+    [&]<int... Is>(std::integer_sequence<int, Is...>) { (f(std::integral_constant<int, Is>{}), ...); }(std::make_integer_sequence<int, N>{});
 }
 
 // One staged fold level: `body(uniform, index)` runs the level.  At a key level of the grouped fold (KEY) the tile is asked whether
@@ -281,73 +290,95 @@ template <class Model, int K, bool TAB = false>
 struct PairMap {
     typedef PairPark<Model, K> PK;
     static constexpr int D = Model::D, NIT = D + 2, UL = D, UR = D + 1;
-    __host__ __device__ static constexpr bool ltab() { return TAB && K >= 2; }     // cores 0, 1 enter through tabL
-    __host__ __device__ static constexpr bool rtab() { return TAB && K <= D - 3; } // cores d-2, d-1 through tabR
     __host__ __device__ static constexpr bool mg(int m) { return (PK::merged() >> m) & 1u; }
-    __host__ __device__ static constexpr int first_l()
-    { // the merged dimension at which U_L is created (the smallest), -1: none
-        for (int m = 0; m < K; m++)
-            if (mg(m)) return m;
-        return -1;
-    }
-    __host__ __device__ static constexpr int first_r()
-    { // ... U_R (the largest)
-        for (int m = D - 1; m > K; m--)
-            if (mg(m)) return m;
-        return -1;
-    }
+    // One side of K: the cores 0 .. K-1, folded ascending into the row vector L (LEFT), or D-1 .. K+1, folded descending into
+    // the column R.  Everything that is mirrored about K is written here once, in the side's own coordinate: the depth of a
+    // core, 0 at the edge core and NC at K.  The kernel runs the staged steps of both sides through it (fold_step).
+    template <bool LEFT>
+    struct Side {
+        static constexpr bool ROWVEC = LEFT;                                  // L <- L G_m, R <- G_m R
+        static constexpr int NC = LEFT ? K : D - 1 - K;                       // cores of the side
+        static constexpr int EDGE = LEFT ? 0 : D - 1;                         // the edge core
+        static constexpr int U = LEFT ? UL : UR;                              // the merged item
+        __host__ __device__ static constexpr int depth(int m) { return LEFT ? m : D - 1 - m; }
+        __host__ __device__ static constexpr int core(int q) { return LEFT ? q : D - 1 - q; }
+        // the product table (tabL: cores 0, 1; tabR: cores d-2, d-1) absorbs the edge core and the next
+        __host__ __device__ static constexpr bool tab() { return TAB && NC >= 2; }
+        // the staged steps: first(), then towards K
+        __host__ __device__ static constexpr int first() { return core(tab() ? 2 : 1); }
+        __host__ __device__ static constexpr int nsteps() { return NC - depth(first()) > 0 ? NC - depth(first()) : 0; }
+        __host__ __device__ static constexpr int step(int i) { return core(depth(first()) + i); }
+        __host__ __device__ static constexpr int first_merged()
+        { // the merged dimension at which U is created (the nearest to the edge), -1: none
+            for (int q = 0; q < NC; q++)
+                if (mg(core(q))) return core(q);
+            return -1;
+        }
+        __host__ __device__ static constexpr int nv()
+        {
+            int c = count(U);
+            for (int q = 0; q < NC; q++) c += count(core(q));
+            return c;
+        }
+        // fold work of U and of the pair of m in vector-matrix products (edge cores combine rows, the tables' levels are
+        // gathered rows: free)
+        __host__ __device__ static constexpr int cost_u()
+        {
+            int c = NC - 1 - depth(first_merged()) - (tab() && first_merged() == EDGE);
+            for (int q = depth(first()); q < NC; q++) c += 2 * mg(core(q));
+            return c;
+        }
+        __host__ __device__ static constexpr int cost_pair(int m)
+        {
+            return (tab() && depth(m) <= 1) ? 2 * (NC - 2) : (m != EDGE ? 2 : 0) + 2 * (NC - 1 - depth(m));
+        }
+        // the item the core step m creates: the pair of m, or U at its first merged dimension; -1: none
+        __host__ __device__ static constexpr int created(int m) { return !mg(m) ? m : (m == first_merged() ? U : -1); }
+        // own vectors of wave H that exist before the step m (created nearer to the edge): a wave keeps its vectors in creation
+        // order, left ones first
+        template <int H>
+        __host__ __device__ static constexpr int before(int m)
+        {
+            int c = 0;
+            for (int q = 0; q < depth(m) && q < NC; q++)
+                if (created(core(q)) >= 0 && owner(created(core(q))) == H) c += count(created(core(q)));
+            return c;
+        }
+        template <int H>
+        __host__ __device__ static constexpr int base() { return LEFT ? 0 : Side<true>::template before<H>(K); } // first slot in W
+        template <int H>
+        __host__ __device__ static constexpr int slot(int it) { return base<H>() + before<H>(it == U ? first_merged() : it); }
+    };
+    typedef Side<true> SL;
+    typedef Side<false> SR;
     __host__ __device__ static constexpr bool valid(int it)
     {
-        return it == UL ? first_l() >= 0 : (it == UR ? first_r() >= 0 : (it != K && !mg(it)));
+        return it == UL ? SL::first_merged() >= 0 : (it == UR ? SR::first_merged() >= 0 : (it != K && !mg(it)));
     }
     __host__ __device__ static constexpr int count(int it) { return !valid(it) ? 0 : (it < D ? 2 : 1); }
-    __host__ __device__ static constexpr int nvl()
-    {
-        int c = count(UL);
-        for (int m = 0; m < K; m++) c += count(m);
-        return c;
-    }
-    __host__ __device__ static constexpr int nvr()
-    {
-        int c = count(UR);
-        for (int m = K + 1; m < D; m++) c += count(m);
-        return c;
-    }
-    __host__ __device__ static constexpr int nv() { return nvl() + nvr(); }
+    __host__ __device__ static constexpr int nv() { return SL::nv() + SR::nv(); }
     __host__ __device__ static constexpr int gslot(int it)
     { // first node-loop slot of an item
         if (it == UL) return 0;
-        if (it == UR) return nvl();
-        int c = it < K ? count(UL) : nvl() + count(UR);
+        if (it == UR) return SL::nv();
+        int c = it < K ? count(UL) : SL::nv() + count(UR);
         for (int m = it < K ? 0 : K + 1; m < it; m++) c += count(m);
         return c;
     }
-    // fold work of an item in vector-matrix products (edge cores combine rows, the tables' levels are gathered rows: free)
     __host__ __device__ static constexpr int cost(int it)
     {
         if (!valid(it)) return 0;
-        constexpr int lf = ltab() ? 2 : 1, rf = rtab() ? D - 3 : D - 2; // plan().lfirst, .rfirst
-        if (it == UL) {
-            int c = K - 1 - first_l() - (ltab() && first_l() == 0);
-            for (int m = lf; m < K; m++) c += 2 * mg(m);
-            return c;
-        }
-        if (it == UR) {
-            int c = first_r() - K - 1 - (rtab() && first_r() == D - 1);
-            for (int m = K + 1; m <= rf; m++) c += 2 * mg(m);
-            return c;
-        }
-        if (it < K) return (ltab() && it <= 1) ? 2 * (K - 2) : (it > 0 ? 2 : 0) + 2 * (K - 1 - it);
-        return (rtab() && it >= D - 2) ? 2 * (D - 3 - K) : (it < D - 1 ? 2 : 0) + 2 * (it - K - 1);
+        if (it == UL) return SL::cost_u();
+        if (it == UR) return SR::cost_u();
+        return it < K ? SL::cost_pair(it) : SR::cost_pair(it);
     }
     // What the fold of a tile does: the kernel takes its step ranges from here, the tests its counts.
     __host__ __device__ static constexpr FoldPlan plan()
     {
         // an edge core on its own is staged too unless the tables are on (then it is read from the arena)
-        FoldPlan p{ltab() ? 2 : 1, rtab() ? D - 3 : D - 2, K > 0 && !TAB, K < D - 1 && !TAB, 0, 0};
-        const int ls = K - p.lfirst > 0 ? K - p.lfirst : 0, rs = p.rfirst - K > 0 ? p.rfirst - K : 0;
-        p.staged = ls + rs + p.ledge + p.redge;
-        p.products = ls + rs; // L and R through every staged middle core
+        FoldPlan p{SL::first(), SR::first(), K > 0 && !TAB, K < D - 1 && !TAB, 0, 0};
+        p.staged = SL::nsteps() + SR::nsteps() + p.ledge + p.redge;
+        p.products = SL::nsteps() + SR::nsteps(); // L and R through every staged middle core
         for (int it = 0; it < NIT; it++) p.products += cost(it);
         return p;
     }
@@ -356,7 +387,7 @@ struct PairMap {
     // and the level's staging round is left out.  The sum over all staged levels is plan().products.
     __host__ __device__ static constexpr int level_products(int m)
     {
-        return 3 + (m < K ? left_before<0>(m) + left_before<1>(m) : right_after<0>(m) + right_after<1>(m));
+        return 3 + (m < K ? SL::template before<0>(m) + SL::template before<1>(m) : SR::template before<0>(m) + SR::template before<1>(m));
     }
     __host__ __device__ static constexpr int uniform_rounds() { return fpp_key_levels(D, K, TAB).n; }
     __host__ __device__ static constexpr int uniform_products()
@@ -384,37 +415,10 @@ struct PairMap {
         }
         return own[it];
     }
-    // the item a left (right) core step m creates: the pair of m, or U at its first merged dimension; -1: none
-    __host__ __device__ static constexpr int created(int m)
-    {
-        if (m == K) return -1;
-        if (!mg(m)) return m;
-        return m < K ? (m == first_l() ? UL : -1) : (m == first_r() ? UR : -1);
-    }
-    // own vectors of wave H that exist before the left step m (created at dimensions < m), resp. before the right step m (> m):
-    // a wave keeps its vectors in creation order, left ones first
-    template <int H>
-    __host__ __device__ static constexpr int left_before(int m)
-    {
-        int c = 0;
-        for (int q = 0; q < m && q < K; q++)
-            if (created(q) >= 0 && owner(created(q)) == H) c += count(created(q));
-        return c;
-    }
-    template <int H>
-    __host__ __device__ static constexpr int right_after(int m)
-    {
-        int c = 0;
-        for (int q = D - 1; q > m && q > K; q--)
-            if (created(q) >= 0 && owner(created(q)) == H) c += count(created(q));
-        return c;
-    }
     template <int H>
     __host__ __device__ static constexpr int lslot(int it)
     { // slot of an item in its owner's W
-        if (it == UL) return left_before<H>(first_l());
-        if (it == UR) return left_before<H>(K) + right_after<H>(first_r());
-        return it < K ? left_before<H>(it) : left_before<H>(K) + right_after<H>(it);
+        return (it == UL || it < K) ? SL::template slot<H>(it) : SR::template slot<H>(it);
     }
 };
 
@@ -462,6 +466,87 @@ struct PairPre {
         tlast = now__;                                                    \
     }
 
+// One staged core step m of a side (PairMap::Side): the side's running vector V (L or R) and the own vectors W[BASE ..) of wavefront
+// H through G_m[i_m]; `combine` is the side's table combine, run behind the side's first staging round.  The tile's locals come as
+// arguments and fiber_pair_body calls it from one small lambda per side (left_step, right_step): with the closures of the body
+// where they were when each side had its own copy, every pair kernel compiles to the instructions it compiled to then.
+template <class Model, int RP, int K, int H, bool PART, bool LEFT, int m, int NOWN, class Combine>
+__device__ __attribute__((always_inline)) inline void fold_step(const KArgs &A, const double *__restrict__ ro, double *sK,
+                                                               const int (&fi)[Model::D], const int (&nbm)[Model::D], const int (&nbp)[Model::D],
+                                                               const double (&rpm)[Model::D], const double (&rpp)[Model::D], double (&V)[RP],
+                                                               double (&W)[NOWN][RP], unsigned long long (&seg)[12], unsigned long long &tlast,
+                                                               Combine &&combine)
+{
+    constexpr int D = Model::D;
+    constexpr bool DIRECT = fpp_direct<Model, RP>();
+    typedef PairMap<Model, K, fpp_edge_tables<Model, RP>()> PM;
+    typedef typename PM::template Side<LEFT> SD;
+    constexpr bool RV = SD::ROWVEC;
+    constexpr int BASE = SD::template base<H>();
+    constexpr KeyLevels KL = fpp_group_levels(D, RP, K);
+    constexpr bool GROUP = PART && KL.n > 0;
+    // UNI: the tile shares fi[m] = iu -- one matrix per product, from the arena on the scalar path, nothing staged
+    auto body = [&](auto uc, int iu) __attribute__((always_inline)) {
+        constexpr bool UNI = decltype(uc)::value;
+        constexpr int str = (DIRECT || UNI) ? RP * RP : fpl_lds_stride(RP * RP);
+        constexpr int before = SD::template before<H>(m); // own vectors created so far
+        constexpr bool PAIR = !PM::mg(m) && PM::owner(m) == H, ACC = PM::mg(m) && PM::owner(SD::U) == H;
+        double nw[RP]; // a merged dimension's share of U
+        const double *src = sK;
+        FPP_STAMP(1)
+        if constexpr (DIRECT || UNI) src = ro + A.core_off[m];
+        else {
+            pair_barrier();
+            stage_core_image<H>(sK, A.img_base + A.pair_img_off[m], A.ngrid[m] * str);
+            pair_barrier();
+        }
+        if constexpr (SD::tab() && m == SD::first()) combine();
+        FPP_STAMP(7)
+        const double *G = src + (UNI ? iu : fi[m]) * str;
+        if constexpr (PAIR || ACC) { // the new pair first: it needs the prefix (suffix) BEFORE this core
+            double t0[1][RP], t1[1][RP];
+#pragma unroll
+            for (int a = 0; a < RP; a++) { t0[0][a] = V[a]; t1[0][a] = V[a]; }
+            if constexpr (DIRECT) {
+                apply_glb<RP, 1, RV>(src + nbm[m] * str, t0);
+                apply_glb<RP, 1, RV>(src + nbp[m] * str, t1);
+            } else if constexpr (UNI) { // functions of the shared index: uniform too
+                apply_uni<RP, 1, RV>(src + __builtin_amdgcn_readfirstlane(nbm[m]) * str, t0);
+                apply_uni<RP, 1, RV>(src + __builtin_amdgcn_readfirstlane(nbp[m]) * str, t1);
+            } else if constexpr (RV) {
+                vecmat_lds<RP, 1>(src + nbm[m] * str, t0);
+                vecmat_lds<RP, 1>(src + nbp[m] * str, t1);
+            } else {
+                matvec_lds<RP, 1>(src + nbm[m] * str, t0);
+                matvec_lds<RP, 1>(src + nbp[m] * str, t1);
+            }
+#pragma unroll
+            for (int a = 0; a < RP; a++) {
+                if constexpr (PAIR) { W[BASE + before][a] = t0[0][a]; W[BASE + before + 1][a] = t1[0][a]; }
+                else nw[a] = fma(rpp[m], t1[0][a], rpm[m] * t0[0][a]);
+            }
+        }
+        if constexpr (DIRECT) {
+            double tl[1][RP];
+#pragma unroll
+            for (int a = 0; a < RP; a++) tl[0][a] = V[a];
+            apply_glb<RP, 1, RV>(G, tl);
+#pragma unroll
+            for (int a = 0; a < RP; a++) V[a] = tl[0][a];
+            apply_range_glb<RP, NOWN, BASE, before, RV>(G, W);
+        } else if constexpr (UNI)
+            apply_uni_and<RP, NOWN, BASE, before, RV>(G, W, V);
+        else
+            apply_core_and<RP, NOWN, BASE, before, RV>(G, W, V);
+        if constexpr (ACC) { // U: created here, or carried through this core above and added to
+            constexpr int su = SD::template slot<H>(SD::U);
+#pragma unroll
+            for (int a = 0; a < RP; a++) W[su][a] = (m == SD::first_merged()) ? nw[a] : W[su][a] + nw[a];
+        }
+    };
+    fold_level<GROUP && (m == KL.major || (KL.n > 1 && m == KL.minor))>(fi[m], body);
+}
+
 template <class Model, int RP, int K, int H, bool FORCED, bool PART>
 __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArgs &A, const double *__restrict__ ro,
                                                                      const int32_t *__restrict__ idx, double *__restrict__ outv,
@@ -477,9 +562,9 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
     typedef PairMap<Model, K, ET> PM;
     constexpr FoldPlan PL = PM::plan();
     constexpr int NV = PM::nv();                            // folded vectors in total: 2(D-1) when nothing is merged
-    constexpr int NVL = PM::nvl();                          // ... of which left of K (dotted with c)
-    constexpr int NOL = PM::template left_before<H>(K);     // own left vectors (slots [0, NOL))
-    constexpr int NOR = PM::template right_after<H>(K);     // own right vectors (slots [NOL, NOL+NOR))
+    constexpr int NVL = PM::SL::nv();                       // ... of which left of K (dotted with c)
+    constexpr int NOL = PM::SL::template before<H>(K);      // own left vectors (slots [0, NOL))
+    constexpr int NOR = PM::SR::template before<H>(K);      // own right vectors (slots [NOL, NOL+NOR))
     constexpr int NOWN = (NOL + NOR) > 0 ? (NOL + NOR) : 1;
     constexpr int NP = NV + 1; // partial sums per node: NV neighbour values + the node value
     constexpr bool DIRECT = fpp_direct<Model, RP>();
@@ -596,10 +681,10 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
         if constexpr (K > 0) {
             // rows of tabL: T(a, b) = G_0[a] G_1[b].  All loads of the side are issued here, ahead of the first staging round,
             // and combined (left_combine) behind it: their L2 round trip runs under the staging wait.
-            constexpr bool OWN0 = PM::ltab() && (PM::mg(0) ? PM::owner(PM::UL) == H : PM::owner(0) == H);
-            constexpr bool OWN1 = PM::ltab() && (PM::mg(1) ? PM::owner(PM::UL) == H : PM::owner(1) == H);
+            constexpr bool OWN0 = PM::SL::tab() && (PM::mg(0) ? PM::owner(PM::UL) == H : PM::owner(0) == H);
+            constexpr bool OWN1 = PM::SL::tab() && (PM::mg(1) ? PM::owner(PM::UL) == H : PM::owner(1) == H);
             double t0m[OWN0 ? RP : 1], t0p[OWN0 ? RP : 1], t1m[OWN1 ? RP : 1], t1p[OWN1 ? RP : 1];
-            if constexpr (PM::ltab()) {
+            if constexpr (PM::SL::tab()) {
                 const double *T = ro + pair_tabL_off(A, RP);
                 const int n1 = A.ngrid[1];
                 load_row16<RP>(T + ((long)fi[0] * n1 + fi[1]) * RP, L);
@@ -613,7 +698,7 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
-            auto left_combine = [&]() __attribute__((always_inline)) { // what the edge block and left_step<1> leave in W
+            auto left_combine = [&]() __attribute__((always_inline)) { // what the edge block and the step of core 1 leave in W
                 if constexpr (OWN0) {
 #pragma unroll
                     for (int b = 0; b < RP; b++) {
@@ -622,19 +707,19 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
                     }
                 }
                 if constexpr (OWN1) {
-                    constexpr int before = PM::template left_before<H>(1);
+                    constexpr int before = PM::SL::template before<H>(1);
 #pragma unroll
                     for (int b = 0; b < RP; b++) {
                         if constexpr (PM::mg(1)) {
                             constexpr int su = PM::template lslot<H>(PM::UL);
                             const double nw = fma(rpp[1], t1p[b], rpm[1] * t1m[b]);
-                            W[su][b] = (1 == PM::first_l()) ? nw : W[su][b] + nw;
+                            W[su][b] = (1 == PM::SL::first_merged()) ? nw : W[su][b] + nw;
                         } else { W[before][b] = t1m[b]; W[before + 1][b] = t1p[b]; }
                     }
                 }
             };
-            if constexpr (PM::ltab() && K == PL.lfirst) left_combine(); // no staged core on this side
-            if constexpr (!PM::ltab()) {
+            if constexpr (PM::SL::tab() && K == PL.lfirst) left_combine(); // no staged core on this side
+            if constexpr (!PM::SL::tab()) {
                 constexpr bool GLB = DIRECT || !PL.ledge; // tables on, K = 1: the lone edge core straight from the arena
                 constexpr int str = GLB ? RP : fpl_lds_stride(RP);
                 const double *src = sK;
@@ -658,76 +743,18 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
                 }
             }
             auto left_step = [&](auto mc) __attribute__((always_inline)) {
-                constexpr int m = decltype(mc)::value;
-                // UNI: the tile shares fi[m] = iu -- one matrix per product, from the arena on the scalar path, nothing staged
-                auto body = [&](auto uc, int iu) __attribute__((always_inline)) {
-                    constexpr bool UNI = decltype(uc)::value;
-                    constexpr int str = (DIRECT || UNI) ? RP * RP : fpl_lds_stride(RP * RP);
-                    constexpr int before = PM::template left_before<H>(m); // own vectors created so far
-                    constexpr bool PAIR = !PM::mg(m) && PM::owner(m) == H, ACC = PM::mg(m) && PM::owner(PM::UL) == H;
-                    double nw[RP]; // a merged dimension's share of U_L
-                    const double *src = sK;
-                    FPP_STAMP(1)
-                    if constexpr (DIRECT || UNI) src = ro + A.core_off[m];
-                    else {
-                        pair_barrier();
-                        stage_core_image<H>(sK, A.img_base + A.pair_img_off[m], A.ngrid[m] * str);
-                        pair_barrier();
-                    }
-                    if constexpr (PM::ltab() && m == PL.lfirst) left_combine();
-                    FPP_STAMP(7)
-                    const double *G = src + (UNI ? iu : fi[m]) * str;
-                    if constexpr (PAIR || ACC) { // the new pair first: it needs the prefix BEFORE this core
-                        double t0[1][RP], t1[1][RP];
-#pragma unroll
-                        for (int a = 0; a < RP; a++) { t0[0][a] = L[a]; t1[0][a] = L[a]; }
-                        if constexpr (DIRECT) {
-                            apply_glb<RP, 1, true>(src + nbm[m] * str, t0);
-                            apply_glb<RP, 1, true>(src + nbp[m] * str, t1);
-                        } else if constexpr (UNI) { // functions of the shared index: uniform too
-                            apply_uni<RP, 1, true>(src + __builtin_amdgcn_readfirstlane(nbm[m]) * str, t0);
-                            apply_uni<RP, 1, true>(src + __builtin_amdgcn_readfirstlane(nbp[m]) * str, t1);
-                        } else {
-                            vecmat_lds<RP, 1>(src + nbm[m] * str, t0);
-                            vecmat_lds<RP, 1>(src + nbp[m] * str, t1);
-                        }
-#pragma unroll
-                        for (int a = 0; a < RP; a++) {
-                            if constexpr (PAIR) { W[before][a] = t0[0][a]; W[before + 1][a] = t1[0][a]; }
-                            else nw[a] = fma(rpp[m], t1[0][a], rpm[m] * t0[0][a]);
-                        }
-                    }
-                    if constexpr (DIRECT) {
-                        double tl[1][RP];
-#pragma unroll
-                        for (int a = 0; a < RP; a++) tl[0][a] = L[a];
-                        apply_glb<RP, 1, true>(G, tl);
-#pragma unroll
-                        for (int a = 0; a < RP; a++) L[a] = tl[0][a];
-                        apply_range_glb<RP, NOWN, 0, before, true>(G, W);
-                    } else if constexpr (UNI)
-                        apply_uni_and<RP, NOWN, 0, before, true>(G, W, L);
-                    else
-                        apply_core_and<RP, NOWN, 0, before, true>(G, W, L);
-                    if constexpr (ACC) { // U_L: created here, or carried through this core above and added to
-                        constexpr int su = PM::template lslot<H>(PM::UL);
-#pragma unroll
-                        for (int a = 0; a < RP; a++) W[su][a] = (m == PM::first_l()) ? nw[a] : W[su][a] + nw[a];
-                    }
-                };
-                fold_level<GROUP && (m == KL.major || (KL.n > 1 && m == KL.minor))>(fi[m], body);
+                fold_step<Model, RP, K, H, PART, true, decltype(mc)::value>(A, ro, sK, fi, nbm, nbp, rpm, rpp, L, W, seg, tlast, left_combine);
             };
-            [&]<int... Ms>(std::integer_sequence<int, Ms...>) { (left_step(std::integral_constant<int, Ms + PL.lfirst>{}), ...); }
-            (std::make_integer_sequence<int, (K > PL.lfirst ? K - PL.lfirst : 0)>{});
+            static_for<PM::SL::nsteps()>([&](auto ic) __attribute__((always_inline)) { left_step(std::integral_constant<int, PM::SL::step(decltype(ic)::value)>{}); });
         }
 
         // ------------------------------------------------------------ fold the suffix side
         if constexpr (K < D - 1) {
             // rows of tabR: T(a, b) = G_{d-2}[a] G_{d-1}[b], as on the left
-            constexpr bool OWN0 = PM::rtab() && (PM::mg(D - 1) ? PM::owner(PM::UR) == H : PM::owner(D - 1) == H);
-            constexpr bool OWN1 = PM::rtab() && (PM::mg(D - 2) ? PM::owner(PM::UR) == H : PM::owner(D - 2) == H);
+            constexpr bool OWN0 = PM::SR::tab() && (PM::mg(D - 1) ? PM::owner(PM::UR) == H : PM::owner(D - 1) == H);
+            constexpr bool OWN1 = PM::SR::tab() && (PM::mg(D - 2) ? PM::owner(PM::UR) == H : PM::owner(D - 2) == H);
             double t0m[OWN0 ? RP : 1], t0p[OWN0 ? RP : 1], t1m[OWN1 ? RP : 1], t1p[OWN1 ? RP : 1];
-            if constexpr (PM::rtab()) {
+            if constexpr (PM::SR::tab()) {
                 const double *T = ro + pair_tabR_off(A, RP);
                 const int n1 = A.ngrid[D - 1];
                 load_row16<RP>(T + ((long)fi[D - 2] * n1 + fi[D - 1]) * RP, R);
@@ -741,7 +768,7 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
-            auto right_combine = [&]() __attribute__((always_inline)) { // what the edge block and right_step<D-2> leave in W
+            auto right_combine = [&]() __attribute__((always_inline)) { // what the edge block and the step of core d-2 leave in W
                 if constexpr (OWN0) {
 #pragma unroll
                     for (int a = 0; a < RP; a++) {
@@ -750,19 +777,19 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
                     }
                 }
                 if constexpr (OWN1) {
-                    constexpr int after = PM::template right_after<H>(D - 2);
+                    constexpr int after = PM::SR::template before<H>(D - 2);
 #pragma unroll
                     for (int a = 0; a < RP; a++) {
                         if constexpr (PM::mg(D - 2)) {
                             constexpr int su = PM::template lslot<H>(PM::UR);
                             const double nw = fma(rpp[D - 2], t1p[a], rpm[D - 2] * t1m[a]);
-                            W[su][a] = (D - 2 == PM::first_r()) ? nw : W[su][a] + nw;
+                            W[su][a] = (D - 2 == PM::SR::first_merged()) ? nw : W[su][a] + nw;
                         } else { W[NOL + after][a] = t1m[a]; W[NOL + after + 1][a] = t1p[a]; }
                     }
                 }
             };
-            if constexpr (PM::rtab() && K == PL.rfirst) right_combine(); // no staged core on this side
-            if constexpr (!PM::rtab()) {
+            if constexpr (PM::SR::tab() && K == PL.rfirst) right_combine(); // no staged core on this side
+            if constexpr (!PM::SR::tab()) {
                 constexpr bool GLB = DIRECT || !PL.redge; // tables on, K = d-2: the lone edge core straight from the arena
                 constexpr int str = GLB ? RP : fpl_lds_stride(RP);
                 const double *src = sK;
@@ -787,66 +814,9 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
                 }
             }
             auto right_step = [&](auto mc) __attribute__((always_inline)) {
-                constexpr int m = decltype(mc)::value; // D-2 down to K+1
-                auto body = [&](auto uc, int iu) __attribute__((always_inline)) { // UNI: as in left_step
-                    constexpr bool UNI = decltype(uc)::value;
-                    constexpr int str = (DIRECT || UNI) ? RP * RP : fpl_lds_stride(RP * RP);
-                    constexpr int after = PM::template right_after<H>(m);
-                    constexpr bool PAIR = !PM::mg(m) && PM::owner(m) == H, ACC = PM::mg(m) && PM::owner(PM::UR) == H;
-                    double nw[RP];
-                    const double *src = sK;
-                    FPP_STAMP(1)
-                    if constexpr (DIRECT || UNI) src = ro + A.core_off[m];
-                    else {
-                        pair_barrier();
-                        stage_core_image<H>(sK, A.img_base + A.pair_img_off[m], A.ngrid[m] * str);
-                        pair_barrier();
-                    }
-                    if constexpr (PM::rtab() && m == PL.rfirst) right_combine();
-                    FPP_STAMP(7)
-                    const double *G = src + (UNI ? iu : fi[m]) * str;
-                    if constexpr (PAIR || ACC) {
-                        double t0[1][RP], t1[1][RP];
-#pragma unroll
-                        for (int a = 0; a < RP; a++) { t0[0][a] = R[a]; t1[0][a] = R[a]; }
-                        if constexpr (DIRECT) {
-                            apply_glb<RP, 1, false>(src + nbm[m] * str, t0);
-                            apply_glb<RP, 1, false>(src + nbp[m] * str, t1);
-                        } else if constexpr (UNI) {
-                            apply_uni<RP, 1, false>(src + __builtin_amdgcn_readfirstlane(nbm[m]) * str, t0);
-                            apply_uni<RP, 1, false>(src + __builtin_amdgcn_readfirstlane(nbp[m]) * str, t1);
-                        } else {
-                            matvec_lds<RP, 1>(src + nbm[m] * str, t0);
-                            matvec_lds<RP, 1>(src + nbp[m] * str, t1);
-                        }
-#pragma unroll
-                        for (int a = 0; a < RP; a++) {
-                            if constexpr (PAIR) { W[NOL + after][a] = t0[0][a]; W[NOL + after + 1][a] = t1[0][a]; }
-                            else nw[a] = fma(rpp[m], t1[0][a], rpm[m] * t0[0][a]);
-                        }
-                    }
-                    if constexpr (DIRECT) {
-                        double tr[1][RP];
-#pragma unroll
-                        for (int a = 0; a < RP; a++) tr[0][a] = R[a];
-                        apply_glb<RP, 1, false>(G, tr);
-#pragma unroll
-                        for (int a = 0; a < RP; a++) R[a] = tr[0][a];
-                        apply_range_glb<RP, NOWN, NOL, after, false>(G, W);
-                    } else if constexpr (UNI)
-                        apply_uni_and<RP, NOWN, NOL, after, false>(G, W, R);
-                    else
-                        apply_core_and<RP, NOWN, NOL, after, false>(G, W, R);
-                    if constexpr (ACC) {
-                        constexpr int su = PM::template lslot<H>(PM::UR);
-#pragma unroll
-                        for (int a = 0; a < RP; a++) W[su][a] = (m == PM::first_r()) ? nw[a] : W[su][a] + nw[a];
-                    }
-                };
-                fold_level<GROUP && (m == KL.major || (KL.n > 1 && m == KL.minor))>(fi[m], body);
+                fold_step<Model, RP, K, H, PART, false, decltype(mc)::value>(A, ro, sK, fi, nbm, nbp, rpm, rpp, R, W, seg, tlast, right_combine);
             };
-            [&]<int... Ms>(std::integer_sequence<int, Ms...>) { (right_step(std::integral_constant<int, PL.rfirst - Ms>{}), ...); }
-            (std::make_integer_sequence<int, (PL.rfirst - K > 0 ? PL.rfirst - K : 0)>{});
+            static_for<PM::SR::nsteps()>([&](auto ic) __attribute__((always_inline)) { right_step(std::integral_constant<int, PM::SR::step(decltype(ic)::value)>{}); });
         }
 
         } // dbg & 1
@@ -887,11 +857,9 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
             };
             auto half = [&](auto pc) __attribute__((always_inline)) {
                 pair_barrier();
-                [&]<int... Ms>(std::integer_sequence<int, Ms...>) { (put_get_own(std::integral_constant<int, Ms>{}, pc), ...); }
-                (std::make_integer_sequence<int, PM::NIT>{});
+                static_for<PM::NIT>([&](auto ic) __attribute__((always_inline)) { put_get_own(ic, pc); });
                 pair_barrier();
-                [&]<int... Ms>(std::integer_sequence<int, Ms...>) { (get_other(std::integral_constant<int, Ms>{}, pc), ...); }
-                (std::make_integer_sequence<int, PM::NIT>{});
+                static_for<PM::NIT>([&](auto ic) __attribute__((always_inline)) { get_other(ic, pc); });
             };
             half(std::integral_constant<int, 0>{});
             half(std::integral_constant<int, 1>{});
@@ -914,8 +882,7 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
                     }
                 }
             };
-            [&]<int... Ms>(std::integer_sequence<int, Ms...>) { (put_get_own(std::integral_constant<int, Ms>{}), ...); }
-            (std::make_integer_sequence<int, PM::NIT>{});
+            static_for<PM::NIT>(put_get_own);
             pair_barrier();
             auto get_other = [&](auto ic) __attribute__((always_inline)) {
                 constexpr int it = decltype(ic)::value;
@@ -928,8 +895,7 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
                     }
                 }
             };
-            [&]<int... Ms>(std::integer_sequence<int, Ms...>) { (get_other(std::integral_constant<int, Ms>{}), ...); }
-            (std::make_integer_sequence<int, PM::NIT>{});
+            static_for<PM::NIT>(get_other);
             pair_barrier();
         }
         // L and R move to LDS (rows of 64 lanes): both waves hold the same values, wave 0 stores L, wave 1 R.
