@@ -96,6 +96,37 @@ __global__ void k_core_images(double *__restrict__ arena, const ImgJobs J)
     }
 }
 
+// The fiber-pair kernel's three-core product tables (kernel_common.hpp: pair_tab3L_off), one thread per entry, blockIdx.y = side:
+//   left:  row (c, a, b)[beta]  = sum_alpha tabL(a, b)[alpha] G_2[c][alpha + beta RP]
+//   right: row (a, b, c)[alpha] = sum_beta  G_{d-3}[a][alpha + beta RP] tabR(b, c)[beta]
+// Each entry is ONE fma chain from 0.0 with the summed index ascending, as in k_core_images: a row is bit for bit the two-core row
+// pushed through the third core by vecmat_lds / matvec_lds or the uniform products.  Inputs are the padded core and the two-core
+// table, so padding stays exact zero.
+struct Tab3Jobs {
+    long tab2[2], core[2], dst[2]; // the side's two-core table, its third core, the three-core table
+    int n3[2], npairs[2];          // nodes of the third core; index pairs of the two-core table
+};
+__global__ void k_pair_tab3(double *__restrict__ arena, const Tab3Jobs J, int RP)
+{
+    const int sd = blockIdx.y;
+    const bool left = sd == 0;
+    const double *tab2 = arena + J.tab2[sd], *core = arena + J.core[sd];
+    double *dst = arena + J.dst[sd];
+    const long np = J.npairs[sd], total = (long)J.n3[sd] * np * RP;
+    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
+        const long row = e / RP;
+        const int c = (int)(e - row * RP);
+        // left: the third index is the slowest of the row; right: it is the slowest too (a = i_{d-3}), the pair (b, c) behind it
+        const long i3 = row / np, pair = row - i3 * np;
+        const double *vec = tab2 + pair * RP;
+        const double *mat = left ? core + i3 * RP * RP + (long)c * RP : core + i3 * RP * RP + c;
+        const int ms = left ? 1 : RP;
+        double t = 0.0;
+        for (int s = 0; s < RP; s++) t = fma(vec[s], mat[(long)s * ms], t);
+        dst[e] = t;
+    }
+}
+
 // Derived copies of a rank-padded middle core for the fiber-quad kernel (kernel_fiber_quad.hpp), made on the device from
 // the padded core itself: (1) the row-major transpose, (2) the two MFMA A operands of the varying-core products
 // c = G R (x = a, y = b) and a = L G (x = b, y = a): element [prod][mb][s][l] = M[x][y] with x = (i%4) C + 4 mb + i/4
@@ -283,6 +314,7 @@ static int pick_rp(int d, int maxrank, int model, int variant)
     return rp;
 }
 
+static unsigned long long g_tab3_launches = 0; // ... of which fiber-pair launches with the three-core tables (c3sc_hip_table3_launch_count)
 static unsigned long long g_launches = 0; // Bellman / stencil kernel launches of this process (c3sc_hip_launch_count)
 static int fill_args(c3sc_hip_ctx *c, int k, size_t F, KArgs &A, bool need_model);
 
@@ -455,6 +487,7 @@ void c3sc_hip_ctx_destroy(c3sc_hip_ctx *c)
         if (c->join_ev[i]) (void)hipEventDestroy(c->join_ev[i]);
     }
     if (c->fork_ev) (void)hipEventDestroy(c->fork_ev);
+    if (c->tab3_ev) (void)hipEventDestroy(c->tab3_ev);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     delete c;
@@ -682,6 +715,14 @@ static int prepare_value(c3sc_hip_ctx *c, const size_t *ranks, size_t *cores_dou
         tabR_off = (long)off;
         off += (size_t)pair_tab_doubles(c->ngrid[d - 2], c->ngrid[d - 1], rp);
     }
+    // the three-core tables behind them, where a three-core instantiation exists and the tables stay within their memory bound
+    long tab3L_off = 0, tab3R_off = 0;
+    if (tabL_off && pair_tab3_reserved(d, c->ngrid, rp)) {
+        tab3L_off = (long)off;
+        off += (size_t)pair_tab3_doubles(c->ngrid[0], c->ngrid[1], c->ngrid[2], rp);
+        tab3R_off = (long)off;
+        off += (size_t)pair_tab3_doubles(c->ngrid[d - 3], c->ngrid[d - 2], c->ngrid[d - 1], rp);
+    }
     long qimgL_off[MAXD] = {0}, qimgR_off[MAXD] = {0};
     if (rp % 4 == 0 && have_quad) { // LDS images for the duo kernel's double-buffered LDS-DMA staging
         for (int m = 0; m < d; m++) {
@@ -704,6 +745,9 @@ static int prepare_value(c3sc_hip_ctx *c, const size_t *ranks, size_t *cores_dou
     for (int m = 0; m < d; m++) { c->core_off[m] = core_off[m]; c->coreT_off[m] = coreT_off[m]; c->aop_off[m] = aop_off[m]; c->img_off[m] = img_off[m]; c->qimgL_off[m] = qimgL_off[m]; c->qimgR_off[m] = qimgR_off[m]; }
     c->tabL_off = tabL_off;
     c->tabR_off = tabR_off;
+    c->tab3L_off = tab3L_off;
+    c->tab3R_off = tab3R_off;
+    c->tab3_stale = true; // both upload paths come through here: the next three-core launch rebuilds the tables (ensure_tab3)
     for (int m = 0; m <= d; m++) c->ranks[m] = ranks[m];
     c->rp = rp;
     *cores_doubles = primary_end - stat;
@@ -894,6 +938,8 @@ static int fill_args(c3sc_hip_ctx *c, int k, size_t F, KArgs &A, bool need_model
     A.img_base = c->arena;
     if (c->tabL_off && (c->tabL_off != pair_tabL_off(A, c->rp) || c->tabR_off != pair_tabR_off(A, c->rp)))
         return fail(c, C3SC_ERR_ARG, "launch: the pair kernel's product tables are not where the kernel looks for them");
+    if (c->tab3L_off && (c->tab3L_off != pair_tab3L_off(A, c->rp) || c->tab3R_off != pair_tab3R_off(A, c->rp)))
+        return fail(c, C3SC_ERR_ARG, "launch: the pair kernel's three-core tables are not where the kernel looks for them");
     A.cends = c->cends;
     A.memo_keys = nullptr; // only the launch paths that found a fiber-per-wave kernel switch the memo epilogue on
     A.skip = c->skip_flag;
@@ -978,16 +1024,58 @@ static long fiber_group_floor()
     return v > 0 ? v : -1;
 }
 
+// whether partition_fibers runs its pass for this launch
+static bool partitions(const KernelEntry *e, const KArgs &A)
+{
+    if (e->variant != C3SC_VARIANT_FIBER_PAIR || e->rtc || A.ncand > 64) return false;
+    bool faces = false;
+    for (int m = 0; m < A.d; m++) faces = faces || (m != A.k && A.bctype[m] == C3SC_ABSORB);
+    const long fmin = fiber_partition_min();
+    return faces && fmin >= 0 && A.F >= fmin && A.F <= 0x40000000L; // perm and nlive are int32
+}
+
+// Three-core product tables (kernel_common.hpp: pair_tab3L_off).  C3SC_PAIR_TABLE3, read at every launch like
+// C3SC_FIBER_PARTITION: 0 runs the two-core kernels in the same build.  A launch runs a three-core kernel when it partitions, the
+// tables are reserved and not switched off, and its K is not on the opt-out list (launch_fpp picks the kernel by LaunchIO::tab3).
+static bool runs_tab3(const c3sc_hip_ctx *c, const KernelEntry *e, const KArgs &A)
+{
+    if (!c->tab3L_off || fpp_table3_optout(A.d, e->rp, A.k) || !partitions(e, A)) return false;
+    const char *env = getenv("C3SC_PAIR_TABLE3");
+    return !(env && *env && atol(env) == 0);
+}
+
+// The tables are built lazily, so that the solver's small batches and every launch without a partition never pay for them: after an
+// upload the first launch that runs a three-core kernel enqueues the build on its stream, ahead of its pre-pass
+// (c3sc_hip_bellman_fibers_all: before it forks its streams).  A later launch on another stream waits for the build's event.  The
+// build is not counted by c3sc_hip_launch_count: it belongs to the upload, like k_core_images.
+static int ensure_tab3(c3sc_hip_ctx *c, hipStream_t st)
+{
+    if (!c->tab3_stale) {
+        if (st != c->tab3_stream) HIPCHK(c, hipStreamWaitEvent(st, c->tab3_ev, 0));
+        return C3SC_OK;
+    }
+    const int d = c->d, rp = c->rp;
+    if (!c->tab3_ev) HIPCHK(c, hipEventCreateWithFlags(&c->tab3_ev, hipEventDisableTiming));
+    Tab3Jobs J;
+    J.tab2[0] = c->tabL_off; J.core[0] = c->core_off[2]; J.dst[0] = c->tab3L_off;
+    J.n3[0] = c->ngrid[2]; J.npairs[0] = c->ngrid[0] * c->ngrid[1];
+    J.tab2[1] = c->tabR_off; J.core[1] = c->core_off[d - 3]; J.dst[1] = c->tab3R_off;
+    J.n3[1] = c->ngrid[d - 3]; J.npairs[1] = c->ngrid[d - 2] * c->ngrid[d - 1];
+    const long total = std::max((long)J.n3[0] * J.npairs[0], (long)J.n3[1] * J.npairs[1]) * rp;
+    hipLaunchKernelGGL(k_pair_tab3, dim3((unsigned)std::min<long>((total + 255) / 256, 4096), 2), dim3(256), 0, st, c->arena, J, rp);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->tab3_ev, st));
+    c->tab3_stream = st;
+    c->tab3_stale = false;
+    return C3SC_OK;
+}
+
 static int partition_fibers(c3sc_hip_ctx *c, const KernelEntry *e, const KArgs &A, LaunchIO &io, int slot, int &launched)
 {
     io.perm = nullptr;
     io.nlive = nullptr;
     launched = 0;
-    if (e->variant != C3SC_VARIANT_FIBER_PAIR || e->rtc || A.ncand > 64) return C3SC_OK;
-    bool faces = false;
-    for (int m = 0; m < A.d; m++) faces = faces || (m != A.k && A.bctype[m] == C3SC_ABSORB);
-    const long fmin = fiber_partition_min();
-    if (!faces || fmin < 0 || A.F < fmin || A.F > 0x40000000L) return C3SC_OK; // perm and nlive are int32
+    if (!partitions(e, A)) return C3SC_OK;
     PartArgs P;
     P.d = A.d;
     P.k = A.k;
@@ -1053,6 +1141,11 @@ static int launch_bellman(c3sc_hip_ctx *c, int k, size_t F, const int32_t *d_idx
         }
         c->last_kernel = e->name;
         arm_memo(c, e, A);
+        io.tab3 = runs_tab3(c, e, A);
+        if (io.tab3) {
+            rc = ensure_tab3(c, io.stream);
+            if (rc != C3SC_OK) return rc;
+        }
         rc = partition_fibers(c, e, A, io, part_slot, part_launches);
         if (rc != C3SC_OK) return rc;
         he = launch_entry(*e, A, io);
@@ -1062,6 +1155,7 @@ static int launch_bellman(c3sc_hip_ctx *c, int k, size_t F, const int32_t *d_idx
         declined.push_back(e);
     }
     g_launches += 1 + part_launches;
+    if (io.tab3 && io.perm) g_tab3_launches++;
     c->status_cache_valid = false;
     HIPCHK(c, he);
     return C3SC_OK;
@@ -1094,6 +1188,22 @@ static int launch_bellman_all(c3sc_hip_ctx *c, int nk, const int *ks, const size
             if (d_out[q] == d_out[s] && F[s] > 0) return fail(c, C3SC_ERR_ARG, "bellman_fibers_all: two segments share an output array");
     }
     hipStream_t st = (hipStream_t)stream;
+    if (overlap && c->tab3L_off && c->tab3_stale && c->game_gsz == 0 && c->hz_dt <= 0.0) {
+        // stale three-core tables: built here, ahead of the fork, if a segment is going to run a three-core kernel -- every
+        // side stream is then ordered behind the build by the fork itself
+        const long fmin = fiber_partition_min();
+        for (int s = 0; s < nk && c->tab3_stale; s++) {
+            if (F[s] == 0 || fmin < 0 || (long)F[s] < fmin) continue; // no partition, no three-core kernel: nothing to look up
+            KArgs A;
+            int rc = fill_args(c, ks[s], F[s], A, true);
+            if (rc != C3SC_OK) return rc;
+            const KernelEntry *e = find_kernel(c->model, c->d, c->rp, A.N, c->variant, ks[s], F[s]);
+            if (e && e->rp == c->rp && runs_tab3(c, e, A)) {
+                rc = ensure_tab3(c, st);
+                if (rc != C3SC_OK) return rc;
+            }
+        }
+    }
     if (overlap) {
         HIPCHK(c, hipSetDevice(c->device));
         if (!c->fork_ev) {
@@ -1724,6 +1834,7 @@ int c3sc_hip_normals(uint64_t seed, uint64_t traj0, size_t ntraj, uint64_t step0
 }
 
 unsigned long long c3sc_hip_launch_count(void) { return g_launches; }
+unsigned long long c3sc_hip_table3_launch_count(void) { return g_tab3_launches; }
 
 int c3sc_hip_last_partition(c3sc_hip_ctx *c, int slot, int32_t *perm, size_t cap, size_t *F, int *nlive)
 {

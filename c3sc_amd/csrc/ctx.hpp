@@ -59,6 +59,13 @@ struct c3sc_hip_ctx {
     long img_off[c3sc::MAXD] = {0};                        // fiber-pair LDS images of all cores (padded node stride)
     long qimgL_off[c3sc::MAXD] = {0}, qimgR_off[c3sc::MAXD] = {0}; // fiber-quad-duo LDS images (node stride elems + 2)
     long tabL_off = 0, tabR_off = 0;                       // fiber-pair product tables of the two outer cores of each side (0 = none)
+    // ... and of the three outer cores (kernel_common.hpp: pair_tab3L_off; 0 = not reserved).  Built lazily: an upload marks them
+    // stale, the first launch that runs a three-core kernel enqueues the build on its stream (ensure_tab3) and records tab3_ev; a
+    // later launch on another stream waits for that event
+    long tab3L_off = 0, tab3R_off = 0;
+    bool tab3_stale = true;
+    hipStream_t tab3_stream = nullptr;
+    hipEvent_t tab3_ev = nullptr;
     int obs_off = 0, cands_off = 0, tab_off[4] = {0, 0, 0, 0}, cfeat_off = 0;
     unsigned *d_status = nullptr;
     // the status word as of the last c3sc_hip_cross_fetch, valid until the next launch through this context: the solver reads the

@@ -23,6 +23,18 @@ CAR7_MAP(3, 0x04u, 11) // 2
 CAR7_MAP(4, 0x0Bu, 7)  // 0,1,3
 CAR7_MAP(5, 0x0Fu, 5)  // 0,1,2,3
 CAR7_MAP(6, 0x17u, 5)  // 0,1,2,4
+// three-core product tables: rank 10 only; the plan of every K, of which fpp_table3_optout leaves K = 0, 1 to run
+C3SC_FPP_TABLE3(Car7D, 10)
+#define CAR7_PLAN3(K, ROUNDS, PRODUCTS)                                                                                  \
+    static_assert(PairMap<Car7D, K, true, true>::plan().staged == (ROUNDS), "car7d: three-core staging rounds of K = " #K); \
+    static_assert(PairMap<Car7D, K, true, true>::plan().products == (PRODUCTS), "car7d: three-core products of K = " #K);
+CAR7_PLAN3(0, 3, 24)
+CAR7_PLAN3(1, 2, 16)
+CAR7_PLAN3(2, 1, 8)
+CAR7_PLAN3(3, 0, 0)
+CAR7_PLAN3(4, 1, 6)
+CAR7_PLAN3(5, 2, 8)
+CAR7_PLAN3(6, 3, 16)
 REG7P(4)
 REG7P(10)
 } // namespace c3sc

@@ -97,8 +97,22 @@ struct KArgs {
 __host__ __device__ constexpr long arena_block(long doubles) { return (doubles + 15) & ~15L; }
 __host__ __device__ constexpr long pair_img_doubles(int nodes, int per) { return arena_block((long)nodes * (per | 1) + 2); } // +2: the last 16-byte piece may overhang
 __host__ __device__ constexpr long pair_tab_doubles(int na, int nb, int rp) { return arena_block((long)na * nb * rp); }
-__host__ __device__ inline long pair_tabL_off(const KArgs &A, int rp) { return A.pair_img_off[A.d - 1] + pair_img_doubles(A.ngrid[A.d - 1], rp); }
-__host__ __device__ inline long pair_tabR_off(const KArgs &A, int rp) { return pair_tabL_off(A, rp) + pair_tab_doubles(A.ngrid[0], A.ngrid[1], rp); }
+__host__ __device__ constexpr long pair_tabL_off(const KArgs &A, int rp) { return A.pair_img_off[A.d - 1] + pair_img_doubles(A.ngrid[A.d - 1], rp); }
+__host__ __device__ constexpr long pair_tabR_off(const KArgs &A, int rp) { return pair_tabL_off(A, rp) + pair_tab_doubles(A.ngrid[0], A.ngrid[1], rp); }
+
+// Three-core product tables (kernel_fiber_pair.hpp: PairMap::Side::td() == 3): the next matrix level of each side folded into the
+// two-core rows, one row of RP doubles per index triple,
+//   tab3L[((c N_0 + a) N_1 + b) RP + beta]          = sum_alpha tabL(a, b)[alpha] G_2[c][alpha, beta]
+//   tab3R[((a N_{d-2} + b) N_{d-1} + c) RP + alpha] = sum_beta  G_{d-3}[a][alpha, beta] tabR(b, c)[beta],
+// the index of the level nearest K slowest (c = i_2 on the left, a = i_{d-3} on the right): a tile that shares it reads one
+// contiguous slice.  They FOLLOW tabR, tab3L then tab3R, and are reserved only where a three-core instantiation of the
+// (dimension count, padded rank) is registered and neither table exceeds PAIR_TAB3_MAX_BYTES -- a bound on the memory a context
+// may take for them, not a tuned number; beyond it the two-core kernels run.  Built lazily (c3sc_hip.hip: ensure_tab3), by the
+// first launch after an upload that runs a three-core kernel.
+constexpr long PAIR_TAB3_MAX_BYTES = 16L << 20;
+__host__ __device__ constexpr long pair_tab3_doubles(int na, int nb, int nc, int rp) { return arena_block((long)na * nb * nc * rp); }
+__host__ __device__ constexpr long pair_tab3L_off(const KArgs &A, int rp) { return pair_tabR_off(A, rp) + pair_tab_doubles(A.ngrid[A.d - 2], A.ngrid[A.d - 1], rp); }
+__host__ __device__ constexpr long pair_tab3R_off(const KArgs &A, int rp) { return pair_tab3L_off(A, rp) + pair_tab3_doubles(A.ngrid[0], A.ngrid[1], A.ngrid[2], rp); }
 
 // Key levels of the grouped fold (fiber_partition.hpp groups the live fibers of a partitioned fiber-pair batch by them,
 // kernel_fiber_pair.hpp folds a tile that shares one from SGPRs).  With `tab` (fpp_edge_tables) the staged matrix levels are the
@@ -131,6 +145,29 @@ __host__ __device__ constexpr KeyLevels fpp_key_levels(int d, int k, bool tab)
 //   fibers -- inside the spread; its key levels carry 16 of 23 products (a count, not a share of the time) but it keeps a staging
 //   round, and the grouped instantiation spilled 83 VGPRs against 59 (profiles/r07_car7d_grouped_fold.txt, section 5)
 __host__ __device__ constexpr bool fpp_group_fold_optout(int d, int rp, int k) { return d == 7 && rp == 10 && k == 1; }
+// Three-core tables (pair_tab3L_off): the (dimension count, padded rank) with registered three-core instantiations -- car7d at
+// rank 10 (inst_car7d_fpp.hip) -- and whether a grid gets the tables.
+__host__ __device__ constexpr bool fpp_table3_registered(int d, int rp) { return FPP_EDGE_TABLES && d == 7 && rp == 10; }
+__host__ __device__ constexpr bool pair_tab3_reserved(int d, const int *ngrid, int rp)
+{
+    return d >= 6 && fpp_table3_registered(d, rp) &&
+           pair_tab3_doubles(ngrid[0], ngrid[1], ngrid[2], rp) * (long)sizeof(double) <= PAIR_TAB3_MAX_BYTES &&
+           pair_tab3_doubles(ngrid[d - 3], ngrid[d - 2], ngrid[d - 1], rp) * (long)sizeof(double) <= PAIR_TAB3_MAX_BYTES;
+}
+// The opt-out list of the three-core tables: instantiations (dimension count, padded rank, K) that run the two-core kernel, with
+// the reason.  Timed on car7d at 2^20 fibers, five alternating runs of the parent and of a build with K = 0 .. 3 on the tables
+// (profiles/r09_car7d_three_core_tables.txt); a K stays where its mean launch time fell by more than the parent's own spread.
+//   d = 7, rank 10, K = 2: 1.4751-1.4820 ms per launch without the tables, 1.4701-1.4780 with them -- inside the spread
+//   d = 7, rank 10, K = 3: 1.4641-1.4783 without, 1.4791-1.4907 with them -- slower.  At K = 2, 3 the levels the tables absorb are
+//   key levels of the pre-pass: 89 % of the tiles fold them from SGPRs without a staging round already, and the tables put seven
+//   gathered rows per side in the place of those uniform products (K = 0, 1 absorb level 4, which is no key there: 1.0066-1.0120 ->
+//   0.9493-0.9541 and 1.3526-1.3633 -> 1.2780-1.2878)
+//   d = 7, rank 10, K = 4, 5, 6 (car7d): NOT timed.  Their left side creates the merged vector U_L ahead of the third core (dims 0,
+//   1 are merged), so a three-core row turns U_L G_2[i_2] -- a product of a rate-weighted sum -- into a sum of rate-weighted
+//   products: the values move in the last bits, and a partitioned launch would no longer give the bits of an unpartitioned one,
+//   which the grouped-fold and absorbed-tiles tests hold at every K.  At K = 0 .. 3 no merged vector exists ahead of an absorbed
+//   level and every row is bit for bit the vector the two-core kernel folds.  They carry 12 of the 47 products the tables remove.
+__host__ __device__ constexpr bool fpp_table3_optout(int d, int rp, int k) { return d == 7 && rp == 10 && k >= 2; }
 // the key levels of the fiber-pair instantiation (d, padded rank, k), for the host's pre-pass and the kernel alike: none for the
 // direct-fold kernels (nothing is staged) and the opt-outs
 __host__ __device__ constexpr KeyLevels fpp_group_levels(int d, int rp, int k)

@@ -286,7 +286,7 @@ struct FoldPlan {
     int staged;         // staging rounds per tile
     int products;       // vector-matrix products per tile, both wavefronts, L / R carried once
 };
-template <class Model, int K, bool TAB = false>
+template <class Model, int K, bool TAB = false, bool TAB3 = false>
 struct PairMap {
     typedef PairPark<Model, K> PK;
     static constexpr int D = Model::D, NIT = D + 2, UL = D, UR = D + 1;
@@ -302,10 +302,12 @@ struct PairMap {
         static constexpr int U = LEFT ? UL : UR;                              // the merged item
         __host__ __device__ static constexpr int depth(int m) { return LEFT ? m : D - 1 - m; }
         __host__ __device__ static constexpr int core(int q) { return LEFT ? q : D - 1 - q; }
-        // the product table (tabL: cores 0, 1; tabR: cores d-2, d-1) absorbs the edge core and the next
+        // the product table (tabL: cores 0, 1; tabR: cores d-2, d-1) absorbs the edge core and the next; with TAB3 a side of three
+        // cores or more enters through tab3L / tab3R (kernel_common.hpp), which absorb one more.  td(): the cores a table absorbs
         __host__ __device__ static constexpr bool tab() { return TAB && NC >= 2; }
+        __host__ __device__ static constexpr int td() { return !tab() ? 0 : (TAB3 && NC >= 3 ? 3 : 2); }
         // the staged steps: first(), then towards K
-        __host__ __device__ static constexpr int first() { return core(tab() ? 2 : 1); }
+        __host__ __device__ static constexpr int first() { return core(tab() ? td() : 1); }
         __host__ __device__ static constexpr int nsteps() { return NC - depth(first()) > 0 ? NC - depth(first()) : 0; }
         __host__ __device__ static constexpr int step(int i) { return core(depth(first()) + i); }
         __host__ __device__ static constexpr int first_merged()
@@ -324,13 +326,14 @@ struct PairMap {
         // gathered rows: free)
         __host__ __device__ static constexpr int cost_u()
         {
-            int c = NC - 1 - depth(first_merged()) - (tab() && first_merged() == EDGE);
+            int c = NC - 1 - depth(first_merged()); // U through every core behind the one that creates it ...
+            if (td() > depth(first_merged()) + 1) c = NC - td(); // ... that no table absorbs
             for (int q = depth(first()); q < NC; q++) c += 2 * mg(core(q));
             return c;
         }
         __host__ __device__ static constexpr int cost_pair(int m)
         {
-            return (tab() && depth(m) <= 1) ? 2 * (NC - 2) : (m != EDGE ? 2 : 0) + 2 * (NC - 1 - depth(m));
+            return depth(m) < td() ? 2 * (NC - td()) : (m != EDGE ? 2 : 0) + 2 * (NC - 1 - depth(m));
         }
         // the item the core step m creates: the pair of m, or U at its first merged dimension; -1: none
         __host__ __device__ static constexpr int created(int m) { return !mg(m) ? m : (m == first_merged() ? U : -1); }
@@ -348,6 +351,9 @@ struct PairMap {
         __host__ __device__ static constexpr int base() { return LEFT ? 0 : Side<true>::template before<H>(K); } // first slot in W
         template <int H>
         __host__ __device__ static constexpr int slot(int it) { return base<H>() + before<H>(it == U ? first_merged() : it); }
+        // wave H folds what the core step m creates or adds to: the pair of m, or the merged vector
+        template <int H>
+        __host__ __device__ static constexpr bool owns(int m) { return owner(mg(m) ? U : m) == H; }
     };
     typedef Side<true> SL;
     typedef Side<false> SR;
@@ -389,11 +395,17 @@ struct PairMap {
     {
         return 3 + (m < K ? SL::template before<0>(m) + SL::template before<1>(m) : SR::template before<0>(m) + SR::template before<1>(m));
     }
-    __host__ __device__ static constexpr int uniform_rounds() { return fpp_key_levels(D, K, TAB).n; }
+    // a key level counts where it is still staged: the three-core tables absorb the minor one of K = 2, 3, 4 (and both of K = 3)
+    __host__ __device__ static constexpr bool staged(int m) { return m < K ? m >= SL::first() : (m > K && m <= SR::first()); }
+    __host__ __device__ static constexpr int uniform_rounds()
+    {
+        constexpr KeyLevels kl = fpp_key_levels(D, K, TAB);
+        return (kl.n > 0 && staged(kl.major)) + (kl.n > 1 && staged(kl.minor));
+    }
     __host__ __device__ static constexpr int uniform_products()
     {
         constexpr KeyLevels kl = fpp_key_levels(D, K, TAB);
-        return (kl.n > 0 ? level_products(kl.major) : 0) + (kl.n > 1 ? level_products(kl.minor) : 0);
+        return (kl.n > 0 && staged(kl.major) ? level_products(kl.major) : 0) + (kl.n > 1 && staged(kl.minor) ? level_products(kl.minor) : 0);
     }
     // Which wave folds an item.  Nothing merged: pair_owner (alternate by distance from K).  Otherwise that is no longer balanced
     // -- a side that collapsed to one carried vector costs a fraction of its pairs -- and the items are dealt by their cost
@@ -470,7 +482,7 @@ struct PairPre {
 // H through G_m[i_m]; `combine` is the side's table combine, run behind the side's first staging round.  The tile's locals come as
 // arguments and fiber_pair_body calls it from one small lambda per side (left_step, right_step): with the closures of the body
 // where they were when each side had its own copy, every pair kernel compiles to the instructions it compiled to then.
-template <class Model, int RP, int K, int H, bool PART, bool LEFT, int m, int NOWN, class Combine>
+template <class Model, int RP, int K, int H, bool PART, bool T3, bool LEFT, int m, int NOWN, class Combine>
 __device__ __attribute__((always_inline)) inline void fold_step(const KArgs &A, const double *__restrict__ ro, double *sK,
                                                                const int (&fi)[Model::D], const int (&nbm)[Model::D], const int (&nbp)[Model::D],
                                                                const double (&rpm)[Model::D], const double (&rpp)[Model::D], double (&V)[RP],
@@ -479,7 +491,7 @@ __device__ __attribute__((always_inline)) inline void fold_step(const KArgs &A, 
 {
     constexpr int D = Model::D;
     constexpr bool DIRECT = fpp_direct<Model, RP>();
-    typedef PairMap<Model, K, fpp_edge_tables<Model, RP>()> PM;
+    typedef PairMap<Model, K, fpp_edge_tables<Model, RP>(), T3> PM;
     typedef typename PM::template Side<LEFT> SD;
     constexpr bool RV = SD::ROWVEC;
     constexpr int BASE = SD::template base<H>();
@@ -547,7 +559,7 @@ __device__ __attribute__((always_inline)) inline void fold_step(const KArgs &A, 
     fold_level<GROUP && (m == KL.major || (KL.n > 1 && m == KL.minor))>(fi[m], body);
 }
 
-template <class Model, int RP, int K, int H, bool FORCED, bool PART>
+template <class Model, int RP, int K, int H, bool FORCED, bool PART, bool T3 = false>
 __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArgs &A, const double *__restrict__ ro,
                                                                      const int32_t *__restrict__ idx, double *__restrict__ outv,
                                                                      int32_t *__restrict__ uidx, int32_t *__restrict__ absorbed,
@@ -559,7 +571,10 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
     constexpr int RH = RP / 2;
     typedef PairPark<Model, K> PK;
     constexpr bool ET = fpp_edge_tables<Model, RP>();
-    typedef PairMap<Model, K, ET> PM;
+    typedef PairMap<Model, K, ET, T3> PM;
+    static_assert(!T3 || (PART && ET), "the three-core tables serve the partitioned kernels with edge tables");
+    static_assert(PM::nv() == PairMap<Model, K, ET>::nv() && PM::gslot(D + 1) == PairMap<Model, K, ET>::gslot(D + 1),
+                  "the table depth moves no slot of the node loop");
     constexpr FoldPlan PL = PM::plan();
     constexpr int NV = PM::nv();                            // folded vectors in total: 2(D-1) when nothing is merged
     constexpr int NVL = PM::SL::nv();                       // ... of which left of K (dotted with c)
@@ -675,10 +690,63 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
 #pragma unroll
         for (int a = 0; a < RP; a++) { L[a] = (a == 0) ? 1.0 : 0.0; R[a] = (a == 0) ? 1.0 : 0.0; }
 
+        // A side whose three outer cores enter through tab3L / tab3R (PairMap::Side::td() == 3): V (L or R) is the row of the side's
+        // index triple, the pair of each absorbed dimension the two rows with that index moved to its neighbours, a merged one's
+        // share of U the same rows rate-weighted -- the expression of the two-core rows.  As there, all loads of the side are
+        // issued ahead of its first remaining staging round and combined behind it; the cores left run through fold_step.
+        auto side3 = [&](auto lc, double (&V)[RP]) __attribute__((always_inline)) {
+            constexpr bool LEFT = decltype(lc)::value;
+            typedef typename PM::template Side<LEFT> SD;
+            constexpr int c0 = SD::core(0), c1 = SD::core(1), c2 = SD::core(2); // by depth: the edge core first
+            constexpr int BASE = SD::template base<H>();
+            const double *T = ro + (LEFT ? pair_tab3L_off(A, RP) : pair_tab3R_off(A, RP));
+            const int n0 = A.ngrid[c0], n1 = A.ngrid[c1];
+            auto row = [&](int j0, int j1, int j2) __attribute__((always_inline)) -> const double * { // the index of core c2 slowest
+                return T + (LEFT ? ((long)j2 * n0 + j0) * n1 + j1 : ((long)j2 * n1 + j1) * n0 + j0) * RP;
+            };
+            constexpr bool OWN0 = SD::template owns<H>(c0), OWN1 = SD::template owns<H>(c1), OWN2 = SD::template owns<H>(c2);
+            double tm[3][RP], tp[3][RP]; // rows of a dimension this wavefront does not fold are never loaded
+            load_row16<RP>(row(fi[c0], fi[c1], fi[c2]), V);
+            if constexpr (OWN0) {
+                load_row16<RP>(row(nbm[c0], fi[c1], fi[c2]), tm[0]);
+                load_row16<RP>(row(nbp[c0], fi[c1], fi[c2]), tp[0]);
+            }
+            if constexpr (OWN1) {
+                load_row16<RP>(row(fi[c0], nbm[c1], fi[c2]), tm[1]);
+                load_row16<RP>(row(fi[c0], nbp[c1], fi[c2]), tp[1]);
+            }
+            if constexpr (OWN2) {
+                load_row16<RP>(row(fi[c0], fi[c1], nbm[c2]), tm[2]);
+                load_row16<RP>(row(fi[c0], fi[c1], nbp[c2]), tp[2]);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            auto combine = [&]() __attribute__((always_inline)) { // what the edge block and the steps of c1, c2 leave in W
+                static_for<3>([&](auto qc) __attribute__((always_inline)) {
+                    constexpr int q = decltype(qc)::value, m = SD::core(q);
+                    if constexpr (SD::template owns<H>(m)) {
+                        constexpr int before = SD::template before<H>(m);
+#pragma unroll
+                        for (int b = 0; b < RP; b++) {
+                            if constexpr (PM::mg(m)) {
+                                constexpr int su = PM::template lslot<H>(SD::U);
+                                const double nw = fma(rpp[m], tp[q][b], rpm[m] * tm[q][b]);
+                                W[su][b] = (m == SD::first_merged()) ? nw : W[su][b] + nw;
+                            } else { W[BASE + before][b] = tm[q][b]; W[BASE + before + 1][b] = tp[q][b]; }
+                        }
+                    }
+                });
+            };
+            if constexpr (SD::nsteps() == 0) combine(); // no staged core on this side
+            static_for<SD::nsteps()>([&](auto ic) __attribute__((always_inline)) {
+                fold_step<Model, RP, K, H, PART, T3, LEFT, SD::step(decltype(ic)::value)>(A, ro, sK, fi, nbm, nbp, rpm, rpp, V, W, seg, tlast, combine);
+            });
+        };
+
         // ------------------------------------------------------------ fold the prefix side
         FPP_STAMP(0) // tile setup
         if (!(C3SC_STAMPS_ON && (A.dbg & 1))) {
-        if constexpr (K > 0) {
+        if constexpr (K > 0 && PM::SL::td() == 3) side3(std::true_type{}, L);
+        else if constexpr (K > 0) {
             // rows of tabL: T(a, b) = G_0[a] G_1[b].  All loads of the side are issued here, ahead of the first staging round,
             // and combined (left_combine) behind it: their L2 round trip runs under the staging wait.
             constexpr bool OWN0 = PM::SL::tab() && (PM::mg(0) ? PM::owner(PM::UL) == H : PM::owner(0) == H);
@@ -743,13 +811,14 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
                 }
             }
             auto left_step = [&](auto mc) __attribute__((always_inline)) {
-                fold_step<Model, RP, K, H, PART, true, decltype(mc)::value>(A, ro, sK, fi, nbm, nbp, rpm, rpp, L, W, seg, tlast, left_combine);
+                fold_step<Model, RP, K, H, PART, T3, true, decltype(mc)::value>(A, ro, sK, fi, nbm, nbp, rpm, rpp, L, W, seg, tlast, left_combine);
             };
             static_for<PM::SL::nsteps()>([&](auto ic) __attribute__((always_inline)) { left_step(std::integral_constant<int, PM::SL::step(decltype(ic)::value)>{}); });
         }
 
         // ------------------------------------------------------------ fold the suffix side
-        if constexpr (K < D - 1) {
+        if constexpr (K < D - 1 && PM::SR::td() == 3) side3(std::false_type{}, R);
+        else if constexpr (K < D - 1) {
             // rows of tabR: T(a, b) = G_{d-2}[a] G_{d-1}[b], as on the left
             constexpr bool OWN0 = PM::SR::tab() && (PM::mg(D - 1) ? PM::owner(PM::UR) == H : PM::owner(D - 1) == H);
             constexpr bool OWN1 = PM::SR::tab() && (PM::mg(D - 2) ? PM::owner(PM::UR) == H : PM::owner(D - 2) == H);
@@ -814,7 +883,7 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
                 }
             }
             auto right_step = [&](auto mc) __attribute__((always_inline)) {
-                fold_step<Model, RP, K, H, PART, false, decltype(mc)::value>(A, ro, sK, fi, nbm, nbp, rpm, rpp, R, W, seg, tlast, right_combine);
+                fold_step<Model, RP, K, H, PART, T3, false, decltype(mc)::value>(A, ro, sK, fi, nbm, nbp, rpm, rpp, R, W, seg, tlast, right_combine);
             };
             static_for<PM::SR::nsteps()>([&](auto ic) __attribute__((always_inline)) { right_step(std::integral_constant<int, PM::SR::step(decltype(ic)::value)>{}); });
         }
@@ -1421,6 +1490,22 @@ __global__ void __launch_bounds__(FPP_THREADS, (fpp_waves_per_simd<Model, RP>())
     const int h = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (h == 0) fiber_pair_body<Model, RP, K, 0, FORCED, true>(A, ro, idx, outv, uidx, absorbed, perm, nlive_p, sKp, st);
     else fiber_pair_body<Model, RP, K, 1, FORCED, true>(A, ro, idx, outv, uidx, absorbed, perm, nlive_p, sKp, st);
+    if (st) atomicOr(A.status, st);
+}
+
+// the partitioned kernel with the three-core tables (PairMap::Side::td() == 3); a kernel of its own again: the launcher picks it
+// where the tables are built and the K is not on fpp_table3_optout, everything else runs the kernels above unchanged
+template <class Model, int RP, int K, bool FORCED>
+__global__ void __launch_bounds__(FPP_THREADS, (fpp_waves_per_simd<Model, RP>()))
+    k_fiber_pair_part3(const KArgs A, const double *__restrict__ ro, const int32_t *__restrict__ idx, double *__restrict__ outv,
+                       int32_t *__restrict__ uidx, int32_t *__restrict__ absorbed, const int32_t *__restrict__ perm,
+                       const int32_t *__restrict__ nlive_p)
+{
+    extern __shared__ double sKp[];
+    unsigned st = 0;
+    const int h = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (h == 0) fiber_pair_body<Model, RP, K, 0, FORCED, true, true>(A, ro, idx, outv, uidx, absorbed, perm, nlive_p, sKp, st);
+    else fiber_pair_body<Model, RP, K, 1, FORCED, true, true>(A, ro, idx, outv, uidx, absorbed, perm, nlive_p, sKp, st);
     if (st) atomicOr(A.status, st);
 }
 

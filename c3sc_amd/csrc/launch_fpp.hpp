@@ -19,7 +19,24 @@ __host__ __device__ constexpr size_t fpp_tile_doubles(bool node_split)
     return swap > rows ? swap : rows;
 }
 
-template <class Model, int RP, int K, bool FORCED, bool PART>
+// Three-core instantiations (k_fiber_pair_part3) exist where an instantiation file says so, ahead of its registrations:
+// C3SC_FPP_TABLE3(Model, RP).  fpp_table3_registered (kernel_common.hpp) tells the host which (dimension count, padded rank) get
+// the tables; the two are held together by a static assert in the macro.
+template <class Model, int RP>
+struct FppTable3 {
+    static constexpr bool value = false;
+};
+#define C3SC_FPP_TABLE3(MODEL, RP)                                                                                              \
+    template <>                                                                                                                 \
+    struct FppTable3<MODEL, RP> {                                                                                               \
+        static constexpr bool value = true;                                                                                     \
+        static_assert(fpp_table3_registered(MODEL::D, RP) && fpp_edge_tables<MODEL, RP>(), "the host reserves no tables here"); \
+    };
+// ... and run for the K that are not on the opt-out list
+template <class Model, int RP, int K>
+constexpr bool fpp_table3() { return FppTable3<Model, RP>::value && !fpp_table3_optout(Model::D, RP, K); }
+
+template <class Model, int RP, int K, bool FORCED, bool PART, bool T3 = false>
 hipError_t launch_fpp_impl(const KArgs &A, const LaunchIO &io)
 {
     constexpr int D = Model::D;
@@ -40,7 +57,9 @@ hipError_t launch_fpp_impl(const KArgs &A, const LaunchIO &io)
     B.tbl_off = (int)doubles;
     doubles += (size_t)CandLds<Model>::doubles(A.ncand) + (size_t)NodeLds<Model, K>::doubles(A.N);
     const size_t shmem = doubles * sizeof(double);
+    static_assert(!T3 || PART, "the three-core kernel is a partitioned one");
     const void *kern = PART ? (const void *)k_fiber_pair_part<Model, RP, K, FORCED> : (const void *)k_fiber_pair<Model, RP, K, FORCED>;
+    if constexpr (T3) kern = (const void *)k_fiber_pair_part3<Model, RP, K, FORCED>; // instantiated only where it is registered
     static LaunchCache cache;
     int blocks_per_cu = 1, num_cu = 256;
     hipError_t e = cache.prepare(kern, FPP_THREADS, shmem, blocks_per_cu, num_cu);
@@ -56,7 +75,10 @@ hipError_t launch_fpp_impl(const KArgs &A, const LaunchIO &io)
     int grid = (int)(ntiles < cap ? ntiles : cap);
     if (ntiles >= 8 * cap && ntiles < 0x7fffffffL) grid = (int)ntiles;
     if (grid < 1) grid = 1;
-    if constexpr (PART)
+    if constexpr (T3)
+        hipLaunchKernelGGL((k_fiber_pair_part3<Model, RP, K, FORCED>), dim3(grid), dim3(FPP_THREADS), shmem, io.stream, B, io.ro, io.idx, io.out,
+                           io.uidx, io.absorbed, io.perm, io.nlive);
+    else if constexpr (PART)
         hipLaunchKernelGGL((k_fiber_pair_part<Model, RP, K, FORCED>), dim3(grid), dim3(FPP_THREADS), shmem, io.stream, B, io.ro, io.idx, io.out,
                            io.uidx, io.absorbed, io.perm, io.nlive);
     else
@@ -68,6 +90,8 @@ hipError_t launch_fpp_impl(const KArgs &A, const LaunchIO &io)
 template <class Model, int RP, int K>
 hipError_t launch_fpp(const KArgs &A, const LaunchIO &io)
 {
+    if constexpr (fpp_table3<Model, RP, K>()) // io.tab3: the host reserved the tables, built them and did not switch them off
+        if (io.perm && io.tab3) return A.forced ? launch_fpp_impl<Model, RP, K, true, true, true>(A, io) : launch_fpp_impl<Model, RP, K, false, true, true>(A, io);
     if (io.perm) return A.forced ? launch_fpp_impl<Model, RP, K, true, true>(A, io) : launch_fpp_impl<Model, RP, K, false, true>(A, io);
     return A.forced ? launch_fpp_impl<Model, RP, K, true, false>(A, io) : launch_fpp_impl<Model, RP, K, false, false>(A, io);
 }

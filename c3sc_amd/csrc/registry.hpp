@@ -28,6 +28,7 @@ struct LaunchIO {
     // null = batch order
     const int32_t *perm = nullptr;
     const int32_t *nlive = nullptr;
+    bool tab3 = false; // ... and the three-core product tables are built: a partitioned launch may run its three-core kernel
 };
 #endif
 

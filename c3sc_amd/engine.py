@@ -31,7 +31,7 @@ EXPORTS = [
     "c3sc_hip_set_control_box", "c3sc_hip_bellman_fibers_box", "c3sc_hip_bellman_fibers_box_host", "c3sc_hip_policy_fibers_box",
     "c3sc_hip_policy_fibers_box_host",
     "c3sc_hip_stencil_fibers_host", "c3sc_hip_stencil_fibers_nb", "c3sc_hip_stencil_fibers_nb_host", "c3sc_hip_sync", "c3sc_hip_get_status", "c3sc_hip_last_kernel",
-    "c3sc_hip_debug_read", "c3sc_hip_launch_count", "c3sc_hip_last_partition", "c3sc_hip_timer_start", "c3sc_hip_timer_stop", "c3sc_hip_peak_fma_f64", "c3sc_hip_peak_mfma_f64",
+    "c3sc_hip_debug_read", "c3sc_hip_launch_count", "c3sc_hip_table3_launch_count", "c3sc_hip_last_partition", "c3sc_hip_timer_start", "c3sc_hip_timer_stop", "c3sc_hip_peak_fma_f64", "c3sc_hip_peak_mfma_f64",
     "c3sc_hip_set_interp", "c3sc_hip_stencil_points", "c3sc_hip_simulate", "c3sc_hip_simulate_host", "c3sc_hip_normals",
     "c3sc_hip_integrate", "c3sc_hip_integrate_host",
     "c3sc_hip_model_compile", "c3sc_hip_model_code_object", "c3sc_hip_model_log",
@@ -122,6 +122,7 @@ def load_library():
         L.c3sc_hip_bellman_fibers_tables_host.argtypes = [C.c_void_p, C.c_int, C.c_size_t] + [C.c_void_p] * 6
         L.c3sc_hip_policy_fibers_tables_host.argtypes = [C.c_void_p, C.c_int, C.c_size_t] + [C.c_void_p] * 6
         L.c3sc_hip_launch_count.restype = C.c_ulonglong
+        L.c3sc_hip_table3_launch_count.restype = C.c_ulonglong
         L.c3sc_hip_last_partition.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
         L.c3sc_hip_sync.argtypes = [C.c_void_p, C.c_void_p]
         L.c3sc_hip_timer_start.argtypes = [C.c_void_p, C.c_void_p]

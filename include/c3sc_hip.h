@@ -137,7 +137,8 @@ int c3sc_hip_set_variant(c3sc_hip_ctx *ctx, int variant);
  * matrices; C3SC_FIBER_PARTITION=0 in the environment switches the pass off, n > 0 sets the smallest such batch,
  * C3SC_FIBER_GROUP=0 keeps the pass but leaves the live fibers in batch order, n > 0 sets the fewest fibers per key a level is
  * grouped by -- meant for tests: 1 groups every batch, which costs a production batch more than it gains; the results do not
- * depend on any of them) into
+ * depend on any of them; C3SC_PAIR_TABLE3=0 keeps a partitioned launch on the two-core product tables where a kernel with
+ * three-core tables exists -- the same values bit for bit) into
  * scratch the context owns: the Bellman launches of ONE context must be ordered with respect to each other (one stream, or
  * events between streams); c3sc_hip_bellman_fibers_all orders its own. */
 int c3sc_hip_bellman_fibers(c3sc_hip_ctx *ctx, int k, size_t F, const int32_t *d_idx, double *d_out,
@@ -543,6 +544,8 @@ int c3sc_hip_debug_read(c3sc_hip_ctx *ctx, unsigned long long *out, size_t n);
 /* diagnostics: Bellman / policy / stencil kernel launches made by this process so far (the reference calls its fiber
  * callback once per fiber, bellman.c:1295; here one launch serves a batch -- this counts them) */
 unsigned long long c3sc_hip_launch_count(void);
+/* ... and how many of them ran a fiber-pair kernel with the three-core product tables (tests: C3SC_PAIR_TABLE3=0 switches them off) */
+unsigned long long c3sc_hip_table3_launch_count(void);
 /* tests: the last partition a fiber-pair launch ran in scratch block `slot` (0: the caller's stream and the single-launch entry
  * points; 1, 2: the side streams of c3sc_hip_bellman_fibers_all).  Synchronises that launch's stream, then copies perm[F] (fiber
  * of every tile position: live fibers first, grouped by the fold's key levels, dead ones last) into `perm` (cap entries; NULL: not

@@ -5,7 +5,8 @@
 
 For every kernel whose symbol contains the --match string, the instruction lines and labels of its body and the lines of
 its .amdhsa_kernel descriptor are compared with comments (everything from ';'), blank lines and the per-translation-unit
-__hip_cuid_* symbol left out.  Prints one line per kernel that differs and a total; the exit status is 0 when every
+__hip_cuid_* symbol left out.  Block labels carry the number of the function in its translation unit (.LBB52_5); it is left out
+too, so that a kernel added to the file does not make every kernel behind it differ.  Prints one line per kernel that differs and a total; the exit status is 0 when every
 kernel is identical and both listings hold the same kernels.
 """
 import argparse
@@ -38,7 +39,7 @@ def kernels(path, match):
         if m:
             cur = m.group(1) if match in m.group(1) else None
         if cur:
-            out[cur].append(code.strip())
+            out[cur].append(re.sub(r"\.LBB\d+_", ".LBB_", code.strip()))
         if re.match(r"\s*\.end_amdhsa_kernel", code):
             cur = None
     return out
