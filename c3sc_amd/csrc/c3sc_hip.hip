@@ -327,6 +327,15 @@ static int check_horizon_model(c3sc_hip_ctx *c, const char *what)
     return C3SC_OK;
 }
 
+// stopping is served by the stop kernels of the model set now (set_model may have replaced the model set_stopping checked), and
+// never together with a game
+static int check_stop_model(c3sc_hip_ctx *c, const char *what)
+{
+    if (c->stopping && !(c->model >= C3SC_MODEL_USER && rtc_model_stop(c->model) && c->game_gsz == 0))
+        return fail(c, C3SC_ERR_UNSUPPORTED, what);
+    return C3SC_OK;
+}
+
 // game mode is served by the game kernels of the model set now (set_model may have replaced the model set_game checked)
 static int check_game_model(c3sc_hip_ctx *c, const char *what)
 {
@@ -574,6 +583,23 @@ int c3sc_hip_set_horizon_step(c3sc_hip_ctx *c, double dt)
     return C3SC_OK;
 }
 
+int c3sc_hip_set_stopping(c3sc_hip_ctx *c, int on)
+{
+    if (!c) return C3SC_ERR_ARG;
+    if (!on) {
+        c->stopping = 0;
+        return C3SC_OK;
+    }
+    if (c->model == 0) return fail(c, C3SC_ERR_ARG, "set_stopping: set_model first");
+    if (c->model < C3SC_MODEL_USER || !rtc_model_known(c->model))
+        return fail(c, C3SC_ERR_UNSUPPORTED, "set_stopping: stopping needs a run-time compiled model (c3sc_hip_model_compile_os with stop = 1)");
+    if (!rtc_model_stop(c->model))
+        return fail(c, C3SC_ERR_UNSUPPORTED, "set_stopping: this model was compiled without stop kernels (c3sc_hip_model_compile_os, stop = 1)");
+    if (c->game_gsz > 0) return fail(c, C3SC_ERR_UNSUPPORTED, "set_stopping: stopping games are not offered");
+    c->stopping = 1;
+    return C3SC_OK;
+}
+
 int c3sc_hip_set_model(c3sc_hip_ctx *c, int model, const double *params, int nparams)
 {
     if (!c || model <= 0 || nparams < 0 || nparams > C3SC_MAX_PARAMS) return fail(c, C3SC_ERR_ARG, "set_model: bad arguments");
@@ -607,6 +633,7 @@ int c3sc_hip_set_game(c3sc_hip_ctx *c, int du_min, int nu, const double *U, int 
     if (c->model == 0) return fail(c, C3SC_ERR_ARG, "set_game: set_model first");
     if (c->model == C3SC_MODEL_TABLE) return fail(c, C3SC_ERR_UNSUPPORTED, "set_game: the TABLE model has no game kernels");
     if (c->hz_dt > 0.0) return fail(c, C3SC_ERR_UNSUPPORTED, "set_game: games have no horizon form (c3sc_hip_set_horizon_step(ctx, 0) first)");
+    if (c->stopping) return fail(c, C3SC_ERR_UNSUPPORTED, "set_game: stopping games are not offered (c3sc_hip_set_stopping(ctx, 0) first)");
     int mdu = 0;
     bool has_game = false;
     if (c->model < C3SC_MODEL_USER || !rtc_model_info(c->model, mdu, has_game))
@@ -1121,10 +1148,18 @@ static int launch_bellman(c3sc_hip_ctx *c, int k, size_t F, const int32_t *d_idx
             return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers: horizon mode runs on the fiber-per-wave kernel only (the pair and quad variants have no horizon form)");
         variant = C3SC_VARIANT_FIBER_PER_WAVE;
     }
+    if (c->stopping) { // and with stopping on: the combined form when the horizon step is set as well
+        rc = check_stop_model(c, "bellman_fibers: stopping needs a model compiled with stop kernels (and no game)");
+        if (rc != C3SC_OK) return rc;
+        if (variant != C3SC_VARIANT_AUTO && variant != C3SC_VARIANT_FIBER_PER_WAVE)
+            return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers: stopping runs on the fiber-per-wave kernel only (the pair and quad variants have no stop form)");
+        variant = C3SC_VARIANT_FIBER_PER_WAVE;
+    }
     if (F == 0) return C3SC_OK;
     if (!d_idx || !d_out) return fail(c, C3SC_ERR_ARG, "bellman_fibers: null buffer");
     A.forced = d_policy;
     LaunchIO io{c->arena, d_idx, d_out, d_uidx, d_absorbed, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream};
+    io.stop = c->stopping != 0;
     // A launcher declines (nothing launched) when its LDS layout does not fit this grid or it does not serve this call; the
     // next-best instantiation of the same padded rank is tried then (e.g. the duo kernel's two staging buffers hold N <= 25 at
     // rank 16, the one-buffer quad kernel behind it N <= 75, the per-wave kernel behind that only stages the varying core).
@@ -1188,7 +1223,7 @@ static int launch_bellman_all(c3sc_hip_ctx *c, int nk, const int *ks, const size
             if (d_out[q] == d_out[s] && F[s] > 0) return fail(c, C3SC_ERR_ARG, "bellman_fibers_all: two segments share an output array");
     }
     hipStream_t st = (hipStream_t)stream;
-    if (overlap && c->tab3L_off && c->tab3_stale && c->game_gsz == 0 && c->hz_dt <= 0.0) {
+    if (overlap && c->tab3L_off && c->tab3_stale && c->game_gsz == 0 && c->hz_dt <= 0.0 && !c->stopping) {
         // stale three-core tables: built here, ahead of the fork, if a segment is going to run a three-core kernel -- every
         // side stream is then ordered behind the build by the fork itself
         const long fmin = fiber_partition_min();
@@ -1250,6 +1285,7 @@ static int launch_box(c3sc_hip_ctx *c, int k, size_t F, const int32_t *d_idx, co
     if (c->box_du == 0) return fail(c, C3SC_ERR_ARG, "bellman_fibers_box: c3sc_hip_set_control_box first");
     if (c->game_gsz > 0) return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_box: games have no control-box form");
     if (c->hz_dt > 0.0) return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_box: horizon mode has no control-box form");
+    if (c->stopping) return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_box: stopping has no control-box form");
     if (model_ncf(c->model) != 0 && c->model != C3SC_MODEL_COTHRUST6D) // cothrust forms its features from u on the device (models.hpp: CF_FROM_U)
         return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_box: this model needs transcendental functions of the control");
     KArgs A;
@@ -1322,6 +1358,7 @@ static int launch_tables(c3sc_hip_ctx *c, int k, size_t F, const int32_t *d_idx,
     const int saved_model = c->model;
     if (c->game_gsz > 0) return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_tables: the TABLE model has no game kernels");
     if (c->hz_dt > 0.0) return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_tables: the TABLE model has no horizon kernels");
+    if (c->stopping) return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_tables: the TABLE model has no stop kernels");
     c->model = C3SC_MODEL_TABLE; // fill_args only checks that a model is set
     KArgs A;
     int rc = fill_args(c, k, F, A, true);
@@ -1613,6 +1650,10 @@ int c3sc_hip_simulate(c3sc_hip_ctx *c, const c3sc_hip_sim_args *a, void *stream)
             return fail(c, C3SC_ERR_ARG, "simulate: in horizon mode dt must equal the horizon step (c3sc_hip_set_horizon_step)");
         if (a->nsteps + 1 > (size_t)c->hz_nstack) return fail(c, C3SC_ERR_ARG, "simulate: nsteps exceeds the value stack (nstack - 1 stages)");
     }
+    if (c->stopping) {
+        if (check_stop_model(c, "simulate: stopping needs a model compiled with stop kernels (and no game)") != C3SC_OK) return C3SC_ERR_UNSUPPORTED;
+        if (a->box) return fail(c, C3SC_ERR_UNSUPPORTED, "simulate: stopping has no control-box form");
+    }
     KArgs A;
     rc = fill_args(c, 0, 0, A, false);
     if (rc != C3SC_OK) return rc;
@@ -1673,6 +1714,7 @@ int c3sc_hip_simulate(c3sc_hip_ctx *c, const c3sc_hip_sim_args *a, void *stream)
             ro = c->hz_stack;
         }
         LaunchIO io{ro, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream, &S};
+        io.stop = c->stopping != 0;
         rc = launch_one(c, ek, A, io, "simulate: this rollout kernel has no box minimiser");
         if (rc != C3SC_OK) return rc;
         s0 = S.s1;
@@ -1729,6 +1771,7 @@ int c3sc_hip_integrate(c3sc_hip_ctx *c, const c3sc_hip_ode_args *a, void *stream
     int rc = closed_loop_setup(c, who, a);
     if (rc != C3SC_OK) return rc;
     if (c->hz_dt > 0.0) return fail(c, C3SC_ERR_UNSUPPORTED, "integrate: deterministic closed loops are not offered in horizon mode");
+    if (c->stopping) return fail(c, C3SC_ERR_UNSUPPORTED, "integrate: deterministic closed loops are not offered for stopping problems");
     KArgs A;
     rc = fill_args(c, 0, 0, A, false);
     if (rc != C3SC_OK) return rc;

@@ -37,6 +37,8 @@ struct c3sc_hip_ctx {
     // laid out for a static section of hz_stack_static doubles; stage s padded to hz_rp[s], its cores at hz_core_off[s * MAXD + m]
     double hz_dt = 0.0;
     int hz_off = 0;
+    // optimal stopping (c3sc_hip_set_stopping): the launches take the stop forms of the run-time compiled model's kernels
+    int stopping = 0;
     double *hz_stack = nullptr;
     size_t hz_stack_static = 0;
     int hz_nstack = 0;

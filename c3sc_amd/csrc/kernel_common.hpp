@@ -215,6 +215,20 @@ constexpr bool model_horizon()
     else return false;
 }
 
+// The optimal-stopping instantiations are those of a model wrapped in StopOf, in the style of GameOf and
+// HorizonOf: k_fiber_per_wave and k_rollout pass model_stop<Model>() to node_backup as STOP, which then compares the scan's
+// result once per node with Model::stopcost.  StopOf<HorizonOf<M>> is the finite-horizon (American) form.
+template <class M>
+struct StopOf : M {
+    static constexpr bool STOP = true;
+};
+template <class Model>
+constexpr bool model_stop()
+{
+    if constexpr (requires { Model::STOP; }) return Model::STOP;
+    else return false;
+}
+
 // Output pointers of one launch (separate __restrict__ kernel parameters).
 struct KOut {
     double *out;       // [F][N]            (bellman kernel)
@@ -682,8 +696,25 @@ __device__ __forceinline__ void upwind_rates(double t, double t2, double b, doub
 // candidate (it is neither skipped nor flagged STATIONARY).  A candidate with Q delta / h^2 > 1 (a negative self-loop) still
 // takes part and raises C3SC_STATUS_CFL.  Scan order, first strict '<', absorbed nodes and the forced path are the plain
 // scan's.  delta, exp(-beta delta) and delta / h^2 are wave-uniform host values in `ro` at A.hz_off.
+//
+// STOP (optimal stopping): one more action, "stop and pay psi(x) = Model::stopcost", with the index ncand.  It
+// is scanned last: the candidate scan runs as it does without it (the fraction comparison at beta = 0 and its single division
+// included) and psi is compared once per node with the scan's result, by the scan's rule -- psi wins where it is strictly
+// smaller, and where the scan left no valid candidate (the value is then psi, not 0).  Stop raises no status bit of its own.
+// Forced path: fu == ncand yields psi and applies no candidate; any other fu applies that candidate without the comparison.
+template <bool STOP, class Model>
+__device__ __forceinline__ void stop_action(const KArgs &A, const double (&x)[Model::D], int nc, bool forced, int fu, double &best, int &ui)
+{
+    if constexpr (STOP) {
+        const double psi = Model::stopcost(A.prm, x);
+        const bool take = forced ? (fu == nc) : ((ui < 0) | (psi < best));
+        best = take ? psi : best;
+        ui = take ? nc : ui;
+    }
+}
+
 template <class Model, int CG = 1, int CGD = 1, class Cand = CandRegs<Model>, bool SPLIT = true, class Pre = NoPre, bool GAME = false,
-          bool HORIZON = false>
+          bool HORIZON = false, bool STOP = false>
 __device__ inline double node_backup(const KArgs &A, const double *__restrict__ ro, const double (&x)[Model::D],
                                      const double (&tv)[Model::NTAB > 0 ? Model::NTAB : 1], const Cand &cr,
                                      const double (&V)[2 * Model::D + 1], int ab, int &ui, unsigned &st, bool forced = false,
@@ -693,6 +724,7 @@ __device__ inline double node_backup(const KArgs &A, const double *__restrict__ 
     // applied instead of the minimiser's; same rates, same bellmanrhs.
     constexpr int D = Model::D, DU = Model::DU;
     static_assert(!GAME || (CG == 1 && CGD == 1), "the game scan takes one candidate per trip");
+    static_assert(!(STOP && GAME), "stopping games are not offered");
     const int nc = __builtin_amdgcn_readfirstlane(A.ncand); // keeps the candidate loops' trip test on the scalar unit
     ui = -1;
     // game: which reductions are maxima (wave-uniform), the group length, the forced pair as a list position
@@ -807,6 +839,7 @@ __device__ inline double node_backup(const KArgs &A, const double *__restrict__ 
         }
         if (cfl & (ab == 0)) st |= C3SC_STATUS_CFL;
         best = (ui >= 0) ? bestv : 0.0;
+        stop_action<STOP, Model>(A, x, nc, forced, fu, best, ui);
         best = (ab != 0) ? absorbed_cost : best;
         ui = (ab != 0) ? -1 : ui;
         return best;
@@ -938,6 +971,7 @@ __device__ inline double node_backup(const KArgs &A, const double *__restrict__ 
             best = (ui >= 0) ? fma(pself, V[2 * D], bnum * inv) : 0.0;
         }
         if constexpr (GAME) ui = (ui >= 0) ? game_list_to_pair(A, ui) : ui;
+        stop_action<STOP, Model>(A, x, nc, forced, fu, best, ui);
         best = (ab != 0) ? absorbed_cost : best;
         ui = (ab != 0) ? -1 : ui;
         return best;
@@ -1066,6 +1100,7 @@ __device__ inline double node_backup(const KArgs &A, const double *__restrict__ 
     if (anybad_g & (ab == 0)) st |= C3SC_STATUS_STATIONARY;
     best = (ui >= 0) ? bestg : 0.0;
     if constexpr (GAME) ui = (ui >= 0) ? game_list_to_pair(A, ui) : ui;
+    stop_action<STOP, Model>(A, x, nc, forced, fu, best, ui);
     best = (ab != 0) ? absorbed_cost : best;
     ui = (ab != 0) ? -1 : ui;
     return best;

@@ -341,8 +341,8 @@ __global__ void __launch_bounds__(256, (RP >= 20 ? 1 : 2)) // rank 20 is LDS-bou
                 } else {
                     double tv[Model::NTAB > 0 ? Model::NTAB : 1];
                     table_values<Model>(A, ro, ix, tv);
-                    val = node_backup<Model, 1, 1, CandLds<Model>, true, NoPre, model_game<Model>(), model_horizon<Model>()>(A, ro, x, tv, cr, V, ab, ui, st,
-                                                                                                                       forced, fu);
+                    val = node_backup<Model, 1, 1, CandLds<Model>, true, NoPre, model_game<Model>(), model_horizon<Model>(), model_stop<Model>()>(
+                        A, ro, x, tv, cr, V, ab, ui, st, forced, fu);
                 }
                 if (A.memo_keys) { // wave-uniform: node memo of the device-resident cross iterations
                     int ins = 0, ovf = 0;

@@ -306,6 +306,11 @@ __global__ void __launch_bounds__(256) k_rollout(const KArgs A, const SimK S, co
     }
     const double beta = A.discount, dt = S.dt;
     unsigned st = 0;
+    // stop models: a voluntary stop at step k is kept as -(k + 2), so "still running" is -1 alone there
+    auto running = [&]() {
+        if constexpr (model_stop<Model>()) return ex == -1;
+        else return ex < 0;
+    };
     // exit at x_s: outside [lb, ub] on an absorbing dimension or inside an obstacle; the exit cost is charged once
     auto exit_test = [&](int s, double disc) {
         const bool inobs = in_obstacle<D>(A, ro, x);
@@ -315,7 +320,7 @@ __global__ void __launch_bounds__(256) k_rollout(const KArgs A, const SimK S, co
             const double *g = ro + A.xg_off[m];
             out = out || ((A.bctype[m] == C3SC_ABSORB) && ((x[m] < g[0]) || (x[m] > g[A.ngrid[m] - 1])));
         }
-        const bool now = (ex < 0) && (inobs || out);
+        const bool now = running() && (inobs || out);
         const double term = inobs ? Model::obscost(A.prm, x) : Model::boundcost(A.prm, x);
         J = now ? J + disc * term : J;
         ex = now ? (long long)s : ex;
@@ -323,7 +328,7 @@ __global__ void __launch_bounds__(256) k_rollout(const KArgs A, const SimK S, co
     for (int s = S.s0; s < S.s1; s++) {
         const double disc = exp(-beta * ((double)s * dt));
         exit_test(s, disc);
-        const bool alive = ex < 0;
+        bool alive = running();
         double xin[D];
         if (S.wrap) wrap_periodic<D>(A, ro, x, xin);
         else
@@ -350,7 +355,16 @@ __global__ void __launch_bounds__(256) k_rollout(const KArgs A, const SimK S, co
         }
         if (!boxed) {
             int ui;
-            (void)node_backup<Model, 1, 1, CandLds<Model>, true, NoPre, model_game<Model>(), model_horizon<Model>()>(A, ro, xin, tv, cr, V, ab, ui, st);
+            (void)node_backup<Model, 1, 1, CandLds<Model>, true, NoPre, model_game<Model>(), model_horizon<Model>(), model_stop<Model>()>(
+                A, ro, xin, tv, cr, V, ab, ui, st);
+            if constexpr (model_stop<Model>()) { // the controller stops here: the lane pays psi and is frozen like an exited one.  psi is
+                                                 // taken at the state the controller saw (wrapped, with S.wrap): the amount that won
+                const bool stopnow = alive && (ui == A.ncand);
+                J = stopnow ? J + disc * Model::stopcost(A.prm, xin) : J;
+                ex = stopnow ? -((long long)s + 2) : ex;
+                alive = alive && !stopnow;
+                ui = (ui == A.ncand) ? -1 : ui; // the candidate table has no row ncand: u = 0
+            }
             const int uc = ui < 0 ? 0 : (model_game<Model>() ? game_pair_to_list(A, ui) : ui); // game: the saddle pair's list position
 #pragma unroll
             for (int k = 0; k < DU; k++) u[k] = (ui >= 0) ? ro[A.cands_off + uc * DU + k] : 0.0; // obstacle: u = 0
@@ -403,7 +417,7 @@ __global__ void __launch_bounds__(256) k_rollout(const KArgs A, const SimK S, co
             rollout_input<D>(A, ro, S.wrap, x, xin);
             offgrid_stencil<D, RP>(A, ro, xin, S.constelm, V, ab);
             if (S.vend) S.vend[i] = V[2 * D];
-            if constexpr (model_horizon<Model>()) J = (ex < 0) ? J + dend * V[2 * D] : J;
+            if constexpr (model_horizon<Model>()) J = running() ? J + dend * V[2 * D] : J;
         }
     }
 #pragma unroll

@@ -37,6 +37,7 @@ EXPORTS = [
     "c3sc_hip_model_compile", "c3sc_hip_model_code_object", "c3sc_hip_model_log",
     "c3sc_hip_set_game", "c3sc_hip_model_compile_ex", "c3sc_hip_model_code_object_ex",
     "c3sc_hip_model_compile_fh", "c3sc_hip_model_code_object_fh", "c3sc_hip_set_horizon_step", "c3sc_hip_upload_value_stack",
+    "c3sc_hip_model_compile_os", "c3sc_hip_model_code_object_os", "c3sc_hip_set_stopping",
 ]
 
 class SimArgs(C.Structure):
@@ -76,6 +77,11 @@ class ModelSpecEx(C.Structure):
 class ModelSpecFh(C.Structure):
     """struct c3sc_hip_model_spec_fh (include/c3sc_hip.h): the _ex spec plus the horizon flag"""
     _fields_ = [("ex", ModelSpecEx), ("horizon", C.c_int)]
+
+
+class ModelSpecOs(C.Structure):
+    """struct c3sc_hip_model_spec_os (include/c3sc_hip.h): the _fh spec plus the stop flag"""
+    _fields_ = [("fh", ModelSpecFh), ("stop", C.c_int)]
 
 
 MODEL_USER = 1000  # C3SC_MODEL_USER: first id of the run-time compiled models
@@ -154,6 +160,9 @@ def load_library():
         L.c3sc_hip_model_code_object_fh.argtypes = [C.POINTER(ModelSpecFh), C.c_void_p, c_size_p]
         L.c3sc_hip_set_horizon_step.argtypes = [C.c_void_p, C.c_double]
         L.c3sc_hip_upload_value_stack.argtypes = [C.c_void_p, C.c_int, c_size_p, C.POINTER(c_double_p)]
+        L.c3sc_hip_model_compile_os.argtypes = [C.POINTER(ModelSpecOs), c_int_p]
+        L.c3sc_hip_model_code_object_os.argtypes = [C.POINTER(ModelSpecOs), C.c_void_p, c_size_p]
+        L.c3sc_hip_set_stopping.argtypes = [C.c_void_p, C.c_int]
         _LIB = L
     return _LIB
 
@@ -183,16 +192,21 @@ def _model_fail(rc, what):
 
 
 def compile_model(source: str, d: int, du: int, ranks=(4, 8), box: bool = False, udep_mask: int = 0, uconst_mask: int = 0,
-                  stage_udep: bool = True, name: Optional[str] = None, game: bool = False, horizon: bool = False) -> int:
+                  stage_udep: bool = True, name: Optional[str] = None, game: bool = False, horizon: bool = False,
+                  stop: bool = False) -> int:
     """Compile a device model from source (c3sc_hip_model_compile, include/c3sc_hip.h states the source contract) and return
     its model id (>= MODEL_USER), usable wherever a built-in model id is.  No GPU is needed.  Raises C3scHipError with the
     compiler's log on failure; the error code is args[1].  game=True (c3sc_hip_model_compile_ex) adds the game kernels that
     BellmanEngine.set_game needs: the control vector is then (u, w) of the two players.  horizon=True
-    (c3sc_hip_model_compile_fh) adds the finite-horizon kernels that BellmanEngine.set_horizon_step needs."""
+    (c3sc_hip_model_compile_fh) adds the finite-horizon kernels that BellmanEngine.set_horizon_step needs.  stop=True
+    (c3sc_hip_model_compile_os) adds the stop kernels that BellmanEngine.set_stopping needs: the source then defines stopcost."""
     L = load_library()
     spec = _model_spec(source, d, du, tuple(ranks), box, udep_mask, uconst_mask, stage_udep, name)
     mid = C.c_int(0)
-    if horizon:
+    if stop:
+        os_ = ModelSpecOs(ModelSpecFh(ModelSpecEx(spec, 1 if game else 0), 1 if horizon else 0), 1)
+        rc = L.c3sc_hip_model_compile_os(C.byref(os_), C.byref(mid))
+    elif horizon:
         fh = ModelSpecFh(ModelSpecEx(spec, 1 if game else 0), 1)
         rc = L.c3sc_hip_model_compile_fh(C.byref(fh), C.byref(mid))
     elif game:
@@ -206,17 +220,21 @@ def compile_model(source: str, d: int, du: int, ranks=(4, 8), box: bool = False,
 
 
 def code_object(source: str, d: int, du: int, ranks=(4, 8), box: bool = False, udep_mask: int = 0, uconst_mask: int = 0,
-                stage_udep: bool = True, name: Optional[str] = None, game: bool = False, horizon: bool = False) -> bytes:
+                stage_udep: bool = True, name: Optional[str] = None, game: bool = False, horizon: bool = False,
+                stop: bool = False) -> bytes:
     """The gfx950 code object of this spec (c3sc_hip_model_code_object): the loaded one if compile_model already compiled the
     spec, otherwise what compile_model would build now (its id and default name are in the kernel names), compiled and not
-    registered."""
+    registered.  game, horizon and stop select the spec as in compile_model (stop: c3sc_hip_model_code_object_os)."""
     L = load_library()
     spec = _model_spec(source, d, du, tuple(ranks), box, udep_mask, uconst_mask, stage_udep, name)
     cap = 16 << 20  # one compile when the code object fits; a larger one is compiled again into a buffer of its size
     for _ in range(2):
         buf = C.create_string_buffer(cap)
         size = C.c_size_t(cap)
-        if horizon:
+        if stop:
+            os_ = ModelSpecOs(ModelSpecFh(ModelSpecEx(spec, 1 if game else 0), 1 if horizon else 0), 1)
+            rc = L.c3sc_hip_model_code_object_os(C.byref(os_), buf, C.byref(size))
+        elif horizon:
             fh = ModelSpecFh(ModelSpecEx(spec, 1 if game else 0), 1)
             rc = L.c3sc_hip_model_code_object_fh(C.byref(fh), buf, C.byref(size))
         elif game:
@@ -239,6 +257,17 @@ def game_split(index, nw: int):
     if np.ndim(index) == 0:
         return int(iu), int(iw)
     return iu, iw
+
+
+def decode_exit(exit_step):
+    """d_exit of a rollout with stopping on (c3sc_hip_set_stopping) as (step, stopped): an exit at step k >= 0 is (k, 0), a
+    voluntary stop stored as -(k + 2) is (k, 1), never (-1) is (-1, 0); works elementwise on arrays."""
+    e = np.asarray(exit_step)
+    stopped = e <= -2
+    step = np.where(stopped, -e - 2, e)
+    if np.ndim(exit_step) == 0:
+        return int(step), int(stopped)
+    return step, stopped.astype(np.int32)
 
 
 def _f64(a):
@@ -264,6 +293,7 @@ class BellmanEngine:
         self.h = h
         self.device = device
         self.w = None
+        self.stopping = False
 
     def close(self):
         if getattr(self, "h", None):
@@ -331,6 +361,13 @@ class BellmanEngine:
         dt, one stage back from the uploaded value; dt = 0 ends it.  The model must be compiled with horizon=True."""
         self._chk(self.L.c3sc_hip_set_horizon_step(self.h, C.c_double(dt)), "set_horizon_step")
         self.horizon_dt = float(dt)
+
+    def set_stopping(self, on: bool = True):
+        """Optimal stopping (c3sc_hip_set_stopping): the Bellman calls add the stop action (index ncand, cost stopcost(x)) to
+        the scan, and simulate stops a trajectory where the controller picks it (decode_exit).  The model must be compiled with
+        stop=True, and with horizon=True as well to combine it with set_horizon_step."""
+        self._chk(self.L.c3sc_hip_set_stopping(self.h, C.c_int(1 if on else 0)), "set_stopping")
+        self.stopping = bool(on)
 
     def upload_value_stack(self, ranks, cores):
         """V_0 .. V_N for simulate in horizon mode (c3sc_hip_upload_value_stack): ranks[s] is stage s's rank list (d + 1 entries),

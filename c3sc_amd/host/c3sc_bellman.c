@@ -376,6 +376,9 @@ struct DPparam {
     int nprm;
     int model_checked;
     double hz_dt; /* finite-horizon step delta (c3control_set_horizon_step); 0: the infinite-horizon operator */
+    /* optimal stopping (c3control_add_stopcost / c3control_set_stopping): psi(t, x) and the switch */
+    int (*stopcost)(double, const double *, double *);
+    int stopping;
 };
 
 struct DPparam *dp_param_create(size_t dx, size_t du, size_t dw, double discount)
@@ -412,6 +415,7 @@ struct ControlParams {
     struct Workspace *work;
     struct c3Opt *opt;
     int res_last_grad;
+    int stopped_last; /* bellman_optimal in stop mode: the last node's decision was the stop action */
 };
 
 struct ControlParams *control_params_create(size_t dx, size_t dw, struct DPparam *dp, struct MCAparam *mca,
@@ -511,6 +515,18 @@ int bellman_optimal(size_t du, double *u, double *val, void *arg)
     c3opt_add_objective(opt, &bellman_control, mem);
     c3opt_minimize(opt, u, val); /* BRUTEFORCE: list scan; otherwise the box minimiser (grid + golden section) */
     c3opt_free(opt);
+    p->stopped_last = 0;
+    if (p->dp->stopping) { /* node_backup's STOP action, scanned last: psi wins where it is strictly smaller */
+        double psi;
+        int r = p->dp->stopcost(p->time, p->x + mem->private * p->dx, &psi);
+        assert(r == 0);
+        (void)r;
+        if (psi < *val) {
+            *val = psi;
+            for (size_t i = 0; i < du; i++) u[i] = 0.0;
+            p->stopped_last = 1;
+        }
+    }
     return 0;
 }
 
@@ -586,6 +602,9 @@ static struct c3sc_hip_ctx *sync_device_ctx(struct ControlParams *cp, struct c3s
     if (dp->hz_dt > 0.0 && (!brute || gorder >= 0 || dp->model == 0))
         DIE("bellman_vi: horizon mode needs a device model compiled with horizon kernels (c3sc_hip_model_compile_fh) and a plain candidate list");
     sig = fnv(sig, &dp->hz_dt, sizeof(double));
+    if (dp->stopping && (!brute || gorder >= 0 || dp->model == 0))
+        DIE("bellman_vi: stopping needs a device model compiled with stop kernels (c3sc_hip_model_compile_os) and a plain candidate list");
+    sig = fnv(sig, &dp->stopping, sizeof(int));
     if (brute) sig = fnv(sig, c3opt_get_brute_vals(cp->opt), c3opt_get_nbrute(cp->opt) * odu * sizeof(double));
     else {
         const size_t g = c3opt_get_box_grid(cp->opt), pl = c3opt_get_box_polish(cp->opt);
@@ -600,6 +619,8 @@ static struct c3sc_hip_ctx *sync_device_ctx(struct ControlParams *cp, struct c3s
         hipok(ctx, c3sc_hip_set_boundary(ctx, bc, (int)nobs, lb, ub), "c3sc_hip_set_boundary");
         hipok(ctx, c3sc_hip_set_mca(ctx, mca->h2, mca->t, dp->discount), "c3sc_hip_set_mca");
         hipok(ctx, c3sc_hip_set_consistent_ends(ctx, cends), "c3sc_hip_set_consistent_ends");
+        /* a context left in stop mode by an earlier problem would refuse set_game: off first, on again after the controls */
+        hipok(ctx, c3sc_hip_set_stopping(ctx, 0), "c3sc_hip_set_stopping");
         if (dp->model != 0) hipok(ctx, c3sc_hip_set_model(ctx, dp->model, dp->prm, dp->nprm), "c3sc_hip_set_model");
         if (brute && gorder >= 0)
             hipok(ctx, c3sc_hip_set_game(ctx, (int)gdu_min, (int)gnu, gU, (int)gnw, gW, gorder), "c3sc_hip_set_game");
@@ -609,6 +630,7 @@ static struct c3sc_hip_ctx *sync_device_ctx(struct ControlParams *cp, struct c3s
             hipok(ctx, c3sc_hip_set_control_box(ctx, (int)odu, c3opt_get_lb(cp->opt), c3opt_get_ub(cp->opt), (int)c3opt_get_box_grid(cp->opt),
                                                 (int)c3opt_get_box_polish(cp->opt)), "c3sc_hip_set_control_box");
         hipok(ctx, c3sc_hip_set_horizon_step(ctx, dp->hz_dt), "c3sc_hip_set_horizon_step");
+        hipok(ctx, c3sc_hip_set_stopping(ctx, dp->stopping), "c3sc_hip_set_stopping");
         g_ctx[sl].cfg_set = 1;
         g_ctx[sl].cfg_sig = sig;
         g_ctx[sl].version = 0; /* set_grid invalidates the resident value function */
@@ -941,6 +963,13 @@ static void refuse_game_pi(const struct c3Opt *opt, const char *who)
         DIE("%s: policy iteration is not offered for games (c3opt_set_brute_force_game); use value iteration", who);
 }
 
+/* nor for stopping problems */
+static void refuse_stop_pi(const struct DPparam *dp, const char *who)
+{
+    if (dp != NULL && dp->stopping)
+        DIE("%s: policy iteration is not offered for stopping problems (c3control_set_stopping); use value iteration", who);
+}
+
 /* nor in horizon mode: a finite-horizon problem has no stationary policy to iterate on */
 static void refuse_horizon_pi(const struct DPparam *dp, const char *who)
 {
@@ -953,6 +982,7 @@ static int pi_core(struct PIparam *pi, size_t F, size_t k0, const int32_t *idx, 
     struct ControlParams *cp = pi->cp;
     refuse_game_pi(cp->opt, "bellman_pi");
     refuse_horizon_pi(cp->dp, "bellman_pi");
+    refuse_stop_pi(cp->dp, "bellman_pi");
     struct MCAparam *mca = cp->mca;
     struct DPparam *dp = cp->dp;
     const size_t dx = mca->dx, N = mca->ngrid[k0];
@@ -1200,6 +1230,14 @@ void c3control_add_diff(struct C3Control *c, c3sc_dyn_fn s, void *a) { dp_param_
 void c3control_add_stagecost(struct C3Control *c, int (*f)(double, const double *, const double *, double *, double *)) { dp_param_add_stagecost(c->dp, f); }
 void c3control_add_boundcost(struct C3Control *c, int (*f)(double, const double *, double *)) { dp_param_add_boundcost(c->dp, f); }
 void c3control_add_obscost(struct C3Control *c, int (*f)(const double *, double *)) { dp_param_add_obscost(c->dp, f); }
+void c3control_add_stopcost(struct C3Control *c, int (*f)(double, const double *, double *)) { c->dp->stopcost = f; }
+void c3control_set_stopping(struct C3Control *c, int on)
+{
+    if (on && c->dp->stopcost == NULL) DIE("c3control_set_stopping: c3control_add_stopcost first");
+    c->dp->stopping = on ? 1 : 0;
+    c->dp->model_checked = 0; /* the first-fiber check runs again, against the operator now in force */
+}
+int c3control_get_stopping(const struct C3Control *c) { return c->dp->stopping; }
 void c3control_set_device_model(struct C3Control *c, int model, const double *params, size_t n) { dp_param_set_device_model(c->dp, model, params, n); }
 
 void c3control_set_consistent_ends(struct C3Control *c, int on)
@@ -1266,6 +1304,7 @@ void c3control_begin_pi_step(struct C3Control *c, struct PIparam *pi, struct Val
 { /* c3control_step_pi before valuef_interp (bellman.c:2236-2249) */
     refuse_game_pi(opt, "c3control_step_pi");
     refuse_horizon_pi(c->dp, "c3control_step_pi");
+    refuse_stop_pi(c->dp, "c3control_step_pi");
     c->cp_active = control_params_create(c->dx, c->dw, c->dp, c->mca, c->work, opt);
     pi_param_add_cp(pi, c->cp_active);
     pi_param_add_value(pi, vf);
@@ -1554,6 +1593,7 @@ struct ValueF *c3control_pi_solve(struct C3Control *c, size_t maxiter, double ab
 { /* bellman.c:2343-2407 */
     refuse_game_pi(opt, "c3control_pi_solve");
     refuse_horizon_pi(c->dp, "c3control_pi_solve");
+    refuse_stop_pi(c->dp, "c3control_pi_solve");
     struct ValueF *start = valuef_copy(policy);
     struct PIparam *poli = c3control_begin_pi(c, policy);
     double stot = 1.0;
@@ -1620,10 +1660,10 @@ void c3control_add_policy_sim(struct C3Control *c, struct ValueF *pol, struct c3
     c->transform_sim = transform;
 }
 
-int c3control_policy_eval(struct C3Control *c, double t, const double *x, double *u)
+int c3control_policy_eval_stop(struct C3Control *c, double t, const double *x, double *u, int *stopped)
 { /* bellman.c:2105-2158: one state, host callbacks (a single node is not GPU work) */
     assert(c->policy_sim != NULL && c->opt_sim != NULL);
-    if (c->dp->stagecost == NULL) DIE("c3control_policy_eval: the host callbacks (add_drift/diff/stagecost/...) are needed");
+    if (c->dp->stagecost == NULL) DIE("c3control_policy_eval(_stop): the host callbacks (add_drift/diff/stagecost/...) are needed");
     int *absorbed = workspace_get_absorbed(c->work, 0);
     double *costs = workspace_get_costs(c->work, 0);
     struct ControlParams *cp = control_params_create(c->dx, c->dw, c->dp, c->mca, c->work, c->opt_sim);
@@ -1642,8 +1682,14 @@ int c3control_policy_eval(struct C3Control *c, double t, const double *x, double
     assert(res2 == 0);
     (void)res2;
     for (size_t i = 0; i < c->du; i++) c->prevpol[i] = u[i];
+    if (stopped != NULL) *stopped = cp->stopped_last;
     control_params_destroy(cp);
     return 0;
+}
+
+int c3control_policy_eval(struct C3Control *c, double t, const double *x, double *u)
+{ /* where the policy stops (c3control_set_stopping) u is 0 */
+    return c3control_policy_eval_stop(c, t, x, u, NULL);
 }
 
 int c3control_controller(double t, const double *x, double *u, void *args)
@@ -1765,6 +1811,7 @@ int c3control_integrate(struct C3Control *c, const char *method, double dt_int, 
      for one trajectory, over the user's callbacks and c3control_controller; the host twin of c3sc_hip_integrate */
     const char *who = "c3control_integrate";
     if (c == NULL || x0 == NULL) return reject(who, "null control or x0");
+    if (c->dp->stopping) return reject(who, "deterministic closed loops are not offered for stopping problems (c3control_set_stopping)");
     if (c->policy_sim == NULL || c->opt_sim == NULL) return reject(who, "no implicit policy (c3control_add_policy_sim)");
     if (c->dp->drift == NULL || c->dp->stagecost == NULL || c->dp->boundcost == NULL || c->dp->obscost == NULL)
         return reject(who, "the host callbacks (drift, stagecost, boundcost, obscost) are needed");
@@ -1846,6 +1893,7 @@ int c3control_integrate_batch(struct C3Control *c, size_t ntraj, const double *x
     const char *who = "c3control_integrate_batch";
     int rc = batch_policy_check(who, c, wrap_periodic);
     if (rc != 0) return rc;
+    if (c->dp->stopping) return reject(who, "deterministic closed loops are not offered for stopping problems (c3control_set_stopping)");
     size_t nsub;
     rc = integrate_check(who, c->dx, method, dt_int, dt_out, nout, goal, keep, &nsub);
     if (rc != 0) return rc;
@@ -1891,6 +1939,8 @@ int c3control_simulate(struct C3Control *c, const double *x0, double dt, size_t 
      x_{n+1} = x_n + b(x_n, u_n) dt + sigma(x_n, u_n) dW_n, u_n = controller(x_n); noise = nsteps x dw standard normals
      or NULL.  traj: (nsteps+1) x dx, utraj: nsteps x du (may be NULL). */
     const size_t dx = c->dx, du = c->du, dw = c->dw;
+    if (c->dp->stopping)
+        return reject("c3control_simulate", "the single-trajectory loop has no stop action; use c3control_simulate_batch (c3control_set_stopping)");
     double *b = xcalloc(dx, sizeof(double)), *s = xcalloc(dx * dw, sizeof(double)), *u = xcalloc(du, sizeof(double));
     memcpy(traj, x0, dx * sizeof(double));
     const double sq = sqrt(dt);

@@ -189,6 +189,22 @@ void c3control_set_horizon_step(struct C3Control *, double delta);
 double c3control_get_horizon_step(const struct C3Control *);
 struct ValueF **c3control_fh_solve(struct C3Control *, size_t nstages, double delta, struct ValueF *terminal, struct ApproxArgs *,
                                    struct c3Opt *, int verbose);
+/* new: optimal stopping.  c3control_add_stopcost gives the stopping cost psi(t, x); c3control_set_stopping(c, 1)
+ * adds the stop action to the Bellman operator, V = min(psi, min_u backup): scanned last, it wins where psi is strictly smaller
+ * than the minimiser's value.  It holds for the host scan (bellman_optimal), the first-fiber check and the device context (which
+ * needs a model compiled with c3sc_hip_model_compile_os, stop = 1, whose stopcost is the device form of psi, and a candidate
+ * list).  c3control_step_vi, c3control_vi_solve and, with the horizon step, c3control_fh_solve (American options) work in stop
+ * mode; policy iteration stops with a message.  c3control_policy_eval_stop is c3control_policy_eval with the decision: *stopped
+ * = 1 where the policy stops, and u is 0 there (as it is from c3control_policy_eval and c3control_controller).
+ * c3control_simulate_batch returns the exit step encoded as c3sc_hip_simulate does: k >= 0 an exit at step k, -1 never, -(k + 2)
+ * a voluntary stop at step k.  c3control_simulate and c3control_integrate(_batch) return an error in stop mode.
+ * One difference from the device: at a node whose candidates are all stationary (Q < 1e-14) the device returns psi with the stop
+ * index, while the host scan stops at the first stationary candidate as it does without stopping (bellman_control asserts, as
+ * bellman.c:452 does): a first-fiber check over such a node ends the program instead of agreeing. */
+void c3control_add_stopcost(struct C3Control *, int (*)(double t, const double *x, double *out));
+void c3control_set_stopping(struct C3Control *, int on);
+int c3control_get_stopping(const struct C3Control *);
+int c3control_policy_eval_stop(struct C3Control *, double t, const double *x, double *u, int *stopped);
 struct ValueF *c3control_vi_solve(struct C3Control *, size_t maxiter, double abs_conv_tol, struct ValueF *vo,
                                   struct ApproxArgs *, struct c3Opt *, int verbose, struct Diag **diag); /* :2282-2340 */
 struct ValueF *c3control_pi_solve(struct C3Control *, size_t maxiter, double abs_conv_tol, struct ValueF *policy,

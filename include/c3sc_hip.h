@@ -534,6 +534,43 @@ int c3sc_hip_set_horizon_step(c3sc_hip_ctx *ctx, double dt);
  * mean of J estimates V_0(x_0)), and d_vend is V_nsteps(x_nsteps).  The noise keying is the infinite-horizon rollouts'. */
 int c3sc_hip_upload_value_stack(c3sc_hip_ctx *ctx, int nstack, const size_t *ranks, const double *const *cores);
 
+/* Optimal stopping: the controller may end the process at any node and pay a stopping cost psi(x) instead of
+ * continuing.  A stopping model's source defines one more function,
+ *   __device__ double stopcost(const double *prm, const double *x);
+ * and the operator gains one action with the index ncand:
+ *     V(x)   = min( psi(x), min_u [plain backup] )                                      (infinite horizon)
+ *     V_n(x) = min( psi(x), min_u [ g delta + e^{-beta delta} ( V_self + (delta / h^2) (PV - Q V_self) ) ] )   (horizon mode)
+ * The stop action is scanned last and wins by the rule of every other candidate, the first strict '<': the candidate scan runs as
+ * it does without it (at beta = 0 with its fraction comparison and single division) and psi is compared once per node with the
+ * scan's result.  psi also wins where the scan left no valid candidate: the value is then psi and no longer 0.  uidx is 0..ncand,
+ * -1 on absorbed nodes.  Stop raises neither C3SC_STATUS_STATIONARY nor C3SC_STATUS_CFL; the bits the scanned candidates raise
+ * are unchanged.  Policy evaluation (policy_fibers*): a forced index ncand yields psi and applies no candidate, any other index
+ * applies that candidate and does not compare with psi.  Absorbed and obstacle nodes, the end-point rule and the node memo are
+ * unchanged.
+ * The stop kernels exist only in run-time compiled models built with c3sc_hip_model_compile_os and stop = 1: the stop forms of
+ * the per-wave kernels and of k_rollout at every requested rank, and with fh.horizon = 1 their combined (American) forms as
+ * well; k_rollout_ode has none.  stop = 1 with a game or the box returns C3SC_ERR_UNSUPPORTED, a flag other than 0 or 1
+ * C3SC_ERR_ARG; stop = 0 is exactly c3sc_hip_model_compile_fh, and the source need not define stopcost then. */
+typedef struct c3sc_hip_model_spec_os {
+    c3sc_hip_model_spec_fh fh;
+    int stop;
+} c3sc_hip_model_spec_os;
+int c3sc_hip_model_compile_os(const c3sc_hip_model_spec_os *spec, int *model_id);
+int c3sc_hip_model_code_object_os(const c3sc_hip_model_spec_os *spec, void *buf, size_t *size);
+/* stopping on (on != 0) or off.  C3SC_ERR_UNSUPPORTED for built-in and TABLE models, a model compiled without stop kernels (also
+ * one set after this call: the launch then refuses) and a context in game mode; c3sc_hip_set_game is refused while stopping is
+ * on.  Honoured by bellman_fibers(_all|_host), policy_fibers(_all|_host) (on the fiber-per-wave kernel: AUTO picks it, a forced
+ * pair or quad variant is refused), the cross calls that launch through them, and simulate.  With the horizon step set as well
+ * the launches take the combined form, which needs a model compiled with both flags.  Refused (C3SC_ERR_UNSUPPORTED): the box
+ * and TABLE calls, cross_iteration_pi and integrate.
+ * c3sc_hip_simulate with stopping on: a trajectory whose controller returns the stop action at step k stops there, pays
+ * e^{-beta k dt} psi(x_k) and is frozen like an exited one; its saved controls from k on are 0.  With wrap_periodic psi is taken
+ * at the wrapped state, the one the controller compared it at (stage and exit costs are charged at the state itself).  d_exit tells the two apart:
+ * an exit keeps its step k >= 0, "never" stays -1, a voluntary stop at step k is stored as -(k + 2).  In horizon mode under a
+ * value stack the decision at step k uses V_{k+1}, as the controls do, and a trajectory alive after nsteps still adds the
+ * discounted V_nsteps. */
+int c3sc_hip_set_stopping(c3sc_hip_ctx *ctx, int on);
+
 int c3sc_hip_sync(c3sc_hip_ctx *ctx, void *stream);
 int c3sc_hip_get_status(c3sc_hip_ctx *ctx, unsigned *flags, int clear);
 /* name of the kernel the last launch used (for profiles) */
