@@ -248,6 +248,7 @@ static int upload_static(c3sc_hip_ctx *c)
         st[c->hz_off + 1] = std::exp(-c->discount * c->hz_dt);
         st[c->hz_off + 2] = c->hz_dt / c->h2;
     }
+    st[c->hz_off + 3] = c->constelm ? 1.0 : 0.0; // the interpolation class of the jump targets (kernel_common.hpp: jump_constelm)
     HIPCHK(c, hipMemcpy(c->arena, st.data(), st.size() * sizeof(double), hipMemcpyHostToDevice));
     c->static_dirty = false;
     return C3SC_OK;
@@ -332,6 +333,14 @@ static int check_horizon_model(c3sc_hip_ctx *c, const char *what)
 static int check_stop_model(c3sc_hip_ctx *c, const char *what)
 {
     if (c->stopping && !(c->model >= C3SC_MODEL_USER && rtc_model_stop(c->model) && c->game_gsz == 0))
+        return fail(c, C3SC_ERR_UNSUPPORTED, what);
+    return C3SC_OK;
+}
+
+// jumps are served by the jump kernels of the model set now, never together with a game
+static int check_jump_model(c3sc_hip_ctx *c, const char *what)
+{
+    if (c->jumps && !(c->model >= C3SC_MODEL_USER && rtc_model_njump(c->model) > 0 && c->game_gsz == 0))
         return fail(c, C3SC_ERR_UNSUPPORTED, what);
     return C3SC_OK;
 }
@@ -600,6 +609,23 @@ int c3sc_hip_set_stopping(c3sc_hip_ctx *c, int on)
     return C3SC_OK;
 }
 
+int c3sc_hip_set_jumps(c3sc_hip_ctx *c, int on)
+{
+    if (!c) return C3SC_ERR_ARG;
+    if (!on) {
+        c->jumps = 0;
+        return C3SC_OK;
+    }
+    if (c->model == 0) return fail(c, C3SC_ERR_ARG, "set_jumps: set_model first");
+    if (c->model < C3SC_MODEL_USER || !rtc_model_known(c->model))
+        return fail(c, C3SC_ERR_UNSUPPORTED, "set_jumps: jumps need a run-time compiled model (c3sc_hip_model_compile_jd with njump > 0)");
+    if (rtc_model_njump(c->model) == 0)
+        return fail(c, C3SC_ERR_UNSUPPORTED, "set_jumps: this model was compiled without jump kernels (c3sc_hip_model_compile_jd, njump > 0)");
+    if (c->game_gsz > 0) return fail(c, C3SC_ERR_UNSUPPORTED, "set_jumps: games with jumps are not offered");
+    c->jumps = 1;
+    return C3SC_OK;
+}
+
 int c3sc_hip_set_model(c3sc_hip_ctx *c, int model, const double *params, int nparams)
 {
     if (!c || model <= 0 || nparams < 0 || nparams > C3SC_MAX_PARAMS) return fail(c, C3SC_ERR_ARG, "set_model: bad arguments");
@@ -634,6 +660,7 @@ int c3sc_hip_set_game(c3sc_hip_ctx *c, int du_min, int nu, const double *U, int 
     if (c->model == C3SC_MODEL_TABLE) return fail(c, C3SC_ERR_UNSUPPORTED, "set_game: the TABLE model has no game kernels");
     if (c->hz_dt > 0.0) return fail(c, C3SC_ERR_UNSUPPORTED, "set_game: games have no horizon form (c3sc_hip_set_horizon_step(ctx, 0) first)");
     if (c->stopping) return fail(c, C3SC_ERR_UNSUPPORTED, "set_game: stopping games are not offered (c3sc_hip_set_stopping(ctx, 0) first)");
+    if (c->jumps) return fail(c, C3SC_ERR_UNSUPPORTED, "set_game: games with jumps are not offered (c3sc_hip_set_jumps(ctx, 0) first)");
     int mdu = 0;
     bool has_game = false;
     if (c->model < C3SC_MODEL_USER || !rtc_model_info(c->model, mdu, has_game))
@@ -1155,11 +1182,19 @@ static int launch_bellman(c3sc_hip_ctx *c, int k, size_t F, const int32_t *d_idx
             return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers: stopping runs on the fiber-per-wave kernel only (the pair and quad variants have no stop form)");
         variant = C3SC_VARIANT_FIBER_PER_WAVE;
     }
+    if (c->jumps) { // and with jumps on: the jump form of whichever of the forms above the other switches select
+        rc = check_jump_model(c, "bellman_fibers: jumps need a model compiled with jump kernels (and no game)");
+        if (rc != C3SC_OK) return rc;
+        if (variant != C3SC_VARIANT_AUTO && variant != C3SC_VARIANT_FIBER_PER_WAVE)
+            return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers: jumps run on the fiber-per-wave kernel only (the pair and quad variants have no jump form)");
+        variant = C3SC_VARIANT_FIBER_PER_WAVE;
+    }
     if (F == 0) return C3SC_OK;
     if (!d_idx || !d_out) return fail(c, C3SC_ERR_ARG, "bellman_fibers: null buffer");
     A.forced = d_policy;
     LaunchIO io{c->arena, d_idx, d_out, d_uidx, d_absorbed, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream};
     io.stop = c->stopping != 0;
+    io.jump = c->jumps != 0;
     // A launcher declines (nothing launched) when its LDS layout does not fit this grid or it does not serve this call; the
     // next-best instantiation of the same padded rank is tried then (e.g. the duo kernel's two staging buffers hold N <= 25 at
     // rank 16, the one-buffer quad kernel behind it N <= 75, the per-wave kernel behind that only stages the varying core).
@@ -1223,7 +1258,7 @@ static int launch_bellman_all(c3sc_hip_ctx *c, int nk, const int *ks, const size
             if (d_out[q] == d_out[s] && F[s] > 0) return fail(c, C3SC_ERR_ARG, "bellman_fibers_all: two segments share an output array");
     }
     hipStream_t st = (hipStream_t)stream;
-    if (overlap && c->tab3L_off && c->tab3_stale && c->game_gsz == 0 && c->hz_dt <= 0.0 && !c->stopping) {
+    if (overlap && c->tab3L_off && c->tab3_stale && c->game_gsz == 0 && c->hz_dt <= 0.0 && !c->stopping && !c->jumps) {
         // stale three-core tables: built here, ahead of the fork, if a segment is going to run a three-core kernel -- every
         // side stream is then ordered behind the build by the fork itself
         const long fmin = fiber_partition_min();
@@ -1286,6 +1321,7 @@ static int launch_box(c3sc_hip_ctx *c, int k, size_t F, const int32_t *d_idx, co
     if (c->game_gsz > 0) return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_box: games have no control-box form");
     if (c->hz_dt > 0.0) return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_box: horizon mode has no control-box form");
     if (c->stopping) return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_box: stopping has no control-box form");
+    if (c->jumps) return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_box: jumps have no control-box form");
     if (model_ncf(c->model) != 0 && c->model != C3SC_MODEL_COTHRUST6D) // cothrust forms its features from u on the device (models.hpp: CF_FROM_U)
         return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_box: this model needs transcendental functions of the control");
     KArgs A;
@@ -1359,6 +1395,7 @@ static int launch_tables(c3sc_hip_ctx *c, int k, size_t F, const int32_t *d_idx,
     if (c->game_gsz > 0) return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_tables: the TABLE model has no game kernels");
     if (c->hz_dt > 0.0) return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_tables: the TABLE model has no horizon kernels");
     if (c->stopping) return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_tables: the TABLE model has no stop kernels");
+    if (c->jumps) return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_tables: the TABLE model has no jump kernels");
     c->model = C3SC_MODEL_TABLE; // fill_args only checks that a model is set
     KArgs A;
     int rc = fill_args(c, k, F, A, true);
@@ -1500,6 +1537,7 @@ int c3sc_hip_get_status(c3sc_hip_ctx *c, unsigned *flags, int clear)
 int c3sc_hip_set_interp(c3sc_hip_ctx *c, int constelm)
 {
     if (!c) return C3SC_ERR_ARG;
+    if (c->constelm != (constelm ? 1 : 0)) c->static_dirty = true; // the jump kernels read the class from the static section
     c->constelm = constelm ? 1 : 0;
     return C3SC_OK;
 }
@@ -1650,6 +1688,10 @@ int c3sc_hip_simulate(c3sc_hip_ctx *c, const c3sc_hip_sim_args *a, void *stream)
             return fail(c, C3SC_ERR_ARG, "simulate: in horizon mode dt must equal the horizon step (c3sc_hip_set_horizon_step)");
         if (a->nsteps + 1 > (size_t)c->hz_nstack) return fail(c, C3SC_ERR_ARG, "simulate: nsteps exceeds the value stack (nstack - 1 stages)");
     }
+    if (c->jumps) {
+        if (check_jump_model(c, "simulate: jumps need a model compiled with jump kernels (and no game)") != C3SC_OK) return C3SC_ERR_UNSUPPORTED;
+        if (a->box) return fail(c, C3SC_ERR_UNSUPPORTED, "simulate: jumps have no control-box form");
+    }
     if (c->stopping) {
         if (check_stop_model(c, "simulate: stopping needs a model compiled with stop kernels (and no game)") != C3SC_OK) return C3SC_ERR_UNSUPPORTED;
         if (a->box) return fail(c, C3SC_ERR_UNSUPPORTED, "simulate: stopping has no control-box form");
@@ -1715,6 +1757,7 @@ int c3sc_hip_simulate(c3sc_hip_ctx *c, const c3sc_hip_sim_args *a, void *stream)
         }
         LaunchIO io{ro, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream, &S};
         io.stop = c->stopping != 0;
+        io.jump = c->jumps != 0;
         rc = launch_one(c, ek, A, io, "simulate: this rollout kernel has no box minimiser");
         if (rc != C3SC_OK) return rc;
         s0 = S.s1;
@@ -1772,6 +1815,7 @@ int c3sc_hip_integrate(c3sc_hip_ctx *c, const c3sc_hip_ode_args *a, void *stream
     if (rc != C3SC_OK) return rc;
     if (c->hz_dt > 0.0) return fail(c, C3SC_ERR_UNSUPPORTED, "integrate: deterministic closed loops are not offered in horizon mode");
     if (c->stopping) return fail(c, C3SC_ERR_UNSUPPORTED, "integrate: deterministic closed loops are not offered for stopping problems");
+    if (c->jumps) return fail(c, C3SC_ERR_UNSUPPORTED, "integrate: deterministic closed loops are not offered for jump diffusions");
     KArgs A;
     rc = fill_args(c, 0, 0, A, false);
     if (rc != C3SC_OK) return rc;
@@ -1873,6 +1917,13 @@ int c3sc_hip_normals(uint64_t seed, uint64_t traj0, size_t ntraj, uint64_t step0
         for (size_t k = 0; k < nsteps; k++)
             for (int j = 0; j < dw; j++)
                 out[(t * nsteps + k) * dw + j] = philox_normal(seed, traj0 + t, (uint32_t)(step0 + k), (uint32_t)j);
+    return C3SC_OK;
+}
+
+int c3sc_hip_jump_uniforms(uint64_t seed, uint64_t traj, uint64_t step, double *out)
+{
+    if (!out) return C3SC_ERR_ARG;
+    philox_jump_uniforms(seed, traj, (uint32_t)step, out[0], out[1]);
     return C3SC_OK;
 }
 

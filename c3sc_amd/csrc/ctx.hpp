@@ -39,6 +39,8 @@ struct c3sc_hip_ctx {
     int hz_off = 0;
     // optimal stopping (c3sc_hip_set_stopping): the launches take the stop forms of the run-time compiled model's kernels
     int stopping = 0;
+    // jump diffusions (c3sc_hip_set_jumps): the launches take the jump forms of the run-time compiled model's kernels
+    int jumps = 0;
     double *hz_stack = nullptr;
     size_t hz_stack_static = 0;
     int hz_nstack = 0;

@@ -229,6 +229,31 @@ constexpr bool model_stop()
     else return false;
 }
 
+// The jump-diffusion instantiations are those of a model wrapped in JumpOf, in the style of the wrappers above:
+// k_fiber_per_wave forms the node's jump term (jump_term, kernel_rollout.hpp) and passes model_jump<Model>() to node_backup as
+// JUMP.  The model supplies jumprate, jump and the number of marks NJUMP.  JumpOf<StopOf<HorizonOf<M>>> is the American form.
+template <class M>
+struct JumpOf : M {
+    static constexpr bool JUMP = true;
+};
+template <class Model>
+constexpr bool model_jump()
+{
+    if constexpr (requires { Model::JUMP; }) return Model::JUMP;
+    else return false;
+}
+// defined in kernel_rollout.hpp, beside the off-grid evaluation it is built on; only JUMP instantiations call it
+template <class Model, int RP>
+__device__ inline void jump_term(const KArgs &A, const double *__restrict__ ro, const double (&x)[Model::D], int constelm, double &rate,
+                                 double &J);
+// The interpolation class of the jump targets (c3sc_hip_set_interp), wave-uniform: the fourth double of the horizon block, which
+// follows the candidate features in the static section (c3sc_hip.hip: static_layout) and is there in every mode
+template <class Model>
+__device__ inline int jump_constelm(const KArgs &A, const double *__restrict__ ro)
+{
+    return ro[A.cfeat_off + Model::NCF * A.ncand + 3] != 0.0;
+}
+
 // Output pointers of one launch (separate __restrict__ kernel parameters).
 struct KOut {
     double *out;       // [F][N]            (bellman kernel)
@@ -713,18 +738,24 @@ __device__ __forceinline__ void stop_action(const KArgs &A, const double (&x)[Mo
     }
 }
 
+// JUMP (jump diffusions): one more transition with the un-normalised rate jrate = h^2 lambda(x) to the mark
+// average jval = J(x) = sum_m pi_m Vjump(y_m), formed by the caller (jump_term).  It enters Q0 and PV0 like a control-independent
+// dimension, so every scan, the explicit scheme and the forced path see it: dt = h^2 / Q with the jump rate inside Q, the term
+// delta lambda (J - V_self) in horizon mode with the rate in the CFL test, and a node with no drift and no diffusion but
+// lambda > 0 is not stationary.  jrate = 0 leaves every bit: Q0 + 0.0 and fma(0, J, PV0) are exact for finite J.
 template <class Model, int CG = 1, int CGD = 1, class Cand = CandRegs<Model>, bool SPLIT = true, class Pre = NoPre, bool GAME = false,
-          bool HORIZON = false, bool STOP = false>
+          bool HORIZON = false, bool STOP = false, bool JUMP = false>
 __device__ inline double node_backup(const KArgs &A, const double *__restrict__ ro, const double (&x)[Model::D],
                                      const double (&tv)[Model::NTAB > 0 ? Model::NTAB : 1], const Cand &cr,
                                      const double (&V)[2 * Model::D + 1], int ab, int &ui, unsigned &st, bool forced = false,
-                                     int fu = -1, const Pre &pre = Pre())
+                                     int fu = -1, const Pre &pre = Pre(), double jrate = 0.0, double jval = 0.0)
 {
     // forced (wave-uniform) = policy evaluation, bellman_pi (bellman.c:1702-1886): the candidate fu (per lane) is
     // applied instead of the minimiser's; same rates, same bellmanrhs.
     constexpr int D = Model::D, DU = Model::DU;
     static_assert(!GAME || (CG == 1 && CGD == 1), "the game scan takes one candidate per trip");
     static_assert(!(STOP && GAME), "stopping games are not offered");
+    static_assert(!(JUMP && GAME), "games with jumps are not offered");
     const int nc = __builtin_amdgcn_readfirstlane(A.ncand); // keeps the candidate loops' trip test on the scalar unit
     ui = -1;
     // game: which reductions are maxima (wave-uniform), the group length, the forced pair as a list position
@@ -784,6 +815,10 @@ __device__ inline double node_backup(const KArgs &A, const double *__restrict__ 
             Q0 += pre.q();
             PV0 += pre.pv();
         }
+    }
+    if constexpr (JUMP) {
+        Q0 += jrate;
+        PV0 = fma(jrate, jval, PV0);
     }
     double best = 0.0;
     constexpr int NCFa = Model::NCF > 0 ? Model::NCF : 1;

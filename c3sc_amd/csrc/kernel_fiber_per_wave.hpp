@@ -341,8 +341,12 @@ __global__ void __launch_bounds__(256, (RP >= 20 ? 1 : 2)) // rank 20 is LDS-bou
                 } else {
                     double tv[Model::NTAB > 0 ? Model::NTAB : 1];
                     table_values<Model>(A, ro, ix, tv);
-                    val = node_backup<Model, 1, 1, CandLds<Model>, true, NoPre, model_game<Model>(), model_horizon<Model>(), model_stop<Model>()>(
-                        A, ro, x, tv, cr, V, ab, ui, st, forced, fu);
+                    // jump models: the node's rate h^2 lambda and mark average J, one arbitrary point per lane and mark.  Idle and
+                    // absorbed lanes evaluate their (valid) node as well and are overwritten as they are without jumps
+                    double jrate = 0.0, jval = 0.0;
+                    if constexpr (model_jump<Model>()) jump_term<Model, RP>(A, ro, x, jump_constelm<Model>(A, ro), jrate, jval);
+                    val = node_backup<Model, 1, 1, CandLds<Model>, true, NoPre, model_game<Model>(), model_horizon<Model>(), model_stop<Model>(),
+                                      model_jump<Model>()>(A, ro, x, tv, cr, V, ab, ui, st, forced, fu, NoPre(), jrate, jval);
                 }
                 if (A.memo_keys) { // wave-uniform: node memo of the device-resident cross iterations
                     int ins = 0, ovf = 0;

@@ -227,6 +227,90 @@ __device__ inline void wrap_periodic(const KArgs &A, const double *__restrict__ 
     }
 }
 
+// The interpolant valuef_eval and the rollouts use at one arbitrary point y per lane (the V[2D] of offgrid_stencil alone):
+// L = G_0(y_0) G_1(y_1) ... G_{D-1}(y_{D-1}), one offgrid_cell per dimension and D - 1 vector-matrix products.  Every core entry
+// is gathered per lane from the padded cores in the arena, so there is no SGPR matrix operand and no LDS table here.  The row
+// loops stay rolled and L is read by rotation, as in offgrid_stencil: unrolled, every core load stays in flight.
+//
+// Cell indices are in range for EVERY double y.  offgrid_cell keeps 0 <= lo < hi <= N - 1 through the bisection whatever the
+// comparisons return, so lo is in [0, N - 2]; the result is 0, N - 2 or lo, and core_at reads nodes i and i + 1 <= N - 1.  A NaN
+// fails every comparison (lo stays 0, neither clamp fires: cell 0 with a NaN weight), +-inf take the clamps (cells N - 2 and 0
+// with weights 1 and 0).  A non-finite y therefore gives a non-finite or clamped VALUE and never an address outside core m.
+template <int D, int RP>
+__device__ inline double offgrid_value(const KArgs &A, const double *__restrict__ ro, const double (&y)[D], int constelm)
+{
+    static_assert(D >= 2, "dimension");
+    int ic[D];
+    double wc[D];
+#pragma unroll
+    for (int m = 0; m < D; m++) offgrid_cell(ro + A.xg_off[m], A.ngrid[m], y[m], constelm, ic[m], wc[m]);
+    double L[RP];
+    {
+        const double *G = ro + A.core_off[0];
+#pragma unroll
+        for (int b = 0; b < RP; b++) L[b] = core_at<RP>(G, RP, ic[0], wc[0], b);
+    }
+    static_for<1, D - 1>([&](auto mc) {
+        constexpr int m = decltype(mc)::value;
+        const double *G = ro + A.core_off[m];
+        double Ln[RP];
+#pragma unroll
+        for (int b = 0; b < RP; b++) Ln[b] = 0.0;
+#pragma unroll 1
+        for (int a = 0; a < RP; a++) {
+            const double la = rot_left<RP>(L);
+#pragma unroll
+            for (int b = 0; b < RP; b++) Ln[b] += la * core_at<RP>(G, RP * RP, ic[m], wc[m], a + b * RP);
+        }
+#pragma unroll
+        for (int b = 0; b < RP; b++) L[b] = Ln[b];
+    });
+    const double *G = ro + A.core_off[D - 1];
+    double v = 0.0;
+#pragma unroll
+    for (int a = 0; a < RP; a++) v += L[a] * core_at<RP>(G, RP, ic[D - 1], wc[D - 1], a);
+    return v;
+}
+
+// The value a jump to the state yin pays: periodic dimensions are wrapped; a target the rollouts' exit_test
+// calls exited -- inside an obstacle, or outside [lb, ub] on an absorbing dimension -- pays obscost or boundcost there, by
+// exit_test's choice; any other target pays the interpolant, which clamps to the grid hull (reflecting dimensions clamp).
+// Selects only: an exited lane evaluates the interpolant at its clamped cell as well.
+template <class Model, int RP>
+__device__ inline double jump_target_value(const KArgs &A, const double *__restrict__ ro, const double (&yin)[Model::D], int constelm)
+{
+    constexpr int D = Model::D;
+    double y[D];
+    wrap_periodic<D>(A, ro, yin, y);
+    const bool inobs = in_obstacle<D>(A, ro, y);
+    bool out = false;
+#pragma unroll
+    for (int m = 0; m < D; m++) {
+        const double *g = ro + A.xg_off[m];
+        out = out || ((A.bctype[m] == C3SC_ABSORB) && ((y[m] < g[0]) || (y[m] > g[A.ngrid[m] - 1])));
+    }
+    const double term = inobs ? Model::obscost(A.prm, y) : Model::boundcost(A.prm, y);
+    const double v = offgrid_value<D, RP>(A, ro, y, constelm);
+    return (inobs || out) ? term : v;
+}
+
+// The jump term of the node (or off-grid state) x: rate = h^2 lambda(x) and J = sum_m pi_m(x) Vjump(y_m), m ascending, one fma
+// chain from 0.0.  The marks stay a rolled loop: one point evaluation's registers, not NJUMP of them.
+template <class Model, int RP>
+__device__ inline void jump_term(const KArgs &A, const double *__restrict__ ro, const double (&x)[Model::D], int constelm, double &rate,
+                                 double &J)
+{
+    static_assert(Model::NJUMP >= 1 && Model::NJUMP <= C3SC_JUMP_MAX, "number of marks");
+    rate = A.h2 * Model::jumprate(A.prm, x);
+    J = 0.0;
+#pragma unroll 1
+    for (int m = 0; m < Model::NJUMP; m++) {
+        double y[Model::D];
+        const double pi = Model::jump(A.prm, x, m, y);
+        J = fma(pi, jump_target_value<Model, RP>(A, ro, y, constelm), J);
+    }
+}
+
 template <int MID, class Model>
 __device__ inline void offgrid_tables(const double (&x)[Model::D], double (&tv)[Model::NTAB > 0 ? Model::NTAB : 1])
 {
@@ -355,8 +439,11 @@ __global__ void __launch_bounds__(256) k_rollout(const KArgs A, const SimK S, co
         }
         if (!boxed) {
             int ui;
-            (void)node_backup<Model, 1, 1, CandLds<Model>, true, NoPre, model_game<Model>(), model_horizon<Model>(), model_stop<Model>()>(
-                A, ro, xin, tv, cr, V, ab, ui, st);
+            // jump models: the controller's backup gets the jump term at the state it sees
+            double jrate = 0.0, jval = 0.0;
+            if constexpr (model_jump<Model>()) jump_term<Model, RP>(A, ro, xin, S.constelm, jrate, jval);
+            (void)node_backup<Model, 1, 1, CandLds<Model>, true, NoPre, model_game<Model>(), model_horizon<Model>(), model_stop<Model>(),
+                              model_jump<Model>()>(A, ro, xin, tv, cr, V, ab, ui, st, false, -1, NoPre(), jrate, jval);
             if constexpr (model_stop<Model>()) { // the controller stops here: the lane pays psi and is frozen like an exited one.  psi is
                                                  // taken at the state the controller saw (wrapped, with S.wrap): the amount that won
                 const bool stopnow = alive && (ui == A.ncand);
@@ -396,10 +483,33 @@ __global__ void __launch_bounds__(256) k_rollout(const KArgs A, const SimK S, co
         else
 #pragma unroll
             for (int m = 0; m < D; m++) xi[m] = philox_normal(S.seed, (unsigned long long)(S.traj_offset + i), (unsigned)s, (unsigned)m);
+        // jump models: the compound-Poisson increment of the step, evaluated at x_k like the Euler-Maruyama increment.  An event
+        // when u0 < min(lambda dt, 1) (no transcendental: the host twin takes the same branch); the mark is the first m with
+        // u1 < pi_0 + .. + pi_m, and the last mark catches what rounding leaves.  Both uniforms are Philox's, with caller-supplied
+        // normals too.  Selects only.
+        double dj[D];
+#pragma unroll
+        for (int m = 0; m < D; m++) dj[m] = 0.0;
+        if constexpr (model_jump<Model>()) {
+            double u0, u1;
+            philox_jump_uniforms(S.seed, (unsigned long long)(S.traj_offset + i), (unsigned)s, u0, u1);
+            const bool event = u0 < fmin(Model::jumprate(A.prm, x) * dt, 1.0);
+            double cum = 0.0;
+            bool found = false;
+            for (int mk = 0; mk < Model::NJUMP; mk++) {
+                double y[D];
+                cum += Model::jump(A.prm, x, mk, y);
+                const bool take = event && !found && ((u1 < cum) || (mk == Model::NJUMP - 1));
+#pragma unroll
+                for (int m = 0; m < D; m++) dj[m] = take ? y[m] - x[m] : dj[m];
+                found = found || take;
+            }
+        }
 #pragma unroll
         for (int m = 0; m < D; m++) {
             double acc = x[m] + b[m] * dt; // c3control_simulate's order
             acc += sg[m] * S.sqdt * xi[m];
+            if constexpr (model_jump<Model>()) acc += dj[m];
             x[m] = alive ? acc : x[m];
         }
         if (S.traj && se > 0 && (s + 1) % se == 0)

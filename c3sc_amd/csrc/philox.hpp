@@ -144,4 +144,15 @@ __host__ __device__ inline double philox_normal(uint64_t seed, uint64_t traj, ui
     return rr * ((j & 1u) ? sn : cs);
 }
 
+// the two uniforms of the compound-Poisson increment of step `step` of global trajectory `traj`: the event
+// test and the mark.  Counter component 0x80000000: the normals use j >> 1 there, far below it, so no normal shares a counter
+// with them and the diffusion noise of a run keeps its bits whether or not the model jumps
+__host__ __device__ inline void philox_jump_uniforms(uint64_t seed, uint64_t traj, uint32_t step, double &u0, double &u1)
+{
+    const Philox4 c = {{(uint32_t)traj, (uint32_t)(traj >> 32), step, 0x80000000u}};
+    const Philox4 o = philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+    u0 = u53(o.v[0], o.v[1]);
+    u1 = u53(o.v[2], o.v[3]);
+}
+
 } // namespace c3sc

@@ -3,7 +3,8 @@
 // rtc.hip compiles one program per model with hipRTC: this header, the kernel headers it includes, and before them the
 // user's source wrapped in namespace c3sc_user, which defines (include/c3sc_hip.h states the contract)
 //   drift(prm, x, u, b)  sigma(prm, x, u, s)  stage(prm, x, u)  boundcost(prm, x)  obscost(prm, x)
-// and, for a stopping model, stopcost(prm, x)
+// and, for a stopping model, stopcost(prm, x); for a jump-diffusion model, jumprate(prm, x) and
+// jump(prm, x, m, y)
 // with C3SC_D / C3SC_DU defined.  RtcModel presents them as the Model concept of models.hpp: no tables and no candidate
 // features (the user's code evaluates its own transcendentals with the device libm), an empty Node.  The masks come from the
 // spec; their safe defaults (every dimension depends on u, none is a constant of the candidate, the stage cost reads u) are
@@ -43,6 +44,14 @@ struct RtcModel {
     __device__ static inline double obscost(const double *prm, const double (&x)[D]) { return ::c3sc_user::obscost(prm, x); }
 #ifdef C3SC_RTC_STOP // a spec with the stop flag (c3sc_hip_model_compile_os): only then must the source define stopcost
     __device__ static inline double stopcost(const double *prm, const double (&x)[D]) { return ::c3sc_user::stopcost(prm, x); }
+#endif
+#ifdef C3SC_RTC_JUMP // a spec with njump > 0 (c3sc_hip_model_compile_jd): only then must the source define jumprate and jump
+    static constexpr int NJUMP = C3SC_NJUMP;
+    __device__ static inline double jumprate(const double *prm, const double (&x)[D]) { return ::c3sc_user::jumprate(prm, x); }
+    __device__ static inline double jump(const double *prm, const double (&x)[D], int m, double (&y)[D])
+    {
+        return ::c3sc_user::jump(prm, x, m, y);
+    }
 #endif
 };
 

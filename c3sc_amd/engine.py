@@ -38,6 +38,7 @@ EXPORTS = [
     "c3sc_hip_set_game", "c3sc_hip_model_compile_ex", "c3sc_hip_model_code_object_ex",
     "c3sc_hip_model_compile_fh", "c3sc_hip_model_code_object_fh", "c3sc_hip_set_horizon_step", "c3sc_hip_upload_value_stack",
     "c3sc_hip_model_compile_os", "c3sc_hip_model_code_object_os", "c3sc_hip_set_stopping",
+    "c3sc_hip_model_compile_jd", "c3sc_hip_model_code_object_jd", "c3sc_hip_set_jumps", "c3sc_hip_jump_uniforms",
 ]
 
 class SimArgs(C.Structure):
@@ -82,6 +83,14 @@ class ModelSpecFh(C.Structure):
 class ModelSpecOs(C.Structure):
     """struct c3sc_hip_model_spec_os (include/c3sc_hip.h): the _fh spec plus the stop flag"""
     _fields_ = [("fh", ModelSpecFh), ("stop", C.c_int)]
+
+
+class ModelSpecJd(C.Structure):
+    """struct c3sc_hip_model_spec_jd (include/c3sc_hip.h): the _os spec plus the number of jump marks"""
+    _fields_ = [("os", ModelSpecOs), ("njump", C.c_int)]
+
+
+JUMP_MAX = 8  # C3SC_JUMP_MAX: most atoms of a discretised mark distribution
 
 
 MODEL_USER = 1000  # C3SC_MODEL_USER: first id of the run-time compiled models
@@ -163,6 +172,10 @@ def load_library():
         L.c3sc_hip_model_compile_os.argtypes = [C.POINTER(ModelSpecOs), c_int_p]
         L.c3sc_hip_model_code_object_os.argtypes = [C.POINTER(ModelSpecOs), C.c_void_p, c_size_p]
         L.c3sc_hip_set_stopping.argtypes = [C.c_void_p, C.c_int]
+        L.c3sc_hip_model_compile_jd.argtypes = [C.POINTER(ModelSpecJd), c_int_p]
+        L.c3sc_hip_model_code_object_jd.argtypes = [C.POINTER(ModelSpecJd), C.c_void_p, c_size_p]
+        L.c3sc_hip_set_jumps.argtypes = [C.c_void_p, C.c_int]
+        L.c3sc_hip_jump_uniforms.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, c_double_p]
         _LIB = L
     return _LIB
 
@@ -193,17 +206,22 @@ def _model_fail(rc, what):
 
 def compile_model(source: str, d: int, du: int, ranks=(4, 8), box: bool = False, udep_mask: int = 0, uconst_mask: int = 0,
                   stage_udep: bool = True, name: Optional[str] = None, game: bool = False, horizon: bool = False,
-                  stop: bool = False) -> int:
+                  stop: bool = False, njump: int = 0) -> int:
     """Compile a device model from source (c3sc_hip_model_compile, include/c3sc_hip.h states the source contract) and return
     its model id (>= MODEL_USER), usable wherever a built-in model id is.  No GPU is needed.  Raises C3scHipError with the
     compiler's log on failure; the error code is args[1].  game=True (c3sc_hip_model_compile_ex) adds the game kernels that
     BellmanEngine.set_game needs: the control vector is then (u, w) of the two players.  horizon=True
     (c3sc_hip_model_compile_fh) adds the finite-horizon kernels that BellmanEngine.set_horizon_step needs.  stop=True
-    (c3sc_hip_model_compile_os) adds the stop kernels that BellmanEngine.set_stopping needs: the source then defines stopcost."""
+    (c3sc_hip_model_compile_os) adds the stop kernels that BellmanEngine.set_stopping needs: the source then defines stopcost.
+    njump=M > 0 (c3sc_hip_model_compile_jd) adds the jump kernels that BellmanEngine.set_jumps needs: the source then defines
+    jumprate and jump for M marks."""
     L = load_library()
     spec = _model_spec(source, d, du, tuple(ranks), box, udep_mask, uconst_mask, stage_udep, name)
     mid = C.c_int(0)
-    if stop:
+    if njump:
+        jd = ModelSpecJd(ModelSpecOs(ModelSpecFh(ModelSpecEx(spec, 1 if game else 0), 1 if horizon else 0), 1 if stop else 0), int(njump))
+        rc = L.c3sc_hip_model_compile_jd(C.byref(jd), C.byref(mid))
+    elif stop:
         os_ = ModelSpecOs(ModelSpecFh(ModelSpecEx(spec, 1 if game else 0), 1 if horizon else 0), 1)
         rc = L.c3sc_hip_model_compile_os(C.byref(os_), C.byref(mid))
     elif horizon:
@@ -221,17 +239,22 @@ def compile_model(source: str, d: int, du: int, ranks=(4, 8), box: bool = False,
 
 def code_object(source: str, d: int, du: int, ranks=(4, 8), box: bool = False, udep_mask: int = 0, uconst_mask: int = 0,
                 stage_udep: bool = True, name: Optional[str] = None, game: bool = False, horizon: bool = False,
-                stop: bool = False) -> bytes:
+                stop: bool = False, njump: int = 0) -> bytes:
     """The gfx950 code object of this spec (c3sc_hip_model_code_object): the loaded one if compile_model already compiled the
     spec, otherwise what compile_model would build now (its id and default name are in the kernel names), compiled and not
-    registered.  game, horizon and stop select the spec as in compile_model (stop: c3sc_hip_model_code_object_os)."""
+    registered.  game, horizon, stop and njump select the spec as in compile_model (stop: c3sc_hip_model_code_object_os,
+    njump: c3sc_hip_model_code_object_jd)."""
     L = load_library()
     spec = _model_spec(source, d, du, tuple(ranks), box, udep_mask, uconst_mask, stage_udep, name)
     cap = 16 << 20  # one compile when the code object fits; a larger one is compiled again into a buffer of its size
     for _ in range(2):
         buf = C.create_string_buffer(cap)
         size = C.c_size_t(cap)
-        if stop:
+        if njump:
+            jd = ModelSpecJd(ModelSpecOs(ModelSpecFh(ModelSpecEx(spec, 1 if game else 0), 1 if horizon else 0), 1 if stop else 0),
+                             int(njump))
+            rc = L.c3sc_hip_model_code_object_jd(C.byref(jd), buf, C.byref(size))
+        elif stop:
             os_ = ModelSpecOs(ModelSpecFh(ModelSpecEx(spec, 1 if game else 0), 1 if horizon else 0), 1)
             rc = L.c3sc_hip_model_code_object_os(C.byref(os_), buf, C.byref(size))
         elif horizon:
@@ -270,6 +293,15 @@ def decode_exit(exit_step):
     return step, stopped.astype(np.int32)
 
 
+def jump_uniforms(seed: int, traj: int, step: int):
+    """(u0, u1) of c3sc_hip_jump_uniforms: the event and mark uniforms of one rollout step (no GPU needed)"""
+    out = (C.c_double * 2)()
+    rc = load_library().c3sc_hip_jump_uniforms(C.c_uint64(seed), C.c_uint64(traj), C.c_uint64(step), out)
+    if rc != 0:
+        raise C3scHipError(f"jump_uniforms failed (code {rc})")
+    return float(out[0]), float(out[1])
+
+
 def _f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
 
@@ -294,6 +326,7 @@ class BellmanEngine:
         self.device = device
         self.w = None
         self.stopping = False
+        self.jumps = False
 
     def close(self):
         if getattr(self, "h", None):
@@ -368,6 +401,14 @@ class BellmanEngine:
         stop=True, and with horizon=True as well to combine it with set_horizon_step."""
         self._chk(self.L.c3sc_hip_set_stopping(self.h, C.c_int(1 if on else 0)), "set_stopping")
         self.stopping = bool(on)
+
+    def set_jumps(self, on: bool = True):
+        """Jump diffusions (c3sc_hip_set_jumps): the Bellman calls add the Poisson jump term h^2 lambda(x) (J(x) - V) to the
+        backup, J the mark average of the value at the jump targets, and simulate adds a compound-Poisson increment to every
+        step (jump_uniforms is the host twin of its two uniforms).  The model must be compiled with njump=M > 0, and with
+        horizon / stop as well to combine it with set_horizon_step / set_stopping."""
+        self._chk(self.L.c3sc_hip_set_jumps(self.h, C.c_int(1 if on else 0)), "set_jumps")
+        self.jumps = bool(on)
 
     def upload_value_stack(self, ranks, cores):
         """V_0 .. V_N for simulate in horizon mode (c3sc_hip_upload_value_stack): ranks[s] is stage s's rank list (d + 1 entries),

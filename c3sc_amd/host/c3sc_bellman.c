@@ -379,6 +379,12 @@ struct DPparam {
     /* optimal stopping (c3control_add_stopcost / c3control_set_stopping): psi(t, x) and the switch */
     int (*stopcost)(double, const double *, double *);
     int stopping;
+    /* jump diffusions (c3control_add_jumps / c3control_set_jumps): M marks, lambda(x), y = x + q_m(x) with its
+     * weight pi_m(x) -- the host forms of the device model's jumprate and jump -- and the switch */
+    int njump;
+    double (*jumprate)(const double *);
+    double (*jumpmark)(const double *, int, double *);
+    int jumps;
 };
 
 struct DPparam *dp_param_create(size_t dx, size_t du, size_t dw, double discount)
@@ -416,6 +422,10 @@ struct ControlParams {
     struct c3Opt *opt;
     int res_last_grad;
     int stopped_last; /* bellman_optimal in stop mode: the last node's decision was the stop action */
+    /* jump mode: the value function the jump targets are read from (set by whoever pairs this block with one), and the current
+     * node's un-normalised jump rate h^2 lambda and mark average J, formed by bellman_optimal for bellman_control */
+    struct ValueF *vf;
+    double jrate, jval;
 };
 
 struct ControlParams *control_params_create(size_t dx, size_t dw, struct DPparam *dp, struct MCAparam *mca,
@@ -435,9 +445,9 @@ struct Memory { void *shared; size_t private; }; /* bellman.c:59-63 */
  * assemble_rates un-normalised, Q = sum p_i, PV = sum p_i V_i, and g delta + e^{-beta delta} (V_self + (delta / h^2) (PV - Q V_self)).
  * No division: Q = 0 is a legal "stay" candidate */
 static double horizon_rhs(size_t dx, double h2, const double *tv, double delta, double beta, const double *drift, const double *diff,
-                          double stage, const double *costs)
+                          double stage, const double *costs, double jrate, double jval)
 {
-    double Q = 0.0, PV = 0.0;
+    double Q = jrate, PV = jrate * jval; /* jump mode: one more transition (0 otherwise) */
     for (size_t m = 0; m < dx; m++) {
         const double t = tv[2 * m], t2 = tv[2 * m + 1], s = diff[m * dx + m];
         const double half = t2 * (s * s) / 2.0, tb = t * drift[m];
@@ -475,7 +485,26 @@ double bellman_control(size_t du, const double *u, double *grad_u, void *args)
         res = diff_eval(dp->diff, p->time, x, u, diff, NULL); assert(res == 0);
         res = dp->stagecost(p->time, x, u, &stage, NULL); assert(res == 0);
         (void)res;
-        return horizon_rhs(dx, p->mca->h2, p->mca->t, dp->hz_dt, dp->discount, drift, diff, stage, costs);
+        return horizon_rhs(dx, p->mca->h2, p->mca->t, dp->hz_dt, dp->discount, drift, diff, stage, costs, p->jrate, p->jval);
+    }
+    if (dp->jumps) { /* node_backup's JUMP form: the upwind rates un-normalised, the jump rate inside Q, dt = h^2 / Q */
+        if (grad_u != NULL) DIE("bellman_control: jump mode has no gradient (control-box) form");
+        res = drift_eval(dp->drift, p->time, x, u, drift, NULL); assert(res == 0);
+        res = diff_eval(dp->diff, p->time, x, u, diff, NULL); assert(res == 0);
+        res = dp->stagecost(p->time, x, u, &stage, NULL); assert(res == 0);
+        (void)res;
+        double Q = p->jrate, PV = p->jrate * p->jval;
+        for (size_t m = 0; m < dx; m++) {
+            const double t = p->mca->t[2 * m], t2 = p->mca->t[2 * m + 1], s = diff[m * dx + m];
+            const double half = t2 * (s * s) / 2.0, tb = t * drift[m];
+            const double pm = drift[m] < -1e-14 ? half - tb : half, pp = drift[m] > 1e-14 ? half + tb : half;
+            Q += pm;
+            Q += pp;
+            PV += pm * costs[2 * m] + pp * costs[2 * m + 1];
+        }
+        assert(!(Q < 1e-14)); /* bellman.c:452 */
+        *dt = p->mca->h2 / Q;
+        return *dt * stage + exp(-dp->discount * *dt) * (PV / Q + (1.0 - Q / Q) * costs[2 * dx]);
     }
     if (grad_u != NULL) {
         double *gdrift = workspace_get_grad_drift(w, node), *gdiff = workspace_get_grad_diff(w, node);
@@ -501,6 +530,53 @@ double bellman_control(size_t du, const double *u, double *grad_u, void *args)
     return val;
 }
 
+/* the value a jump to y pays (jump_target_value of the kernels): periodic dimensions wrapped; inside an obstacle
+ * the obstacle cost, outside [lb, ub] on an absorbing dimension the boundary cost; otherwise the host interpolant, which clamps */
+static double jump_target_value_host(struct ControlParams *p, const double *yin)
+{
+    struct DPparam *dp = p->dp;
+    const size_t dx = p->dx;
+    double y[C3SC_MAX_DIM];
+    int out = 0;
+    for (size_t m = 0; m < dx; m++) {
+        const double lb = p->mca->xgrid[m][0], ub = p->mca->xgrid[m][p->mca->ngrid[m] - 1], len = ub - lb;
+        const enum EBTYPE b = boundary_type_dim(dp->bound, m, 0);
+        y[m] = yin[m];
+        if (b == PERIODIC) {
+            double v = yin[m] - floor((yin[m] - lb) / len) * len;
+            if (v >= ub) v -= len;
+            if (v < lb) v += len;
+            y[m] = v;
+        }
+        if (b == ABSORB && (y[m] < lb || y[m] > ub)) out = 1;
+    }
+    double val = 0.0;
+    int r = 0;
+    if (boundary_in_obstacle(dp->bound, y)) r = dp->obscost(y, &val);
+    else if (out) r = dp->boundcost(p->time, y, &val);
+    else val = valuef_eval(p->vf, y);
+    assert(r == 0);
+    (void)r;
+    return val;
+}
+
+/* jump mode: the node's h^2 lambda and J = sum_m pi_m Vjump(y_m), m ascending; the weights must sum to 1 */
+static void jump_term_host(struct ControlParams *p, const double *x)
+{
+    struct DPparam *dp = p->dp;
+    if (p->vf == NULL) DIE("bellman_optimal: jump mode needs the value function the jump targets are read from");
+    double y[C3SC_MAX_DIM], J = 0.0, sum = 0.0;
+    for (int m = 0; m < dp->njump; m++) {
+        const double pi = dp->jumpmark(x, m, y);
+        assert(pi >= 0.0);
+        sum += pi;
+        J += pi * jump_target_value_host(p, y);
+    }
+    if (!(fabs(sum - 1.0) <= 1e-12)) DIE("bellman_optimal: the jump weights sum to %.17g, not 1 (c3control_add_jumps)", sum);
+    p->jrate = p->mca->h2 * dp->jumprate(x);
+    p->jval = J;
+}
+
 int bellman_optimal(size_t du, double *u, double *val, void *arg)
 { /* bellman.c:504-543 (BRUTEFORCE) and the box branch of :545-1118: single node on the host (c3control_controller) */
     struct Memory *mem = arg;
@@ -511,6 +587,8 @@ int bellman_optimal(size_t du, double *u, double *val, void *arg)
         *val = bellman_control(du, u, NULL, arg);
         return 0;
     }
+    p->jrate = p->jval = 0.0;
+    if (p->dp->jumps) jump_term_host(p, p->x + mem->private * p->dx);
     struct c3Opt *opt = c3opt_copy(p->opt);
     c3opt_add_objective(opt, &bellman_control, mem);
     c3opt_minimize(opt, u, val); /* BRUTEFORCE: list scan; otherwise the box minimiser (grid + golden section) */
@@ -605,6 +683,9 @@ static struct c3sc_hip_ctx *sync_device_ctx(struct ControlParams *cp, struct c3s
     if (dp->stopping && (!brute || gorder >= 0 || dp->model == 0))
         DIE("bellman_vi: stopping needs a device model compiled with stop kernels (c3sc_hip_model_compile_os) and a plain candidate list");
     sig = fnv(sig, &dp->stopping, sizeof(int));
+    if (dp->jumps && (!brute || gorder >= 0 || dp->model == 0))
+        DIE("bellman_vi: jumps need a device model compiled with jump kernels (c3sc_hip_model_compile_jd) and a plain candidate list");
+    sig = fnv(sig, &dp->jumps, sizeof(int));
     if (brute) sig = fnv(sig, c3opt_get_brute_vals(cp->opt), c3opt_get_nbrute(cp->opt) * odu * sizeof(double));
     else {
         const size_t g = c3opt_get_box_grid(cp->opt), pl = c3opt_get_box_polish(cp->opt);
@@ -621,6 +702,7 @@ static struct c3sc_hip_ctx *sync_device_ctx(struct ControlParams *cp, struct c3s
         hipok(ctx, c3sc_hip_set_consistent_ends(ctx, cends), "c3sc_hip_set_consistent_ends");
         /* a context left in stop mode by an earlier problem would refuse set_game: off first, on again after the controls */
         hipok(ctx, c3sc_hip_set_stopping(ctx, 0), "c3sc_hip_set_stopping");
+        hipok(ctx, c3sc_hip_set_jumps(ctx, 0), "c3sc_hip_set_jumps"); /* likewise a context left in jump mode */
         if (dp->model != 0) hipok(ctx, c3sc_hip_set_model(ctx, dp->model, dp->prm, dp->nprm), "c3sc_hip_set_model");
         if (brute && gorder >= 0)
             hipok(ctx, c3sc_hip_set_game(ctx, (int)gdu_min, (int)gnu, gU, (int)gnw, gW, gorder), "c3sc_hip_set_game");
@@ -631,6 +713,7 @@ static struct c3sc_hip_ctx *sync_device_ctx(struct ControlParams *cp, struct c3s
                                                 (int)c3opt_get_box_polish(cp->opt)), "c3sc_hip_set_control_box");
         hipok(ctx, c3sc_hip_set_horizon_step(ctx, dp->hz_dt), "c3sc_hip_set_horizon_step");
         hipok(ctx, c3sc_hip_set_stopping(ctx, dp->stopping), "c3sc_hip_set_stopping");
+        hipok(ctx, c3sc_hip_set_jumps(ctx, dp->jumps), "c3sc_hip_set_jumps");
         g_ctx[sl].cfg_set = 1;
         g_ctx[sl].cfg_sig = sig;
         g_ctx[sl].version = 0; /* set_grid invalidates the resident value function */
@@ -657,6 +740,7 @@ static void cross_check_model(struct VIparam *vi, struct c3sc_hip_ctx *ctx, size
     int32_t *ab = xcalloc(N, sizeof(int32_t));
     hipok(ctx, c3sc_hip_stencil_fibers_host(ctx, (int)k, 1, idx, costs, ab), "c3sc_hip_stencil_fibers_host");
     control_params_add_time_and_states(cp, 0.0, N, x);
+    cp->vf = vi->vf; /* jump mode: the host twin reads the jump targets from the value function the device holds */
     double u[16];
     size_t checked = 0;
     size_t live = 0;
@@ -1238,6 +1322,20 @@ void c3control_set_stopping(struct C3Control *c, int on)
     c->dp->model_checked = 0; /* the first-fiber check runs again, against the operator now in force */
 }
 int c3control_get_stopping(const struct C3Control *c) { return c->dp->stopping; }
+void c3control_add_jumps(struct C3Control *c, int M, double (*rate)(const double *), double (*mark)(const double *, int, double *))
+{
+    if (M < 1 || M > C3SC_JUMP_MAX || rate == NULL || mark == NULL) DIE("c3control_add_jumps: 1 <= M <= C3SC_JUMP_MAX marks and both callbacks are needed");
+    c->dp->njump = M;
+    c->dp->jumprate = rate;
+    c->dp->jumpmark = mark;
+}
+void c3control_set_jumps(struct C3Control *c, int on)
+{
+    if (on && c->dp->jumprate == NULL) DIE("c3control_set_jumps: c3control_add_jumps first");
+    c->dp->jumps = on ? 1 : 0;
+    c->dp->model_checked = 0; /* the first-fiber check runs again, against the operator now in force */
+}
+int c3control_get_jumps(const struct C3Control *c) { return c->dp->jumps; }
 void c3control_set_device_model(struct C3Control *c, int model, const double *params, size_t n) { dp_param_set_device_model(c->dp, model, params, n); }
 
 void c3control_set_consistent_ends(struct C3Control *c, int on)
@@ -1660,7 +1758,7 @@ void c3control_add_policy_sim(struct C3Control *c, struct ValueF *pol, struct c3
     c->transform_sim = transform;
 }
 
-int c3control_policy_eval_stop(struct C3Control *c, double t, const double *x, double *u, int *stopped)
+int c3control_policy_eval_value(struct C3Control *c, double t, const double *x, double *u, int *stopped, double *value)
 { /* bellman.c:2105-2158: one state, host callbacks (a single node is not GPU work) */
     assert(c->policy_sim != NULL && c->opt_sim != NULL);
     if (c->dp->stagecost == NULL) DIE("c3control_policy_eval(_stop): the host callbacks (add_drift/diff/stagecost/...) are needed");
@@ -1676,6 +1774,7 @@ int c3control_policy_eval_stop(struct C3Control *c, double t, const double *x, d
     if (c->prevpol == NULL) c->prevpol = xcalloc(c->du, sizeof(double));
     for (size_t i = 0; i < c->du; i++) u[i] = c->prevpol[i];
     control_params_add_time_and_states(cp, t, 1, x);
+    cp->vf = c->policy_sim;
     struct Memory mem = {cp, 0};
     double val;
     int res2 = bellman_optimal(c->du, u, &val, &mem);
@@ -1683,8 +1782,14 @@ int c3control_policy_eval_stop(struct C3Control *c, double t, const double *x, d
     (void)res2;
     for (size_t i = 0; i < c->du; i++) c->prevpol[i] = u[i];
     if (stopped != NULL) *stopped = cp->stopped_last;
+    if (value != NULL) *value = val;
     control_params_destroy(cp);
     return 0;
+}
+
+int c3control_policy_eval_stop(struct C3Control *c, double t, const double *x, double *u, int *stopped)
+{
+    return c3control_policy_eval_value(c, t, x, u, stopped, NULL);
 }
 
 int c3control_policy_eval(struct C3Control *c, double t, const double *x, double *u)
@@ -1812,6 +1917,7 @@ int c3control_integrate(struct C3Control *c, const char *method, double dt_int, 
     const char *who = "c3control_integrate";
     if (c == NULL || x0 == NULL) return reject(who, "null control or x0");
     if (c->dp->stopping) return reject(who, "deterministic closed loops are not offered for stopping problems (c3control_set_stopping)");
+    if (c->dp->jumps) return reject(who, "deterministic closed loops are not offered for jump diffusions (c3control_set_jumps)");
     if (c->policy_sim == NULL || c->opt_sim == NULL) return reject(who, "no implicit policy (c3control_add_policy_sim)");
     if (c->dp->drift == NULL || c->dp->stagecost == NULL || c->dp->boundcost == NULL || c->dp->obscost == NULL)
         return reject(who, "the host callbacks (drift, stagecost, boundcost, obscost) are needed");
@@ -1894,6 +2000,7 @@ int c3control_integrate_batch(struct C3Control *c, size_t ntraj, const double *x
     int rc = batch_policy_check(who, c, wrap_periodic);
     if (rc != 0) return rc;
     if (c->dp->stopping) return reject(who, "deterministic closed loops are not offered for stopping problems (c3control_set_stopping)");
+    if (c->dp->jumps) return reject(who, "deterministic closed loops are not offered for jump diffusions (c3control_set_jumps)");
     size_t nsub;
     rc = integrate_check(who, c->dx, method, dt_int, dt_out, nout, goal, keep, &nsub);
     if (rc != 0) return rc;
@@ -1941,6 +2048,8 @@ int c3control_simulate(struct C3Control *c, const double *x0, double dt, size_t 
     const size_t dx = c->dx, du = c->du, dw = c->dw;
     if (c->dp->stopping)
         return reject("c3control_simulate", "the single-trajectory loop has no stop action; use c3control_simulate_batch (c3control_set_stopping)");
+    if (c->dp->jumps)
+        return reject("c3control_simulate", "the single-trajectory loop draws no jumps; use c3control_simulate_batch (c3control_set_jumps)");
     double *b = xcalloc(dx, sizeof(double)), *s = xcalloc(dx * dw, sizeof(double)), *u = xcalloc(du, sizeof(double));
     memcpy(traj, x0, dx * sizeof(double));
     const double sq = sqrt(dt);

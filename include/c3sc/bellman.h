@@ -205,6 +205,22 @@ void c3control_add_stopcost(struct C3Control *, int (*)(double t, const double *
 void c3control_set_stopping(struct C3Control *, int on);
 int c3control_get_stopping(const struct C3Control *);
 int c3control_policy_eval_stop(struct C3Control *, double t, const double *x, double *u, int *stopped);
+/* new: jump diffusions.  c3control_add_jumps registers the host forms of the device model's jumprate and jump
+ * for M marks (1 <= M <= C3SC_JUMP_MAX): rate(x) = lambda(x) >= 0; mark(x, m, y) writes the post-jump state y = x + q_m(x) and
+ * returns the weight pi_m(x) >= 0, the weights summing to 1 (the host twin stops with a message when |sum - 1| > 1e-12).
+ * c3control_set_jumps(c, 1) adds the jump term to the Bellman operator, Q += h^2 lambda, PV += h^2 lambda sum_m pi_m Vjump(y_m):
+ * in the host scan (bellman_optimal, which reads the jump targets with valuef_eval, the exit costs beyond absorbing faces and
+ * in obstacles), the first-fiber check and the device context (which needs a model compiled with c3sc_hip_model_compile_jd,
+ * njump = M, and a candidate list).  c3control_step_vi, c3control_vi_solve, with the horizon step c3control_fh_solve, and
+ * c3control_simulate_batch work in jump mode, and it combines with c3control_set_stopping; policy iteration launches through the
+ * same context (the forced path shares the jump term).  c3control_simulate
+ * and c3control_integrate(_batch) return an error in jump mode. */
+void c3control_add_jumps(struct C3Control *, int M, double (*rate)(const double *x), double (*mark)(const double *x, int m, double *y));
+void c3control_set_jumps(struct C3Control *, int on);
+int c3control_get_jumps(const struct C3Control *);
+/* c3control_policy_eval_stop with the backup's value at x as well (the host twin's number: what the first-fiber check compares
+ * with the device); stopped and value may be NULL */
+int c3control_policy_eval_value(struct C3Control *, double t, const double *x, double *u, int *stopped, double *value);
 struct ValueF *c3control_vi_solve(struct C3Control *, size_t maxiter, double abs_conv_tol, struct ValueF *vo,
                                   struct ApproxArgs *, struct c3Opt *, int verbose, struct Diag **diag); /* :2282-2340 */
 struct ValueF *c3control_pi_solve(struct C3Control *, size_t maxiter, double abs_conv_tol, struct ValueF *policy,

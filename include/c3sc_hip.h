@@ -571,6 +571,48 @@ int c3sc_hip_model_code_object_os(const c3sc_hip_model_spec_os *spec, void *buf,
  * discounted V_nsteps. */
 int c3sc_hip_set_stopping(c3sc_hip_ctx *ctx, int on);
 
+/* Jump diffusions: dx = b dt + sigma dw + a compound-Poisson term with intensity lambda(x) whose mark
+ * distribution is discretised into M atoms, 1 <= M <= C3SC_JUMP_MAX.  A jump model's source defines two more functions,
+ *   __device__ double jumprate(const double *prm, const double (&x)[C3SC_D]);                          lambda(x) >= 0
+ *   __device__ double jump(const double *prm, const double (&x)[C3SC_D], int m, double (&y)[C3SC_D]);  y = x + q_m(x), returns pi_m(x)
+ * with weights pi_m >= 0 that sum to 1 over m = 0 .. M-1; neither may depend on the control.  The chain is the rate form of
+ * Kushner and Dupuis, section 5.6: a jump is one more transition with the un-normalised rate h^2 lambda(x),
+ *     Q0 += h^2 lambda,   PV0 = fma(h^2 lambda, J, PV0),   J(x) = sum_m pi_m(x) Vjump(y_m)   (m ascending, one fma chain from 0.0)
+ * and everything downstream is the backup of the other switches: dt = h^2 / Q with the jump rate inside Q; in horizon mode the
+ * term delta lambda (J - V_self), with the rate in the CFL test; a node with b = sigma = 0 and lambda > 0 is not STATIONARY;
+ * the forced (policy) path uses the same Q0 and PV0.  lambda = 0 leaves every bit of the backup without jumps.
+ * Vjump(y): periodic dimensions of y are wrapped into [lb, ub); a target inside an obstacle, or outside [lb, ub] on an absorbing
+ * dimension, pays obscost(y) resp. boundcost(y) (the choice c3sc_hip_simulate's exit test makes); any other target pays the
+ * interpolant of c3sc_hip_stencil_points at y -- multilinear, or the nearer node under c3sc_hip_set_interp(ctx, 1) -- clamped to
+ * the grid hull, so reflecting dimensions clamp.
+ * The jump kernels exist only in run-time compiled models built with c3sc_hip_model_compile_jd and njump = M > 0: the jump forms
+ * of the per-wave kernels and of k_rollout that the other flags select (plain, horizon, stop, horizon with stop) at every
+ * requested rank; k_rollout_ode has none.  njump = 0
+ * is exactly c3sc_hip_model_compile_os, and the source need not define the two functions then; njump outside 0..C3SC_JUMP_MAX
+ * returns C3SC_ERR_ARG, njump > 0 with a game or the box C3SC_ERR_UNSUPPORTED. */
+#define C3SC_JUMP_MAX 8
+typedef struct c3sc_hip_model_spec_jd {
+    c3sc_hip_model_spec_os os;
+    int njump;
+} c3sc_hip_model_spec_jd;
+int c3sc_hip_model_compile_jd(const c3sc_hip_model_spec_jd *spec, int *model_id);
+int c3sc_hip_model_code_object_jd(const c3sc_hip_model_spec_jd *spec, void *buf, size_t *size);
+/* jumps on (on != 0) or off.  C3SC_ERR_UNSUPPORTED for built-in and TABLE models, a model compiled without jump kernels (also
+ * one set after this call: the launch then refuses) and a context in game mode; c3sc_hip_set_game is refused while jumps are on.
+ * Honoured by bellman_fibers(_all|_host), policy_fibers(_all|_host) (on the fiber-per-wave kernel: AUTO picks it, a forced pair
+ * or quad variant is refused), the cross calls that launch through them, cross_iteration_pi included, and simulate.  Combines
+ * with the horizon step and the stopping switch; the model must then be compiled with those flags as well.  Refused
+ * (C3SC_ERR_UNSUPPORTED): the box and TABLE calls and integrate.
+ * c3sc_hip_simulate with jumps on: the controller's backup gets the jump term at the state it sees, and the step adds a
+ * compound-Poisson increment evaluated at x_k like the Euler-Maruyama increment.  Two uniforms per (seed, trajectory, step)
+ * come from a Philox counter component no normal uses (c3sc_hip_jump_uniforms is the host twin), with caller-supplied normals
+ * too; the diffusion noise of a run keeps its bits.  A jump happens when u0 < min(lambda(x_k) dt, 1); its mark is the first m
+ * with u1 < pi_0 + .. + pi_m (the last mark catches rounding); x_{k+1} = x_k + b dt + sigma sqrt(dt) xi + (y_m(x_k) - x_k).  A
+ * trajectory that jumps out of the domain is an exit at step k + 1 like any other. */
+int c3sc_hip_set_jumps(c3sc_hip_ctx *ctx, int on);
+/* out[0], out[1] = the uniforms (u0, u1) in (0, 1) of step `step` of global trajectory `traj` under `seed` */
+int c3sc_hip_jump_uniforms(uint64_t seed, uint64_t traj, uint64_t step, double *out);
+
 int c3sc_hip_sync(c3sc_hip_ctx *ctx, void *stream);
 int c3sc_hip_get_status(c3sc_hip_ctx *ctx, unsigned *flags, int clear);
 /* name of the kernel the last launch used (for profiles) */
