@@ -462,6 +462,14 @@ def scenario_policy(make, oracle, case):
     candidate, new nodes take P2's); tag 8 (every node takes P2's)."""
     w, V, _, ranks, I, J = make_case(case, max_cands=fk.MAX_CANDS)
     P1, P2 = policy_values(w)
+    return run_policy_scenario(make, w, V, P1, P2, ranks, I, J, PolicyMemoProblem(oracle, w, V, P1), f"{case[0]} policy",
+                               new_nodes=case[0] in POLICY_CASES_WITH_NEW_NODES)
+
+
+def run_policy_scenario(make, w, V, P1, P2, ranks, I, J, model, label, new_nodes=False):
+    """the three calls of (h) on contexts from make(w, cores), each held to `model` -- a policy memo model under V and P1 with
+    set_policy, new_tag and the counts of PolicyMemoProblem (tests/jump_policy_model.py has the one of jump mode).  new_nodes: the
+    second call of tag 7 must store nodes.  The reports carry the model's counts of their call."""
     ev, pol = make(w, V), make(w, P1)
     try:
         _setup(ev, ranks, I, J, 1)
@@ -483,8 +491,6 @@ def scenario_policy(make, oracle, case):
     finally:
         ev.close()
         pol.close()
-    label = f"{case[0]} policy"
-    model = PolicyMemoProblem(oracle, w, V, P1)
     reps = []
     for t, (J0, got, what) in enumerate(((J, f1, "tag 7 under P1"), (f1[2], f2, "tag 7 under P2"), (f2[2], f3, "tag 8 under P2"))):
         if t == 1:
@@ -493,7 +499,7 @@ def scenario_policy(make, oracle, case):
             model.new_tag()
         s0, h0, d0 = model.stores, model.hits, model.policy_differing
         rep = cr.check_iteration(model, ranks, J0, got[0], got[1], got[2], None, swap_tol=0.05, label=f"{label} {what}")
-        rep["policies_stored"] = model.stores - s0
+        rep["policies_stored"], rep["hits"], rep["policy_differing"] = model.stores - s0, model.hits - h0, model.policy_differing - d0
         reps.append(rep)
         print(f"{label} {what}: info {got[3]}; model {model.stores - s0} policies stored, {model.hits - h0} hits, {model.policy_differing - d0} "
               f"of them at nodes where P1 and P2 choose differently; worst residual {max(s['residual'] or 0.0 for s in rep['steps']):.1e}, "
@@ -504,7 +510,7 @@ def scenario_policy(make, oracle, case):
             hits, seen = model.hits - h0, model.policy_differing - d0
             if not (hits > 0 and seen >= 0.1 * hits):
                 raise CaseRefused(f"{label}: {seen} of {hits} hits at nodes where the greedy candidate differs: 10 % wanted")
-            if case[0] in POLICY_CASES_WITH_NEW_NODES and not got[3][0] > 0:  # 'new nodes take P2's' needs new nodes
+            if new_nodes and not got[3][0] > 0:  # 'new nodes take P2's' needs new nodes
                 raise CaseRefused(f"{label} {what}: no new node in the second call of tag 7")
         if t == 2:
             assert got[3][0] == len(model.live), f"{label} {what}: info[0] = {got[3][0]}, {len(model.live)} live nodes"

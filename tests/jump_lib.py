@@ -1,6 +1,8 @@
 """Jump diffusions (c3sc_hip_set_jumps): device sources of a jump LQR in two and three dimensions, of a
-known-answer model and of Merton's American put, and a numpy restatement of the backup with the Poisson jump term.  Shared by
-the CPU and GPU tests and tools/jump_bench.py.  It shares no code with the kernels.
+known-answer model and of Merton's American put, and a numpy restatement of the backup with the Poisson jump term; dense value
+and policy iteration of the jump LQR on a whole small grid (dense_vi, dense_pi) and the child processes that drive the
+reference API (vi_child, pi_child, fh_child).  Shared by the CPU and GPU tests and tools/jump_bench.py.  It shares no code with
+the kernels.
 
 The chain is the rate form of Kushner and Dupuis, section 5.6: a jump is one more transition with the un-normalised rate
 h2 lambda(x) to the mark average J(x) = sum_m pi_m(x) Vjump(y_m), so Q and PV of every candidate gain h2 lambda and h2 lambda J
@@ -10,6 +12,7 @@ cost, one outside [lb, ub] on an absorbing dimension the boundary cost (the obst
 any other target pays the interpolant of the function train -- multilinear, or the nearer node with constelm -- clamped to
 the grid hull."""
 import dataclasses
+import os
 
 import numpy as np
 
@@ -575,6 +578,32 @@ def dense_vi(w, host, jumps, bcost, V0, nsweeps):
     return np.array(out)
 
 
+def dense_pi(w, host, jumps, bcost, P, nsweeps, mu=None):
+    """policy iteration sweeps of the jump operator on the whole grid of the same class of workload: the greedy policy of P
+    (candidate index per node and its margin, jump terms from the bilinear interpolant of P), then V_0 = P and V_{s+1} = that
+    policy's backup of V_s at the live nodes (jump terms from the interpolant of V_s), the boundary cost at the absorbed ones --
+    what c3control_pi_solve(maxiter = s, policy = P) applies.  mu [n0, n1]: a policy to evaluate in place of the greedy one.
+    Returns (mu [n0, n1] (-1: absorbed), margin [n0, n1] (inf: absorbed), [V_0, V_1, .. V_nsweeps])"""
+    n0, n1 = w.ngrid
+    x, ab, sten = _grid2(w)
+    h2, t = H.mca_constants(w)
+    C = np.asarray(w.cands, dtype=np.float64)
+
+    def vals(Vn):
+        jrate, J = jump_terms(w, jumps, Nodal(w, Vn), x, bcost, lambda xx: np.full(len(xx), 5.0))
+        return candidate_values(host, w.params, x, sten(Vn), C, h2, t, w.discount, jrate, J)[0]
+
+    Vn = np.asarray(P, dtype=np.float64).reshape(n0, n1)
+    _, greedy, margin = backup(vals(Vn))
+    pol = greedy if mu is None else np.asarray(mu).reshape(-1)
+    out = [Vn]
+    for _ in range(nsweeps):
+        v, _, _ = backup(vals(Vn), forced=pol)
+        Vn = np.where(ab, bcost(x), v).reshape(n0, n1)
+        out.append(Vn)
+    return np.where(ab, -1, pol).reshape(n0, n1), np.where(ab, np.inf, margin).reshape(n0, n1), np.array(out)
+
+
 def vi_child(out_path, nsweeps=LQR_VI_SWEEPS):
     """the jump LQR through the reference API (run in a child process by tests/test_gpu_jump.py): c3control_vi_solve one sweep
     at a time from V_0 = s |x|^2, the nodal values after every sweep saved; then c3control_simulate_batch of the last sweep's
@@ -624,6 +653,52 @@ def _approx_args(L, rank=11):
     L.approx_args_set_startrank(aa, C.c_size_t(rank))
     L.approx_args_set_maxrank(aa, C.c_size_t(rank))
     return aa
+
+
+PI_BEFORE, PI_AFTER = (1, 3), (1, 3, 6)  # evaluation sweeps asked of c3control_pi_solve before and after the vi step
+PI_MARKERS = ("jump_lib.pi_child: host-driven policy iteration done", "jump_lib.pi_child: first-fiber check done")
+
+
+def pi_child(out_path):
+    """policy iteration on the jump LQR through the reference API (run in a child process by tests/test_gpu_jump_policy.py):
+    c3control_pi_solve(K, policy = V_0 = s |x|^2) for K in PI_BEFORE while the device model is not yet checked against the host
+    callbacks (the host-driven pi_core whatever the environment), one c3control_vi_solve step from V_0 (the first-fiber check),
+    then K in PI_AFTER (the device-resident cross_iteration_pi unless C3SC_HOST_CROSS is set).  A marker line on stderr after
+    each of the first two parts; the nodal values of every result saved"""
+    import ctypes as C
+    import sys
+
+    import facade_lib as fl
+    from c3sc_amd import engine as E
+
+    mid = E.compile_model(LQR, 2, 2, ranks=(12,), name="lqr_jd_pi_api", njump=LQR_NJUMP, **LQR_MASKS)
+    w = lqr_vi_workload(mid)
+    L = fl.lib()
+    for n in ("c3control_init_value", "c3control_vi_solve", "c3control_pi_solve"):
+        getattr(L, n).restype = C.c_void_p
+    L.valuef_eval_ind.restype = C.c_double
+    ctl = fl.Control(w, callbacks=H.lqr_callbacks(LQR_PRM), consistent_ends=None)
+    keep = add_jumps(L, ctl, lqr_jumps, LQR_PRM, 2, LQR_NJUMP)
+    aa = _approx_args(L)
+    v0, keep2 = SL._init_value(L, ctl, aa, lambda xx: H.lqr_terminal(LQR_PRM, xx))
+    n0, n1 = w.ngrid
+
+    def pi(K):
+        v = C.c_void_p(L.c3control_pi_solve(ctl.h, C.c_size_t(K), C.c_double(0.0), v0, aa, ctl.opt, C.c_int(0), None))
+        return SL._nodal(L, v.value, n0, n1)
+
+    def mark(line):
+        sys.stdout.flush()
+        sys.stderr.flush()
+        os.write(2, (line + "\n").encode())  # unbuffered, in order with the library's own fprintf(stderr)
+
+    before = [pi(K) for K in PI_BEFORE]
+    mark(PI_MARKERS[0])
+    v1 = C.c_void_p(L.c3control_vi_solve(ctl.h, C.c_size_t(1), C.c_double(0.0), v0, aa, ctl.opt, C.c_int(0), None))
+    vi = SL._nodal(L, v1.value, n0, n1)
+    mark(PI_MARKERS[1])
+    after = [pi(K) for K in PI_AFTER]
+    np.savez(out_path, V0=SL._nodal(L, v0.value, n0, n1), before=np.array(before), vi=vi, after=np.array(after))
 
 
 def fh_child(out_path, delta=PUT_DELTA, nstages=PUT_STAGES):

@@ -8,7 +8,13 @@ uniforms (c3sc_hip_jump_uniforms).  No GPU is needed.
 - The weights of every test model sum to 1, and the marks of the 2-D LQR reach the four kinds of target.
 - The index-margin precondition of the GPU tests, on the stencils the restatement forms itself along the periodic dimension of
   the ragged grid (end-point rule included): at most 0.1 % of the live nodes have |best - second| below 1e-9.
-- The uniforms' twin: in (0, 1), a function of (seed, trajectory, step) alone, on a counter no normal uses."""
+- The uniforms' twin: in (0, 1), a function of (seed, trajectory, step) alone, on a counter no normal uses.
+- Dense policy iteration (jump_lib.dense_pi), the reference of tests/test_gpu_jump_policy.py: its first sweep is dense_vi's bit
+  for bit, the greedy policy of s |x|^2 has a margin of at least 1e-6 at every live node, the jump term changes it at 20 nodes
+  or more, and a policy without the jump term, an evaluation without it and a policy re-taken every sweep each move the result
+  by more than 1e-2; successive sweeps contract.
+- The policy memo in jump mode (jump_policy_model.py): both step-level cases of the GPU test pass on a numpy device, and fail
+  with the policy taken from the jump-free operator or the policy tag not reset."""
 import ctypes as C
 import dataclasses
 
@@ -17,8 +23,10 @@ import pytest
 
 from c3sc_amd import engine as E
 from c3sc_amd import workloads as wl
+import cross_memo_model as mm
 import horizon_lib as H
 import jump_lib as JL
+import jump_policy_model as JP
 import offgrid_ref as OR
 import stop_lib as SL
 
@@ -141,6 +149,83 @@ def test_put_rollout_restatement_holds_the_pinned_gap():
     se = J.std() / np.sqrt(len(J))
     assert abs(J.mean() - v0) <= JL.PUT_GAP + 4 * se, (J.mean(), v0, se)
     assert JL.PUT_BOUND == 2 * JL.PUT_GAP
+
+
+# ---------------------------------------------------------------------------------------------------- dense policy iteration
+@pytest.fixture(scope="module")
+def lqr_pi():
+    """the 11 x 11 jump LQR of the reference-API tests: (workload, boundary cost, P = s |x|^2 at the nodes, dense_pi of six sweeps)"""
+    w = JL.lqr_vi_workload(0)
+    xg = w.xgrid()
+    X = np.stack(np.meshgrid(xg[0], xg[1], indexing="ij"), axis=-1)
+    bcost = lambda x: H.lqr_terminal(JL.LQR_PRM, x)
+    P = H.lqr_terminal(JL.LQR_PRM, X)
+    return w, bcost, P, JL.dense_pi(w, SL.lqrn_host, JL.lqr_jumps, bcost, P, 6)
+
+
+def test_dense_pi_first_sweep_is_the_value_iteration_sweep(lqr_pi):
+    w, bcost, P, (mu, margin, V) = lqr_pi
+    vi = JL.dense_vi(w, SL.lqrn_host, JL.lqr_jumps, bcost, P, 2)
+    np.testing.assert_array_equal(V[0], P)
+    np.testing.assert_array_equal(V[1], vi[1])
+    live = mu >= 0
+    assert live.sum() == 81 and (mu[~live] == -1).all() and np.isinf(margin[~live]).all()
+    print("dense_pi: smallest margin of the greedy policy over the live nodes", margin[live].min())
+    assert margin[live].min() >= 1e-6, "every node is compared: the greedy candidate of P is pinned at every live node"
+    # a frozen policy is not value iteration: the second sweep already differs
+    assert np.abs(vi[2] - V[2]).max() > 1e-2
+
+
+def test_dense_pi_sees_the_jumps_in_the_policy_and_in_the_evaluation(lqr_pi):
+    """the preconditions of tests/test_gpu_jump_policy.py: the jumps and the frozen policy move the solution"""
+    w, bcost, P, (mu, _, V) = lqr_pi
+    w0 = dataclasses.replace(w, params=JL.LQR_ZERO_RATE_PRM)
+    mu0, _, _ = JL.dense_pi(w0, SL.lqrn_host, JL.lqr_jumps, bcost, P, 0)
+    live = mu >= 0
+    print("dense_pi: the jump term changes the greedy candidate at", (mu0 != mu)[live].sum(), "of", live.sum(), "live nodes")
+    assert (mu0 != mu)[live].sum() >= 20
+    _, _, Va = JL.dense_pi(w, SL.lqrn_host, JL.lqr_jumps, bcost, P, 4, mu=mu0)   # greedy policy of the jump-free operator
+    _, _, Vb = JL.dense_pi(w0, SL.lqrn_host, JL.lqr_jumps, bcost, P, 4, mu=mu)   # evaluation without the jump term
+    print("dense_pi after four sweeps: policy without jumps", np.abs(Va[4] - V[4]).max(), "evaluation without jumps", np.abs(Vb[4] - V[4]).max())
+    assert np.abs(Va[4] - V[4]).max() > 1e-2
+    assert np.abs(Vb[4] - V[4]).max() > 1e-2
+    # mu given back reproduces the chain bit for bit
+    np.testing.assert_array_equal(JL.dense_pi(w, SL.lqrn_host, JL.lqr_jumps, bcost, P, 4, mu=mu)[2], V[:5])
+
+
+def test_dense_pi_sweeps_contract(lqr_pi):
+    _, _, _, (_, _, V) = lqr_pi
+    steps = [np.abs(V[s + 1] - V[s]).max() for s in range(6)]
+    print("dense_pi: max |V_{s+1} - V_s|", steps)
+    assert all(b < a for a, b in zip(steps, steps[1:])), steps
+
+
+# ---------------------------------------------------------------------------------------------------- the policy memo in jump mode
+def _sim_maker(oracle, case, fault=None):
+    _, jumps = JP.workload(case)
+    return lambda w, cores: JP.JumpSimDevice(oracle, w, cores, jumps, fault=fault)
+
+
+@pytest.mark.parametrize("case", JP.CASES, ids=[c[0] for c in JP.CASES])
+def test_jump_policy_cases_pass_on_the_stand_in(oracle, case):
+    """the cases of tests/test_gpu_jump_policy.py on the numpy stand-in: admitted (margins, 10 % of the hits of the second call
+    where P1 and P2 choose differently) and passed, before a GPU sees them"""
+    reps = JP.scenario(_sim_maker(oracle, case), oracle, case)
+    assert len(reps) == 3 and reps[0]["policies_stored"] > 0 and reps[1]["hits"] > 0
+    if case[0] in JP.CASES_WITH_NEW_NODES:  # 'stored nodes keep P1's candidate and new nodes take P2's'
+        assert reps[1]["policies_stored"] > 0
+    w, _ = JP.workload(case)
+    assert len(set(w.bc)) == w.dx, "every dimension has a boundary type of its own"
+
+
+@pytest.mark.parametrize("case", JP.CASES, ids=[c[0] for c in JP.CASES])
+@pytest.mark.parametrize("fault,match", [("policy-without-jumps", "tag 7 under P1"), ("policy-tag-not-reset", "tag 8 under P2")])
+def test_a_mistake_planted_in_the_jump_policy_stand_in_is_caught(oracle, case, fault, match):
+    assert fault in JP.FAULTS
+    with pytest.raises(AssertionError, match=match) as e:
+        JP.scenario(_sim_maker(oracle, case, fault), oracle, case)
+    assert not isinstance(e.value, mm.CaseRefused), f"the case was refused, not failed: {e.value}"
+    print(f"{case[0]}, {fault}: {type(e.value).__name__}: {str(e.value)[:200]}")
 
 
 def test_jump_uniforms_twin():
