@@ -345,6 +345,14 @@ static int check_jump_model(c3sc_hip_ctx *c, const char *what)
     return C3SC_OK;
 }
 
+// interventions are served by the impulse kernels of the model set now, never together with a game, a horizon or stopping
+static int check_impulse_model(c3sc_hip_ctx *c, const char *what)
+{
+    if (c->impulses && !(c->model >= C3SC_MODEL_USER && rtc_model_nimpulse(c->model) > 0 && c->game_gsz == 0 && c->hz_dt <= 0.0 && !c->stopping))
+        return fail(c, C3SC_ERR_UNSUPPORTED, what);
+    return C3SC_OK;
+}
+
 // game mode is served by the game kernels of the model set now (set_model may have replaced the model set_game checked)
 static int check_game_model(c3sc_hip_ctx *c, const char *what)
 {
@@ -587,6 +595,7 @@ int c3sc_hip_set_horizon_step(c3sc_hip_ctx *c, double dt)
     if (!rtc_model_horizon(c->model))
         return fail(c, C3SC_ERR_UNSUPPORTED, "set_horizon_step: this model was compiled without horizon kernels (c3sc_hip_model_compile_fh, horizon = 1)");
     if (c->game_gsz > 0) return fail(c, C3SC_ERR_UNSUPPORTED, "set_horizon_step: games have no horizon form");
+    if (c->impulses) return fail(c, C3SC_ERR_UNSUPPORTED, "set_horizon_step: impulse control has no horizon form (c3sc_hip_set_impulses(ctx, 0) first)");
     c->hz_dt = dt;
     c->static_dirty = true;
     return C3SC_OK;
@@ -605,6 +614,7 @@ int c3sc_hip_set_stopping(c3sc_hip_ctx *c, int on)
     if (!rtc_model_stop(c->model))
         return fail(c, C3SC_ERR_UNSUPPORTED, "set_stopping: this model was compiled without stop kernels (c3sc_hip_model_compile_os, stop = 1)");
     if (c->game_gsz > 0) return fail(c, C3SC_ERR_UNSUPPORTED, "set_stopping: stopping games are not offered");
+    if (c->impulses) return fail(c, C3SC_ERR_UNSUPPORTED, "set_stopping: impulse control has no stop form (c3sc_hip_set_impulses(ctx, 0) first)");
     c->stopping = 1;
     return C3SC_OK;
 }
@@ -623,6 +633,25 @@ int c3sc_hip_set_jumps(c3sc_hip_ctx *c, int on)
         return fail(c, C3SC_ERR_UNSUPPORTED, "set_jumps: this model was compiled without jump kernels (c3sc_hip_model_compile_jd, njump > 0)");
     if (c->game_gsz > 0) return fail(c, C3SC_ERR_UNSUPPORTED, "set_jumps: games with jumps are not offered");
     c->jumps = 1;
+    return C3SC_OK;
+}
+
+int c3sc_hip_set_impulses(c3sc_hip_ctx *c, int on)
+{
+    if (!c) return C3SC_ERR_ARG;
+    if (!on) {
+        c->impulses = 0;
+        return C3SC_OK;
+    }
+    if (c->model == 0) return fail(c, C3SC_ERR_ARG, "set_impulses: set_model first");
+    if (c->model < C3SC_MODEL_USER || !rtc_model_known(c->model))
+        return fail(c, C3SC_ERR_UNSUPPORTED, "set_impulses: interventions need a run-time compiled model (c3sc_hip_model_compile_ic with nimpulse > 0)");
+    if (rtc_model_nimpulse(c->model) == 0)
+        return fail(c, C3SC_ERR_UNSUPPORTED, "set_impulses: this model was compiled without impulse kernels (c3sc_hip_model_compile_ic, nimpulse > 0)");
+    if (c->game_gsz > 0) return fail(c, C3SC_ERR_UNSUPPORTED, "set_impulses: games with interventions are not offered");
+    if (c->hz_dt > 0.0) return fail(c, C3SC_ERR_UNSUPPORTED, "set_impulses: impulse control has no horizon form (c3sc_hip_set_horizon_step(ctx, 0) first)");
+    if (c->stopping) return fail(c, C3SC_ERR_UNSUPPORTED, "set_impulses: impulse control has no stop form (c3sc_hip_set_stopping(ctx, 0) first)");
+    c->impulses = 1;
     return C3SC_OK;
 }
 
@@ -661,6 +690,7 @@ int c3sc_hip_set_game(c3sc_hip_ctx *c, int du_min, int nu, const double *U, int 
     if (c->hz_dt > 0.0) return fail(c, C3SC_ERR_UNSUPPORTED, "set_game: games have no horizon form (c3sc_hip_set_horizon_step(ctx, 0) first)");
     if (c->stopping) return fail(c, C3SC_ERR_UNSUPPORTED, "set_game: stopping games are not offered (c3sc_hip_set_stopping(ctx, 0) first)");
     if (c->jumps) return fail(c, C3SC_ERR_UNSUPPORTED, "set_game: games with jumps are not offered (c3sc_hip_set_jumps(ctx, 0) first)");
+    if (c->impulses) return fail(c, C3SC_ERR_UNSUPPORTED, "set_game: games with interventions are not offered (c3sc_hip_set_impulses(ctx, 0) first)");
     int mdu = 0;
     bool has_game = false;
     if (c->model < C3SC_MODEL_USER || !rtc_model_info(c->model, mdu, has_game))
@@ -1189,12 +1219,20 @@ static int launch_bellman(c3sc_hip_ctx *c, int k, size_t F, const int32_t *d_idx
             return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers: jumps run on the fiber-per-wave kernel only (the pair and quad variants have no jump form)");
         variant = C3SC_VARIANT_FIBER_PER_WAVE;
     }
+    if (c->impulses) { // and with interventions on: the impulse form of the plain or the jump form
+        rc = check_impulse_model(c, "bellman_fibers: interventions need a model compiled with impulse kernels (and no game, horizon or stopping)");
+        if (rc != C3SC_OK) return rc;
+        if (variant != C3SC_VARIANT_AUTO && variant != C3SC_VARIANT_FIBER_PER_WAVE)
+            return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers: interventions run on the fiber-per-wave kernel only (the pair and quad variants have no impulse form)");
+        variant = C3SC_VARIANT_FIBER_PER_WAVE;
+    }
     if (F == 0) return C3SC_OK;
     if (!d_idx || !d_out) return fail(c, C3SC_ERR_ARG, "bellman_fibers: null buffer");
     A.forced = d_policy;
     LaunchIO io{c->arena, d_idx, d_out, d_uidx, d_absorbed, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream};
     io.stop = c->stopping != 0;
     io.jump = c->jumps != 0;
+    io.impulse = c->impulses != 0;
     // A launcher declines (nothing launched) when its LDS layout does not fit this grid or it does not serve this call; the
     // next-best instantiation of the same padded rank is tried then (e.g. the duo kernel's two staging buffers hold N <= 25 at
     // rank 16, the one-buffer quad kernel behind it N <= 75, the per-wave kernel behind that only stages the varying core).
@@ -1258,7 +1296,7 @@ static int launch_bellman_all(c3sc_hip_ctx *c, int nk, const int *ks, const size
             if (d_out[q] == d_out[s] && F[s] > 0) return fail(c, C3SC_ERR_ARG, "bellman_fibers_all: two segments share an output array");
     }
     hipStream_t st = (hipStream_t)stream;
-    if (overlap && c->tab3L_off && c->tab3_stale && c->game_gsz == 0 && c->hz_dt <= 0.0 && !c->stopping && !c->jumps) {
+    if (overlap && c->tab3L_off && c->tab3_stale && c->game_gsz == 0 && c->hz_dt <= 0.0 && !c->stopping && !c->jumps && !c->impulses) {
         // stale three-core tables: built here, ahead of the fork, if a segment is going to run a three-core kernel -- every
         // side stream is then ordered behind the build by the fork itself
         const long fmin = fiber_partition_min();
@@ -1322,6 +1360,7 @@ static int launch_box(c3sc_hip_ctx *c, int k, size_t F, const int32_t *d_idx, co
     if (c->hz_dt > 0.0) return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_box: horizon mode has no control-box form");
     if (c->stopping) return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_box: stopping has no control-box form");
     if (c->jumps) return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_box: jumps have no control-box form");
+    if (c->impulses) return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_box: interventions have no control-box form");
     if (model_ncf(c->model) != 0 && c->model != C3SC_MODEL_COTHRUST6D) // cothrust forms its features from u on the device (models.hpp: CF_FROM_U)
         return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_box: this model needs transcendental functions of the control");
     KArgs A;
@@ -1396,6 +1435,7 @@ static int launch_tables(c3sc_hip_ctx *c, int k, size_t F, const int32_t *d_idx,
     if (c->hz_dt > 0.0) return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_tables: the TABLE model has no horizon kernels");
     if (c->stopping) return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_tables: the TABLE model has no stop kernels");
     if (c->jumps) return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_tables: the TABLE model has no jump kernels");
+    if (c->impulses) return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_tables: the TABLE model has no impulse kernels");
     c->model = C3SC_MODEL_TABLE; // fill_args only checks that a model is set
     KArgs A;
     int rc = fill_args(c, k, F, A, true);
@@ -1692,6 +1732,11 @@ int c3sc_hip_simulate(c3sc_hip_ctx *c, const c3sc_hip_sim_args *a, void *stream)
         if (check_jump_model(c, "simulate: jumps need a model compiled with jump kernels (and no game)") != C3SC_OK) return C3SC_ERR_UNSUPPORTED;
         if (a->box) return fail(c, C3SC_ERR_UNSUPPORTED, "simulate: jumps have no control-box form");
     }
+    if (c->impulses) {
+        if (check_impulse_model(c, "simulate: interventions need a model compiled with impulse kernels (and no game, horizon or stopping)") != C3SC_OK)
+            return C3SC_ERR_UNSUPPORTED;
+        if (a->box) return fail(c, C3SC_ERR_UNSUPPORTED, "simulate: interventions have no control-box form");
+    }
     if (c->stopping) {
         if (check_stop_model(c, "simulate: stopping needs a model compiled with stop kernels (and no game)") != C3SC_OK) return C3SC_ERR_UNSUPPORTED;
         if (a->box) return fail(c, C3SC_ERR_UNSUPPORTED, "simulate: stopping has no control-box form");
@@ -1758,6 +1803,7 @@ int c3sc_hip_simulate(c3sc_hip_ctx *c, const c3sc_hip_sim_args *a, void *stream)
         LaunchIO io{ro, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream, &S};
         io.stop = c->stopping != 0;
         io.jump = c->jumps != 0;
+        io.impulse = c->impulses != 0;
         rc = launch_one(c, ek, A, io, "simulate: this rollout kernel has no box minimiser");
         if (rc != C3SC_OK) return rc;
         s0 = S.s1;
@@ -1816,6 +1862,7 @@ int c3sc_hip_integrate(c3sc_hip_ctx *c, const c3sc_hip_ode_args *a, void *stream
     if (c->hz_dt > 0.0) return fail(c, C3SC_ERR_UNSUPPORTED, "integrate: deterministic closed loops are not offered in horizon mode");
     if (c->stopping) return fail(c, C3SC_ERR_UNSUPPORTED, "integrate: deterministic closed loops are not offered for stopping problems");
     if (c->jumps) return fail(c, C3SC_ERR_UNSUPPORTED, "integrate: deterministic closed loops are not offered for jump diffusions");
+    if (c->impulses) return fail(c, C3SC_ERR_UNSUPPORTED, "integrate: deterministic closed loops are not offered for impulse control");
     KArgs A;
     rc = fill_args(c, 0, 0, A, false);
     if (rc != C3SC_OK) return rc;

@@ -41,6 +41,8 @@ struct c3sc_hip_ctx {
     int stopping = 0;
     // jump diffusions (c3sc_hip_set_jumps): the launches take the jump forms of the run-time compiled model's kernels
     int jumps = 0;
+    // impulse control (c3sc_hip_set_impulses): the launches take the impulse forms of the run-time compiled model's kernels
+    int impulses = 0;
     double *hz_stack = nullptr;
     size_t hz_stack_static = 0;
     int hz_nstack = 0;

@@ -254,6 +254,25 @@ __device__ inline int jump_constelm(const KArgs &A, const double *__restrict__ r
     return ro[A.cfeat_off + Model::NCF * A.ncand + 3] != 0.0;
 }
 
+// The impulse-control instantiations are those of a model wrapped in ImpulseOf, in the style of the wrappers
+// above: k_fiber_per_wave and k_rollout form the best intervention of the node (impulse_term, kernel_rollout.hpp) and pass
+// model_impulse<Model>() to node_backup as IMPULSE, which compares it once per node with the scan's result.  The model supplies
+// impulse and the number of interventions NIMPULSE.  ImpulseOf<JumpOf<M>> is the combined form.
+template <class M>
+struct ImpulseOf : M {
+    static constexpr bool IMPULSE = true;
+};
+template <class Model>
+constexpr bool model_impulse()
+{
+    if constexpr (requires { Model::IMPULSE; }) return Model::IMPULSE;
+    else return false;
+}
+// defined in kernel_rollout.hpp, beside the off-grid evaluation it is built on; only IMPULSE instantiations call it
+template <class Model, int RP>
+__device__ inline void impulse_term(const KArgs &A, const double *__restrict__ ro, const double (&x)[Model::D], int constelm, bool forced,
+                                    int fu, double &ival, int &imark);
+
 // Output pointers of one launch (separate __restrict__ kernel parameters).
 struct KOut {
     double *out;       // [F][N]            (bellman kernel)
@@ -738,17 +757,37 @@ __device__ __forceinline__ void stop_action(const KArgs &A, const double (&x)[Mo
     }
 }
 
+// IMPULSE (impulse control): M more actions, "pay k_m(x) and move to y_m(x)", with the indices ncand + 1 + m
+// (ncand stays the stop action's whether or not stop is compiled).  The caller forms ival = min_m [k_m(x) + V(y_m(x))] and its
+// mark imark (impulse_term: first strict '<' from +inf, so imark = -1 where no intervention is admissible); it is compared once
+// per node, after the candidate scan and the stop action's place, by the scan's rule: it wins where it is strictly smaller and
+// where the scan left no valid candidate.  No status bit.  Forced path: fu > ncand takes the mark fu - ncand - 1 (the select
+// is impulse_term's) and applies no candidate; any other fu applies that candidate without the comparison (an index above
+// ncand + NIMPULSE gives 0.0 and -1, as an out-of-range candidate index does).
+template <bool IMPULSE>
+__device__ __forceinline__ void impulse_action(int nc, bool forced, int fu, double ival, int imark, double &best, int &ui)
+{
+    if constexpr (IMPULSE) {
+        // forced: impulse_term's select has set imark for fu = nc + 1 + m, m < NIMPULSE; an index beyond the interventions names
+        // nothing, and like an out-of-range candidate index it leaves 0.0 and -1
+        const bool take = forced ? ((fu > nc) & (imark >= 0)) : ((imark >= 0) & ((ui < 0) | (ival < best)));
+        best = take ? ival : best;
+        ui = take ? nc + 1 + imark : ui;
+    }
+}
+
 // JUMP (jump diffusions): one more transition with the un-normalised rate jrate = h^2 lambda(x) to the mark
 // average jval = J(x) = sum_m pi_m Vjump(y_m), formed by the caller (jump_term).  It enters Q0 and PV0 like a control-independent
 // dimension, so every scan, the explicit scheme and the forced path see it: dt = h^2 / Q with the jump rate inside Q, the term
 // delta lambda (J - V_self) in horizon mode with the rate in the CFL test, and a node with no drift and no diffusion but
 // lambda > 0 is not stationary.  jrate = 0 leaves every bit: Q0 + 0.0 and fma(0, J, PV0) are exact for finite J.
 template <class Model, int CG = 1, int CGD = 1, class Cand = CandRegs<Model>, bool SPLIT = true, class Pre = NoPre, bool GAME = false,
-          bool HORIZON = false, bool STOP = false, bool JUMP = false>
+          bool HORIZON = false, bool STOP = false, bool JUMP = false, bool IMPULSE = false>
 __device__ inline double node_backup(const KArgs &A, const double *__restrict__ ro, const double (&x)[Model::D],
                                      const double (&tv)[Model::NTAB > 0 ? Model::NTAB : 1], const Cand &cr,
                                      const double (&V)[2 * Model::D + 1], int ab, int &ui, unsigned &st, bool forced = false,
-                                     int fu = -1, const Pre &pre = Pre(), double jrate = 0.0, double jval = 0.0)
+                                     int fu = -1, const Pre &pre = Pre(), double jrate = 0.0, double jval = 0.0, double ival = 0.0,
+                                     int imark = -1)
 {
     // forced (wave-uniform) = policy evaluation, bellman_pi (bellman.c:1702-1886): the candidate fu (per lane) is
     // applied instead of the minimiser's; same rates, same bellmanrhs.
@@ -756,6 +795,7 @@ __device__ inline double node_backup(const KArgs &A, const double *__restrict__ 
     static_assert(!GAME || (CG == 1 && CGD == 1), "the game scan takes one candidate per trip");
     static_assert(!(STOP && GAME), "stopping games are not offered");
     static_assert(!(JUMP && GAME), "games with jumps are not offered");
+    static_assert(!(IMPULSE && (GAME || HORIZON || STOP)), "impulse control is not offered with games, horizons or stopping");
     const int nc = __builtin_amdgcn_readfirstlane(A.ncand); // keeps the candidate loops' trip test on the scalar unit
     ui = -1;
     // game: which reductions are maxima (wave-uniform), the group length, the forced pair as a list position
@@ -875,6 +915,7 @@ __device__ inline double node_backup(const KArgs &A, const double *__restrict__ 
         if (cfl & (ab == 0)) st |= C3SC_STATUS_CFL;
         best = (ui >= 0) ? bestv : 0.0;
         stop_action<STOP, Model>(A, x, nc, forced, fu, best, ui);
+        impulse_action<IMPULSE>(nc, forced, fu, ival, imark, best, ui);
         best = (ab != 0) ? absorbed_cost : best;
         ui = (ab != 0) ? -1 : ui;
         return best;
@@ -1007,6 +1048,7 @@ __device__ inline double node_backup(const KArgs &A, const double *__restrict__ 
         }
         if constexpr (GAME) ui = (ui >= 0) ? game_list_to_pair(A, ui) : ui;
         stop_action<STOP, Model>(A, x, nc, forced, fu, best, ui);
+        impulse_action<IMPULSE>(nc, forced, fu, ival, imark, best, ui);
         best = (ab != 0) ? absorbed_cost : best;
         ui = (ab != 0) ? -1 : ui;
         return best;
@@ -1136,6 +1178,7 @@ __device__ inline double node_backup(const KArgs &A, const double *__restrict__ 
     best = (ui >= 0) ? bestg : 0.0;
     if constexpr (GAME) ui = (ui >= 0) ? game_list_to_pair(A, ui) : ui;
     stop_action<STOP, Model>(A, x, nc, forced, fu, best, ui);
+    impulse_action<IMPULSE>(nc, forced, fu, ival, imark, best, ui);
     best = (ab != 0) ? absorbed_cost : best;
     ui = (ab != 0) ? -1 : ui;
     return best;

@@ -345,8 +345,14 @@ __global__ void __launch_bounds__(256, (RP >= 20 ? 1 : 2)) // rank 20 is LDS-bou
                     // absorbed lanes evaluate their (valid) node as well and are overwritten as they are without jumps
                     double jrate = 0.0, jval = 0.0;
                     if constexpr (model_jump<Model>()) jump_term<Model, RP>(A, ro, x, jump_constelm<Model>(A, ro), jrate, jval);
+                    // impulse models: the best intervention of the node, M more points per lane; the jump term's registers are dead
+                    double ival = 0.0;
+                    int imark = -1;
+                    if constexpr (model_impulse<Model>())
+                        impulse_term<Model, RP>(A, ro, x, jump_constelm<Model>(A, ro), forced, fu, ival, imark);
                     val = node_backup<Model, 1, 1, CandLds<Model>, true, NoPre, model_game<Model>(), model_horizon<Model>(), model_stop<Model>(),
-                                      model_jump<Model>()>(A, ro, x, tv, cr, V, ab, ui, st, forced, fu, NoPre(), jrate, jval);
+                                      model_jump<Model>(), model_impulse<Model>()>(A, ro, x, tv, cr, V, ab, ui, st, forced, fu, NoPre(), jrate,
+                                                                                   jval, ival, imark);
                 }
                 if (A.memo_keys) { // wave-uniform: node memo of the device-resident cross iterations
                     int ins = 0, ovf = 0;

@@ -272,7 +272,8 @@ __device__ inline double offgrid_value(const KArgs &A, const double *__restrict_
     return v;
 }
 
-// The value a jump to the state yin pays: periodic dimensions are wrapped; a target the rollouts' exit_test
+// The value a jump or an intervention to the state yin pays (jump_term and impulse_term call it):
+// periodic dimensions are wrapped; a target the rollouts' exit_test
 // calls exited -- inside an obstacle, or outside [lb, ub] on an absorbing dimension -- pays obscost or boundcost there, by
 // exit_test's choice; any other target pays the interpolant, which clamps to the grid hull (reflecting dimensions clamp).
 // Selects only: an exited lane evaluates the interpolant at its clamped cell as well.
@@ -308,6 +309,30 @@ __device__ inline void jump_term(const KArgs &A, const double *__restrict__ ro, 
         double y[Model::D];
         const double pi = Model::jump(A.prm, x, m, y);
         J = fma(pi, jump_target_value<Model, RP>(A, ro, y, constelm), J);
+    }
+}
+
+// The best intervention at the node (or off-grid state) x: c_m = k_m(x) + Vt(y_m), m ascending, Vt exactly the
+// value a jump to y_m pays (jump_target_value).  The running minimum starts at +inf and is taken by the first strict '<', so
+// imark = -1 where no c_m is finite (k_m = +inf or NaN: "not admissible at x").  On the forced path a lane whose fu names an
+// intervention takes exactly that mark, by a select in the same loop: the trip count is NIMPULSE on every lane.  The marks stay
+// a rolled loop: one point evaluation's registers, not NIMPULSE of them.
+template <class Model, int RP>
+__device__ inline void impulse_term(const KArgs &A, const double *__restrict__ ro, const double (&x)[Model::D], int constelm, bool forced,
+                                    int fu, double &ival, int &imark)
+{
+    static_assert(Model::NIMPULSE >= 1 && Model::NIMPULSE <= C3SC_IMPULSE_MAX, "number of interventions");
+    ival = __builtin_inf();
+    imark = -1;
+    const int fm = fu - A.ncand - 1;
+#pragma unroll 1
+    for (int m = 0; m < Model::NIMPULSE; m++) {
+        double y[Model::D];
+        const double k = Model::impulse(A.prm, x, m, y);
+        const double c = k + jump_target_value<Model, RP>(A, ro, y, constelm);
+        const bool take = forced ? (m == fm) : ((__builtin_fabs(k) < __builtin_inf()) & (c < ival)); // -inf is not a cost either
+        ival = take ? c : ival;
+        imark = take ? m : imark;
     }
 }
 
@@ -359,6 +384,17 @@ __device__ inline void rollout_input(const KArgs &A, const double *__restrict__ 
 #pragma unroll
         for (int m = 0; m < D; m++) xin[m] = x[m];
 }
+
+// impulse models: the intervention of one step of one lane; empty for every other model, whose kernels keep
+// their registers
+template <int D, bool ON>
+struct ImpulseStep {
+};
+template <int D>
+struct ImpulseStep<D, true> {
+    bool now = false;
+    double y[D] = {};
+};
 
 // state in, controller, Euler-Maruyama step, exit test, state out
 // BOX: the instantiation also serves the control-box minimiser (A.cmode == 1, a wave-uniform switch)
@@ -437,13 +473,26 @@ __global__ void __launch_bounds__(256) k_rollout(const KArgs A, const SimK S, co
                 if constexpr (requires { Model::CF_FROM_U; }) Model::features(u, cf);
             }
         }
+        ImpulseStep<D, model_impulse<Model>()> iv; // impulse models: whether this lane's controller intervenes at this step, and where to
         if (!boxed) {
             int ui;
             // jump models: the controller's backup gets the jump term at the state it sees
             double jrate = 0.0, jval = 0.0;
             if constexpr (model_jump<Model>()) jump_term<Model, RP>(A, ro, xin, S.constelm, jrate, jval);
+            // impulse models: ... and the best intervention there, after the jump term's registers are dead
+            double ival = 0.0;
+            int imark = -1;
+            if constexpr (model_impulse<Model>()) impulse_term<Model, RP>(A, ro, xin, S.constelm, false, -1, ival, imark);
             (void)node_backup<Model, 1, 1, CandLds<Model>, true, NoPre, model_game<Model>(), model_horizon<Model>(), model_stop<Model>(),
-                              model_jump<Model>()>(A, ro, xin, tv, cr, V, ab, ui, st, false, -1, NoPre(), jrate, jval);
+                              model_jump<Model>(), model_impulse<Model>()>(A, ro, xin, tv, cr, V, ab, ui, st, false, -1, NoPre(), jrate,
+                                                                           jval, ival, imark);
+            if constexpr (model_impulse<Model>()) { // the controller intervenes here: the lane pays k_m at the state the controller saw
+                                                    // and moves there to y_m; the step slot carries no stage cost and no increment
+                iv.now = alive && (ui > A.ncand);
+                const double kc = Model::impulse(A.prm, xin, iv.now ? ui - A.ncand - 1 : 0, iv.y);
+                J = iv.now ? J + disc * kc : J;
+                ui = (ui > A.ncand) ? -1 : ui; // the candidate table has no row >= ncand: u = 0
+            }
             if constexpr (model_stop<Model>()) { // the controller stops here: the lane pays psi and is frozen like an exited one.  psi is
                                                  // taken at the state the controller saw (wrapped, with S.wrap): the amount that won
                 const bool stopnow = alive && (ui == A.ncand);
@@ -464,7 +513,8 @@ __global__ void __launch_bounds__(256) k_rollout(const KArgs A, const SimK S, co
 #pragma unroll
             for (int k = 0; k < DU; k++) S.u[((size_t)i * nurow + s / se) * DU + k] = u[k];
         const double stage = Model::stage(A.prm, x, u);
-        J = alive ? J + disc * stage * dt : J;
+        if constexpr (model_impulse<Model>()) J = (alive && !iv.now) ? J + disc * stage * dt : J; // an intervention step pays no stage cost
+        else J = alive ? J + disc * stage * dt : J;
         // the dynamics at x itself (the controller may have seen the wrapped state)
         double tvx[NT];
         if (S.wrap) offgrid_tables<MID, Model>(x, tvx);
@@ -510,6 +560,7 @@ __global__ void __launch_bounds__(256) k_rollout(const KArgs A, const SimK S, co
             double acc = x[m] + b[m] * dt; // c3control_simulate's order
             acc += sg[m] * S.sqdt * xi[m];
             if constexpr (model_jump<Model>()) acc += dj[m];
+            if constexpr (model_impulse<Model>()) acc = iv.now ? iv.y[m] : acc;
             x[m] = alive ? acc : x[m];
         }
         if (S.traj && se > 0 && (s + 1) % se == 0)

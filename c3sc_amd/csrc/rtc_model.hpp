@@ -4,7 +4,7 @@
 // user's source wrapped in namespace c3sc_user, which defines (include/c3sc_hip.h states the contract)
 //   drift(prm, x, u, b)  sigma(prm, x, u, s)  stage(prm, x, u)  boundcost(prm, x)  obscost(prm, x)
 // and, for a stopping model, stopcost(prm, x); for a jump-diffusion model, jumprate(prm, x) and
-// jump(prm, x, m, y)
+// jump(prm, x, m, y); for an impulse-control model, impulse(prm, x, m, y)
 // with C3SC_D / C3SC_DU defined.  RtcModel presents them as the Model concept of models.hpp: no tables and no candidate
 // features (the user's code evaluates its own transcendentals with the device libm), an empty Node.  The masks come from the
 // spec; their safe defaults (every dimension depends on u, none is a constant of the candidate, the stage cost reads u) are
@@ -51,6 +51,13 @@ struct RtcModel {
     __device__ static inline double jump(const double *prm, const double (&x)[D], int m, double (&y)[D])
     {
         return ::c3sc_user::jump(prm, x, m, y);
+    }
+#endif
+#ifdef C3SC_RTC_IMPULSE // a spec with nimpulse > 0 (c3sc_hip_model_compile_ic): only then must the source define impulse
+    static constexpr int NIMPULSE = C3SC_NIMPULSE;
+    __device__ static inline double impulse(const double *prm, const double (&x)[D], int m, double (&y)[D])
+    {
+        return ::c3sc_user::impulse(prm, x, m, y);
     }
 #endif
 };

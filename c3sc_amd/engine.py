@@ -39,6 +39,7 @@ EXPORTS = [
     "c3sc_hip_model_compile_fh", "c3sc_hip_model_code_object_fh", "c3sc_hip_set_horizon_step", "c3sc_hip_upload_value_stack",
     "c3sc_hip_model_compile_os", "c3sc_hip_model_code_object_os", "c3sc_hip_set_stopping",
     "c3sc_hip_model_compile_jd", "c3sc_hip_model_code_object_jd", "c3sc_hip_set_jumps", "c3sc_hip_jump_uniforms",
+    "c3sc_hip_model_compile_ic", "c3sc_hip_model_code_object_ic", "c3sc_hip_set_impulses",
 ]
 
 class SimArgs(C.Structure):
@@ -91,6 +92,14 @@ class ModelSpecJd(C.Structure):
 
 
 JUMP_MAX = 8  # C3SC_JUMP_MAX: most atoms of a discretised mark distribution
+
+
+class ModelSpecIc(C.Structure):
+    """struct c3sc_hip_model_spec_ic (include/c3sc_hip.h): the _jd spec plus the number of interventions"""
+    _fields_ = [("jd", ModelSpecJd), ("nimpulse", C.c_int)]
+
+
+IMPULSE_MAX = 8  # C3SC_IMPULSE_MAX: most interventions of an impulse-control model
 
 
 MODEL_USER = 1000  # C3SC_MODEL_USER: first id of the run-time compiled models
@@ -176,6 +185,9 @@ def load_library():
         L.c3sc_hip_model_code_object_jd.argtypes = [C.POINTER(ModelSpecJd), C.c_void_p, c_size_p]
         L.c3sc_hip_set_jumps.argtypes = [C.c_void_p, C.c_int]
         L.c3sc_hip_jump_uniforms.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, c_double_p]
+        L.c3sc_hip_model_compile_ic.argtypes = [C.POINTER(ModelSpecIc), c_int_p]
+        L.c3sc_hip_model_code_object_ic.argtypes = [C.POINTER(ModelSpecIc), C.c_void_p, c_size_p]
+        L.c3sc_hip_set_impulses.argtypes = [C.c_void_p, C.c_int]
         _LIB = L
     return _LIB
 
@@ -206,7 +218,7 @@ def _model_fail(rc, what):
 
 def compile_model(source: str, d: int, du: int, ranks=(4, 8), box: bool = False, udep_mask: int = 0, uconst_mask: int = 0,
                   stage_udep: bool = True, name: Optional[str] = None, game: bool = False, horizon: bool = False,
-                  stop: bool = False, njump: int = 0) -> int:
+                  stop: bool = False, njump: int = 0, nimpulse: int = 0) -> int:
     """Compile a device model from source (c3sc_hip_model_compile, include/c3sc_hip.h states the source contract) and return
     its model id (>= MODEL_USER), usable wherever a built-in model id is.  No GPU is needed.  Raises C3scHipError with the
     compiler's log on failure; the error code is args[1].  game=True (c3sc_hip_model_compile_ex) adds the game kernels that
@@ -214,11 +226,16 @@ def compile_model(source: str, d: int, du: int, ranks=(4, 8), box: bool = False,
     (c3sc_hip_model_compile_fh) adds the finite-horizon kernels that BellmanEngine.set_horizon_step needs.  stop=True
     (c3sc_hip_model_compile_os) adds the stop kernels that BellmanEngine.set_stopping needs: the source then defines stopcost.
     njump=M > 0 (c3sc_hip_model_compile_jd) adds the jump kernels that BellmanEngine.set_jumps needs: the source then defines
-    jumprate and jump for M marks."""
+    jumprate and jump for M marks.  nimpulse=M > 0 (c3sc_hip_model_compile_ic) adds the impulse kernels that
+    BellmanEngine.set_impulses needs: the source then defines impulse for M interventions."""
     L = load_library()
     spec = _model_spec(source, d, du, tuple(ranks), box, udep_mask, uconst_mask, stage_udep, name)
     mid = C.c_int(0)
-    if njump:
+    if nimpulse:
+        ic = ModelSpecIc(ModelSpecJd(ModelSpecOs(ModelSpecFh(ModelSpecEx(spec, 1 if game else 0), 1 if horizon else 0), 1 if stop else 0),
+                                     int(njump)), int(nimpulse))
+        rc = L.c3sc_hip_model_compile_ic(C.byref(ic), C.byref(mid))
+    elif njump:
         jd = ModelSpecJd(ModelSpecOs(ModelSpecFh(ModelSpecEx(spec, 1 if game else 0), 1 if horizon else 0), 1 if stop else 0), int(njump))
         rc = L.c3sc_hip_model_compile_jd(C.byref(jd), C.byref(mid))
     elif stop:
@@ -239,18 +256,22 @@ def compile_model(source: str, d: int, du: int, ranks=(4, 8), box: bool = False,
 
 def code_object(source: str, d: int, du: int, ranks=(4, 8), box: bool = False, udep_mask: int = 0, uconst_mask: int = 0,
                 stage_udep: bool = True, name: Optional[str] = None, game: bool = False, horizon: bool = False,
-                stop: bool = False, njump: int = 0) -> bytes:
+                stop: bool = False, njump: int = 0, nimpulse: int = 0) -> bytes:
     """The gfx950 code object of this spec (c3sc_hip_model_code_object): the loaded one if compile_model already compiled the
     spec, otherwise what compile_model would build now (its id and default name are in the kernel names), compiled and not
-    registered.  game, horizon, stop and njump select the spec as in compile_model (stop: c3sc_hip_model_code_object_os,
-    njump: c3sc_hip_model_code_object_jd)."""
+    registered.  game, horizon, stop, njump and nimpulse select the spec as in compile_model (stop: c3sc_hip_model_code_object_os,
+    njump: c3sc_hip_model_code_object_jd, nimpulse: c3sc_hip_model_code_object_ic)."""
     L = load_library()
     spec = _model_spec(source, d, du, tuple(ranks), box, udep_mask, uconst_mask, stage_udep, name)
     cap = 16 << 20  # one compile when the code object fits; a larger one is compiled again into a buffer of its size
     for _ in range(2):
         buf = C.create_string_buffer(cap)
         size = C.c_size_t(cap)
-        if njump:
+        if nimpulse:
+            ic = ModelSpecIc(ModelSpecJd(ModelSpecOs(ModelSpecFh(ModelSpecEx(spec, 1 if game else 0), 1 if horizon else 0),
+                                                     1 if stop else 0), int(njump)), int(nimpulse))
+            rc = L.c3sc_hip_model_code_object_ic(C.byref(ic), buf, C.byref(size))
+        elif njump:
             jd = ModelSpecJd(ModelSpecOs(ModelSpecFh(ModelSpecEx(spec, 1 if game else 0), 1 if horizon else 0), 1 if stop else 0),
                              int(njump))
             rc = L.c3sc_hip_model_code_object_jd(C.byref(jd), buf, C.byref(size))
@@ -293,6 +314,17 @@ def decode_exit(exit_step):
     return step, stopped.astype(np.int32)
 
 
+def decode_action(uidx, ncand: int):
+    """A reported action index as (kind, index): 0 .. ncand-1 is ("control", i), ncand ("stop", 0), ncand + 1 + m
+    ("impulse", m) (c3sc_hip_set_impulses), -1 on absorbed nodes ("absorbed", -1).  On arrays: kind as an array of strings."""
+    i = np.asarray(uidx)
+    kind = np.where(i < 0, "absorbed", np.where(i < ncand, "control", np.where(i == ncand, "stop", "impulse")))
+    idx = np.where(i < 0, -1, np.where(i < ncand, i, np.where(i == ncand, 0, i - ncand - 1)))
+    if np.ndim(uidx) == 0:
+        return str(kind), int(idx)
+    return kind, idx
+
+
 def jump_uniforms(seed: int, traj: int, step: int):
     """(u0, u1) of c3sc_hip_jump_uniforms: the event and mark uniforms of one rollout step (no GPU needed)"""
     out = (C.c_double * 2)()
@@ -327,6 +359,7 @@ class BellmanEngine:
         self.w = None
         self.stopping = False
         self.jumps = False
+        self.impulses = False
 
     def close(self):
         if getattr(self, "h", None):
@@ -409,6 +442,14 @@ class BellmanEngine:
         horizon / stop as well to combine it with set_horizon_step / set_stopping."""
         self._chk(self.L.c3sc_hip_set_jumps(self.h, C.c_int(1 if on else 0)), "set_jumps")
         self.jumps = bool(on)
+
+    def set_impulses(self, on: bool = True):
+        """Impulse control (c3sc_hip_set_impulses): the Bellman calls compare the candidates' result with the best intervention
+        min_m [k_m(x) + V(y_m(x))], reported as the index ncand + 1 + m (decode_action), and simulate moves a trajectory whose
+        controller intervenes to y_m in one step slot.  The model must be compiled with nimpulse=M > 0, and with njump as well
+        to combine it with set_jumps; not offered with games, the horizon step or stopping."""
+        self._chk(self.L.c3sc_hip_set_impulses(self.h, C.c_int(1 if on else 0)), "set_impulses")
+        self.impulses = bool(on)
 
     def upload_value_stack(self, ranks, cores):
         """V_0 .. V_N for simulate in horizon mode (c3sc_hip_upload_value_stack): ranks[s] is stage s's rank list (d + 1 entries),

@@ -385,6 +385,11 @@ struct DPparam {
     double (*jumprate)(const double *);
     double (*jumpmark)(const double *, int, double *);
     int jumps;
+    /* impulse control (c3control_add_impulses / c3control_set_impulses): M interventions, impulse(x, m, y) writes
+     * y = y_m(x) and returns k_m(x) -- the host form of the device model's impulse -- and the switch */
+    int nimpulse;
+    double (*impulse)(const double *, int, double *);
+    int impulses;
 };
 
 struct DPparam *dp_param_create(size_t dx, size_t du, size_t dw, double discount)
@@ -426,6 +431,7 @@ struct ControlParams {
      * node's un-normalised jump rate h^2 lambda and mark average J, formed by bellman_optimal for bellman_control */
     struct ValueF *vf;
     double jrate, jval;
+    int impulse_last; /* bellman_optimal in impulse mode: the intervention the last node's decision took, -1: none */
 };
 
 struct ControlParams *control_params_create(size_t dx, size_t dw, struct DPparam *dp, struct MCAparam *mca,
@@ -582,6 +588,7 @@ int bellman_optimal(size_t du, double *u, double *val, void *arg)
     struct Memory *mem = arg;
     struct ControlParams *p = mem->shared;
     const int ab = *workspace_get_absorbed(p->work, mem->private);
+    p->impulse_last = -1; /* an absorbed node takes no intervention */
     if (ab != 0) {
         for (size_t i = 0; i < du; i++) u[i] = 0.0;
         *val = bellman_control(du, u, NULL, arg);
@@ -603,6 +610,28 @@ int bellman_optimal(size_t du, double *u, double *val, void *arg)
             *val = psi;
             for (size_t i = 0; i < du; i++) u[i] = 0.0;
             p->stopped_last = 1;
+        }
+    }
+    if (p->dp->impulses) { /* node_backup's IMPULSE actions, after the stop action's place: c_m = k_m + Vt(y_m), m
+                            * ascending, the running minimum from +inf by the first strict '<'; a cost that is not finite never
+                            * wins; the best intervention wins where it is strictly smaller than the scan's result */
+        if (p->vf == NULL) DIE("bellman_optimal: impulse mode needs the value function the targets are read from");
+        const double *x = p->x + mem->private * p->dx;
+        double y[C3SC_MAX_DIM], ival = INFINITY;
+        int imark = -1;
+        for (int m = 0; m < p->dp->nimpulse; m++) {
+            const double k = p->dp->impulse(x, m, y);
+            if (!isfinite(k)) continue;
+            const double c = k + jump_target_value_host(p, y);
+            if (c < ival) {
+                ival = c;
+                imark = m;
+            }
+        }
+        if (imark >= 0 && ival < *val) {
+            *val = ival;
+            for (size_t i = 0; i < du; i++) u[i] = 0.0;
+            p->impulse_last = imark;
         }
     }
     return 0;
@@ -686,6 +715,10 @@ static struct c3sc_hip_ctx *sync_device_ctx(struct ControlParams *cp, struct c3s
     if (dp->jumps && (!brute || gorder >= 0 || dp->model == 0))
         DIE("bellman_vi: jumps need a device model compiled with jump kernels (c3sc_hip_model_compile_jd) and a plain candidate list");
     sig = fnv(sig, &dp->jumps, sizeof(int));
+    if (dp->impulses && (!brute || gorder >= 0 || dp->model == 0 || dp->hz_dt > 0.0 || dp->stopping))
+        DIE("bellman_vi: interventions need a device model compiled with impulse kernels (c3sc_hip_model_compile_ic), a plain candidate "
+            "list, and neither the horizon step nor the stopping switch");
+    sig = fnv(sig, &dp->impulses, sizeof(int));
     if (brute) sig = fnv(sig, c3opt_get_brute_vals(cp->opt), c3opt_get_nbrute(cp->opt) * odu * sizeof(double));
     else {
         const size_t g = c3opt_get_box_grid(cp->opt), pl = c3opt_get_box_polish(cp->opt);
@@ -703,6 +736,7 @@ static struct c3sc_hip_ctx *sync_device_ctx(struct ControlParams *cp, struct c3s
         /* a context left in stop mode by an earlier problem would refuse set_game: off first, on again after the controls */
         hipok(ctx, c3sc_hip_set_stopping(ctx, 0), "c3sc_hip_set_stopping");
         hipok(ctx, c3sc_hip_set_jumps(ctx, 0), "c3sc_hip_set_jumps"); /* likewise a context left in jump mode */
+        hipok(ctx, c3sc_hip_set_impulses(ctx, 0), "c3sc_hip_set_impulses"); /* ... or in impulse mode, which refuses the horizon step too */
         if (dp->model != 0) hipok(ctx, c3sc_hip_set_model(ctx, dp->model, dp->prm, dp->nprm), "c3sc_hip_set_model");
         if (brute && gorder >= 0)
             hipok(ctx, c3sc_hip_set_game(ctx, (int)gdu_min, (int)gnu, gU, (int)gnw, gW, gorder), "c3sc_hip_set_game");
@@ -714,6 +748,7 @@ static struct c3sc_hip_ctx *sync_device_ctx(struct ControlParams *cp, struct c3s
         hipok(ctx, c3sc_hip_set_horizon_step(ctx, dp->hz_dt), "c3sc_hip_set_horizon_step");
         hipok(ctx, c3sc_hip_set_stopping(ctx, dp->stopping), "c3sc_hip_set_stopping");
         hipok(ctx, c3sc_hip_set_jumps(ctx, dp->jumps), "c3sc_hip_set_jumps");
+        hipok(ctx, c3sc_hip_set_impulses(ctx, dp->impulses), "c3sc_hip_set_impulses");
         g_ctx[sl].cfg_set = 1;
         g_ctx[sl].cfg_sig = sig;
         g_ctx[sl].version = 0; /* set_grid invalidates the resident value function */
@@ -1054,6 +1089,13 @@ static void refuse_stop_pi(const struct DPparam *dp, const char *who)
         DIE("%s: policy iteration is not offered for stopping problems (c3control_set_stopping); use value iteration", who);
 }
 
+/* nor for impulse control */
+static void refuse_impulse_pi(const struct DPparam *dp, const char *who)
+{
+    if (dp != NULL && dp->impulses)
+        DIE("%s: policy iteration is not offered for impulse control (c3control_set_impulses); use value iteration", who);
+}
+
 /* nor in horizon mode: a finite-horizon problem has no stationary policy to iterate on */
 static void refuse_horizon_pi(const struct DPparam *dp, const char *who)
 {
@@ -1067,6 +1109,7 @@ static int pi_core(struct PIparam *pi, size_t F, size_t k0, const int32_t *idx, 
     refuse_game_pi(cp->opt, "bellman_pi");
     refuse_horizon_pi(cp->dp, "bellman_pi");
     refuse_stop_pi(cp->dp, "bellman_pi");
+    refuse_impulse_pi(cp->dp, "bellman_pi");
     struct MCAparam *mca = cp->mca;
     struct DPparam *dp = cp->dp;
     const size_t dx = mca->dx, N = mca->ngrid[k0];
@@ -1261,6 +1304,7 @@ struct C3Control {
     struct c3Opt *opt_sim;
     void (*transform_sim)(size_t, const double *, double *);
     double *prevpol;
+    int impulse_last; /* the intervention the last c3control_policy_eval* took in impulse mode, -1: none */
     /* fibers of every core step sharded over the GPUs of a node (c3control_set_fiber_sharding) */
     size_t shard_world, shard_rank;
     c3sc_exchange_fn shard_exchange;
@@ -1336,6 +1380,19 @@ void c3control_set_jumps(struct C3Control *c, int on)
     c->dp->model_checked = 0; /* the first-fiber check runs again, against the operator now in force */
 }
 int c3control_get_jumps(const struct C3Control *c) { return c->dp->jumps; }
+void c3control_add_impulses(struct C3Control *c, int M, double (*fn)(const double *, int, double *))
+{
+    if (M < 1 || M > C3SC_IMPULSE_MAX || fn == NULL) DIE("c3control_add_impulses: 1 <= M <= C3SC_IMPULSE_MAX interventions and the callback are needed");
+    c->dp->nimpulse = M;
+    c->dp->impulse = fn;
+}
+void c3control_set_impulses(struct C3Control *c, int on)
+{
+    if (on && c->dp->impulse == NULL) DIE("c3control_set_impulses: c3control_add_impulses first");
+    c->dp->impulses = on ? 1 : 0;
+    c->dp->model_checked = 0; /* the first-fiber check runs again, against the operator now in force */
+}
+int c3control_get_impulses(const struct C3Control *c) { return c->dp->impulses; }
 void c3control_set_device_model(struct C3Control *c, int model, const double *params, size_t n) { dp_param_set_device_model(c->dp, model, params, n); }
 
 void c3control_set_consistent_ends(struct C3Control *c, int on)
@@ -1403,6 +1460,7 @@ void c3control_begin_pi_step(struct C3Control *c, struct PIparam *pi, struct Val
     refuse_game_pi(opt, "c3control_step_pi");
     refuse_horizon_pi(c->dp, "c3control_step_pi");
     refuse_stop_pi(c->dp, "c3control_step_pi");
+    refuse_impulse_pi(c->dp, "c3control_step_pi");
     c->cp_active = control_params_create(c->dx, c->dw, c->dp, c->mca, c->work, opt);
     pi_param_add_cp(pi, c->cp_active);
     pi_param_add_value(pi, vf);
@@ -1667,6 +1725,7 @@ struct ValueF **c3control_fh_solve(struct C3Control *c, size_t nstages, double d
                                    struct ApproxArgs *apargs, struct c3Opt *opt, int verbose)
 { /* V_N = terminal, V_n = one explicit step back from V_{n+1} (c3control_step_vi in horizon mode) */
     if (nstages < 1 || terminal == NULL || !(delta > 0.0)) DIE("c3control_fh_solve: nstages >= 1, a terminal value and delta > 0");
+    if (c->dp->impulses) DIE("c3control_fh_solve: impulse control has no horizon form (c3control_set_impulses)");
     c3control_set_horizon_step(c, delta);
     workspace_reset_vi_htable(c->work);
     struct ValueF **V = xcalloc(nstages + 1, sizeof(struct ValueF *));
@@ -1692,6 +1751,7 @@ struct ValueF *c3control_pi_solve(struct C3Control *c, size_t maxiter, double ab
     refuse_game_pi(opt, "c3control_pi_solve");
     refuse_horizon_pi(c->dp, "c3control_pi_solve");
     refuse_stop_pi(c->dp, "c3control_pi_solve");
+    refuse_impulse_pi(c->dp, "c3control_pi_solve");
     struct ValueF *start = valuef_copy(policy);
     struct PIparam *poli = c3control_begin_pi(c, policy);
     double stot = 1.0;
@@ -1783,6 +1843,7 @@ int c3control_policy_eval_value(struct C3Control *c, double t, const double *x, 
     for (size_t i = 0; i < c->du; i++) c->prevpol[i] = u[i];
     if (stopped != NULL) *stopped = cp->stopped_last;
     if (value != NULL) *value = val;
+    c->impulse_last = cp->impulse_last;
     control_params_destroy(cp);
     return 0;
 }
@@ -1790,6 +1851,15 @@ int c3control_policy_eval_value(struct C3Control *c, double t, const double *x, 
 int c3control_policy_eval_stop(struct C3Control *c, double t, const double *x, double *u, int *stopped)
 {
     return c3control_policy_eval_value(c, t, x, u, stopped, NULL);
+}
+
+int c3control_policy_eval_impulse(struct C3Control *c, const double *x, int *m)
+{ /* the decision of the implicit policy at x in impulse mode: *m = the intervention it takes, -1: it steers with a control */
+    double *u = xcalloc(c->du, sizeof(double));
+    const int rc = c3control_policy_eval_value(c, 0.0, x, u, NULL, NULL);
+    free(u);
+    if (m != NULL) *m = c->impulse_last;
+    return rc;
 }
 
 int c3control_policy_eval(struct C3Control *c, double t, const double *x, double *u)
@@ -1918,6 +1988,7 @@ int c3control_integrate(struct C3Control *c, const char *method, double dt_int, 
     if (c == NULL || x0 == NULL) return reject(who, "null control or x0");
     if (c->dp->stopping) return reject(who, "deterministic closed loops are not offered for stopping problems (c3control_set_stopping)");
     if (c->dp->jumps) return reject(who, "deterministic closed loops are not offered for jump diffusions (c3control_set_jumps)");
+    if (c->dp->impulses) return reject(who, "deterministic closed loops are not offered for impulse control (c3control_set_impulses)");
     if (c->policy_sim == NULL || c->opt_sim == NULL) return reject(who, "no implicit policy (c3control_add_policy_sim)");
     if (c->dp->drift == NULL || c->dp->stagecost == NULL || c->dp->boundcost == NULL || c->dp->obscost == NULL)
         return reject(who, "the host callbacks (drift, stagecost, boundcost, obscost) are needed");
@@ -2001,6 +2072,7 @@ int c3control_integrate_batch(struct C3Control *c, size_t ntraj, const double *x
     if (rc != 0) return rc;
     if (c->dp->stopping) return reject(who, "deterministic closed loops are not offered for stopping problems (c3control_set_stopping)");
     if (c->dp->jumps) return reject(who, "deterministic closed loops are not offered for jump diffusions (c3control_set_jumps)");
+    if (c->dp->impulses) return reject(who, "deterministic closed loops are not offered for impulse control (c3control_set_impulses)");
     size_t nsub;
     rc = integrate_check(who, c->dx, method, dt_int, dt_out, nout, goal, keep, &nsub);
     if (rc != 0) return rc;
@@ -2050,6 +2122,8 @@ int c3control_simulate(struct C3Control *c, const double *x0, double dt, size_t 
         return reject("c3control_simulate", "the single-trajectory loop has no stop action; use c3control_simulate_batch (c3control_set_stopping)");
     if (c->dp->jumps)
         return reject("c3control_simulate", "the single-trajectory loop draws no jumps; use c3control_simulate_batch (c3control_set_jumps)");
+    if (c->dp->impulses)
+        return reject("c3control_simulate", "the single-trajectory loop has no interventions; use c3control_simulate_batch (c3control_set_impulses)");
     double *b = xcalloc(dx, sizeof(double)), *s = xcalloc(dx * dw, sizeof(double)), *u = xcalloc(du, sizeof(double));
     memcpy(traj, x0, dx * sizeof(double));
     const double sq = sqrt(dt);

@@ -221,6 +221,22 @@ int c3control_get_jumps(const struct C3Control *);
 /* c3control_policy_eval_stop with the backup's value at x as well (the host twin's number: what the first-fiber check compares
  * with the device); stopped and value may be NULL */
 int c3control_policy_eval_value(struct C3Control *, double t, const double *x, double *u, int *stopped, double *value);
+/* new: impulse control.  c3control_add_impulses registers the host form of the device model's impulse for M
+ * interventions (1 <= M <= C3SC_IMPULSE_MAX): fn(x, m, y) writes the post-intervention state y = y_m(x) and returns the cost
+ * k_m(x); a return value that is not finite means "not admissible at x".  c3control_set_impulses(c, 1) makes the Bellman operator
+ * the quasi-variational inequality V = min(min_u backup_u, min_m [k_m + Vt(y_m)]): in the host scan (bellman_optimal, after the
+ * minimiser and the stop comparison's place; the targets are read as the jump targets are, with valuef_eval and the exit costs
+ * beyond absorbing faces and in obstacles; m ascending, the first strict '<'), the first-fiber check and the device context
+ * (which needs a model compiled with c3sc_hip_model_compile_ic, nimpulse = M, and a candidate list).  c3control_step_vi,
+ * c3control_vi_solve and c3control_simulate_batch work in impulse mode (a simulated intervention occupies one step slot:
+ * c3sc_hip.h), and it combines with c3control_set_jumps.  c3control_pi_solve and c3control_fh_solve stop with a message;
+ * c3control_simulate and c3control_integrate(_batch) return an error; the horizon step and the stopping switch are refused
+ * when the device context is set up.  c3control_policy_eval_value returns the value; c3control_policy_eval_impulse reports the
+ * decision at x: *m = the intervention taken, -1 where the policy steers with a control (the control is 0 where it intervenes). */
+void c3control_add_impulses(struct C3Control *, int M, double (*fn)(const double *x, int m, double *y));
+void c3control_set_impulses(struct C3Control *, int on);
+int c3control_get_impulses(const struct C3Control *);
+int c3control_policy_eval_impulse(struct C3Control *, const double *x, int *m);
 struct ValueF *c3control_vi_solve(struct C3Control *, size_t maxiter, double abs_conv_tol, struct ValueF *vo,
                                   struct ApproxArgs *, struct c3Opt *, int verbose, struct Diag **diag); /* :2282-2340 */
 struct ValueF *c3control_pi_solve(struct C3Control *, size_t maxiter, double abs_conv_tol, struct ValueF *policy,

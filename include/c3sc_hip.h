@@ -613,6 +613,47 @@ int c3sc_hip_set_jumps(c3sc_hip_ctx *ctx, int on);
 /* out[0], out[1] = the uniforms (u0, u1) in (0, 1) of step `step` of global trajectory `traj` under `seed` */
 int c3sc_hip_jump_uniforms(uint64_t seed, uint64_t traj, uint64_t step, double *out);
 
+/* Impulse control: besides steering through drift and diffusion the controller may at any state pay k_m(x) and
+ * move the state at once to y_m(x), m = 0 .. M-1, 1 <= M <= C3SC_IMPULSE_MAX.  An impulse model's source defines one more function,
+ *   __device__ double impulse(const double *prm, const double (&x)[C3SC_D], int m, double (&y)[C3SC_D]);  y = y_m(x), returns k_m(x)
+ * which may not depend on the control.  A return value that is not finite means "intervention m is not admissible at x": it
+ * never wins (y is not used then).  The operator is the quasi-variational inequality
+ *     V(x) = min( min_u backup_u(x),  min_m [ k_m(x) + Vt(y_m(x)) ] )
+ * with Vt exactly the Vjump of the jump kernels above: periodic wrap, obscost / boundcost at a target inside an obstacle or
+ * beyond an absorbing face, otherwise the interpolant of c3sc_hip_set_interp clamped to the grid hull.  The interventions are
+ * scanned after the candidates, m ascending, and compared by the rule of every candidate, the first strict '<'; they also win
+ * where the scan left no valid candidate.  Intervention m has the index ncand + 1 + m -- ncand stays the stop action's -- so
+ * uidx is 0 .. ncand-1 or ncand+1 .. ncand+M, and -1 on absorbed nodes.  A forced index ncand + 1 + m applies intervention m and
+ * no candidate; a forced index above ncand + M names nothing and gives 0.0 and -1, as an out-of-range candidate index does.
+ * No status bit is raised.
+ * The impulse kernels exist only in run-time compiled models built with c3sc_hip_model_compile_ic and nimpulse = M > 0: the
+ * impulse forms of the per-wave kernels and of k_rollout for the plain model and, with njump > 0, for the jump model too;
+ * k_rollout_ode has none.  nimpulse = 0 is exactly c3sc_hip_model_compile_jd, and the source need not define impulse then;
+ * nimpulse outside 0..C3SC_IMPULSE_MAX returns C3SC_ERR_ARG, nimpulse > 0 with a game, the box, horizon or stop
+ * C3SC_ERR_UNSUPPORTED.  The source may read C3SC_NIMPULSE. */
+#define C3SC_IMPULSE_MAX 8
+typedef struct c3sc_hip_model_spec_ic {
+    c3sc_hip_model_spec_jd jd;
+    int nimpulse;
+} c3sc_hip_model_spec_ic;
+int c3sc_hip_model_compile_ic(const c3sc_hip_model_spec_ic *spec, int *model_id);
+int c3sc_hip_model_code_object_ic(const c3sc_hip_model_spec_ic *spec, void *buf, size_t *size);
+/* interventions on (on != 0) or off.  C3SC_ERR_UNSUPPORTED for built-in and TABLE models, a model compiled without impulse
+ * kernels (also one set after this call: the launch then refuses), a context in game mode, and while the horizon step or the
+ * stopping switch is set; c3sc_hip_set_game, c3sc_hip_set_horizon_step and c3sc_hip_set_stopping are refused while it is on.
+ * Honoured by bellman_fibers(_all|_host), policy_fibers(_all|_host) (on the fiber-per-wave kernel: AUTO picks it, a forced pair
+ * or quad variant is refused), the value-iteration cross calls that launch through them, and simulate.  Combines with
+ * c3sc_hip_set_jumps; the model must then be compiled with njump > 0 as well.  Refused (C3SC_ERR_UNSUPPORTED): the box and TABLE
+ * calls, cross_iteration_pi and integrate.
+ * c3sc_hip_simulate with interventions on: the time of step s is s dt throughout, so an intervention occupies one step slot.
+ * A live trajectory whose controller returns ncand + 1 + m at step s pays exp(-beta s dt) k_m(xin), xin the state the controller
+ * saw (wrapped under wrap), pays no stage cost and takes no drift, diffusion or Poisson increment in that step, and continues
+ * from x_{s+1} = y_m(xin); its saved control of that step is 0.  The exit test of x_{s+1} is the ordinary one at the top of step
+ * s + 1, and exit_step is as without interventions: they are visible in the saved trajectory.  The continuous-time problem
+ * intervenes in no time, so each intervention delays the clock of its trajectory by dt: an O(dt) error per intervention in the
+ * discounting and in the time left, which vanishes with the step. */
+int c3sc_hip_set_impulses(c3sc_hip_ctx *ctx, int on);
+
 int c3sc_hip_sync(c3sc_hip_ctx *ctx, void *stream);
 int c3sc_hip_get_status(c3sc_hip_ctx *ctx, unsigned *flags, int clear);
 /* name of the kernel the last launch used (for profiles) */

@@ -1,0 +1,250 @@
+"""The numpy restatement of the backup with interventions (tests/impulse_lib.py) checked on its own.  No GPU is needed.
+
+- The vectorised decision equals a per-node Python loop written from the rule's words.
+- The known answer: every target beyond a face of constant cost c and constant k_m give min(continuation, min_m k_m + c)
+  exactly, and the tie k_1 = k_2 goes to mark 1.
+- The targets of the 2-D model are of every kind: interior, beyond the absorbing face, inside the obstacle, across the periodic
+  seam, and one intervention is not admissible on part of the domain.
+- The preconditions of the GPU comparison on the fibers it uses (stencils and flags from the CPU oracle, which reads no
+  model; both dimensions of the ragged 21 x 70 grid, and the 128-node dimension of 5 x 128 x 5): interventions win at between
+  10 % and 90 % of the live nodes, each of them somewhere, and the margin between the best and the second-best action exceeds
+  1e-9 at 99.9 % of the live nodes -- in every compared case.
+- dense_vi of the inventory problem of examples/inventory_impulse.c decreases monotonically from the no-intervention solution and
+  meets a fixed point to 1e-10 within the recorded number of sweeps.
+- Planted faults make these comparisons fail: the obstacle read from the previous sweep's continuation instead of V, the index
+  off by one, '<=' instead of '<'.
+- The noisy rollout restatement (inv_rollouts) reproduces the discretisation gap pinned next to it."""
+import dataclasses
+
+import numpy as np
+import pytest
+
+from c3sc_amd import workloads as wl
+import horizon_lib as H
+import impulse_lib as IL
+import jump_lib as JL
+import oracle_lib
+import stop_lib as SL
+
+
+def _case(model, rank, discount, jumps, k):
+    """stencils and flags from the CPU oracle, which reads no model: the fibers of the GPU comparison"""
+    if model == "lqr":
+        w = IL.lqr_workload(0, rank, discount, IL.lqr_cost_scale(rank), jumps)
+    else:
+        w = IL.lqr3_workload(0, discount=discount)
+    cores = wl.synth_cores(w)
+    idx = wl.synth_fibers(w, k, 257)
+    V, ab = oracle_lib.Problem(w, cores).stencil_fibers(k, idx)
+    bcost, ocost = (lambda x: SL.lqrn_terminal(w.params, x)), (lambda x: np.full(len(x), 5.0))
+    return w, JL.Train(w, cores), idx, V, ab, bcost, ocost
+
+
+def _loop_backup(vals, c):
+    """the rule in words, one node at a time"""
+    P, nc = vals.shape
+    out, idx = np.zeros(P), np.full(P, -1)
+    for p in range(P):
+        best, bi = 0.0, -1
+        for a in range(nc):
+            if not np.isnan(vals[p, a]) and (bi < 0 or vals[p, a] < best):
+                best, bi = vals[p, a], a
+        ival, imark = np.inf, -1
+        for m in range(c.shape[1]):
+            if np.isfinite(c[p, m]) and c[p, m] < ival:
+                ival, imark = c[p, m], m
+        if imark >= 0 and (bi < 0 or ival < best):
+            best, bi = ival, nc + 1 + imark
+        out[p], idx[p] = best, bi
+    return out, idx
+
+
+def test_vectorised_backup_equals_the_loop():
+    rng = np.random.default_rng(5)
+    vals = rng.uniform(0.0, 1.0, size=(400, 7))
+    vals[rng.uniform(size=vals.shape) < 0.2] = np.nan
+    vals[:20] = np.nan  # no valid candidate: an intervention wins, or the value is 0 and the index -1
+    c = rng.uniform(0.0, 1.0, size=(400, 3))
+    c[rng.uniform(size=c.shape) < 0.3] = np.inf
+    c[10:30] = np.inf
+    c[40:60, 1] = c[40:60, 2]  # ties among the interventions
+    c[60:80, 0] = np.nanmin(np.where(np.isnan(vals[60:80]), np.inf, vals[60:80]), axis=1)  # a tie with the scan's winner: the candidate stays
+    out, ui, _ = IL.backup(vals, c)
+    l_out, l_ui = _loop_backup(vals, c)
+    np.testing.assert_array_equal(out, l_out)
+    np.testing.assert_array_equal(ui, l_ui)
+    assert (ui[10:20] == -1).all() and (out[10:20] == 0.0).all()
+    assert (ui[:10] > 7).any()
+    assert (ui[60:80] <= 7 + 3).all() and not (ui[60:80] == 7 + 1).any()
+    # forced: an intervention's index applies it, a candidate's index the candidate, -1 / the stop index / a skipped candidate 0.0
+    forced = rng.integers(-1, 7 + 1 + 3, size=400)
+    f_out, f_ui, _ = IL.backup(vals, c, forced)
+    for p in range(400):
+        f = forced[p]
+        if f > 7:
+            assert f_out[p] == c[p, f - 8] and f_ui[p] == f
+        elif 0 <= f < 7 and not np.isnan(vals[p, f]):
+            assert f_out[p] == vals[p, f] and f_ui[p] == f
+        else:
+            assert f_out[p] == 0.0 and f_ui[p] == -1
+
+
+def _known_case():
+    w = IL.known_workload(0)
+    tr = JL.Train(w, wl.synth_cores(w))
+    idx = wl.synth_fibers(w, 1, 9)
+    N = w.ngrid[1]
+    costs = np.random.default_rng(0).uniform(0.2, 0.7, size=(9, N, 5))
+    ab = np.zeros((9, N), dtype=np.int32)
+    bcost, ocost = (lambda x: np.full(len(x), w.params[4])), (lambda x: np.full(len(x), -1.0))
+    return w, tr, idx, costs, ab, bcost, ocost
+
+
+def test_known_answer():
+    w, tr, idx, costs, ab, bcost, ocost = _known_case()
+    out, ui, _, stat, c = IL.impulse_fibers(w, SL.lqrn_host, IL.known_impulses, tr, 1, idx, costs, ab, bcost, ocost)
+    cont, cu, _, _, _ = IL.impulse_fibers(w, SL.lqrn_host, IL.known_impulses, tr, 1, idx, costs, ab, bcost, ocost, with_impulses=False)
+    np.testing.assert_array_equal(out, np.minimum(cont, IL.KNOWN_TARGET))
+    wins = IL.KNOWN_TARGET < cont
+    assert wins.any() and (~wins).any()
+    assert (ui[wins] == w.ncand + 1 + 1).all(), "k_1 = k_2: the first strict '<' keeps mark 1"
+    np.testing.assert_array_equal(ui[~wins], cu[~wins])
+    assert not stat.any()
+
+
+def test_targets_of_every_kind():
+    w = IL.lqr_workload(0, 4, 0.3, 0.08)
+    xg = w.xgrid()
+    x = np.stack(np.meshgrid(xg[0], xg[1], indexing="ij"), axis=-1).reshape(-1, 2)
+    k, y = IL.lqr_impulses(w.params, x)
+    kinds = np.zeros(4, dtype=bool)
+    for m in range(IL.LQR_NIMPULSE):
+        adm = np.isfinite(k[:, m])
+        _, inobs, beyond, moved = JL.target_kinds(w, y[adm, m])
+        kinds |= np.array([(~inobs & ~beyond & ~moved).any(), (beyond & ~inobs).any(), inobs.any(), moved.any()])
+    assert kinds.all(), ("interior, beyond the absorbing face, inside the obstacle, across the seam", kinds)
+    share = np.isinf(k[:, 2]).mean()
+    assert 0.3 < share < 0.7 and np.isfinite(k[:, :2]).all(), "intervention 2 is not admissible on about half the domain"
+    assert np.isinf(IL.lqr_impulses(IL.lqr_prm(np.inf), x)[0]).all(), "K = inf: no intervention is admissible anywhere"
+    k3, y3 = IL.lqr3_impulses(IL.lqr3_prm(), np.random.default_rng(1).uniform(-2, 2, size=(50, 3)))
+    assert np.isfinite(k3).all() and y3.shape == (50, 2, 3)
+
+
+CASES = [("lqr", r, b, j, k) for r in (4, 8, 12) for b in (0.3, 0.0) for j in (False, True) for k in (0, 1)] + \
+        [("lqr3", 12, b, j, 1) for b in (0.3, 0.0) for j in (False, True)]
+
+
+@pytest.mark.parametrize("model,rank,discount,jumps,k", CASES)
+def test_preconditions_of_the_gpu_comparison(model, rank, discount, jumps, k):
+    w, tr, idx, V, ab, bcost, ocost = _case(model, rank, discount, jumps, k)
+    live = ab == 0
+    assert (ab == 1).any() and (ab == -1).any() and live.any()
+    imp, jmp = (IL.lqr_impulses, JL.lqr_jumps) if model == "lqr" else (IL.lqr3_impulses, JL.lqr3_jumps)
+    out, ui, mg, stat, c = IL.impulse_fibers(w, SL.lqrn_host, imp, tr, k, idx, V, ab, bcost, ocost, jumps=jmp if jumps else None)
+    nc = w.ncand
+    share = (ui[live] > nc).mean()
+    assert 0.10 <= share <= 0.90, share
+    for m in range(c.shape[-1]):
+        assert (ui[live] == nc + 1 + m).any(), m
+    assert not (ui == nc).any(), "the stop action's index is reserved and never reported"
+    assert (mg[live] > 1e-9).mean() >= 0.999, (mg[live] <= 1e-9).mean()
+    assert not stat.any()
+    plain = IL.impulse_fibers(w, SL.lqrn_host, imp, tr, k, idx, V, ab, bcost, ocost, jumps=jmp if jumps else None, with_impulses=False)
+    assert (out <= plain[0]).all() and (out[ui > nc] < plain[0][ui > nc]).all()
+    # ... and K = inf is the operator without interventions, bit for bit
+    winf = dataclasses.replace(w, params=w.params[:4] + (np.inf,) + w.params[5:])
+    inf = IL.impulse_fibers(winf, SL.lqrn_host, imp, tr, k, idx, V, ab, bcost, ocost, jumps=jmp if jumps else None)
+    np.testing.assert_array_equal(inf[0], plain[0])
+    np.testing.assert_array_equal(inf[1], plain[1])
+
+
+# ---------------------------------------------------------------------------------------------------- the inventory problem
+@pytest.fixture(scope="module")
+def inventory():
+    w = IL.inv_workload(0)
+    bc = lambda x: IL.inv_bcost(w.params, x)
+    plain, _ = IL.dense_vi(w, IL.inv_host, IL.inv_impulses, bc, np.zeros(w.ngrid), IL.INV_PLAIN_SWEEPS, with_impulses=False)
+    V, dec = IL.dense_vi(w, IL.inv_host, IL.inv_impulses, bc, plain[-1], IL.INV_SWEEPS)
+    return w, bc, plain, V, dec
+
+
+def test_dense_vi_decreases_to_a_fixed_point(inventory):
+    w, bc, plain, V, dec = inventory
+    assert np.abs(plain[-1] - plain[-2]).max() == 0.0, "the no-intervention solution is converged to the last bit"
+    for s in range(IL.INV_SWEEPS):
+        assert (V[s + 1] <= V[s]).all(), s  # a monotone operator from a super-solution: no tolerance
+    assert np.abs(V[-1] - V[-2]).max() <= 1e-10
+    first = next(s for s in range(IL.INV_SWEEPS) if np.abs(V[s + 1] - V[s]).max() <= 1e-10)
+    print("fixed point to 1e-10 after", first, "sweeps; centre", plain[-1][5, 5], "->", V[-1][5, 5])
+    assert first <= IL.INV_SWEEPS
+    assert V[-1][5, 5] < plain[-1][5, 5] - 0.1, "ordering is worth something at the centre"
+    live = dec[-1] >= 0
+    nc = w.ncand
+    assert 0.10 <= (dec[-1][live] > nc).mean() <= 0.90
+    for m in range(IL.INV_NIMPULSE):
+        assert (dec[-1] == nc + 1 + m).any(), m
+    # the reorder region is the low-stock corner: along the diagonal every node below the boundary orders, none above it
+    diag = np.array([dec[-1][i, i] for i in range(1, IL.INV_N - 1)])
+    orders = diag > nc
+    assert orders[0] and not orders[-1] and (np.diff(orders.astype(int)) <= 0).all()
+
+
+def test_planted_faults_are_seen(inventory):
+    w, bc, plain, V, dec = inventory
+    n = 40
+    stale, _ = IL.dense_vi(w, IL.inv_host, IL.inv_impulses, bc, plain[-1], n, fault="stale")
+    assert np.abs(stale[n] - V[n]).max() > 1e-3, "the obstacle must be read from the current V"
+    _, idec = IL.dense_vi(w, IL.inv_host, IL.inv_impulses, bc, plain[-1], n, fault="index")
+    assert (idec[n - 1] != dec[n - 1]).sum() >= 10, "intervention m has the index ncand + 1 + m"
+    # '<=' for '<': the known model's tie k_1 = k_2 goes to mark 2, and a tie with the scan's winner to the intervention
+    kw, tr, idx, costs, ab, bcost, ocost = _known_case()
+    h2, t = H.mca_constants(kw)
+    x = H.node_states(kw, 1, idx).reshape(-1, 2)
+    zero = np.zeros(len(x))
+    vals, _, _ = JL.candidate_values(SL.lqrn_host, kw.params, x, costs.reshape(-1, 5), np.asarray(kw.cands), h2, t, kw.discount, zero, zero)
+    c = IL.impulse_values(kw, IL.known_impulses, tr, x, bcost, ocost)
+    good, bad = IL.backup(vals, c), IL.backup(vals, c, fault="le")
+    wins = good[1] > kw.ncand
+    assert wins.any() and (good[1][wins] == kw.ncand + 2).all() and (bad[1][wins] == kw.ncand + 3).all()
+    np.testing.assert_array_equal(good[0], bad[0])  # only the index tells: the tests compare indices where the margin is clear
+
+
+def test_replay_of_a_hand_made_rollout():
+    """two steps from one state: a drift step, then intervention 0; the replay charges k_0 at the state the controller saw and
+    moves to y_0 with no stage cost"""
+    w = IL.inv_workload(0)
+    prm = w.params
+    dt, beta = 0.1, IL.INV_BETA
+    x0 = np.array([[0.3, -0.2]])
+    u = np.array([[[1.0, 0.5], [0.0, 0.0]]])
+    x1 = x0 + (u[:, 0] - prm[1]) * dt
+    k, y = IL.inv_impulses(prm, x1)
+    traj = np.stack([x0, x1, y[:, 0]], axis=1)
+    marks = np.array([[-1, 0]])
+    drift = lambda x, uu: IL.inv_host(prm, x, uu)[0]
+    stage = lambda x, uu: IL.inv_host(prm, x, uu)[2]
+    nxt, ex, J = IL.replay(w, IL.inv_impulses, drift, stage, lambda x: IL.inv_bcost(prm, x), lambda x: np.zeros(len(x)), traj, u, marks,
+                           dt, beta)
+    np.testing.assert_array_equal(nxt[:, 0], x1)
+    np.testing.assert_array_equal(nxt[:, 1], y[:, 0])
+    assert ex[0] == -1
+    want = stage(x0, u[:, 0])[0] * dt + np.exp(-beta * dt) * k[0, 0]
+    assert abs(J[0] - want) <= 1e-15
+
+
+def test_rollout_restatement_holds_the_pinned_gap():
+    """the constants next to which the gaps are written: 2^16 paths of the numpy rollouts from the second state (where the policy
+    orders at once) reproduce the pinned gap within 4 standard errors, the policy steers at the first state and orders at the
+    other two, and the allowances of the device test are twice the gaps"""
+    w = IL.inv_workload(0)
+    V, dec = IL.inv_fixed_point(w)
+    xg = w.xgrid()[0]
+    nodes = [tuple(int(np.argmin(np.abs(xg - v))) for v in x0) for x0 in IL.INV_X0]
+    assert dec[nodes[0]] < w.ncand and dec[nodes[1]] > w.ncand and dec[nodes[2]] > w.ncand
+    J, niv = IL.inv_rollouts(w, V, IL.INV_X0[1], 1 << 16, IL.INV_SIM_DT, IL.INV_SIM_STEPS, np.random.default_rng(31))
+    se = J.std() / np.sqrt(len(J))
+    gap = J.mean() - V[nodes[1]]
+    print("restatement: mean", J.mean(), "V", V[nodes[1]], "gap", gap, "se", se, "interventions per path", niv.mean())
+    assert abs(gap - IL.INV_GAP[1]) <= 4 * se + 4 * 0.000807, (gap, se)
+    assert niv.min() >= 1 and 1.5 < niv.mean() < 2.5
+    assert IL.INV_ALLOWANCE == tuple(2 * g for g in IL.INV_GAP)
