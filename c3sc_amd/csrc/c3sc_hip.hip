@@ -353,6 +353,14 @@ static int check_impulse_model(c3sc_hip_ctx *c, const char *what)
     return C3SC_OK;
 }
 
+// correlation is served by the corr kernels of the model set now, never together with a game or interventions
+static int check_corr_model(c3sc_hip_ctx *c, const char *what)
+{
+    if (c->correlation && !(c->model >= C3SC_MODEL_USER && rtc_model_ncorr(c->model) > 0 && c->game_gsz == 0 && !c->impulses))
+        return fail(c, C3SC_ERR_UNSUPPORTED, what);
+    return C3SC_OK;
+}
+
 // game mode is served by the game kernels of the model set now (set_model may have replaced the model set_game checked)
 static int check_game_model(c3sc_hip_ctx *c, const char *what)
 {
@@ -651,7 +659,26 @@ int c3sc_hip_set_impulses(c3sc_hip_ctx *c, int on)
     if (c->game_gsz > 0) return fail(c, C3SC_ERR_UNSUPPORTED, "set_impulses: games with interventions are not offered");
     if (c->hz_dt > 0.0) return fail(c, C3SC_ERR_UNSUPPORTED, "set_impulses: impulse control has no horizon form (c3sc_hip_set_horizon_step(ctx, 0) first)");
     if (c->stopping) return fail(c, C3SC_ERR_UNSUPPORTED, "set_impulses: impulse control has no stop form (c3sc_hip_set_stopping(ctx, 0) first)");
+    if (c->correlation) return fail(c, C3SC_ERR_UNSUPPORTED, "set_impulses: impulse control with correlated noise is not offered (c3sc_hip_set_correlation(ctx, 0) first)");
     c->impulses = 1;
+    return C3SC_OK;
+}
+
+int c3sc_hip_set_correlation(c3sc_hip_ctx *c, int on)
+{
+    if (!c) return C3SC_ERR_ARG;
+    if (!on) {
+        c->correlation = 0;
+        return C3SC_OK;
+    }
+    if (c->model == 0) return fail(c, C3SC_ERR_ARG, "set_correlation: set_model first");
+    if (c->model < C3SC_MODEL_USER || !rtc_model_known(c->model))
+        return fail(c, C3SC_ERR_UNSUPPORTED, "set_correlation: correlated noise needs a run-time compiled model (c3sc_hip_model_compile_cd with ncorr > 0)");
+    if (rtc_model_ncorr(c->model) == 0)
+        return fail(c, C3SC_ERR_UNSUPPORTED, "set_correlation: this model was compiled without corr kernels (c3sc_hip_model_compile_cd, ncorr > 0)");
+    if (c->game_gsz > 0) return fail(c, C3SC_ERR_UNSUPPORTED, "set_correlation: games with correlated noise are not offered");
+    if (c->impulses) return fail(c, C3SC_ERR_UNSUPPORTED, "set_correlation: impulse control with correlated noise is not offered (c3sc_hip_set_impulses(ctx, 0) first)");
+    c->correlation = 1;
     return C3SC_OK;
 }
 
@@ -691,6 +718,7 @@ int c3sc_hip_set_game(c3sc_hip_ctx *c, int du_min, int nu, const double *U, int 
     if (c->stopping) return fail(c, C3SC_ERR_UNSUPPORTED, "set_game: stopping games are not offered (c3sc_hip_set_stopping(ctx, 0) first)");
     if (c->jumps) return fail(c, C3SC_ERR_UNSUPPORTED, "set_game: games with jumps are not offered (c3sc_hip_set_jumps(ctx, 0) first)");
     if (c->impulses) return fail(c, C3SC_ERR_UNSUPPORTED, "set_game: games with interventions are not offered (c3sc_hip_set_impulses(ctx, 0) first)");
+    if (c->correlation) return fail(c, C3SC_ERR_UNSUPPORTED, "set_game: games with correlated noise are not offered (c3sc_hip_set_correlation(ctx, 0) first)");
     int mdu = 0;
     bool has_game = false;
     if (c->model < C3SC_MODEL_USER || !rtc_model_info(c->model, mdu, has_game))
@@ -1226,6 +1254,13 @@ static int launch_bellman(c3sc_hip_ctx *c, int k, size_t F, const int32_t *d_idx
             return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers: interventions run on the fiber-per-wave kernel only (the pair and quad variants have no impulse form)");
         variant = C3SC_VARIANT_FIBER_PER_WAVE;
     }
+    if (c->correlation) { // and with correlation on: the corr form of whichever of the forms above the other switches select
+        rc = check_corr_model(c, "bellman_fibers: correlation needs a model compiled with corr kernels (and no game or interventions)");
+        if (rc != C3SC_OK) return rc;
+        if (variant != C3SC_VARIANT_AUTO && variant != C3SC_VARIANT_FIBER_PER_WAVE)
+            return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers: correlation runs on the fiber-per-wave kernel only (the pair and quad variants have no corr form)");
+        variant = C3SC_VARIANT_FIBER_PER_WAVE;
+    }
     if (F == 0) return C3SC_OK;
     if (!d_idx || !d_out) return fail(c, C3SC_ERR_ARG, "bellman_fibers: null buffer");
     A.forced = d_policy;
@@ -1233,6 +1268,7 @@ static int launch_bellman(c3sc_hip_ctx *c, int k, size_t F, const int32_t *d_idx
     io.stop = c->stopping != 0;
     io.jump = c->jumps != 0;
     io.impulse = c->impulses != 0;
+    io.corr = c->correlation != 0;
     // A launcher declines (nothing launched) when its LDS layout does not fit this grid or it does not serve this call; the
     // next-best instantiation of the same padded rank is tried then (e.g. the duo kernel's two staging buffers hold N <= 25 at
     // rank 16, the one-buffer quad kernel behind it N <= 75, the per-wave kernel behind that only stages the varying core).
@@ -1296,7 +1332,7 @@ static int launch_bellman_all(c3sc_hip_ctx *c, int nk, const int *ks, const size
             if (d_out[q] == d_out[s] && F[s] > 0) return fail(c, C3SC_ERR_ARG, "bellman_fibers_all: two segments share an output array");
     }
     hipStream_t st = (hipStream_t)stream;
-    if (overlap && c->tab3L_off && c->tab3_stale && c->game_gsz == 0 && c->hz_dt <= 0.0 && !c->stopping && !c->jumps && !c->impulses) {
+    if (overlap && c->tab3L_off && c->tab3_stale && c->game_gsz == 0 && c->hz_dt <= 0.0 && !c->stopping && !c->jumps && !c->impulses && !c->correlation) {
         // stale three-core tables: built here, ahead of the fork, if a segment is going to run a three-core kernel -- every
         // side stream is then ordered behind the build by the fork itself
         const long fmin = fiber_partition_min();
@@ -1361,6 +1397,7 @@ static int launch_box(c3sc_hip_ctx *c, int k, size_t F, const int32_t *d_idx, co
     if (c->stopping) return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_box: stopping has no control-box form");
     if (c->jumps) return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_box: jumps have no control-box form");
     if (c->impulses) return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_box: interventions have no control-box form");
+    if (c->correlation) return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_box: correlated noise has no control-box form");
     if (model_ncf(c->model) != 0 && c->model != C3SC_MODEL_COTHRUST6D) // cothrust forms its features from u on the device (models.hpp: CF_FROM_U)
         return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_box: this model needs transcendental functions of the control");
     KArgs A;
@@ -1436,6 +1473,7 @@ static int launch_tables(c3sc_hip_ctx *c, int k, size_t F, const int32_t *d_idx,
     if (c->stopping) return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_tables: the TABLE model has no stop kernels");
     if (c->jumps) return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_tables: the TABLE model has no jump kernels");
     if (c->impulses) return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_tables: the TABLE model has no impulse kernels");
+    if (c->correlation) return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_tables: the TABLE model has no corr kernels");
     c->model = C3SC_MODEL_TABLE; // fill_args only checks that a model is set
     KArgs A;
     int rc = fill_args(c, k, F, A, true);
@@ -1732,6 +1770,8 @@ int c3sc_hip_simulate(c3sc_hip_ctx *c, const c3sc_hip_sim_args *a, void *stream)
         if (check_jump_model(c, "simulate: jumps need a model compiled with jump kernels (and no game)") != C3SC_OK) return C3SC_ERR_UNSUPPORTED;
         if (a->box) return fail(c, C3SC_ERR_UNSUPPORTED, "simulate: jumps have no control-box form");
     }
+    if (c->correlation) // correlated increments and off-grid diagonal targets are not offered
+        return fail(c, C3SC_ERR_UNSUPPORTED, "simulate: rollouts are not offered with correlated noise (c3sc_hip_set_correlation(ctx, 0) first)");
     if (c->impulses) {
         if (check_impulse_model(c, "simulate: interventions need a model compiled with impulse kernels (and no game, horizon or stopping)") != C3SC_OK)
             return C3SC_ERR_UNSUPPORTED;
@@ -1863,6 +1903,7 @@ int c3sc_hip_integrate(c3sc_hip_ctx *c, const c3sc_hip_ode_args *a, void *stream
     if (c->stopping) return fail(c, C3SC_ERR_UNSUPPORTED, "integrate: deterministic closed loops are not offered for stopping problems");
     if (c->jumps) return fail(c, C3SC_ERR_UNSUPPORTED, "integrate: deterministic closed loops are not offered for jump diffusions");
     if (c->impulses) return fail(c, C3SC_ERR_UNSUPPORTED, "integrate: deterministic closed loops are not offered for impulse control");
+    if (c->correlation) return fail(c, C3SC_ERR_UNSUPPORTED, "integrate: deterministic closed loops are not offered with correlated noise");
     KArgs A;
     rc = fill_args(c, 0, 0, A, false);
     if (rc != C3SC_OK) return rc;

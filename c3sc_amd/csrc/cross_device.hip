@@ -1693,6 +1693,8 @@ int c3sc_hip_cross_iteration_pi(c3sc_hip_ctx *c, c3sc_hip_ctx *policy_ctx, long 
         return fail(c, C3SC_ERR_UNSUPPORTED, "cross_iteration_pi: policy iteration is not offered in horizon mode (c3sc_hip_set_horizon_step)");
     if ((c && c->stopping) || policy_ctx->stopping)
         return fail(c, C3SC_ERR_UNSUPPORTED, "cross_iteration_pi: policy iteration is not offered for stopping problems (c3sc_hip_set_stopping)");
+    if (c && c->correlation != policy_ctx->correlation)
+        return fail(c, C3SC_ERR_UNSUPPORTED, "cross_iteration_pi: the two contexts differ in correlation mode (c3sc_hip_set_correlation)");
     if ((c && c->impulses) || policy_ctx->impulses)
         return fail(c, C3SC_ERR_UNSUPPORTED, "cross_iteration_pi: policy iteration is not offered for impulse control (c3sc_hip_set_impulses)");
     if (c && c->jumps != policy_ctx->jumps) // improvement and evaluation must apply one operator

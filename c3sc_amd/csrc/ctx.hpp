@@ -43,6 +43,8 @@ struct c3sc_hip_ctx {
     int jumps = 0;
     // impulse control (c3sc_hip_set_impulses): the launches take the impulse forms of the run-time compiled model's kernels
     int impulses = 0;
+    // correlated noise (c3sc_hip_set_correlation): the launches take the corr forms of the run-time compiled model's per-wave kernels
+    int correlation = 0;
     double *hz_stack = nullptr;
     size_t hz_stack_static = 0;
     int hz_nstack = 0;

@@ -273,6 +273,25 @@ template <class Model, int RP>
 __device__ inline void impulse_term(const KArgs &A, const double *__restrict__ ro, const double (&x)[Model::D], int constelm, bool forced,
                                     int fu, double &ival, int &imark);
 
+// The correlated-noise instantiations are those of a model wrapped in CorrOf, in the style of the wrappers above:
+// k_fiber_per_wave forms the node's cross-diffusion correction (corr_term, kernel_rollout.hpp) and passes model_corr<Model>() to
+// node_backup as CORR.  The model supplies covar and the compile-time pair list NCORR, CORR_I[], CORR_J[].
+// CorrOf<JumpOf<StopOf<HorizonOf<M>>>> is the fullest form; games and impulse control have none.
+template <class M>
+struct CorrOf : M {
+    static constexpr bool CORR = true;
+};
+template <class Model>
+constexpr bool model_corr()
+{
+    if constexpr (requires { Model::CORR; }) return Model::CORR;
+    else return false;
+}
+// defined in kernel_rollout.hpp, beside the point evaluation it is built on; only CORR instantiations call it
+template <class Model, int RP>
+__device__ inline void corr_term(const KArgs &A, const double *__restrict__ ro, const double (&x)[Model::D], const int (&ix)[Model::D],
+                                 const double (&V)[2 * Model::D + 1], int ab, double &cq, double &cpv, unsigned &st);
+
 // Output pointers of one launch (separate __restrict__ kernel parameters).
 struct KOut {
     double *out;       // [F][N]            (bellman kernel)
@@ -781,13 +800,21 @@ __device__ __forceinline__ void impulse_action(int nc, bool forced, int fu, doub
 // dimension, so every scan, the explicit scheme and the forced path see it: dt = h^2 / Q with the jump rate inside Q, the term
 // delta lambda (J - V_self) in horizon mode with the rate in the CFL test, and a node with no drift and no diffusion but
 // lambda > 0 is not stationary.  jrate = 0 leaves every bit: Q0 + 0.0 and fma(0, J, PV0) are exact for finite J.
+//
+// CORR (correlated noise): the cross-diffusion terms of Kushner and Dupuis 5.3 are linear in the rates, so the
+// caller (corr_term) hands over two control-independent numbers: cq = sum_p (-2 r_p), what the pairs take off the axis rates and
+// give to the diagonal neighbours, and cpv = sum_p r_p [(V_d1 + V_d2) - (V[2i] + V[2i+1] + V[2j] + V[2j+1])].  They are added to
+// Q0 and PV0 where the jump term is, so every scan, the explicit scheme with its CFL test and the forced path see the corrected
+// Q.  Q0 may now be small or negative where a paired dimension's axis rates arrive in the candidate loop: all_small, all_tiny and
+// q0ok are then false (each compares against Q0 itself) and the general scan runs.  Zero covariances leave every bit:
+// Q0 + (-0.0) and PV0 + 0.0 are exact.
 template <class Model, int CG = 1, int CGD = 1, class Cand = CandRegs<Model>, bool SPLIT = true, class Pre = NoPre, bool GAME = false,
-          bool HORIZON = false, bool STOP = false, bool JUMP = false, bool IMPULSE = false>
+          bool HORIZON = false, bool STOP = false, bool JUMP = false, bool IMPULSE = false, bool CORR = false>
 __device__ inline double node_backup(const KArgs &A, const double *__restrict__ ro, const double (&x)[Model::D],
                                      const double (&tv)[Model::NTAB > 0 ? Model::NTAB : 1], const Cand &cr,
                                      const double (&V)[2 * Model::D + 1], int ab, int &ui, unsigned &st, bool forced = false,
                                      int fu = -1, const Pre &pre = Pre(), double jrate = 0.0, double jval = 0.0, double ival = 0.0,
-                                     int imark = -1)
+                                     int imark = -1, double cq = 0.0, double cpv = 0.0)
 {
     // forced (wave-uniform) = policy evaluation, bellman_pi (bellman.c:1702-1886): the candidate fu (per lane) is
     // applied instead of the minimiser's; same rates, same bellmanrhs.
@@ -796,6 +823,7 @@ __device__ inline double node_backup(const KArgs &A, const double *__restrict__ 
     static_assert(!(STOP && GAME), "stopping games are not offered");
     static_assert(!(JUMP && GAME), "games with jumps are not offered");
     static_assert(!(IMPULSE && (GAME || HORIZON || STOP)), "impulse control is not offered with games, horizons or stopping");
+    static_assert(!(CORR && (GAME || IMPULSE)), "correlated noise is not offered with games or impulse control");
     const int nc = __builtin_amdgcn_readfirstlane(A.ncand); // keeps the candidate loops' trip test on the scalar unit
     ui = -1;
     // game: which reductions are maxima (wave-uniform), the group length, the forced pair as a list position
@@ -859,6 +887,10 @@ __device__ inline double node_backup(const KArgs &A, const double *__restrict__ 
     if constexpr (JUMP) {
         Q0 += jrate;
         PV0 = fma(jrate, jval, PV0);
+    }
+    if constexpr (CORR) {
+        Q0 += cq;
+        PV0 += cpv;
     }
     double best = 0.0;
     constexpr int NCFa = Model::NCF > 0 ? Model::NCF : 1;

@@ -350,9 +350,13 @@ __global__ void __launch_bounds__(256, (RP >= 20 ? 1 : 2)) // rank 20 is LDS-bou
                     int imark = -1;
                     if constexpr (model_impulse<Model>())
                         impulse_term<Model, RP>(A, ro, x, jump_constelm<Model>(A, ro), forced, fu, ival, imark);
+                    // correlated models: the pairs' correction of Q0 and PV0, two grid nodes per lane and pair, after the marks'
+                    // registers are dead
+                    double cq = 0.0, cpv = 0.0;
+                    if constexpr (model_corr<Model>()) corr_term<Model, RP>(A, ro, x, ix, V, ab, cq, cpv, st);
                     val = node_backup<Model, 1, 1, CandLds<Model>, true, NoPre, model_game<Model>(), model_horizon<Model>(), model_stop<Model>(),
-                                      model_jump<Model>(), model_impulse<Model>()>(A, ro, x, tv, cr, V, ab, ui, st, forced, fu, NoPre(), jrate,
-                                                                                   jval, ival, imark);
+                                      model_jump<Model>(), model_impulse<Model>(), model_corr<Model>()>(
+                        A, ro, x, tv, cr, V, ab, ui, st, forced, fu, NoPre(), jrate, jval, ival, imark, cq, cpv);
                 }
                 if (A.memo_keys) { // wave-uniform: node memo of the device-resident cross iterations
                     int ins = 0, ovf = 0;

@@ -336,6 +336,114 @@ __device__ inline void impulse_term(const KArgs &A, const double *__restrict__ r
     }
 }
 
+// The function train at one GRID NODE per lane: L = G_0[idx_0] G_1[idx_1] ... G_{D-1}[idx_{D-1}], gathered from
+// the padded cores in the arena.  offgrid_value's shape -- rolled row loops, L read by rotation, global loads only -- without
+// offgrid_cell and without weights: one entry per core element and lane where core_at gathers two.  The caller keeps
+// 0 <= idx[m] < A.ngrid[m].
+// node_value_sub is the same at the node idx with the indices of the (wave-uniform) dimensions i and j replaced by ni and nj:
+// the substitution is a select per dimension, so a caller inside a rolled loop (corr_term) builds no index vector -- a vector
+// built there and handed on by reference is left behind as a stack object in three dimensions.
+template <int D, int RP>
+__device__ __forceinline__ double node_value_sub(const KArgs &A, const double *__restrict__ ro, const int (&idx)[D], int i, int ni, int j,
+                                                 int nj)
+{
+    static_assert(D >= 2, "dimension");
+    double L[RP];
+    {
+        const int n0 = (i == 0) ? ni : ((j == 0) ? nj : idx[0]);
+        const double *G = ro + A.core_off[0] + (size_t)n0 * RP;
+#pragma unroll
+        for (int b = 0; b < RP; b++) L[b] = G[b];
+    }
+#pragma unroll
+    for (int m = 1; m < D - 1; m++) {
+        const int nm = (i == m) ? ni : ((j == m) ? nj : idx[m]);
+        const double *G = ro + A.core_off[m] + (size_t)nm * (RP * RP);
+        double Ln[RP];
+#pragma unroll
+        for (int b = 0; b < RP; b++) Ln[b] = 0.0;
+#pragma unroll 1
+        for (int a = 0; a < RP; a++) {
+            const double la = rot_left<RP>(L);
+#pragma unroll
+            for (int b = 0; b < RP; b++) Ln[b] += la * G[a + b * RP];
+        }
+#pragma unroll
+        for (int b = 0; b < RP; b++) L[b] = Ln[b];
+    }
+    const int nl = (i == D - 1) ? ni : ((j == D - 1) ? nj : idx[D - 1]);
+    const double *G = ro + A.core_off[D - 1] + (size_t)nl * RP;
+    double v = 0.0;
+#pragma unroll
+    for (int a = 0; a < RP; a++) v += L[a] * G[a];
+    return v;
+}
+template <int D, int RP>
+__device__ inline double node_value(const KArgs &A, const double *__restrict__ ro, const int (&idx)[D])
+{
+    return node_value_sub<D, RP>(A, ro, idx, -1, 0, -1, 0);
+}
+
+// The cross-diffusion correction of the node x with the multi-index ix (Kushner and Dupuis 5.3).  For each pair
+// p = (i, j) of the model's compile-time list, p ascending, with a_p = covar(x, p) and t_m = A.t[2m]:
+//     r_p = (t_i t_j / h^2) |a_p| / 2        the un-normalised rate to each of two diagonal neighbours,
+// (+,+) and (-,-) where a_p > 0, (+,-) and (-,+) otherwise -- a per-lane select of indices -- and the same r_p off each of the
+// four axis rates of i and j:
+//     cq = sum_p (-2 r_p),   cpv = sum_p r_p [(V_d1 + V_d2) - ((V[2i] + V[2i+1]) + (V[2j] + V[2j+1]))]   (one fma chain from 0.0).
+// A diagonal neighbour is a grid node: in both dimensions its index is fixed_neighbors' lo / hi of ix -- for the varying
+// dimension too -- so a reflecting end names the node itself, the periodic seam n - 2 / 1, and a live node on an absorbing
+// face of a fixed dimension itself.  Its value is the function train's there (node_value_sub): no exit test, no obstacle cost,
+// no interpolation.  Dominance: the axis probability of dimension m stays non-negative iff t2_m sigma_m^2 / 2 >= sum_{p with m}
+// r_p, sigma at the first candidate's control as in node_backup's Q0 block (the diffusion of a paired dimension must not read
+// the control); a live lane that violates it raises C3SC_STATUS_DOMINANCE and keeps the algebra's value.
+// The loop over the pairs is unrolled: the list is a compile-time constant, so i and j are, and everything that belongs to them
+// (node index, size, boundary type, t, the axis values) is read directly.  Rolled, with i and j wave-uniform run-time values
+// picked by selects, the three-dimensional forms were left with a 36-byte stack object of scalar spill slots that no instruction
+// addressed.  The two point evaluations of a pair stay a rolled loop, and the pairs' evaluations are independent of each other
+// only through cpv's chain, so the kernel holds little more than one evaluation's registers (DESIGN.md 4.16 has the counts).
+template <class Model, int RP>
+__device__ inline void corr_term(const KArgs &A, const double *__restrict__ ro, const double (&x)[Model::D], const int (&ix)[Model::D],
+                                 const double (&V)[2 * Model::D + 1], int ab, double &cq, double &cpv, unsigned &st)
+{
+    constexpr int D = Model::D, P = Model::NCORR;
+    static_assert(P >= 1 && P <= C3SC_CORR_MAX, "number of pairs");
+    double used[D];
+#pragma unroll
+    for (int m = 0; m < D; m++) used[m] = 0.0;
+    cq = 0.0;
+    cpv = 0.0;
+#pragma unroll
+    for (int p = 0; p < P; p++) {
+        const int i = Model::CORR_I[p], j = Model::CORR_J[p]; // constants of the unrolled trip
+        const double a = Model::covar(A.prm, x, p);
+        const double r = (A.t[2 * i] * A.t[2 * j] / A.h2) * __builtin_fabs(a) / 2.0;
+        const bool pos = a > 0.0;
+        int li, hi_i, lj, hj;
+        (void)fixed_neighbors(ix[i], A.ngrid[i], A.bctype[i], li, hi_i);
+        (void)fixed_neighbors(ix[j], A.ngrid[j], A.bctype[j], lj, hj);
+        double vd = 0.0;
+#pragma unroll 1
+        for (int e = 0; e < 2; e++) { // e = 0: the neighbour on i's + side, e = 1: on its - side
+            const int ni = e ? li : hi_i, nj = ((e != 0) == pos) ? lj : hj;
+            vd += node_value_sub<D, RP>(A, ro, ix, i, ni, j, nj);
+        }
+        cq += -2.0 * r;
+        cpv = fma(r, vd - ((V[2 * i] + V[2 * i + 1]) + (V[2 * j] + V[2 * j + 1])), cpv);
+        used[i] += r;
+        used[j] += r;
+    }
+    bool viol = false;
+    {
+        double u[Model::DU], s[D];
+#pragma unroll
+        for (int c = 0; c < Model::DU; c++) u[c] = ro[A.cands_off + c];
+        Model::sigma(A.prm, x, u, s);
+#pragma unroll
+        for (int m = 0; m < D; m++) viol |= A.t[2 * m + 1] * (s[m] * s[m]) / 2.0 < used[m];
+    }
+    if (viol & (ab == 0)) st |= C3SC_STATUS_DOMINANCE;
+}
+
 template <int MID, class Model>
 __device__ inline void offgrid_tables(const double (&x)[Model::D], double (&tv)[Model::NTAB > 0 ? Model::NTAB : 1])
 {

@@ -4,7 +4,8 @@
 // user's source wrapped in namespace c3sc_user, which defines (include/c3sc_hip.h states the contract)
 //   drift(prm, x, u, b)  sigma(prm, x, u, s)  stage(prm, x, u)  boundcost(prm, x)  obscost(prm, x)
 // and, for a stopping model, stopcost(prm, x); for a jump-diffusion model, jumprate(prm, x) and
-// jump(prm, x, m, y); for an impulse-control model, impulse(prm, x, m, y)
+// jump(prm, x, m, y); for an impulse-control model, impulse(prm, x, m, y); for a model with correlated noise
+// (DESIGN.md 4.16), covar(prm, x, p)
 // with C3SC_D / C3SC_DU defined.  RtcModel presents them as the Model concept of models.hpp: no tables and no candidate
 // features (the user's code evaluates its own transcendentals with the device libm), an empty Node.  The masks come from the
 // spec; their safe defaults (every dimension depends on u, none is a constant of the candidate, the stage cost reads u) are
@@ -59,6 +60,11 @@ struct RtcModel {
     {
         return ::c3sc_user::impulse(prm, x, m, y);
     }
+#endif
+#ifdef C3SC_RTC_CORR // a spec with ncorr > 0 (c3sc_hip_model_compile_cd): only then must the source define covar
+    static constexpr int NCORR = C3SC_NCORR;
+    static constexpr int CORR_I[C3SC_NCORR] = {C3SC_CORR_I}, CORR_J[C3SC_NCORR] = {C3SC_CORR_J};
+    __device__ static inline double covar(const double *prm, const double (&x)[D], int p) { return ::c3sc_user::covar(prm, x, p); }
 #endif
 };
 

@@ -40,6 +40,7 @@ EXPORTS = [
     "c3sc_hip_model_compile_os", "c3sc_hip_model_code_object_os", "c3sc_hip_set_stopping",
     "c3sc_hip_model_compile_jd", "c3sc_hip_model_code_object_jd", "c3sc_hip_set_jumps", "c3sc_hip_jump_uniforms",
     "c3sc_hip_model_compile_ic", "c3sc_hip_model_code_object_ic", "c3sc_hip_set_impulses",
+    "c3sc_hip_model_compile_cd", "c3sc_hip_model_code_object_cd", "c3sc_hip_set_correlation",
 ]
 
 class SimArgs(C.Structure):
@@ -100,6 +101,16 @@ class ModelSpecIc(C.Structure):
 
 
 IMPULSE_MAX = 8  # C3SC_IMPULSE_MAX: most interventions of an impulse-control model
+
+CORR_MAX = 8  # C3SC_CORR_MAX: most pairs of dimensions with a cross-diffusion term
+
+
+class ModelSpecCd(C.Structure):
+    """struct c3sc_hip_model_spec_cd (include/c3sc_hip.h): the _ic spec plus the pairs of correlated dimensions"""
+    _fields_ = [("ic", ModelSpecIc), ("ncorr", C.c_int), ("corr_dims", C.c_int * (2 * CORR_MAX))]
+
+
+STATUS_STATIONARY, STATUS_CFL, STATUS_DOMINANCE = 1, 2, 4  # C3SC_STATUS_*
 
 
 MODEL_USER = 1000  # C3SC_MODEL_USER: first id of the run-time compiled models
@@ -188,6 +199,9 @@ def load_library():
         L.c3sc_hip_model_compile_ic.argtypes = [C.POINTER(ModelSpecIc), c_int_p]
         L.c3sc_hip_model_code_object_ic.argtypes = [C.POINTER(ModelSpecIc), C.c_void_p, c_size_p]
         L.c3sc_hip_set_impulses.argtypes = [C.c_void_p, C.c_int]
+        L.c3sc_hip_model_compile_cd.argtypes = [C.POINTER(ModelSpecCd), c_int_p]
+        L.c3sc_hip_model_code_object_cd.argtypes = [C.POINTER(ModelSpecCd), C.c_void_p, c_size_p]
+        L.c3sc_hip_set_correlation.argtypes = [C.c_void_p, C.c_int]
         _LIB = L
     return _LIB
 
@@ -211,6 +225,16 @@ def _model_spec(source, d, du, ranks, box, udep_mask, uconst_mask, stage_udep, n
     return spec
 
 
+def _spec_cd(spec, game, horizon, stop, njump, nimpulse, corr_pairs):
+    """the _cd spec over `spec`; the pair list is passed as given (the library validates it), cut at CORR_MAX + 1 pairs' count"""
+    pairs = [(int(i), int(j)) for i, j in corr_pairs]
+    cd = ModelSpecCd(ModelSpecIc(ModelSpecJd(ModelSpecOs(ModelSpecFh(ModelSpecEx(spec, 1 if game else 0), 1 if horizon else 0),
+                                                         1 if stop else 0), int(njump)), int(nimpulse)), len(pairs))
+    for p, (i, j) in enumerate(pairs[:CORR_MAX]):
+        cd.corr_dims[2 * p], cd.corr_dims[2 * p + 1] = i, j
+    return cd
+
+
 def _model_fail(rc, what):
     log = load_library().c3sc_hip_model_log().decode(errors="replace")
     raise C3scHipError(f"{what} failed (code {rc}): {log}", rc)
@@ -218,7 +242,7 @@ def _model_fail(rc, what):
 
 def compile_model(source: str, d: int, du: int, ranks=(4, 8), box: bool = False, udep_mask: int = 0, uconst_mask: int = 0,
                   stage_udep: bool = True, name: Optional[str] = None, game: bool = False, horizon: bool = False,
-                  stop: bool = False, njump: int = 0, nimpulse: int = 0) -> int:
+                  stop: bool = False, njump: int = 0, nimpulse: int = 0, corr_pairs=()) -> int:
     """Compile a device model from source (c3sc_hip_model_compile, include/c3sc_hip.h states the source contract) and return
     its model id (>= MODEL_USER), usable wherever a built-in model id is.  No GPU is needed.  Raises C3scHipError with the
     compiler's log on failure; the error code is args[1].  game=True (c3sc_hip_model_compile_ex) adds the game kernels that
@@ -227,11 +251,16 @@ def compile_model(source: str, d: int, du: int, ranks=(4, 8), box: bool = False,
     (c3sc_hip_model_compile_os) adds the stop kernels that BellmanEngine.set_stopping needs: the source then defines stopcost.
     njump=M > 0 (c3sc_hip_model_compile_jd) adds the jump kernels that BellmanEngine.set_jumps needs: the source then defines
     jumprate and jump for M marks.  nimpulse=M > 0 (c3sc_hip_model_compile_ic) adds the impulse kernels that
-    BellmanEngine.set_impulses needs: the source then defines impulse for M interventions."""
+    BellmanEngine.set_impulses needs: the source then defines impulse for M interventions.  corr_pairs=[(i, j), ...]
+    (c3sc_hip_model_compile_cd) adds the corr kernels that BellmanEngine.set_correlation needs: the source then defines covar for
+    these pairs of dimensions, i < j."""
     L = load_library()
     spec = _model_spec(source, d, du, tuple(ranks), box, udep_mask, uconst_mask, stage_udep, name)
     mid = C.c_int(0)
-    if nimpulse:
+    if len(corr_pairs):
+        cd = _spec_cd(spec, game, horizon, stop, njump, nimpulse, corr_pairs)
+        rc = L.c3sc_hip_model_compile_cd(C.byref(cd), C.byref(mid))
+    elif nimpulse:
         ic = ModelSpecIc(ModelSpecJd(ModelSpecOs(ModelSpecFh(ModelSpecEx(spec, 1 if game else 0), 1 if horizon else 0), 1 if stop else 0),
                                      int(njump)), int(nimpulse))
         rc = L.c3sc_hip_model_compile_ic(C.byref(ic), C.byref(mid))
@@ -256,18 +285,21 @@ def compile_model(source: str, d: int, du: int, ranks=(4, 8), box: bool = False,
 
 def code_object(source: str, d: int, du: int, ranks=(4, 8), box: bool = False, udep_mask: int = 0, uconst_mask: int = 0,
                 stage_udep: bool = True, name: Optional[str] = None, game: bool = False, horizon: bool = False,
-                stop: bool = False, njump: int = 0, nimpulse: int = 0) -> bytes:
+                stop: bool = False, njump: int = 0, nimpulse: int = 0, corr_pairs=()) -> bytes:
     """The gfx950 code object of this spec (c3sc_hip_model_code_object): the loaded one if compile_model already compiled the
     spec, otherwise what compile_model would build now (its id and default name are in the kernel names), compiled and not
     registered.  game, horizon, stop, njump and nimpulse select the spec as in compile_model (stop: c3sc_hip_model_code_object_os,
-    njump: c3sc_hip_model_code_object_jd, nimpulse: c3sc_hip_model_code_object_ic)."""
+    njump: c3sc_hip_model_code_object_jd, nimpulse: c3sc_hip_model_code_object_ic, corr_pairs: c3sc_hip_model_code_object_cd)."""
     L = load_library()
     spec = _model_spec(source, d, du, tuple(ranks), box, udep_mask, uconst_mask, stage_udep, name)
     cap = 16 << 20  # one compile when the code object fits; a larger one is compiled again into a buffer of its size
     for _ in range(2):
         buf = C.create_string_buffer(cap)
         size = C.c_size_t(cap)
-        if nimpulse:
+        if len(corr_pairs):
+            cd = _spec_cd(spec, game, horizon, stop, njump, nimpulse, corr_pairs)
+            rc = L.c3sc_hip_model_code_object_cd(C.byref(cd), buf, C.byref(size))
+        elif nimpulse:
             ic = ModelSpecIc(ModelSpecJd(ModelSpecOs(ModelSpecFh(ModelSpecEx(spec, 1 if game else 0), 1 if horizon else 0),
                                                      1 if stop else 0), int(njump)), int(nimpulse))
             rc = L.c3sc_hip_model_code_object_ic(C.byref(ic), buf, C.byref(size))
@@ -360,6 +392,7 @@ class BellmanEngine:
         self.stopping = False
         self.jumps = False
         self.impulses = False
+        self.correlation = False
 
     def close(self):
         if getattr(self, "h", None):
@@ -442,6 +475,14 @@ class BellmanEngine:
         horizon / stop as well to combine it with set_horizon_step / set_stopping."""
         self._chk(self.L.c3sc_hip_set_jumps(self.h, C.c_int(1 if on else 0)), "set_jumps")
         self.jumps = bool(on)
+
+    def set_correlation(self, on: bool = True):
+        """Correlated noise (c3sc_hip_set_correlation): the Bellman calls add the cross-diffusion terms of the model's pairs, two
+        diagonal neighbours per pair, to the backup; status() may then carry STATUS_DOMINANCE.  The model must be compiled with
+        corr_pairs, and with horizon / stop / njump as well to combine it with those switches.  simulate and integrate are
+        refused while it is on."""
+        self._chk(self.L.c3sc_hip_set_correlation(self.h, C.c_int(1 if on else 0)), "set_correlation")
+        self.correlation = bool(on)
 
     def set_impulses(self, on: bool = True):
         """Impulse control (c3sc_hip_set_impulses): the Bellman calls compare the candidates' result with the best intervention

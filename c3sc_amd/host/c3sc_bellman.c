@@ -390,6 +390,12 @@ struct DPparam {
     int nimpulse;
     double (*impulse)(const double *, int, double *);
     int impulses;
+    /* correlated noise (c3control_add_covariance / c3control_set_correlation): P pairs (i_p, j_p), covar(x, p) =
+     * (sigma sigma^T)_{i_p j_p}(x) -- the host form of the device model's covar -- and the switch */
+    int ncorr;
+    size_t corr_i[C3SC_CORR_MAX], corr_j[C3SC_CORR_MAX];
+    double (*covar)(const double *, int);
+    int correlation;
 };
 
 struct DPparam *dp_param_create(size_t dx, size_t du, size_t dw, double discount)
@@ -432,6 +438,10 @@ struct ControlParams {
     struct ValueF *vf;
     double jrate, jval;
     int impulse_last; /* bellman_optimal in impulse mode: the intervention the last node's decision took, -1: none */
+    /* correlation mode: the current node's correction of Q and PV (corr_term of the kernels), formed by bellman_optimal for
+     * bellman_control, and whether the node violates dominance */
+    double cq, cpv;
+    int dominance_last;
 };
 
 struct ControlParams *control_params_create(size_t dx, size_t dw, struct DPparam *dp, struct MCAparam *mca,
@@ -451,9 +461,9 @@ struct Memory { void *shared; size_t private; }; /* bellman.c:59-63 */
  * assemble_rates un-normalised, Q = sum p_i, PV = sum p_i V_i, and g delta + e^{-beta delta} (V_self + (delta / h^2) (PV - Q V_self)).
  * No division: Q = 0 is a legal "stay" candidate */
 static double horizon_rhs(size_t dx, double h2, const double *tv, double delta, double beta, const double *drift, const double *diff,
-                          double stage, const double *costs, double jrate, double jval)
+                          double stage, const double *costs, double q0, double pv0)
 {
-    double Q = jrate, PV = jrate * jval; /* jump mode: one more transition (0 otherwise) */
+    double Q = q0, PV = pv0; /* the control-independent terms: the jump transition and the pairs' correction (0 otherwise) */
     for (size_t m = 0; m < dx; m++) {
         const double t = tv[2 * m], t2 = tv[2 * m + 1], s = diff[m * dx + m];
         const double half = t2 * (s * s) / 2.0, tb = t * drift[m];
@@ -491,15 +501,17 @@ double bellman_control(size_t du, const double *u, double *grad_u, void *args)
         res = diff_eval(dp->diff, p->time, x, u, diff, NULL); assert(res == 0);
         res = dp->stagecost(p->time, x, u, &stage, NULL); assert(res == 0);
         (void)res;
-        return horizon_rhs(dx, p->mca->h2, p->mca->t, dp->hz_dt, dp->discount, drift, diff, stage, costs, p->jrate, p->jval);
+        return horizon_rhs(dx, p->mca->h2, p->mca->t, dp->hz_dt, dp->discount, drift, diff, stage, costs, p->jrate + p->cq,
+                           p->jrate * p->jval + p->cpv);
     }
-    if (dp->jumps) { /* node_backup's JUMP form: the upwind rates un-normalised, the jump rate inside Q, dt = h^2 / Q */
-        if (grad_u != NULL) DIE("bellman_control: jump mode has no gradient (control-box) form");
+    if (dp->jumps || dp->correlation) { /* node_backup's JUMP and CORR forms: the upwind rates un-normalised, the jump rate and the
+                                         * pairs' correction inside Q, dt = h^2 / Q */
+        if (grad_u != NULL) DIE("bellman_control: jump and correlation mode have no gradient (control-box) form");
         res = drift_eval(dp->drift, p->time, x, u, drift, NULL); assert(res == 0);
         res = diff_eval(dp->diff, p->time, x, u, diff, NULL); assert(res == 0);
         res = dp->stagecost(p->time, x, u, &stage, NULL); assert(res == 0);
         (void)res;
-        double Q = p->jrate, PV = p->jrate * p->jval;
+        double Q = p->jrate + p->cq, PV = p->jrate * p->jval + p->cpv;
         for (size_t m = 0; m < dx; m++) {
             const double t = p->mca->t[2 * m], t2 = p->mca->t[2 * m + 1], s = diff[m * dx + m];
             const double half = t2 * (s * s) / 2.0, tb = t * drift[m];
@@ -583,6 +595,76 @@ static void jump_term_host(struct ControlParams *p, const double *x)
     p->jval = J;
 }
 
+/* the coordinates one grid spacing below and above xm in dimension m, by the per-dimension rule of mca_get_neighbor_node_costs:
+ * clamped to the face on absorbing and reflecting dimensions, wrapped on periodic ones.  At a grid node these are the nodes of
+ * the device's index rule (fixed_neighbors) with one exception: ON an absorbing face this rule clamps the outer side only, the
+ * device names the node itself on both sides.  A node there is absorbed -- it pays its boundary cost and no backup runs --
+ * except under the literal end-point rule, where the end nodes of a periodic or reflecting fiber on an absorbing face of a fixed
+ * dimension stay live (quirk Q3): at those nodes the twin and the device read different diagonal neighbours, as their axis
+ * stencils already differ there (mca_get_neighbor_node_costs against process_fibers_neighbor) */
+static void neighbor_coords(const struct ControlParams *p, size_t m, double xm, double *lo, double *hi)
+{
+    const double *g = p->mca->xgrid[m];
+    const double lb = g[0], ub = g[p->mca->ngrid[m] - 1], h = g[1] - g[0];
+    *lo = xm - h;
+    *hi = xm + h;
+    if (((xm + h) < ub) && (xm - h > lb)) return;
+    if ((xm - h) <= lb) {
+        const enum EBTYPE b = boundary_type_dim(p->dp->bound, m, 0);
+        *lo = (b == PERIODIC) ? ((xm > lb) ? ub - (h - (xm - lb)) : (ub - (lb - xm)) - h) : lb;
+    } else {
+        const enum EBTYPE b = boundary_type_dim(p->dp->bound, m, 1);
+        *hi = (b == PERIODIC) ? ((xm < ub) ? lb + (h - (ub - xm)) : (lb + (xm - ub)) + h) : ub;
+    }
+}
+
+/* correlation mode (corr_term of the kernels): for each pair p = (i, j), p ascending, r_p = (t_i t_j / h^2)
+ * |a_p| / 2 to each of the two diagonal targets x +- h_i e_i +- h_j e_j -- (+,+) and (-,-) where a_p > 0, (+,-) and (-,+)
+ * otherwise -- read with valuef_eval, and off each of the four axis rates: cq = sum (-2 r_p), cpv = sum r_p [(V_d1 + V_d2) -
+ * (axis values of i and j)].  At a grid node off the absorbing faces the targets are the nodes the device's index rule names
+ * (neighbor_coords states the exception).  Dominance: t2_m sigma_m^2
+ * / 2 >= sum_{p with m} r_p, sigma at the first candidate */
+static void corr_term_host(struct ControlParams *p, size_t node)
+{
+    struct DPparam *dp = p->dp;
+    const size_t dx = p->dx;
+    const double *x = p->x + node * dx, *costs = workspace_get_costs(p->work, node), *t = p->mca->t;
+    if (p->vf == NULL) DIE("bellman_optimal: correlation mode needs the value function the diagonal neighbours are read from");
+    if (!c3opt_is_bruteforce(p->opt)) DIE("bellman_optimal: correlation mode needs a candidate list");
+    double y[C3SC_MAX_DIM], used[C3SC_MAX_DIM], cq = 0.0, cpv = 0.0;
+    for (size_t m = 0; m < dx; m++) used[m] = 0.0;
+    for (int q = 0; q < dp->ncorr; q++) {
+        const size_t i = dp->corr_i[q], j = dp->corr_j[q];
+        const double a = dp->covar(x, q);
+        const double r = (t[2 * i] * t[2 * j] / p->mca->h2) * fabs(a) / 2.0;
+        double loi, hii, loj, hij;
+        neighbor_coords(p, i, x[i], &loi, &hii);
+        neighbor_coords(p, j, x[j], &loj, &hij);
+        memcpy(y, x, dx * sizeof(double));
+        y[i] = hii;
+        y[j] = a > 0.0 ? hij : loj;
+        double vd = valuef_eval(p->vf, y);
+        y[i] = loi;
+        y[j] = a > 0.0 ? loj : hij;
+        vd += valuef_eval(p->vf, y);
+        cq += -2.0 * r;
+        cpv += r * (vd - ((costs[2 * i] + costs[2 * i + 1]) + (costs[2 * j] + costs[2 * j + 1])));
+        used[i] += r;
+        used[j] += r;
+    }
+    p->cq = cq;
+    p->cpv = cpv;
+    double *diff = workspace_get_diff(p->work, node);
+    int res = diff_eval(dp->diff, p->time, x, c3opt_get_brute_vals(p->opt), diff, NULL);
+    assert(res == 0);
+    (void)res;
+    p->dominance_last = 0;
+    for (size_t m = 0; m < dx; m++) {
+        const double s = diff[m * dx + m];
+        if (t[2 * m + 1] * (s * s) / 2.0 < used[m]) p->dominance_last = 1;
+    }
+}
+
 int bellman_optimal(size_t du, double *u, double *val, void *arg)
 { /* bellman.c:504-543 (BRUTEFORCE) and the box branch of :545-1118: single node on the host (c3control_controller) */
     struct Memory *mem = arg;
@@ -596,6 +678,9 @@ int bellman_optimal(size_t du, double *u, double *val, void *arg)
     }
     p->jrate = p->jval = 0.0;
     if (p->dp->jumps) jump_term_host(p, p->x + mem->private * p->dx);
+    p->cq = p->cpv = 0.0;
+    p->dominance_last = 0;
+    if (p->dp->correlation) corr_term_host(p, mem->private);
     struct c3Opt *opt = c3opt_copy(p->opt);
     c3opt_add_objective(opt, &bellman_control, mem);
     c3opt_minimize(opt, u, val); /* BRUTEFORCE: list scan; otherwise the box minimiser (grid + golden section) */
@@ -719,6 +804,10 @@ static struct c3sc_hip_ctx *sync_device_ctx(struct ControlParams *cp, struct c3s
         DIE("bellman_vi: interventions need a device model compiled with impulse kernels (c3sc_hip_model_compile_ic), a plain candidate "
             "list, and neither the horizon step nor the stopping switch");
     sig = fnv(sig, &dp->impulses, sizeof(int));
+    if (dp->correlation && (!brute || gorder >= 0 || dp->model == 0 || dp->impulses))
+        DIE("bellman_vi: correlation needs a device model compiled with corr kernels (c3sc_hip_model_compile_cd), a plain candidate list "
+            "and no interventions");
+    sig = fnv(sig, &dp->correlation, sizeof(int));
     if (brute) sig = fnv(sig, c3opt_get_brute_vals(cp->opt), c3opt_get_nbrute(cp->opt) * odu * sizeof(double));
     else {
         const size_t g = c3opt_get_box_grid(cp->opt), pl = c3opt_get_box_polish(cp->opt);
@@ -737,6 +826,7 @@ static struct c3sc_hip_ctx *sync_device_ctx(struct ControlParams *cp, struct c3s
         hipok(ctx, c3sc_hip_set_stopping(ctx, 0), "c3sc_hip_set_stopping");
         hipok(ctx, c3sc_hip_set_jumps(ctx, 0), "c3sc_hip_set_jumps"); /* likewise a context left in jump mode */
         hipok(ctx, c3sc_hip_set_impulses(ctx, 0), "c3sc_hip_set_impulses"); /* ... or in impulse mode, which refuses the horizon step too */
+        hipok(ctx, c3sc_hip_set_correlation(ctx, 0), "c3sc_hip_set_correlation"); /* ... or in correlation mode, which refuses set_game */
         if (dp->model != 0) hipok(ctx, c3sc_hip_set_model(ctx, dp->model, dp->prm, dp->nprm), "c3sc_hip_set_model");
         if (brute && gorder >= 0)
             hipok(ctx, c3sc_hip_set_game(ctx, (int)gdu_min, (int)gnu, gU, (int)gnw, gW, gorder), "c3sc_hip_set_game");
@@ -749,6 +839,7 @@ static struct c3sc_hip_ctx *sync_device_ctx(struct ControlParams *cp, struct c3s
         hipok(ctx, c3sc_hip_set_stopping(ctx, dp->stopping), "c3sc_hip_set_stopping");
         hipok(ctx, c3sc_hip_set_jumps(ctx, dp->jumps), "c3sc_hip_set_jumps");
         hipok(ctx, c3sc_hip_set_impulses(ctx, dp->impulses), "c3sc_hip_set_impulses");
+        hipok(ctx, c3sc_hip_set_correlation(ctx, dp->correlation), "c3sc_hip_set_correlation");
         g_ctx[sl].cfg_set = 1;
         g_ctx[sl].cfg_sig = sig;
         g_ctx[sl].version = 0; /* set_grid invalidates the resident value function */
@@ -863,6 +954,17 @@ static double now_s(void) { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &
  * device flag.  The public per-fiber entry points read it after every call; the index-based batch entry points of the
  * solver loops read it once per sweep (c3control_end_vi / end_pi_step) -- a status read is a device round trip. */
 static unsigned g_status_seen; /* every status bit the reads below cleared (c3control_fh_solve looks for C3SC_STATUS_CFL) */
+/* C3SC_STATUS_DOMINANCE seen since the caller cleared g_status_seen: the solver loops stop with this message, as c3control_fh_solve
+ * does on C3SC_STATUS_CFL */
+static int dominance_seen(const char *who, size_t step)
+{
+    if (!(g_status_seen & C3SC_STATUS_DOMINANCE)) return 0;
+    fprintf(stderr, "%s: step %zu raised C3SC_STATUS_DOMINANCE (the pairs of c3control_add_covariance take more off an axis rate than "
+                    "its diffusion supplies: negative transition probability); choose the grid ratios inside the dominance condition\n",
+            who, step);
+    return 1;
+}
+
 static void die_if_stationary(struct c3sc_hip_ctx *ctx)
 {
     unsigned st = 0;
@@ -1389,10 +1491,32 @@ void c3control_add_impulses(struct C3Control *c, int M, double (*fn)(const doubl
 void c3control_set_impulses(struct C3Control *c, int on)
 {
     if (on && c->dp->impulse == NULL) DIE("c3control_set_impulses: c3control_add_impulses first");
+    if (on && c->dp->correlation) DIE("c3control_set_impulses: impulse control with correlated noise is not offered (c3control_set_correlation(c, 0) first)");
     c->dp->impulses = on ? 1 : 0;
     c->dp->model_checked = 0; /* the first-fiber check runs again, against the operator now in force */
 }
 int c3control_get_impulses(const struct C3Control *c) { return c->dp->impulses; }
+void c3control_add_covariance(struct C3Control *c, size_t P, const size_t *dims, double (*covar)(const double *, int))
+{
+    if (P < 1 || P > C3SC_CORR_MAX || dims == NULL || covar == NULL) DIE("c3control_add_covariance: 1 <= P <= C3SC_CORR_MAX pairs, their dimensions and the callback are needed");
+    for (size_t p = 0; p < P; p++) {
+        if (!(dims[2 * p] < dims[2 * p + 1] && dims[2 * p + 1] < c->dx)) DIE("c3control_add_covariance: pair %zu needs i < j < dx", p);
+        for (size_t q = 0; q < p; q++)
+            if (dims[2 * q] == dims[2 * p] && dims[2 * q + 1] == dims[2 * p + 1]) DIE("c3control_add_covariance: pair %zu is listed twice", p);
+        c->dp->corr_i[p] = dims[2 * p];
+        c->dp->corr_j[p] = dims[2 * p + 1];
+    }
+    c->dp->ncorr = (int)P;
+    c->dp->covar = covar;
+}
+void c3control_set_correlation(struct C3Control *c, int on)
+{
+    if (on && c->dp->covar == NULL) DIE("c3control_set_correlation: c3control_add_covariance first");
+    if (on && c->dp->impulses) DIE("c3control_set_correlation: impulse control with correlated noise is not offered (c3control_set_impulses(c, 0) first)");
+    c->dp->correlation = on ? 1 : 0;
+    c->dp->model_checked = 0; /* the first-fiber check runs again, against the operator now in force */
+}
+int c3control_get_correlation(const struct C3Control *c) { return c->dp->correlation; }
 void c3control_set_device_model(struct C3Control *c, int model, const double *params, size_t n) { dp_param_set_device_model(c->dp, model, params, n); }
 
 void c3control_set_consistent_ends(struct C3Control *c, int on)
@@ -1701,7 +1825,13 @@ struct ValueF *c3control_vi_solve(struct C3Control *c, size_t maxiter, double ab
     for (size_t ii = 0; ii < maxiter; ii++) {
         if (ii % 1000 == 0) workspace_reset_vi_htable(c->work); /* precaution against memory growth (2296-2298) */
         size_t nevals = 0;
+        g_status_seen = 0;
         struct ValueF *next = c3control_step_vi(c, start, apargs, opt, verbose - 1, &nevals);
+        if (dominance_seen("c3control_vi_solve", ii)) {
+            valuef_destroy(next);
+            valuef_destroy(start);
+            return NULL;
+        }
         const double diff = valuef_norm2diff(start, next), norm = valuef_norm(next), frac = (double)nevals / stot;
         if (verbose > 0) report("Value Iteration", ii, maxiter, diff, norm, frac);
         if (diag != NULL) diag_append(diag, ii, 1, norm, diff, c->dx, valuef_get_ranks(next), frac);
@@ -1733,9 +1863,13 @@ struct ValueF **c3control_fh_solve(struct C3Control *c, size_t nstages, double d
     for (size_t s = nstages; s-- > 0;) {
         g_status_seen = 0;
         V[s] = c3control_step_vi(c, V[s + 1], apargs, opt, verbose - 1, NULL);
-        if (g_status_seen & C3SC_STATUS_CFL) {
+        int failed = dominance_seen("c3control_fh_solve", s);
+        if (!failed && (g_status_seen & C3SC_STATUS_CFL)) {
             fprintf(stderr, "c3control_fh_solve: stage %zu raised C3SC_STATUS_CFL (a candidate with Q delta > h^2: negative self-loop "
                             "probability); reduce delta\n", s);
+            failed = 1;
+        }
+        if (failed) {
             for (size_t i = s; i <= nstages; i++) valuef_destroy(V[i]);
             free(V);
             return NULL;
@@ -1758,7 +1892,14 @@ struct ValueF *c3control_pi_solve(struct C3Control *c, size_t maxiter, double ab
     for (size_t m = 0; m < c->dx; m++) stot *= (double)c->ngrid[m];
     for (size_t ii = 0; ii < maxiter; ii++) {
         size_t nevals = 0;
+        g_status_seen = 0;
         struct ValueF *next = c3control_step_pi(c, start, poli, apargs, opt, verbose - 1, &nevals);
+        if (dominance_seen("c3control_pi_solve", ii)) {
+            valuef_destroy(next);
+            valuef_destroy(start);
+            pi_param_destroy(poli);
+            return NULL;
+        }
         const double diff = valuef_norm2diff(start, next), norm = valuef_norm(next), frac = (double)nevals / stot;
         if (verbose > 0) report("POLICY ITERATION", ii, maxiter, diff, norm, frac);
         if (diag != NULL) diag_append(diag, ii, 0, norm, diff, c->dx, valuef_get_ranks(next), frac);
@@ -1844,6 +1985,9 @@ int c3control_policy_eval_value(struct C3Control *c, double t, const double *x, 
     if (stopped != NULL) *stopped = cp->stopped_last;
     if (value != NULL) *value = val;
     c->impulse_last = cp->impulse_last;
+    if (cp->dominance_last) /* the host twin's own dominance test: the value is the algebra's, as on the device */
+        fprintf(stderr, "c3control_policy_eval_value: the state violates the dominance condition (C3SC_STATUS_DOMINANCE on the device: "
+                        "the pairs of c3control_add_covariance take more off an axis rate than its diffusion supplies)\n");
     control_params_destroy(cp);
     return 0;
 }
@@ -1918,6 +2062,7 @@ int c3control_simulate_batch(struct C3Control *c, size_t ntraj, const double *x0
     int rc = batch_policy_check(who, c, wrap_periodic);
     if (rc != 0) return rc;
     if (c->dw != c->dx) return reject(who, "the device models have dw = dx (diagonal diffusion)");
+    if (c->dp->correlation) return reject(who, "rollouts are not offered with correlated noise: they need correlated increments (c3control_set_correlation)");
     if (ntraj == 0) return 0;
     if (x0 == NULL) return reject(who, "null x0");
     if (!(dt > 0.0) || !isfinite(dt)) return reject(who, "dt must be positive and finite");
@@ -1989,6 +2134,7 @@ int c3control_integrate(struct C3Control *c, const char *method, double dt_int, 
     if (c->dp->stopping) return reject(who, "deterministic closed loops are not offered for stopping problems (c3control_set_stopping)");
     if (c->dp->jumps) return reject(who, "deterministic closed loops are not offered for jump diffusions (c3control_set_jumps)");
     if (c->dp->impulses) return reject(who, "deterministic closed loops are not offered for impulse control (c3control_set_impulses)");
+    if (c->dp->correlation) return reject(who, "deterministic closed loops are not offered with correlated noise (c3control_set_correlation)");
     if (c->policy_sim == NULL || c->opt_sim == NULL) return reject(who, "no implicit policy (c3control_add_policy_sim)");
     if (c->dp->drift == NULL || c->dp->stagecost == NULL || c->dp->boundcost == NULL || c->dp->obscost == NULL)
         return reject(who, "the host callbacks (drift, stagecost, boundcost, obscost) are needed");
@@ -2073,6 +2219,7 @@ int c3control_integrate_batch(struct C3Control *c, size_t ntraj, const double *x
     if (c->dp->stopping) return reject(who, "deterministic closed loops are not offered for stopping problems (c3control_set_stopping)");
     if (c->dp->jumps) return reject(who, "deterministic closed loops are not offered for jump diffusions (c3control_set_jumps)");
     if (c->dp->impulses) return reject(who, "deterministic closed loops are not offered for impulse control (c3control_set_impulses)");
+    if (c->dp->correlation) return reject(who, "deterministic closed loops are not offered with correlated noise (c3control_set_correlation)");
     size_t nsub;
     rc = integrate_check(who, c->dx, method, dt_int, dt_out, nout, goal, keep, &nsub);
     if (rc != 0) return rc;
@@ -2124,6 +2271,8 @@ int c3control_simulate(struct C3Control *c, const double *x0, double dt, size_t 
         return reject("c3control_simulate", "the single-trajectory loop draws no jumps; use c3control_simulate_batch (c3control_set_jumps)");
     if (c->dp->impulses)
         return reject("c3control_simulate", "the single-trajectory loop has no interventions; use c3control_simulate_batch (c3control_set_impulses)");
+    if (c->dp->correlation)
+        return reject("c3control_simulate", "rollouts are not offered with correlated noise: they need correlated increments (c3control_set_correlation)");
     double *b = xcalloc(dx, sizeof(double)), *s = xcalloc(dx * dw, sizeof(double)), *u = xcalloc(du, sizeof(double));
     memcpy(traj, x0, dx * sizeof(double));
     const double sq = sqrt(dt);

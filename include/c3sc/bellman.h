@@ -237,6 +237,26 @@ void c3control_add_impulses(struct C3Control *, int M, double (*fn)(const double
 void c3control_set_impulses(struct C3Control *, int on);
 int c3control_get_impulses(const struct C3Control *);
 int c3control_policy_eval_impulse(struct C3Control *, const double *x, int *m);
+/* new: correlated noise.  c3control_add_covariance registers P pairs of dimensions, dims = {i_0, j_0, i_1, j_1,
+ * ...} with i_p < j_p < dx, no pair twice, 1 <= P <= C3SC_CORR_MAX, and the host form of the device model's covar:
+ * covar(x, p) = (sigma sigma^T)_{i_p j_p}(x), which reads no control; the diffusion of a paired dimension must not read the
+ * control either.  c3control_set_correlation(c, 1) adds the cross-diffusion terms of Kushner and Dupuis 5.3 to the Bellman
+ * operator: per pair the rate r_p = (h^2 / (h_i h_j)) |a_p| / 2 to two diagonal neighbours and off each of the four axis rates,
+ * i.e. Q += sum (-2 r_p) and PV += sum r_p [(V_d1 + V_d2) - (axis values of i and j)] -- in the host scan (bellman_optimal, which
+ * reads the diagonal targets x +- h_i e_i +- h_j e_j with valuef_eval, each coordinate clamped to an absorbing or reflecting
+ * face and wrapped across a periodic one as mca_get_neighbor_node_costs does, so c3control_policy_eval_value works off the
+ * grid, where it also writes a message to stderr if the state violates the dominance condition below; at a grid node off the
+ * absorbing faces these targets are the nodes the device reads, ON an absorbing face the device reads the node itself on both
+ * sides), the first-fiber check and the device context (which needs a model compiled with c3sc_hip_model_compile_cd and the same
+ * pairs, and a candidate list).  c3control_step_vi, c3control_vi_solve, with the horizon step c3control_fh_solve, and
+ * c3control_pi_solve work in correlation mode, and it combines with c3control_set_stopping and c3control_set_jumps, not with
+ * c3control_set_impulses or a game.  A node whose pairs take more off an axis rate than its diffusion supplies raises
+ * C3SC_STATUS_DOMINANCE on the device; the solver loops then stop with a message and return NULL, as c3control_fh_solve does on
+ * C3SC_STATUS_CFL.  c3control_simulate, c3control_simulate_batch and c3control_integrate(_batch) return an error in correlation
+ * mode: a correlated rollout needs correlated increments. */
+void c3control_add_covariance(struct C3Control *, size_t P, const size_t *dims, double (*covar)(const double *x, int p));
+void c3control_set_correlation(struct C3Control *, int on);
+int c3control_get_correlation(const struct C3Control *);
 struct ValueF *c3control_vi_solve(struct C3Control *, size_t maxiter, double abs_conv_tol, struct ValueF *vo,
                                   struct ApproxArgs *, struct c3Opt *, int verbose, struct Diag **diag); /* :2282-2340 */
 struct ValueF *c3control_pi_solve(struct C3Control *, size_t maxiter, double abs_conv_tol, struct ValueF *policy,

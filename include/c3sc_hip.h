@@ -70,8 +70,11 @@ enum {
 enum {
     C3SC_STATUS_STATIONARY = 1u, /* transition_assemble would have returned 1 (Q < 1e-14, nodeutil.c:365);
                                    the reference asserts (bellman.c:452); the candidate is skipped here */
-    C3SC_STATUS_CFL = 2u         /* horizon mode (c3sc_hip_set_horizon_step): a candidate with Q delta > h^2, i.e. a negative
+    C3SC_STATUS_CFL = 2u,        /* horizon mode (c3sc_hip_set_horizon_step): a candidate with Q delta > h^2, i.e. a negative
                                    self-loop probability 1 - Q delta / h^2; it still took part in the scan */
+    C3SC_STATUS_DOMINANCE = 4u   /* correlation mode (c3sc_hip_set_correlation): a live node where the pairs take more off an axis
+                                   rate than its diffusion supplies (a negative transition probability); the backup still returned
+                                   the algebra's value */
 };
 
 /* kernel variants (c3sc_hip_set_variant); 0 lets the library choose.  Set the variant BEFORE uploading the value: the padded
@@ -653,6 +656,50 @@ int c3sc_hip_model_code_object_ic(const c3sc_hip_model_spec_ic *spec, void *buf,
  * intervenes in no time, so each intervention delays the clock of its trajectory by dt: an O(dt) error per intervention in the
  * discounting and in the time left, which vanishes with the step. */
 int c3sc_hip_set_impulses(c3sc_hip_ctx *ctx, int on);
+
+/* Correlated noise: diffusions whose covariance sigma sigma^T has off-diagonal entries, after Kushner and Dupuis,
+ * section 5.3.  A model declares P unordered pairs (i_p, j_p), i_p < j_p < d, no pair twice, 1 <= P <= C3SC_CORR_MAX, in
+ * corr_dims = {i_0, j_0, i_1, j_1, ...}, and its source defines one more function,
+ *   __device__ double covar(const double *prm, const double (&x)[C3SC_D], int p);     a_p(x) = (sigma sigma^T)_{i_p j_p}(x)
+ * which does not read the control.  Contract: the diffusion of a paired dimension must not read the control either (sigma's
+ * entries of i_p and j_p are taken at the first candidate for the dominance test below).  The source may read C3SC_NCORR, and
+ * C3SC_CORR_I / C3SC_CORR_J, the comma-separated dimension lists.
+ * With t_m = h^2 / h_m, for each pair in ascending p:
+ *     r_p = (t_i t_j / h^2) |a_p| / 2
+ * is the un-normalised rate to each of two diagonal neighbours -- (+,+) and (-,-) where a_p > 0, (+,-) and (-,+) where
+ * a_p < 0 -- and the same r_p is taken off each of the four axis rates of i and j.  All of it is linear in the rates:
+ *     Q0 += sum_p (-2 r_p),   PV0 += sum_p r_p [(V_d1 + V_d2) - ((V[2i] + V[2i+1]) + (V[2j] + V[2j+1]))]   (one fma chain from 0.0)
+ * and everything downstream is the backup of the other switches: dt = h^2 / Q with the corrected Q, the explicit scheme and its
+ * CFL test in horizon mode, the forced (policy) path; the stationary test is unchanged.  a_p = 0 leaves every bit of the backup
+ * without the term.
+ * A diagonal neighbour is a grid node and pays the function train's value there.  In each of the two dimensions its index is
+ * the axis stencil's for a fixed dimension -- of the fiber's varying dimension too: i - 1 / i + 1; at a reflecting end the node
+ * itself; across the periodic seam n - 2 / 1; on an absorbing face the node itself.  No exit test, no obstacle cost and no
+ * interpolation: the bits do not depend on c3sc_hip_set_interp.
+ * Dominance: the transition probabilities along dimension m are non-negative iff t2_m sigma_m^2 / 2 >= sum_{p with m} r_p
+ * (t2_m = h^2 / h_m^2).  A live node that violates it raises C3SC_STATUS_DOMINANCE; the backup still returns the algebra's value,
+ * as with C3SC_STATUS_CFL.
+ * The corr kernels exist only in run-time compiled models built with c3sc_hip_model_compile_cd and ncorr = P > 0: the corr forms
+ * of the per-wave kernels that the other flags select (plain, horizon, stop, njump and their combinations) at every requested
+ * rank; k_rollout and k_rollout_ode have none.  ncorr = 0 is exactly c3sc_hip_model_compile_ic, and the source need not define
+ * covar then.  C3SC_ERR_ARG: ncorr outside 0..C3SC_CORR_MAX, a dimension out of range, i >= j, a repeated pair;
+ * C3SC_ERR_UNSUPPORTED: ncorr > 0 with a game, the box or nimpulse > 0. */
+#define C3SC_CORR_MAX 8
+typedef struct c3sc_hip_model_spec_cd {
+    c3sc_hip_model_spec_ic ic;
+    int ncorr;
+    int corr_dims[2 * C3SC_CORR_MAX];
+} c3sc_hip_model_spec_cd;
+int c3sc_hip_model_compile_cd(const c3sc_hip_model_spec_cd *spec, int *model_id);
+int c3sc_hip_model_code_object_cd(const c3sc_hip_model_spec_cd *spec, void *buf, size_t *size);
+/* correlation on (on != 0) or off.  C3SC_ERR_UNSUPPORTED for built-in and TABLE models, a model compiled without corr kernels
+ * (also one set after this call: the launch then refuses) and a context in game or impulse mode; c3sc_hip_set_game and
+ * c3sc_hip_set_impulses are refused while it is on.  Honoured by bellman_fibers(_all|_host), policy_fibers(_all|_host) (on the
+ * fiber-per-wave kernel: AUTO picks it, a forced pair or quad variant is refused) and the cross calls that launch through them.
+ * Combines with the horizon step, the stopping switch and c3sc_hip_set_jumps; the model must then be compiled with those flags
+ * as well.  Refused (C3SC_ERR_UNSUPPORTED): the box and TABLE calls, simulate and integrate -- a correlated rollout needs
+ * correlated increments and off-grid diagonal targets, which are not offered. */
+int c3sc_hip_set_correlation(c3sc_hip_ctx *ctx, int on);
 
 int c3sc_hip_sync(c3sc_hip_ctx *ctx, void *stream);
 int c3sc_hip_get_status(c3sc_hip_ctx *ctx, unsigned *flags, int clear);
