@@ -319,55 +319,70 @@ static unsigned long long g_tab3_launches = 0; // ... of which fiber-pair launch
 static unsigned long long g_launches = 0; // Bellman / stencil kernel launches of this process (c3sc_hip_launch_count)
 static int fill_args(c3sc_hip_ctx *c, int k, size_t F, KArgs &A, bool need_model);
 
-// horizon mode is served by the horizon kernels of the model set now (set_model may have replaced the model set_horizon_step
-// checked), and never together with a game
-static int check_horizon_model(c3sc_hip_ctx *c, const char *what)
+// One row per feature of the Bellman backup (kernel_common.hpp: FORM_*), in the order refusals are reported: what differs between
+// the features in the messages below.  Which features combine is form_offered's to say
+struct FormRow {
+    unsigned bit;
+    const char *kind;     // its kernels and forms: "stop kernels", "no stop form"
+    const char *subject;  // the feature as the subject of a sentence ...
+    bool plural;          // ... which takes "need" or "needs"
+    const char *problems; // deterministic closed loops are not offered ...
+    const char *compile;  // the entry point that compiles its kernels ...
+    const char *field;    // ... and what its spec asks for them with
+    const char *off;      // the call that switches the feature off
+};
+static const FormRow FORM_ROWS[] = {
+    {FORM_GAME, "game", "game mode", false, "for games", "c3sc_hip_model_compile_ex", "game = 1", "c3sc_hip_set_game with nu = 0"},
+    {FORM_HORIZON, "horizon", "horizon mode", false, "in horizon mode", "c3sc_hip_model_compile_fh", "horizon = 1", "c3sc_hip_set_horizon_step(ctx, 0)"},
+    {FORM_STOP, "stop", "stopping", false, "for stopping problems", "c3sc_hip_model_compile_os", "stop = 1", "c3sc_hip_set_stopping(ctx, 0)"},
+    {FORM_JUMP, "jump", "jumps", true, "for jump diffusions", "c3sc_hip_model_compile_jd", "njump > 0", "c3sc_hip_set_jumps(ctx, 0)"},
+    {FORM_IMPULSE, "impulse", "interventions", true, "for impulse control", "c3sc_hip_model_compile_ic", "nimpulse > 0", "c3sc_hip_set_impulses(ctx, 0)"},
+    {FORM_CORR, "corr", "correlated noise", false, "with correlated noise", "c3sc_hip_model_compile_cd", "ncorr > 0", "c3sc_hip_set_correlation(ctx, 0)"},
+};
+
+static const FormRow &form_row(unsigned bit) { return FORM_ROWS[__builtin_ctz(bit)]; } // the rows are in the order of the bits
+
+static int fails(c3sc_hip_ctx *c, int code, const std::string &msg) { return fail(c, code, msg.c_str()); }
+static std::string verb(const FormRow &r, const char *singular, const char *plural) { return std::string(r.subject) + " " + (r.plural ? plural : singular); }
+static int no_box_form(c3sc_hip_ctx *c, const char *who, const FormRow &r)
 {
-    if (c->hz_dt > 0.0 && !(c->model >= C3SC_MODEL_USER && rtc_model_horizon(c->model) && c->game_gsz == 0))
-        return fail(c, C3SC_ERR_UNSUPPORTED, what);
+    return fails(c, C3SC_ERR_UNSUPPORTED, std::string(who) + ": " + verb(r, "has", "have") + " no control-box form");
+}
+
+// The features among `bits` that are on are served by the model set now (set_model may have replaced the one their setters
+// checked): a run-time compiled model with their kernels, for a game of the game's du.  The first that is not is reported
+static int check_form_model(c3sc_hip_ctx *c, const char *who, unsigned bits = FORM_ALL)
+{
+    const unsigned want = ctx_form(c) & bits, have = c->model >= C3SC_MODEL_USER ? rtc_model_forms(c->model) : 0u;
+    if (want && !form_offered(ctx_form(c))) return fails(c, C3SC_ERR_UNSUPPORTED, std::string(who) + ": this combination of modes is not offered");
+    for (const FormRow &r : FORM_ROWS) {
+        if (!(want & r.bit)) continue;
+        int du = 0;
+        const bool game_du = r.bit != FORM_GAME || (rtc_model_info(c->model, du) && du == c->du);
+        if (!(have & r.bit) || !game_du)
+            return fails(c, C3SC_ERR_UNSUPPORTED, std::string(who) + ": " + verb(r, "needs", "need") + " a model compiled with " + r.kind + " kernels" +
+                                                      (r.bit == FORM_GAME ? " of the game's du" : "") + " (" + r.compile + ", " + r.field + ")");
+    }
     return C3SC_OK;
 }
 
-// stopping is served by the stop kernels of the model set now (set_model may have replaced the model set_stopping checked), and
-// never together with a game
-static int check_stop_model(c3sc_hip_ctx *c, const char *what)
+// Switching the feature of row r on (c3sc_hip_set_game, _set_horizon_step and the four switches): the model must have its
+// kernels, and no feature that is on may exclude it
+static int check_switch_model(c3sc_hip_ctx *c, const FormRow &r, const char *who)
 {
-    if (c->stopping && !(c->model >= C3SC_MODEL_USER && rtc_model_stop(c->model) && c->game_gsz == 0))
-        return fail(c, C3SC_ERR_UNSUPPORTED, what);
+    if (c->model == 0) return fails(c, C3SC_ERR_ARG, std::string(who) + ": set_model first");
+    if (c->model < C3SC_MODEL_USER || !rtc_model_known(c->model))
+        return fails(c, C3SC_ERR_UNSUPPORTED, std::string(who) + ": " + verb(r, "needs", "need") + " a run-time compiled model (" + r.compile + " with " + r.field + ")");
+    if (!(rtc_model_forms(c->model) & r.bit))
+        return fails(c, C3SC_ERR_UNSUPPORTED, std::string(who) + ": this model was compiled without " + r.kind + " kernels (" + r.compile + ", " + r.field + ")");
     return C3SC_OK;
 }
 
-// jumps are served by the jump kernels of the model set now, never together with a game
-static int check_jump_model(c3sc_hip_ctx *c, const char *what)
+static int check_switch_conflicts(c3sc_hip_ctx *c, const FormRow &r, const char *who)
 {
-    if (c->jumps && !(c->model >= C3SC_MODEL_USER && rtc_model_njump(c->model) > 0 && c->game_gsz == 0))
-        return fail(c, C3SC_ERR_UNSUPPORTED, what);
-    return C3SC_OK;
-}
-
-// interventions are served by the impulse kernels of the model set now, never together with a game, a horizon or stopping
-static int check_impulse_model(c3sc_hip_ctx *c, const char *what)
-{
-    if (c->impulses && !(c->model >= C3SC_MODEL_USER && rtc_model_nimpulse(c->model) > 0 && c->game_gsz == 0 && c->hz_dt <= 0.0 && !c->stopping))
-        return fail(c, C3SC_ERR_UNSUPPORTED, what);
-    return C3SC_OK;
-}
-
-// correlation is served by the corr kernels of the model set now, never together with a game or interventions
-static int check_corr_model(c3sc_hip_ctx *c, const char *what)
-{
-    if (c->correlation && !(c->model >= C3SC_MODEL_USER && rtc_model_ncorr(c->model) > 0 && c->game_gsz == 0 && !c->impulses))
-        return fail(c, C3SC_ERR_UNSUPPORTED, what);
-    return C3SC_OK;
-}
-
-// game mode is served by the game kernels of the model set now (set_model may have replaced the model set_game checked)
-static int check_game_model(c3sc_hip_ctx *c, const char *what)
-{
-    int du = 0;
-    bool game = false;
-    if (c->game_gsz > 0 && !(c->model >= C3SC_MODEL_USER && rtc_model_info(c->model, du, game) && game && du == c->du))
-        return fail(c, C3SC_ERR_UNSUPPORTED, what);
+    for (const FormRow &o : FORM_ROWS)
+        if ((ctx_form(c) & o.bit) && !form_offered(r.bit | o.bit))
+            return fails(c, C3SC_ERR_UNSUPPORTED, std::string(who) + ": " + r.subject + " and " + o.subject + " are not offered together (" + o.off + " first)");
     return C3SC_OK;
 }
 
@@ -597,90 +612,33 @@ int c3sc_hip_set_horizon_step(c3sc_hip_ctx *c, double dt)
     }
     if (!(dt > 0.0) || !std::isfinite(dt)) return fail(c, C3SC_ERR_ARG, "set_horizon_step: dt must be positive and finite (0 clears)");
     if (!c->have_mca) return fail(c, C3SC_ERR_ARG, "set_horizon_step: set_mca first");
-    if (c->model == 0) return fail(c, C3SC_ERR_ARG, "set_horizon_step: set_model first");
-    if (c->model < C3SC_MODEL_USER || !rtc_model_known(c->model))
-        return fail(c, C3SC_ERR_UNSUPPORTED, "set_horizon_step: horizon mode needs a run-time compiled model (c3sc_hip_model_compile_fh with horizon = 1)");
-    if (!rtc_model_horizon(c->model))
-        return fail(c, C3SC_ERR_UNSUPPORTED, "set_horizon_step: this model was compiled without horizon kernels (c3sc_hip_model_compile_fh, horizon = 1)");
-    if (c->game_gsz > 0) return fail(c, C3SC_ERR_UNSUPPORTED, "set_horizon_step: games have no horizon form");
-    if (c->impulses) return fail(c, C3SC_ERR_UNSUPPORTED, "set_horizon_step: impulse control has no horizon form (c3sc_hip_set_impulses(ctx, 0) first)");
+    int rc = check_switch_model(c, form_row(FORM_HORIZON), "set_horizon_step");
+    if (rc == C3SC_OK) rc = check_switch_conflicts(c, form_row(FORM_HORIZON), "set_horizon_step");
+    if (rc != C3SC_OK) return rc;
     c->hz_dt = dt;
     c->static_dirty = true;
     return C3SC_OK;
 }
 
-int c3sc_hip_set_stopping(c3sc_hip_ctx *c, int on)
+// the four switches that carry no data: one bit of c->switches each
+static int set_switch(c3sc_hip_ctx *c, unsigned bit, const char *who, int on)
 {
     if (!c) return C3SC_ERR_ARG;
     if (!on) {
-        c->stopping = 0;
+        c->switches &= ~bit;
         return C3SC_OK;
     }
-    if (c->model == 0) return fail(c, C3SC_ERR_ARG, "set_stopping: set_model first");
-    if (c->model < C3SC_MODEL_USER || !rtc_model_known(c->model))
-        return fail(c, C3SC_ERR_UNSUPPORTED, "set_stopping: stopping needs a run-time compiled model (c3sc_hip_model_compile_os with stop = 1)");
-    if (!rtc_model_stop(c->model))
-        return fail(c, C3SC_ERR_UNSUPPORTED, "set_stopping: this model was compiled without stop kernels (c3sc_hip_model_compile_os, stop = 1)");
-    if (c->game_gsz > 0) return fail(c, C3SC_ERR_UNSUPPORTED, "set_stopping: stopping games are not offered");
-    if (c->impulses) return fail(c, C3SC_ERR_UNSUPPORTED, "set_stopping: impulse control has no stop form (c3sc_hip_set_impulses(ctx, 0) first)");
-    c->stopping = 1;
+    int rc = check_switch_model(c, form_row(bit), who);
+    if (rc == C3SC_OK) rc = check_switch_conflicts(c, form_row(bit), who);
+    if (rc != C3SC_OK) return rc;
+    c->switches |= bit;
     return C3SC_OK;
 }
 
-int c3sc_hip_set_jumps(c3sc_hip_ctx *c, int on)
-{
-    if (!c) return C3SC_ERR_ARG;
-    if (!on) {
-        c->jumps = 0;
-        return C3SC_OK;
-    }
-    if (c->model == 0) return fail(c, C3SC_ERR_ARG, "set_jumps: set_model first");
-    if (c->model < C3SC_MODEL_USER || !rtc_model_known(c->model))
-        return fail(c, C3SC_ERR_UNSUPPORTED, "set_jumps: jumps need a run-time compiled model (c3sc_hip_model_compile_jd with njump > 0)");
-    if (rtc_model_njump(c->model) == 0)
-        return fail(c, C3SC_ERR_UNSUPPORTED, "set_jumps: this model was compiled without jump kernels (c3sc_hip_model_compile_jd, njump > 0)");
-    if (c->game_gsz > 0) return fail(c, C3SC_ERR_UNSUPPORTED, "set_jumps: games with jumps are not offered");
-    c->jumps = 1;
-    return C3SC_OK;
-}
-
-int c3sc_hip_set_impulses(c3sc_hip_ctx *c, int on)
-{
-    if (!c) return C3SC_ERR_ARG;
-    if (!on) {
-        c->impulses = 0;
-        return C3SC_OK;
-    }
-    if (c->model == 0) return fail(c, C3SC_ERR_ARG, "set_impulses: set_model first");
-    if (c->model < C3SC_MODEL_USER || !rtc_model_known(c->model))
-        return fail(c, C3SC_ERR_UNSUPPORTED, "set_impulses: interventions need a run-time compiled model (c3sc_hip_model_compile_ic with nimpulse > 0)");
-    if (rtc_model_nimpulse(c->model) == 0)
-        return fail(c, C3SC_ERR_UNSUPPORTED, "set_impulses: this model was compiled without impulse kernels (c3sc_hip_model_compile_ic, nimpulse > 0)");
-    if (c->game_gsz > 0) return fail(c, C3SC_ERR_UNSUPPORTED, "set_impulses: games with interventions are not offered");
-    if (c->hz_dt > 0.0) return fail(c, C3SC_ERR_UNSUPPORTED, "set_impulses: impulse control has no horizon form (c3sc_hip_set_horizon_step(ctx, 0) first)");
-    if (c->stopping) return fail(c, C3SC_ERR_UNSUPPORTED, "set_impulses: impulse control has no stop form (c3sc_hip_set_stopping(ctx, 0) first)");
-    if (c->correlation) return fail(c, C3SC_ERR_UNSUPPORTED, "set_impulses: impulse control with correlated noise is not offered (c3sc_hip_set_correlation(ctx, 0) first)");
-    c->impulses = 1;
-    return C3SC_OK;
-}
-
-int c3sc_hip_set_correlation(c3sc_hip_ctx *c, int on)
-{
-    if (!c) return C3SC_ERR_ARG;
-    if (!on) {
-        c->correlation = 0;
-        return C3SC_OK;
-    }
-    if (c->model == 0) return fail(c, C3SC_ERR_ARG, "set_correlation: set_model first");
-    if (c->model < C3SC_MODEL_USER || !rtc_model_known(c->model))
-        return fail(c, C3SC_ERR_UNSUPPORTED, "set_correlation: correlated noise needs a run-time compiled model (c3sc_hip_model_compile_cd with ncorr > 0)");
-    if (rtc_model_ncorr(c->model) == 0)
-        return fail(c, C3SC_ERR_UNSUPPORTED, "set_correlation: this model was compiled without corr kernels (c3sc_hip_model_compile_cd, ncorr > 0)");
-    if (c->game_gsz > 0) return fail(c, C3SC_ERR_UNSUPPORTED, "set_correlation: games with correlated noise are not offered");
-    if (c->impulses) return fail(c, C3SC_ERR_UNSUPPORTED, "set_correlation: impulse control with correlated noise is not offered (c3sc_hip_set_impulses(ctx, 0) first)");
-    c->correlation = 1;
-    return C3SC_OK;
-}
+int c3sc_hip_set_stopping(c3sc_hip_ctx *c, int on) { return set_switch(c, FORM_STOP, "set_stopping", on); }
+int c3sc_hip_set_jumps(c3sc_hip_ctx *c, int on) { return set_switch(c, FORM_JUMP, "set_jumps", on); }
+int c3sc_hip_set_impulses(c3sc_hip_ctx *c, int on) { return set_switch(c, FORM_IMPULSE, "set_impulses", on); }
+int c3sc_hip_set_correlation(c3sc_hip_ctx *c, int on) { return set_switch(c, FORM_CORR, "set_correlation", on); }
 
 int c3sc_hip_set_model(c3sc_hip_ctx *c, int model, const double *params, int nparams)
 {
@@ -714,16 +672,11 @@ int c3sc_hip_set_game(c3sc_hip_ctx *c, int du_min, int nu, const double *U, int 
     if (order != C3SC_GAME_MINMAX && order != C3SC_GAME_MAXMIN) return fail(c, C3SC_ERR_ARG, "set_game: order must be C3SC_GAME_MINMAX or C3SC_GAME_MAXMIN");
     if (c->model == 0) return fail(c, C3SC_ERR_ARG, "set_game: set_model first");
     if (c->model == C3SC_MODEL_TABLE) return fail(c, C3SC_ERR_UNSUPPORTED, "set_game: the TABLE model has no game kernels");
-    if (c->hz_dt > 0.0) return fail(c, C3SC_ERR_UNSUPPORTED, "set_game: games have no horizon form (c3sc_hip_set_horizon_step(ctx, 0) first)");
-    if (c->stopping) return fail(c, C3SC_ERR_UNSUPPORTED, "set_game: stopping games are not offered (c3sc_hip_set_stopping(ctx, 0) first)");
-    if (c->jumps) return fail(c, C3SC_ERR_UNSUPPORTED, "set_game: games with jumps are not offered (c3sc_hip_set_jumps(ctx, 0) first)");
-    if (c->impulses) return fail(c, C3SC_ERR_UNSUPPORTED, "set_game: games with interventions are not offered (c3sc_hip_set_impulses(ctx, 0) first)");
-    if (c->correlation) return fail(c, C3SC_ERR_UNSUPPORTED, "set_game: games with correlated noise are not offered (c3sc_hip_set_correlation(ctx, 0) first)");
+    int rc = check_switch_conflicts(c, form_row(FORM_GAME), "set_game");
+    if (rc == C3SC_OK) rc = check_switch_model(c, form_row(FORM_GAME), "set_game");
+    if (rc != C3SC_OK) return rc;
     int mdu = 0;
-    bool has_game = false;
-    if (c->model < C3SC_MODEL_USER || !rtc_model_info(c->model, mdu, has_game))
-        return fail(c, C3SC_ERR_UNSUPPORTED, "set_game: games need a run-time compiled model (c3sc_hip_model_compile_ex with game = 1)");
-    if (!has_game) return fail(c, C3SC_ERR_UNSUPPORTED, "set_game: this model was compiled without game kernels (c3sc_hip_model_compile_ex, game = 1)");
+    rtc_model_info(c->model, mdu);
     if (nu < 0 || nw < 1 || du_min < 1 || du_min >= mdu || !U || !W)
         return fail(c, C3SC_ERR_ARG, "set_game: du_min + du_max must equal the model's du, each at least 1, with nu, nw >= 1 and both lists given");
     if ((long long)nu * nw > (1ll << 24)) return fail(c, C3SC_ERR_ARG, "set_game: nu * nw too large");
@@ -1093,12 +1046,20 @@ static void arm_memo(c3sc_hip_ctx *c, const KernelEntry *e, KArgs &A)
 
 // the one launch of a call served by a single kernel entry: counted (c3sc_hip_launch_count), the cached status word dropped; with
 // `unsupported`, a launcher that does not serve the call (hipErrorNotSupported) is reported as C3SC_ERR_UNSUPPORTED with that text
+// every launch through a context carries its switches: a run-time compiled model's kernels of that form run (rtc_launch; the
+// compiled-in kernels and the model-independent stencil kernels have no forms)
+static hipError_t ctx_launch(const c3sc_hip_ctx *c, const KernelEntry &e, const KArgs &A, LaunchIO io)
+{
+    io.form = c->switches;
+    return launch_entry(e, A, io);
+}
+
 static int launch_one(c3sc_hip_ctx *c, const KernelEntry *e, const KArgs &A, const LaunchIO &io, const char *unsupported = nullptr)
 {
     c->last_kernel = e->name;
     g_launches++;
     c->status_cache_valid = false;
-    const hipError_t he = launch_entry(*e, A, io);
+    const hipError_t he = ctx_launch(c, *e, A, io);
     if (he == hipErrorNotSupported && unsupported) return fail(c, C3SC_ERR_UNSUPPORTED, unsupported);
     HIPCHK(c, he);
     return C3SC_OK;
@@ -1219,56 +1180,19 @@ static int launch_bellman(c3sc_hip_ctx *c, int k, size_t F, const int32_t *d_idx
     int rc = fill_args(c, k, F, A, true);
     if (rc != C3SC_OK) return rc;
     int variant = c->variant;
-    if (c->game_gsz > 0) { // only the per-wave kernel has a game form (AUTO picks it)
-        rc = check_game_model(c, "bellman_fibers: game mode needs a model compiled with game kernels of the game's du");
+    for (const FormRow &r : FORM_ROWS) { // a feature that is on: only the per-wave kernel has its form (AUTO picks it)
+        if (!(ctx_form(c) & r.bit)) continue;
+        rc = check_form_model(c, "bellman_fibers", r.bit);
         if (rc != C3SC_OK) return rc;
         if (variant != C3SC_VARIANT_AUTO && variant != C3SC_VARIANT_FIBER_PER_WAVE)
-            return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers: game mode runs on the fiber-per-wave kernel only (the pair and quad variants have no game form)");
-        variant = C3SC_VARIANT_FIBER_PER_WAVE;
-    }
-    if (c->hz_dt > 0.0) { // likewise in horizon mode
-        rc = check_horizon_model(c, "bellman_fibers: horizon mode needs a model compiled with horizon kernels (and no game)");
-        if (rc != C3SC_OK) return rc;
-        if (variant != C3SC_VARIANT_AUTO && variant != C3SC_VARIANT_FIBER_PER_WAVE)
-            return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers: horizon mode runs on the fiber-per-wave kernel only (the pair and quad variants have no horizon form)");
-        variant = C3SC_VARIANT_FIBER_PER_WAVE;
-    }
-    if (c->stopping) { // and with stopping on: the combined form when the horizon step is set as well
-        rc = check_stop_model(c, "bellman_fibers: stopping needs a model compiled with stop kernels (and no game)");
-        if (rc != C3SC_OK) return rc;
-        if (variant != C3SC_VARIANT_AUTO && variant != C3SC_VARIANT_FIBER_PER_WAVE)
-            return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers: stopping runs on the fiber-per-wave kernel only (the pair and quad variants have no stop form)");
-        variant = C3SC_VARIANT_FIBER_PER_WAVE;
-    }
-    if (c->jumps) { // and with jumps on: the jump form of whichever of the forms above the other switches select
-        rc = check_jump_model(c, "bellman_fibers: jumps need a model compiled with jump kernels (and no game)");
-        if (rc != C3SC_OK) return rc;
-        if (variant != C3SC_VARIANT_AUTO && variant != C3SC_VARIANT_FIBER_PER_WAVE)
-            return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers: jumps run on the fiber-per-wave kernel only (the pair and quad variants have no jump form)");
-        variant = C3SC_VARIANT_FIBER_PER_WAVE;
-    }
-    if (c->impulses) { // and with interventions on: the impulse form of the plain or the jump form
-        rc = check_impulse_model(c, "bellman_fibers: interventions need a model compiled with impulse kernels (and no game, horizon or stopping)");
-        if (rc != C3SC_OK) return rc;
-        if (variant != C3SC_VARIANT_AUTO && variant != C3SC_VARIANT_FIBER_PER_WAVE)
-            return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers: interventions run on the fiber-per-wave kernel only (the pair and quad variants have no impulse form)");
-        variant = C3SC_VARIANT_FIBER_PER_WAVE;
-    }
-    if (c->correlation) { // and with correlation on: the corr form of whichever of the forms above the other switches select
-        rc = check_corr_model(c, "bellman_fibers: correlation needs a model compiled with corr kernels (and no game or interventions)");
-        if (rc != C3SC_OK) return rc;
-        if (variant != C3SC_VARIANT_AUTO && variant != C3SC_VARIANT_FIBER_PER_WAVE)
-            return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers: correlation runs on the fiber-per-wave kernel only (the pair and quad variants have no corr form)");
+            return fails(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers: " + verb(r, "runs", "run") + " on the fiber-per-wave kernel only (the pair and quad variants have no " +
+                                                      r.kind + " form)");
         variant = C3SC_VARIANT_FIBER_PER_WAVE;
     }
     if (F == 0) return C3SC_OK;
     if (!d_idx || !d_out) return fail(c, C3SC_ERR_ARG, "bellman_fibers: null buffer");
     A.forced = d_policy;
     LaunchIO io{c->arena, d_idx, d_out, d_uidx, d_absorbed, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream};
-    io.stop = c->stopping != 0;
-    io.jump = c->jumps != 0;
-    io.impulse = c->impulses != 0;
-    io.corr = c->correlation != 0;
     // A launcher declines (nothing launched) when its LDS layout does not fit this grid or it does not serve this call; the
     // next-best instantiation of the same padded rank is tried then (e.g. the duo kernel's two staging buffers hold N <= 25 at
     // rank 16, the one-buffer quad kernel behind it N <= 75, the per-wave kernel behind that only stages the varying core).
@@ -1292,7 +1216,7 @@ static int launch_bellman(c3sc_hip_ctx *c, int k, size_t F, const int32_t *d_idx
         }
         rc = partition_fibers(c, e, A, io, part_slot, part_launches);
         if (rc != C3SC_OK) return rc;
-        he = launch_entry(*e, A, io);
+        he = ctx_launch(c, *e, A, io);
         if (he != hipErrorOutOfMemory && he != hipErrorNotSupported) break;
         c->memo.applied = false;
         if (getenv("C3SC_VERBOSE")) fprintf(stderr, "c3sc: %s declined (%s), trying the next instantiation\n", e->name, hipGetErrorName(he));
@@ -1332,7 +1256,7 @@ static int launch_bellman_all(c3sc_hip_ctx *c, int nk, const int *ks, const size
             if (d_out[q] == d_out[s] && F[s] > 0) return fail(c, C3SC_ERR_ARG, "bellman_fibers_all: two segments share an output array");
     }
     hipStream_t st = (hipStream_t)stream;
-    if (overlap && c->tab3L_off && c->tab3_stale && c->game_gsz == 0 && c->hz_dt <= 0.0 && !c->stopping && !c->jumps && !c->impulses && !c->correlation) {
+    if (overlap && c->tab3L_off && c->tab3_stale && ctx_form(c) == 0) {
         // stale three-core tables: built here, ahead of the fork, if a segment is going to run a three-core kernel -- every
         // side stream is then ordered behind the build by the fork itself
         const long fmin = fiber_partition_min();
@@ -1392,12 +1316,8 @@ static int launch_box(c3sc_hip_ctx *c, int k, size_t F, const int32_t *d_idx, co
 {
     if (!c) return C3SC_ERR_ARG;
     if (c->box_du == 0) return fail(c, C3SC_ERR_ARG, "bellman_fibers_box: c3sc_hip_set_control_box first");
-    if (c->game_gsz > 0) return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_box: games have no control-box form");
-    if (c->hz_dt > 0.0) return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_box: horizon mode has no control-box form");
-    if (c->stopping) return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_box: stopping has no control-box form");
-    if (c->jumps) return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_box: jumps have no control-box form");
-    if (c->impulses) return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_box: interventions have no control-box form");
-    if (c->correlation) return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_box: correlated noise has no control-box form");
+    for (const FormRow &r : FORM_ROWS)
+        if ((ctx_form(c) & r.bit) && !form_offered(r.bit, FORM_BOX)) return no_box_form(c, "bellman_fibers_box", r);
     if (model_ncf(c->model) != 0 && c->model != C3SC_MODEL_COTHRUST6D) // cothrust forms its features from u on the device (models.hpp: CF_FROM_U)
         return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_box: this model needs transcendental functions of the control");
     KArgs A;
@@ -1468,12 +1388,8 @@ static int launch_tables(c3sc_hip_ctx *c, int k, size_t F, const int32_t *d_idx,
 {
     if (!c) return C3SC_ERR_ARG;
     const int saved_model = c->model;
-    if (c->game_gsz > 0) return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_tables: the TABLE model has no game kernels");
-    if (c->hz_dt > 0.0) return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_tables: the TABLE model has no horizon kernels");
-    if (c->stopping) return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_tables: the TABLE model has no stop kernels");
-    if (c->jumps) return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_tables: the TABLE model has no jump kernels");
-    if (c->impulses) return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_tables: the TABLE model has no impulse kernels");
-    if (c->correlation) return fail(c, C3SC_ERR_UNSUPPORTED, "bellman_fibers_tables: the TABLE model has no corr kernels");
+    for (const FormRow &r : FORM_ROWS)
+        if (ctx_form(c) & r.bit) return fails(c, C3SC_ERR_UNSUPPORTED, std::string("bellman_fibers_tables: the TABLE model has no ") + r.kind + " kernels");
     c->model = C3SC_MODEL_TABLE; // fill_args only checks that a model is set
     KArgs A;
     int rc = fill_args(c, k, F, A, true);
@@ -1680,8 +1596,8 @@ static int closed_loop_setup(c3sc_hip_ctx *c, const char *who, const Args *a)
     if (a->box ? c->box_du == 0 : c->ncand == 0) return failw(c, C3SC_ERR_ARG, who, a->box ? ": set_control_box first" : ": set_controls first");
     if (a->box && model_ncf(c->model) != 0 && c->model != C3SC_MODEL_COTHRUST6D)
         return failw(c, C3SC_ERR_UNSUPPORTED, who, ": this model needs transcendental functions of the control in a box");
-    if (a->box && c->game_gsz > 0) return failw(c, C3SC_ERR_UNSUPPORTED, who, ": games have no control-box form");
-    if (check_game_model(c, (std::string(who) + ": game mode needs a model compiled with game kernels").c_str()) != C3SC_OK) return C3SC_ERR_UNSUPPORTED;
+    if (a->box && c->game_gsz > 0) return no_box_form(c, who, form_row(FORM_GAME));
+    if (check_form_model(c, who, FORM_GAME) != C3SC_OK) return C3SC_ERR_UNSUPPORTED;
     return C3SC_OK;
 }
 
@@ -1758,28 +1674,19 @@ int c3sc_hip_simulate(c3sc_hip_ctx *c, const c3sc_hip_sim_args *a, void *stream)
     int rc = closed_loop_setup(c, who, a);
     if (rc != C3SC_OK) return rc;
     const bool hz = c->hz_dt > 0.0; // horizon mode: one launch per step, step k's controller on the cores of V_{k+1}
-    if (hz) {
-        if (check_horizon_model(c, "simulate: horizon mode needs a model compiled with horizon kernels") != C3SC_OK) return C3SC_ERR_UNSUPPORTED;
-        if (a->box) return fail(c, C3SC_ERR_UNSUPPORTED, "simulate: horizon mode has no control-box form");
+    // the features that are on, in this call's own order of refusals (it decides which error a call with several of them gets)
+    for (unsigned bit : {FORM_HORIZON, FORM_JUMP, FORM_CORR, FORM_IMPULSE, FORM_STOP}) {
+        const FormRow &r = form_row(bit);
+        if (!(ctx_form(c) & bit)) continue;
+        if (!form_offered(bit, FORM_ROLLOUT)) // correlated increments and off-grid diagonal targets are not offered
+            return fails(c, C3SC_ERR_UNSUPPORTED, std::string("simulate: rollouts are not offered ") + r.problems + " (" + r.off + " first)");
+        if (check_form_model(c, who, bit) != C3SC_OK) return C3SC_ERR_UNSUPPORTED;
+        if (a->box) return no_box_form(c, who, r);
+        if (bit != FORM_HORIZON) continue;
         if (c->hz_nstack == 0) return fail(c, C3SC_ERR_ARG, "simulate: horizon mode needs the value stack (c3sc_hip_upload_value_stack)");
         if (!(std::fabs(a->dt - c->hz_dt) <= 1e-12 * c->hz_dt))
             return fail(c, C3SC_ERR_ARG, "simulate: in horizon mode dt must equal the horizon step (c3sc_hip_set_horizon_step)");
         if (a->nsteps + 1 > (size_t)c->hz_nstack) return fail(c, C3SC_ERR_ARG, "simulate: nsteps exceeds the value stack (nstack - 1 stages)");
-    }
-    if (c->jumps) {
-        if (check_jump_model(c, "simulate: jumps need a model compiled with jump kernels (and no game)") != C3SC_OK) return C3SC_ERR_UNSUPPORTED;
-        if (a->box) return fail(c, C3SC_ERR_UNSUPPORTED, "simulate: jumps have no control-box form");
-    }
-    if (c->correlation) // correlated increments and off-grid diagonal targets are not offered
-        return fail(c, C3SC_ERR_UNSUPPORTED, "simulate: rollouts are not offered with correlated noise (c3sc_hip_set_correlation(ctx, 0) first)");
-    if (c->impulses) {
-        if (check_impulse_model(c, "simulate: interventions need a model compiled with impulse kernels (and no game, horizon or stopping)") != C3SC_OK)
-            return C3SC_ERR_UNSUPPORTED;
-        if (a->box) return fail(c, C3SC_ERR_UNSUPPORTED, "simulate: interventions have no control-box form");
-    }
-    if (c->stopping) {
-        if (check_stop_model(c, "simulate: stopping needs a model compiled with stop kernels (and no game)") != C3SC_OK) return C3SC_ERR_UNSUPPORTED;
-        if (a->box) return fail(c, C3SC_ERR_UNSUPPORTED, "simulate: stopping has no control-box form");
     }
     KArgs A;
     rc = fill_args(c, 0, 0, A, false);
@@ -1841,9 +1748,6 @@ int c3sc_hip_simulate(c3sc_hip_ctx *c, const c3sc_hip_sim_args *a, void *stream)
             ro = c->hz_stack;
         }
         LaunchIO io{ro, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream, &S};
-        io.stop = c->stopping != 0;
-        io.jump = c->jumps != 0;
-        io.impulse = c->impulses != 0;
         rc = launch_one(c, ek, A, io, "simulate: this rollout kernel has no box minimiser");
         if (rc != C3SC_OK) return rc;
         s0 = S.s1;
@@ -1899,11 +1803,9 @@ int c3sc_hip_integrate(c3sc_hip_ctx *c, const c3sc_hip_ode_args *a, void *stream
     const char *who = "integrate";
     int rc = closed_loop_setup(c, who, a);
     if (rc != C3SC_OK) return rc;
-    if (c->hz_dt > 0.0) return fail(c, C3SC_ERR_UNSUPPORTED, "integrate: deterministic closed loops are not offered in horizon mode");
-    if (c->stopping) return fail(c, C3SC_ERR_UNSUPPORTED, "integrate: deterministic closed loops are not offered for stopping problems");
-    if (c->jumps) return fail(c, C3SC_ERR_UNSUPPORTED, "integrate: deterministic closed loops are not offered for jump diffusions");
-    if (c->impulses) return fail(c, C3SC_ERR_UNSUPPORTED, "integrate: deterministic closed loops are not offered for impulse control");
-    if (c->correlation) return fail(c, C3SC_ERR_UNSUPPORTED, "integrate: deterministic closed loops are not offered with correlated noise");
+    for (const FormRow &r : FORM_ROWS)
+        if ((ctx_form(c) & r.bit) && !form_offered(r.bit, FORM_ROLLOUT_ODE))
+            return fails(c, C3SC_ERR_UNSUPPORTED, std::string("integrate: deterministic closed loops are not offered ") + r.problems);
     KArgs A;
     rc = fill_args(c, 0, 0, A, false);
     if (rc != C3SC_OK) return rc;

@@ -1687,17 +1687,18 @@ int c3sc_hip_cross_wait_core(c3sc_hip_ctx *c, int k, double *h_core)
 int c3sc_hip_cross_iteration_pi(c3sc_hip_ctx *c, c3sc_hip_ctx *policy_ctx, long long policy_tag, void *stream)
 {
     if (!policy_ctx) return fail(c, C3SC_ERR_ARG, "cross_iteration_pi: null policy context");
-    if ((c && c->game_gsz > 0) || policy_ctx->game_gsz > 0)
+    const unsigned fp = ctx_form(policy_ctx), fc = c ? ctx_form(c) : fp, either = fc | fp; // kernel_common.hpp: FORM_*
+    if (either & FORM_GAME)
         return fail(c, C3SC_ERR_UNSUPPORTED, "cross_iteration_pi: policy iteration is not offered for games (c3sc_hip_set_game)");
-    if ((c && c->hz_dt > 0.0) || policy_ctx->hz_dt > 0.0)
+    if (either & FORM_HORIZON)
         return fail(c, C3SC_ERR_UNSUPPORTED, "cross_iteration_pi: policy iteration is not offered in horizon mode (c3sc_hip_set_horizon_step)");
-    if ((c && c->stopping) || policy_ctx->stopping)
+    if (either & FORM_STOP)
         return fail(c, C3SC_ERR_UNSUPPORTED, "cross_iteration_pi: policy iteration is not offered for stopping problems (c3sc_hip_set_stopping)");
-    if (c && c->correlation != policy_ctx->correlation)
+    if ((fc ^ fp) & FORM_CORR)
         return fail(c, C3SC_ERR_UNSUPPORTED, "cross_iteration_pi: the two contexts differ in correlation mode (c3sc_hip_set_correlation)");
-    if ((c && c->impulses) || policy_ctx->impulses)
+    if (either & FORM_IMPULSE)
         return fail(c, C3SC_ERR_UNSUPPORTED, "cross_iteration_pi: policy iteration is not offered for impulse control (c3sc_hip_set_impulses)");
-    if (c && c->jumps != policy_ctx->jumps) // improvement and evaluation must apply one operator
+    if ((fc ^ fp) & FORM_JUMP) // improvement and evaluation must apply one operator
         return fail(c, C3SC_ERR_UNSUPPORTED, "cross_iteration_pi: the two contexts differ in jump mode (c3sc_hip_set_jumps)");
     return cross_iteration_impl(c, policy_ctx, policy_tag, 0, stream);
 }

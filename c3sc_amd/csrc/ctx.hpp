@@ -37,14 +37,10 @@ struct c3sc_hip_ctx {
     // laid out for a static section of hz_stack_static doubles; stage s padded to hz_rp[s], its cores at hz_core_off[s * MAXD + m]
     double hz_dt = 0.0;
     int hz_off = 0;
-    // optimal stopping (c3sc_hip_set_stopping): the launches take the stop forms of the run-time compiled model's kernels
-    int stopping = 0;
-    // jump diffusions (c3sc_hip_set_jumps): the launches take the jump forms of the run-time compiled model's kernels
-    int jumps = 0;
-    // impulse control (c3sc_hip_set_impulses): the launches take the impulse forms of the run-time compiled model's kernels
-    int impulses = 0;
-    // correlated noise (c3sc_hip_set_correlation): the launches take the corr forms of the run-time compiled model's per-wave kernels
-    int correlation = 0;
+    // the switches that carry no data (c3sc_hip_set_stopping / _jumps / _impulses / _correlation): FORM_STOP | FORM_JUMP |
+    // FORM_IMPULSE | FORM_CORR.  The launches take that form of the run-time compiled model's kernels; ctx_form() below is the
+    // whole mask
+    unsigned switches = 0;
     double *hz_stack = nullptr;
     size_t hz_stack_static = 0;
     int hz_nstack = 0;
@@ -127,7 +123,14 @@ struct c3sc_hip_ctx {
     c3sc_cross_dev *cross = nullptr; // owned; freed by c3sc_hip_cross_free (called from c3sc_hip_ctx_destroy)
 };
 
-#define HIPCHK(ctx, call)                                                                    \
+// the form of the Bellman backup this context asks for (kernel_common.hpp: FORM_*): the game and the horizon step from the data
+// they carry, the rest from the switch word
+static inline unsigned ctx_form(const c3sc_hip_ctx *c)
+{
+    return (c->game_gsz > 0 ? c3sc::FORM_GAME : 0u) | (c->hz_dt > 0.0 ? c3sc::FORM_HORIZON : 0u) | c->switches;
+}
+
+#define HIPCHK(ctx, call)                                                                   \
     do {                                                                                     \
         hipError_t e__ = (call);                                                             \
         if (e__ != hipSuccess) {                                                             \

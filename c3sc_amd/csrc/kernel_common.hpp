@@ -188,8 +188,8 @@ __device__ inline int game_pair_to_list(const KArgs &A, int i)
 }
 
 // The game instantiations of the kernels are those of a model wrapped in GameOf: k_fiber_per_wave, k_rollout and k_rollout_ode
-// pass model_game<Model>() to node_backup as GAME.  A wrapper rather than one more template parameter of the kernels keeps the
-// names (and the code) of every existing instantiation as they are.
+// pass model_form<Model>() to node_backup, whose FORM_GAME bit is GAME there.  A wrapper rather than one more template parameter
+// of the kernels keeps the names (and the code) of every existing instantiation as they are.
 template <class M>
 struct GameOf : M {
     static constexpr bool GAME = true;
@@ -202,7 +202,7 @@ constexpr bool model_game()
 }
 
 // The finite-horizon instantiations are those of a model wrapped in HorizonOf, in the style of GameOf:
-// k_fiber_per_wave and k_rollout pass model_horizon<Model>() to node_backup as HORIZON, which then takes the explicit
+// k_fiber_per_wave and k_rollout pass the FORM_HORIZON bit (model_form) to node_backup as HORIZON, which then takes the explicit
 // finalisation with the fixed step delta instead of the per-candidate interpolation interval h^2 / Q.
 template <class M>
 struct HorizonOf : M {
@@ -216,7 +216,7 @@ constexpr bool model_horizon()
 }
 
 // The optimal-stopping instantiations are those of a model wrapped in StopOf, in the style of GameOf and
-// HorizonOf: k_fiber_per_wave and k_rollout pass model_stop<Model>() to node_backup as STOP, which then compares the scan's
+// HorizonOf: k_fiber_per_wave and k_rollout pass the FORM_STOP bit (model_form) to node_backup as STOP, which then compares the scan's
 // result once per node with Model::stopcost.  StopOf<HorizonOf<M>> is the finite-horizon (American) form.
 template <class M>
 struct StopOf : M {
@@ -230,8 +230,9 @@ constexpr bool model_stop()
 }
 
 // The jump-diffusion instantiations are those of a model wrapped in JumpOf, in the style of the wrappers above:
-// k_fiber_per_wave forms the node's jump term (jump_term, kernel_rollout.hpp) and passes model_jump<Model>() to node_backup as
-// JUMP.  The model supplies jumprate, jump and the number of marks NJUMP.  JumpOf<StopOf<HorizonOf<M>>> is the American form.
+// k_fiber_per_wave forms the node's jump term (jump_term, kernel_rollout.hpp) and passes the FORM_JUMP bit (model_form) to
+// node_backup as JUMP.  The model supplies jumprate, jump and the number of marks NJUMP.  JumpOf<StopOf<HorizonOf<M>>> is the
+// American form.
 template <class M>
 struct JumpOf : M {
     static constexpr bool JUMP = true;
@@ -256,8 +257,8 @@ __device__ inline int jump_constelm(const KArgs &A, const double *__restrict__ r
 
 // The impulse-control instantiations are those of a model wrapped in ImpulseOf, in the style of the wrappers
 // above: k_fiber_per_wave and k_rollout form the best intervention of the node (impulse_term, kernel_rollout.hpp) and pass
-// model_impulse<Model>() to node_backup as IMPULSE, which compares it once per node with the scan's result.  The model supplies
-// impulse and the number of interventions NIMPULSE.  ImpulseOf<JumpOf<M>> is the combined form.
+// the FORM_IMPULSE bit (model_form) to node_backup as IMPULSE, which compares it once per node with the scan's result.  The model
+// supplies impulse and the number of interventions NIMPULSE.  ImpulseOf<JumpOf<M>> is the combined form.
 template <class M>
 struct ImpulseOf : M {
     static constexpr bool IMPULSE = true;
@@ -274,8 +275,8 @@ __device__ inline void impulse_term(const KArgs &A, const double *__restrict__ r
                                     int fu, double &ival, int &imark);
 
 // The correlated-noise instantiations are those of a model wrapped in CorrOf, in the style of the wrappers above:
-// k_fiber_per_wave forms the node's cross-diffusion correction (corr_term, kernel_rollout.hpp) and passes model_corr<Model>() to
-// node_backup as CORR.  The model supplies covar and the compile-time pair list NCORR, CORR_I[], CORR_J[].
+// k_fiber_per_wave forms the node's cross-diffusion correction (corr_term, kernel_rollout.hpp) and passes the FORM_CORR bit
+// (model_form) to node_backup as CORR.  The model supplies covar and the compile-time pair list NCORR, CORR_I[], CORR_J[].
 // CorrOf<JumpOf<StopOf<HorizonOf<M>>>> is the fullest form; games and impulse control have none.
 template <class M>
 struct CorrOf : M {
@@ -291,6 +292,41 @@ constexpr bool model_corr()
 template <class Model, int RP>
 __device__ inline void corr_term(const KArgs &A, const double *__restrict__ ro, const double (&x)[Model::D], const int (&ix)[Model::D],
                                  const double (&V)[2 * Model::D + 1], int ab, double &cq, double &cpv, unsigned &st);
+
+// The form of a Bellman backup: one bit per wrapper above.  Host and device code name a variant of the backup by
+// this mask and nothing else: the kernels' template argument, the kernel table of a run-time compiled model, the switches of a
+// context and the mask of a launch are all this word.
+enum : unsigned {
+    FORM_GAME = 1u,
+    FORM_HORIZON = 2u,
+    FORM_STOP = 4u,
+    FORM_JUMP = 8u,
+    FORM_IMPULSE = 16u,
+    FORM_CORR = 32u,
+    FORM_ALL = 63u
+};
+constexpr int FORM_NBITS = 6;
+template <class Model>
+constexpr unsigned model_form()
+{
+    return (model_game<Model>() ? FORM_GAME : 0u) | (model_horizon<Model>() ? FORM_HORIZON : 0u) | (model_stop<Model>() ? FORM_STOP : 0u) |
+           (model_jump<Model>() ? FORM_JUMP : 0u) | (model_impulse<Model>() ? FORM_IMPULSE : 0u) | (model_corr<Model>() ? FORM_CORR : 0u);
+}
+// Which forms exist -- the one statement of the rule.  The per-wave kernels: a game goes with nothing else, impulse control alone
+// or with jumps, and horizon, stop, jump and corr combine freely (1 + 2 + 16 = 19 of the 64 masks).  k_rollout has those without
+// corr (11), k_rollout_ode the plain form and the game (2), the control-box minimiser the plain form only.  The model-independent
+// stencil kernels have no forms: a launch of one carries the mask 0.
+enum FormKind { FORM_PER_WAVE, FORM_ROLLOUT, FORM_ROLLOUT_ODE, FORM_BOX };
+__host__ __device__ constexpr bool form_offered(unsigned form, FormKind kind = FORM_PER_WAVE)
+{
+    if (form & ~FORM_ALL) return false;
+    if (kind == FORM_BOX) return form == 0u;
+    if (kind == FORM_ROLLOUT_ODE) return (form & ~FORM_GAME) == 0u;
+    if (kind == FORM_ROLLOUT && (form & FORM_CORR)) return false;
+    if (form & FORM_GAME) return form == FORM_GAME;
+    if (form & FORM_IMPULSE) return (form & ~(FORM_IMPULSE | FORM_JUMP)) == 0u;
+    return true;
+}
 
 // Output pointers of one launch (separate __restrict__ kernel parameters).
 struct KOut {
@@ -808,8 +844,7 @@ __device__ __forceinline__ void impulse_action(int nc, bool forced, int fu, doub
 // Q.  Q0 may now be small or negative where a paired dimension's axis rates arrive in the candidate loop: all_small, all_tiny and
 // q0ok are then false (each compares against Q0 itself) and the general scan runs.  Zero covariances leave every bit:
 // Q0 + (-0.0) and PV0 + 0.0 are exact.
-template <class Model, int CG = 1, int CGD = 1, class Cand = CandRegs<Model>, bool SPLIT = true, class Pre = NoPre, bool GAME = false,
-          bool HORIZON = false, bool STOP = false, bool JUMP = false, bool IMPULSE = false, bool CORR = false>
+template <class Model, int CG = 1, int CGD = 1, class Cand = CandRegs<Model>, bool SPLIT = true, class Pre = NoPre, unsigned FORM = 0u>
 __device__ inline double node_backup(const KArgs &A, const double *__restrict__ ro, const double (&x)[Model::D],
                                      const double (&tv)[Model::NTAB > 0 ? Model::NTAB : 1], const Cand &cr,
                                      const double (&V)[2 * Model::D + 1], int ab, int &ui, unsigned &st, bool forced = false,
@@ -819,11 +854,10 @@ __device__ inline double node_backup(const KArgs &A, const double *__restrict__ 
     // forced (wave-uniform) = policy evaluation, bellman_pi (bellman.c:1702-1886): the candidate fu (per lane) is
     // applied instead of the minimiser's; same rates, same bellmanrhs.
     constexpr int D = Model::D, DU = Model::DU;
+    static_assert(form_offered(FORM), "this combination of forms is not offered (form_offered)");
+    constexpr bool GAME = FORM & FORM_GAME, HORIZON = FORM & FORM_HORIZON, STOP = FORM & FORM_STOP, JUMP = FORM & FORM_JUMP,
+                   IMPULSE = FORM & FORM_IMPULSE, CORR = FORM & FORM_CORR;
     static_assert(!GAME || (CG == 1 && CGD == 1), "the game scan takes one candidate per trip");
-    static_assert(!(STOP && GAME), "stopping games are not offered");
-    static_assert(!(JUMP && GAME), "games with jumps are not offered");
-    static_assert(!(IMPULSE && (GAME || HORIZON || STOP)), "impulse control is not offered with games, horizons or stopping");
-    static_assert(!(CORR && (GAME || IMPULSE)), "correlated noise is not offered with games or impulse control");
     const int nc = __builtin_amdgcn_readfirstlane(A.ncand); // keeps the candidate loops' trip test on the scalar unit
     ui = -1;
     // game: which reductions are maxima (wave-uniform), the group length, the forced pair as a list position

@@ -354,8 +354,7 @@ __global__ void __launch_bounds__(256, (RP >= 20 ? 1 : 2)) // rank 20 is LDS-bou
                     // registers are dead
                     double cq = 0.0, cpv = 0.0;
                     if constexpr (model_corr<Model>()) corr_term<Model, RP>(A, ro, x, ix, V, ab, cq, cpv, st);
-                    val = node_backup<Model, 1, 1, CandLds<Model>, true, NoPre, model_game<Model>(), model_horizon<Model>(), model_stop<Model>(),
-                                      model_jump<Model>(), model_impulse<Model>(), model_corr<Model>()>(
+                    val = node_backup<Model, 1, 1, CandLds<Model>, true, NoPre, model_form<Model>()>(
                         A, ro, x, tv, cr, V, ab, ui, st, forced, fu, NoPre(), jrate, jval, ival, imark, cq, cpv);
                 }
                 if (A.memo_keys) { // wave-uniform: node memo of the device-resident cross iterations

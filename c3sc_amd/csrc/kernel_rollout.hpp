@@ -591,9 +591,9 @@ __global__ void __launch_bounds__(256) k_rollout(const KArgs A, const SimK S, co
             double ival = 0.0;
             int imark = -1;
             if constexpr (model_impulse<Model>()) impulse_term<Model, RP>(A, ro, xin, S.constelm, false, -1, ival, imark);
-            (void)node_backup<Model, 1, 1, CandLds<Model>, true, NoPre, model_game<Model>(), model_horizon<Model>(), model_stop<Model>(),
-                              model_jump<Model>(), model_impulse<Model>()>(A, ro, xin, tv, cr, V, ab, ui, st, false, -1, NoPre(), jrate,
-                                                                           jval, ival, imark);
+            // no rollout has a corr form (form_offered, FORM_ROLLOUT): the bit is masked off
+            (void)node_backup<Model, 1, 1, CandLds<Model>, true, NoPre, (model_form<Model>() & ~FORM_CORR)>(
+                A, ro, xin, tv, cr, V, ab, ui, st, false, -1, NoPre(), jrate, jval, ival, imark);
             if constexpr (model_impulse<Model>()) { // the controller intervenes here: the lane pays k_m at the state the controller saw
                                                     // and moves there to y_m; the step slot carries no stage cost and no increment
                 iv.now = alive && (ui > A.ncand);

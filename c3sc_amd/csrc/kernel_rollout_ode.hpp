@@ -75,7 +75,7 @@ __device__ inline void ode_policy(const KArgs &A, const double *__restrict__ ro,
     }
     if (!boxed) {
         int ui;
-        (void)node_backup<Model, 1, 1, CandLds<Model>, true, NoPre, model_game<Model>()>(A, ro, xin, tv, cr, V, ab, ui, st);
+        (void)node_backup<Model, 1, 1, CandLds<Model>, true, NoPre, model_form<Model>()>(A, ro, xin, tv, cr, V, ab, ui, st);
         const int uc = ui < 0 ? 0 : (model_game<Model>() ? game_pair_to_list(A, ui) : ui); // game: the saddle pair's list position
 #pragma unroll
         for (int k = 0; k < DU; k++) u[k] = (ui >= 0) ? ro[A.cands_off + uc * DU + k] : 0.0; // obstacle: u = 0

@@ -29,10 +29,9 @@ struct LaunchIO {
     const int32_t *perm = nullptr;
     const int32_t *nlive = nullptr;
     bool tab3 = false; // ... and the three-core product tables are built: a partitioned launch may run its three-core kernel
-    bool stop = false; // stopping is on (c3sc_hip_set_stopping): the stop forms of a run-time compiled model's kernels run
-    bool jump = false; // jumps are on (c3sc_hip_set_jumps): the jump forms of a run-time compiled model's kernels run
-    bool impulse = false; // interventions are on (c3sc_hip_set_impulses): the impulse forms of a run-time compiled model's kernels run
-    bool corr = false; // correlation is on (c3sc_hip_set_correlation): the corr forms of a run-time compiled model's per-wave kernels run
+    // the context's switches (FORM_STOP | FORM_JUMP | FORM_IMPULSE | FORM_CORR, kernel_common.hpp): a run-time compiled model's kernels
+    // of that form run.  The game and horizon bits travel in KArgs (game_gsz, hz_off), whose data the kernels read
+    unsigned form = 0;
 };
 #endif
 
@@ -116,12 +115,8 @@ RtcEntries rtc_entries();
 // launch an entry of either kind
 hipError_t rtc_launch(const KernelEntry &e, const KArgs &A, const LaunchIO &io);
 bool rtc_model_known(int model); // an id c3sc_hip_model_compile returned
-bool rtc_model_info(int model, int &du, bool &game); // its control dimension and whether it has game kernels (false: unknown id)
-bool rtc_model_stop(int model); // it was compiled with the stop kernels (c3sc_hip_model_compile_os, stop = 1)
-int rtc_model_njump(int model); // the number of marks it was compiled with (c3sc_hip_model_compile_jd); 0: no jump kernels
-int rtc_model_ncorr(int model); // the number of pairs it was compiled with (c3sc_hip_model_compile_cd); 0: no corr kernels
-int rtc_model_nimpulse(int model); // the number of interventions it was compiled with (c3sc_hip_model_compile_ic); 0: no impulse kernels
-bool rtc_model_horizon(int model); // it was compiled with the finite-horizon kernels (c3sc_hip_model_compile_fh, horizon = 1)
+bool rtc_model_info(int model, int &du); // its control dimension (false: unknown id)
+unsigned rtc_model_forms(int model); // the FORM_* bits of the features it was compiled with (0: none, or an unknown id)
 inline hipError_t launch_entry(const KernelEntry &e, const KArgs &A, const LaunchIO &io) { return e.rtc ? rtc_launch(e, A, io) : e.fn(A, io); }
 #endif
 

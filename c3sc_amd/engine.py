@@ -225,14 +225,20 @@ def _model_spec(source, d, du, ranks, box, udep_mask, uconst_mask, stage_udep, n
     return spec
 
 
-def _spec_cd(spec, game, horizon, stop, njump, nimpulse, corr_pairs):
-    """the _cd spec over `spec`; the pair list is passed as given (the library validates it), cut at CORR_MAX + 1 pairs' count"""
+def _form_spec(spec, game, horizon, stop, njump, nimpulse, corr_pairs):
+    """The shallowest of the nested spec structs that carries the request, and the suffix of the entry points that take it
+    ("", "_ex", "_fh", "_os", "_jd", "_ic", "_cd": c3sc_hip_model_compile<suffix>, c3sc_hip_model_code_object<suffix>).  The
+    pair list is passed as given (the library validates it), cut at CORR_MAX + 1 pairs' count."""
     pairs = [(int(i), int(j)) for i, j in corr_pairs]
-    cd = ModelSpecCd(ModelSpecIc(ModelSpecJd(ModelSpecOs(ModelSpecFh(ModelSpecEx(spec, 1 if game else 0), 1 if horizon else 0),
-                                                         1 if stop else 0), int(njump)), int(nimpulse)), len(pairs))
+    levels = [(ModelSpecEx, "_ex", 1 if game else 0), (ModelSpecFh, "_fh", 1 if horizon else 0), (ModelSpecOs, "_os", 1 if stop else 0),
+              (ModelSpecJd, "_jd", int(njump)), (ModelSpecIc, "_ic", int(nimpulse)), (ModelSpecCd, "_cd", len(pairs))]
+    depth = max((q + 1 for q, (_, _, v) in enumerate(levels) if v), default=0)
+    suffix = ""
+    for struct, suffix, v in levels[:depth]:
+        spec = struct(spec, v)
     for p, (i, j) in enumerate(pairs[:CORR_MAX]):
-        cd.corr_dims[2 * p], cd.corr_dims[2 * p + 1] = i, j
-    return cd
+        spec.corr_dims[2 * p], spec.corr_dims[2 * p + 1] = i, j
+    return spec, suffix
 
 
 def _model_fail(rc, what):
@@ -255,29 +261,10 @@ def compile_model(source: str, d: int, du: int, ranks=(4, 8), box: bool = False,
     (c3sc_hip_model_compile_cd) adds the corr kernels that BellmanEngine.set_correlation needs: the source then defines covar for
     these pairs of dimensions, i < j."""
     L = load_library()
-    spec = _model_spec(source, d, du, tuple(ranks), box, udep_mask, uconst_mask, stage_udep, name)
+    base = _model_spec(source, d, du, tuple(ranks), box, udep_mask, uconst_mask, stage_udep, name)
+    spec, suffix = _form_spec(base, game, horizon, stop, njump, nimpulse, corr_pairs)
     mid = C.c_int(0)
-    if len(corr_pairs):
-        cd = _spec_cd(spec, game, horizon, stop, njump, nimpulse, corr_pairs)
-        rc = L.c3sc_hip_model_compile_cd(C.byref(cd), C.byref(mid))
-    elif nimpulse:
-        ic = ModelSpecIc(ModelSpecJd(ModelSpecOs(ModelSpecFh(ModelSpecEx(spec, 1 if game else 0), 1 if horizon else 0), 1 if stop else 0),
-                                     int(njump)), int(nimpulse))
-        rc = L.c3sc_hip_model_compile_ic(C.byref(ic), C.byref(mid))
-    elif njump:
-        jd = ModelSpecJd(ModelSpecOs(ModelSpecFh(ModelSpecEx(spec, 1 if game else 0), 1 if horizon else 0), 1 if stop else 0), int(njump))
-        rc = L.c3sc_hip_model_compile_jd(C.byref(jd), C.byref(mid))
-    elif stop:
-        os_ = ModelSpecOs(ModelSpecFh(ModelSpecEx(spec, 1 if game else 0), 1 if horizon else 0), 1)
-        rc = L.c3sc_hip_model_compile_os(C.byref(os_), C.byref(mid))
-    elif horizon:
-        fh = ModelSpecFh(ModelSpecEx(spec, 1 if game else 0), 1)
-        rc = L.c3sc_hip_model_compile_fh(C.byref(fh), C.byref(mid))
-    elif game:
-        ex = ModelSpecEx(spec, 1)
-        rc = L.c3sc_hip_model_compile_ex(C.byref(ex), C.byref(mid))
-    else:
-        rc = L.c3sc_hip_model_compile(C.byref(spec), C.byref(mid))
+    rc = getattr(L, "c3sc_hip_model_compile" + suffix)(C.byref(spec), C.byref(mid))
     if rc != 0:
         _model_fail(rc, "c3sc_hip_model_compile")
     return mid.value
@@ -291,32 +278,13 @@ def code_object(source: str, d: int, du: int, ranks=(4, 8), box: bool = False, u
     registered.  game, horizon, stop, njump and nimpulse select the spec as in compile_model (stop: c3sc_hip_model_code_object_os,
     njump: c3sc_hip_model_code_object_jd, nimpulse: c3sc_hip_model_code_object_ic, corr_pairs: c3sc_hip_model_code_object_cd)."""
     L = load_library()
-    spec = _model_spec(source, d, du, tuple(ranks), box, udep_mask, uconst_mask, stage_udep, name)
+    base = _model_spec(source, d, du, tuple(ranks), box, udep_mask, uconst_mask, stage_udep, name)
+    spec, suffix = _form_spec(base, game, horizon, stop, njump, nimpulse, corr_pairs)
     cap = 16 << 20  # one compile when the code object fits; a larger one is compiled again into a buffer of its size
     for _ in range(2):
         buf = C.create_string_buffer(cap)
         size = C.c_size_t(cap)
-        if len(corr_pairs):
-            cd = _spec_cd(spec, game, horizon, stop, njump, nimpulse, corr_pairs)
-            rc = L.c3sc_hip_model_code_object_cd(C.byref(cd), buf, C.byref(size))
-        elif nimpulse:
-            ic = ModelSpecIc(ModelSpecJd(ModelSpecOs(ModelSpecFh(ModelSpecEx(spec, 1 if game else 0), 1 if horizon else 0),
-                                                     1 if stop else 0), int(njump)), int(nimpulse))
-            rc = L.c3sc_hip_model_code_object_ic(C.byref(ic), buf, C.byref(size))
-        elif njump:
-            jd = ModelSpecJd(ModelSpecOs(ModelSpecFh(ModelSpecEx(spec, 1 if game else 0), 1 if horizon else 0), 1 if stop else 0),
-                             int(njump))
-            rc = L.c3sc_hip_model_code_object_jd(C.byref(jd), buf, C.byref(size))
-        elif stop:
-            os_ = ModelSpecOs(ModelSpecFh(ModelSpecEx(spec, 1 if game else 0), 1 if horizon else 0), 1)
-            rc = L.c3sc_hip_model_code_object_os(C.byref(os_), buf, C.byref(size))
-        elif horizon:
-            fh = ModelSpecFh(ModelSpecEx(spec, 1 if game else 0), 1)
-            rc = L.c3sc_hip_model_code_object_fh(C.byref(fh), buf, C.byref(size))
-        elif game:
-            rc = L.c3sc_hip_model_code_object_ex(C.byref(ModelSpecEx(spec, 1)), buf, C.byref(size))
-        else:
-            rc = L.c3sc_hip_model_code_object(C.byref(spec), buf, C.byref(size))
+        rc = getattr(L, "c3sc_hip_model_code_object" + suffix)(C.byref(spec), buf, C.byref(size))
         if rc == 0:
             return buf.raw[:size.value]
         if size.value <= cap:

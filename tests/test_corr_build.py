@@ -227,7 +227,7 @@ def test_library_kernels_have_no_corr_form(tmp_path):
 
 
 def test_kargs_keeps_its_size(tmp_path):
-    """whether a launch takes the corr form is host state (LaunchIO::corr): the kernels' argument block is the old one"""
+    """whether a launch takes the corr form is host state (the FORM_CORR bit of LaunchIO::form): the kernels' argument block is the old one"""
     src = tmp_path / "kargs.hip"
     src.write_text('#include "kernel_common.hpp"\nstatic_assert(sizeof(c3sc::KArgs) == 1368);\nstruct M0 {};\n'
                    "static_assert(c3sc::model_corr<c3sc::CorrOf<c3sc::JumpOf<M0>>>());\n"

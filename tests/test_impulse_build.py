@@ -198,7 +198,7 @@ def test_library_kernels_have_no_impulse_form(tmp_path):
 
 
 def test_kargs_keeps_its_size(tmp_path):
-    """whether a launch takes the impulse form is host state (LaunchIO::impulse): the kernels' argument block is the old one"""
+    """whether a launch takes the impulse form is host state (the FORM_IMPULSE bit of LaunchIO::form): the kernels' argument block is the old one"""
     src = tmp_path / "kargs.hip"
     src.write_text('#include "kernel_common.hpp"\nstatic_assert(sizeof(c3sc::KArgs) == 1368);\nstruct M0 {};\n'
                    "static_assert(c3sc::model_impulse<c3sc::ImpulseOf<c3sc::JumpOf<M0>>>());\n"
