@@ -9,8 +9,7 @@ rate r_p = (h2 / (h_i h_j)) |a_p| / 2 to each of two diagonal neighbours -- (+,+
 a_p < 0 -- and takes the same r_p off each of the four axis rates of i and j.  Everything is linear in the rates, so Q and PV of
 every candidate gain
     cq = sum_p (-2 r_p),   cpv = sum_p r_p [(V_d1 + V_d2) - (V[2i] + V[2i+1] + V[2j] + V[2j+1])]
-and everything downstream is the backup without the term (jump_lib / stop_lib / horizon_lib state it; it is written out again
-here with the two extra numbers).  A diagonal neighbour is a grid node and pays the value array's entry there.  Its index in
+and everything downstream is the backup without the term (backup_ref states it; the two numbers go into its q0 and pv0).  A diagonal neighbour is a grid node and pays the value array's entry there.  Its index in
 each of the two dimensions, stated here on its own (neighbour_indices): one node down / up in the interior; at a reflecting end
 the node itself on the outer side; across the periodic seam (node 0 and node n - 1 are one point) n - 2 below and 1 above; on an
 absorbing face the node itself on both sides.  The axis probabilities of dimension m stay non-negative iff
@@ -19,6 +18,7 @@ import dataclasses
 
 import numpy as np
 
+import backup_ref as BR
 import horizon_lib as H
 import jump_lib as JL
 import stop_lib as SL
@@ -204,7 +204,7 @@ def full_values(w, cores):
 
 def pair_rates(w, covar, pairs, x):
     """(r [P, npairs], a [P, npairs]): r_p = (h2 / (h_i h_j)) |a_p| / 2"""
-    h2, t = H.mca_constants(w)
+    h2, t = BR.mca_constants(w)
     a = covar(w.params, x)
     r = np.stack([(t[2 * i] * t[2 * j] / h2) * np.abs(a[:, p]) / 2.0 for p, (i, j) in enumerate(pairs)], axis=-1)
     return r, a
@@ -228,7 +228,7 @@ def corr_terms(w, covar, pairs, Vfull, ix, x, V):
 
 def dominance(w, host, pairs, x, r):
     """[P] True where some paired dimension's axis rate would go negative: (h2 / h_m^2) sigma_m^2 / 2 < sum_{p with m} r_p"""
-    h2, t = H.mca_constants(w)
+    h2, t = BR.mca_constants(w)
     C = np.asarray(w.cands, dtype=np.float64)
     _, s, _ = host(w.params, x, np.broadcast_to(C[0], (len(x), C.shape[1])))
     bad = np.zeros(len(x), dtype=bool)
@@ -238,82 +238,31 @@ def dominance(w, host, pairs, x, r):
     return bad
 
 
-def candidate_values(host, prm, x, V, C, h2, t, beta, q0, pv0, delta=None):
-    """values [P, nc] of every candidate with the control-independent terms q0, pv0 [P] inside Q and PV (NaN = skipped:
-    infinite horizon and Q < 1e-14), the per-node stationary flag and the CFL flags [P, nc]; delta: the horizon step"""
-    D = x.shape[1]
-    xx = np.broadcast_to(x[:, None, :], (x.shape[0], len(C), D))
-    uu = np.broadcast_to(C[None], (x.shape[0],) + C.shape)
-    b, s, st = host(prm, xx, uu)
-    Q = np.zeros(b.shape[:-1]) + q0[:, None]
-    PV = np.zeros(b.shape[:-1]) + pv0[:, None]
-    for m in range(D):
-        half = t[2 * m + 1] * (s[..., m] * s[..., m]) / 2.0
-        tb = t[2 * m] * b[..., m]
-        pm = np.where(b[..., m] < -1e-14, half - tb, half)
-        pp = np.where(b[..., m] > 1e-14, half + tb, half)
-        Q += pm + pp
-        PV += pm * V[:, None, 2 * m] + pp * V[:, None, 2 * m + 1]
-    Vs = V[:, None, 2 * D]
-    if delta is not None:
-        dh2 = delta / h2
-        val = st * delta + np.exp(-beta * delta) * (Vs + dh2 * (PV - Q * Vs))
-        return val, np.zeros(len(x), dtype=bool), Q * dh2 > 1.0
-    bad = Q < 1e-14
-    Qs = np.where(bad, 1.0, Q)
-    dt = h2 / Qs
-    val = dt * st + np.exp(-beta * dt) * (PV / Qs + (1.0 - Qs / Qs) * Vs)
-    return np.where(bad, np.nan, val), bad.any(axis=1), np.zeros(val.shape, dtype=bool)
-
-
-def node_indices(w, k, idx):
-    """multi-indices [F * N, D] of the nodes of fibers idx along dim k"""
-    F, N = idx.shape[0], w.ngrid[k]
-    ix = np.empty((F, N, w.dx), dtype=np.int64)
-    for m in range(w.dx):
-        ix[:, :, m] = np.arange(N)[None, :] if m == k else idx[:, m][:, None]
-    return ix.reshape(-1, w.dx)
-
-
 def corr_fibers(w, host, covar, pairs, Vfull, k, idx, costs, absorbed, bcost, ocost, delta=None, psi_fn=None, forced=None,
                 jumps=None, interp=None, with_corr=True):
     """the backup with the cross terms of every node of fibers idx from their axis stencils (costs [F, N, 2D+1], absorbed
     [F, N]) and the full value array Vfull of the same value function; jumps / interp: a jump model and the interpolant of the
     value function for the jump term as well.  Returns (value, index, margin, stationary, cfl, dominance) of shape [F, N]"""
-    h2, t = H.mca_constants(w)
-    x = H.node_states(w, k, idx).reshape(-1, w.dx)
-    ix = node_indices(w, k, idx)
-    V = costs.reshape(-1, 2 * w.dx + 1)
-    C = np.asarray(w.cands, dtype=np.float64)
+    x = BR.node_states(w, k, idx).reshape(-1, w.dx)
     q0, pv0 = np.zeros(len(x)), np.zeros(len(x))
     if jumps is not None:
         jrate, J = JL.jump_terms(w, jumps, interp, x, bcost, ocost)
         q0, pv0 = q0 + jrate, pv0 + jrate * J
     dom = np.zeros(len(x), dtype=bool)
     if with_corr:
-        cq, cpv, r = corr_terms(w, covar, pairs, Vfull, ix, x, V)
+        cq, cpv, r = corr_terms(w, covar, pairs, Vfull, BR.node_indices(w, k, idx), x, costs.reshape(-1, 2 * w.dx + 1))
         q0, pv0 = q0 + cq, pv0 + cpv
         dom = dominance(w, host, pairs, x, r)
-    vals, stat, cfl = candidate_values(host, w.params, x, V, C, h2, t, w.discount, q0, pv0, delta)
-    out, ui, mg = JL.backup(vals, None if psi_fn is None else psi_fn(x), forced)
-    if forced is not None:
-        fi = np.asarray(forced).reshape(-1)
-        cfl = cfl[np.arange(len(fi)), np.clip(fi, 0, len(C) - 1)] & (fi >= 0) & (fi < len(C))
-    else:
-        cfl = cfl.any(axis=1)
-    ab = absorbed.reshape(-1)
-    out = np.where(ab == 1, bcost(x), np.where(ab == -1, ocost(x), out))
-    ui = np.where(ab != 0, -1, ui)
-    sh = absorbed.shape
-    live = ab == 0
-    return (out.reshape(sh), ui.reshape(sh), mg.reshape(sh), (stat & live).reshape(sh), (cfl & live).reshape(sh), (dom & live).reshape(sh))
+    res = BR.fibers(w, host, k, idx, costs, absorbed, bcost, ocost, q0, pv0, None if psi_fn is None else psi_fn(x), delta=delta,
+                    forced=forced)
+    return res + ((dom & (absorbed.reshape(-1) == 0)).reshape(absorbed.shape),)
 
 
 # ---------------------------------------------------------------------------------------------------- the chain itself
 def chain_rows(w, host, covar, pairs, x, ix, u):
     """the un-normalised transition rates of the node x [D] (multi-index ix) under the control u: a dict {neighbour multi-index
     tuple: rate} over the 2D axis neighbours and the 2 npairs diagonal ones (rates to one node are summed), and Q"""
-    h2, t = H.mca_constants(w)
+    h2, t = BR.mca_constants(w)
     x1, ix1 = np.asarray(x, dtype=np.float64)[None], np.asarray(ix)[None]
     b, s, _ = host(w.params, x1, np.asarray(u, dtype=np.float64)[None])
     r, a = pair_rates(w, covar, pairs, x1)
@@ -344,36 +293,27 @@ def chain_rows(w, host, covar, pairs, x, ix, u):
 
 
 # ---------------------------------------------------------------------------------------------------- dense chains
-def _corr_dense(w, covar, pairs, x, Vn, sten):
-    n0, n1 = w.ngrid
-    i0, i1 = np.meshgrid(np.arange(n0), np.arange(n1), indexing="ij")
-    ix = np.stack([i0.reshape(-1), i1.reshape(-1)], axis=-1)
-    return corr_terms(w, covar, pairs, Vn, ix, x, sten(Vn))
+def dense_terms(w, host, covar, pairs):
+    """the per-sweep callable of backup_ref.sweeps: the pairs' correction on the nodal array the sweep reads, and the dominance
+    flag"""
+    x, _, sten = BR.grid2(w)
+    ix = np.stack([a.reshape(-1) for a in np.meshgrid(np.arange(w.ngrid[0]), np.arange(w.ngrid[1]), indexing="ij")], axis=-1)
+
+    def terms(Vn):
+        cq, cpv, r = corr_terms(w, covar, pairs, Vn, ix, x, sten(Vn))
+        return cq, cpv, None, dominance(w, host, pairs, x, r)
+
+    return terms
 
 
 def dense_chain(w, host, covar, pairs, psi_fn, delta, nstages, stopping=True, with_corr=True):
     """the explicit chain with the cross terms of a 2-D workload whose dimensions both absorb: V[s] for s = 0 .. nstages with
     V[nstages] = psi, the boundary nodes keep psi.  Returns (V [nstages + 1, n0, n1], index [nstages, n0, n1], cfl seen,
     dominance violated)"""
-    n0, n1 = w.ngrid
-    x, ab, sten = JL._grid2(w)
-    h2, t = H.mca_constants(w)
-    C = np.asarray(w.cands, dtype=np.float64)
-    psi = psi_fn(x)
-    Vn = psi.reshape(n0, n1)
-    out, dec, anycfl, anydom = [Vn], [], False, False
-    for _ in range(nstages):
-        cq, cpv = np.zeros(len(x)), np.zeros(len(x))
-        if with_corr:
-            cq, cpv, r = _corr_dense(w, covar, pairs, x, Vn, sten)
-            anydom |= bool((dominance(w, host, pairs, x, r) & ~ab).any())
-        vals, _, cfl = candidate_values(host, w.params, x, sten(Vn), C, h2, t, w.discount, cq, cpv, delta)
-        v, ui, _ = JL.backup(vals, psi if stopping else None)
-        anycfl |= bool((cfl.any(axis=1) & ~ab).any())
-        Vn = np.where(ab, psi, v).reshape(n0, n1)
-        out.append(Vn)
-        dec.append(np.where(ab, -1, ui).reshape(n0, n1))
-    return np.array(out[::-1]), np.array(dec[::-1]), anycfl, anydom
+    psi = psi_fn(BR.grid2(w)[0])
+    V, ui, _, anycfl, anydom = BR.sweeps(w, host, psi, psi, nstages, dense_terms(w, host, covar, pairs) if with_corr else None,
+                                         psi if stopping else None, delta)
+    return V[::-1].copy(), ui[::-1].copy(), anycfl, anydom
 
 
 LQR_VI_BETA, LQR_VI_SWEEPS, LQR_VI_AMP = 0.5, 6, 0.8
@@ -387,21 +327,9 @@ def lqr_vi_workload(mid, rank=11):
 def dense_vi(w, host, covar, pairs, bcost, V0, nsweeps, with_corr=True):
     """value iteration sweeps of the correlated operator on the whole grid of a 2-D workload whose dimensions both absorb (the
     boundary nodes keep their boundary cost): [V_0, V_1, .. V_nsweeps]"""
-    n0, n1 = w.ngrid
-    x, ab, sten = JL._grid2(w)
-    h2, t = H.mca_constants(w)
-    C = np.asarray(w.cands, dtype=np.float64)
-    Vn = np.where(ab, bcost(x), V0.reshape(-1)).reshape(n0, n1)
-    out = [Vn]
-    for _ in range(nsweeps):
-        cq, cpv = np.zeros(len(x)), np.zeros(len(x))
-        if with_corr:
-            cq, cpv, _ = _corr_dense(w, covar, pairs, x, Vn, sten)
-        vals, _, _ = candidate_values(host, w.params, x, sten(Vn), C, h2, t, w.discount, cq, cpv)
-        v, _, _ = JL.backup(vals)
-        Vn = np.where(ab, bcost(x), v).reshape(n0, n1)
-        out.append(Vn)
-    return np.array(out)
+    x, ab, _ = BR.grid2(w)
+    return BR.sweeps(w, host, np.where(ab, bcost(x), V0.reshape(-1)), bcost(x), nsweeps,
+                     dense_terms(w, host, covar, pairs) if with_corr else None)[0]
 
 
 # ---------------------------------------------------------------------------------------------------- the reference API
@@ -432,9 +360,11 @@ def add_covariance(L, ctl, covar, prm, d, pairs):
 
 def heston_callbacks(prm=HESTON_PRM):
     """(callbacks, stop callback) of the Heston put for facade_lib.Control, built like stop_lib.put_callbacks"""
+    import facade_lib as fl
+
     psi = lambda x: float(heston_psi(prm, np.asarray(x)))
-    return SL._callbacks(lambda x, u: [prm[0] - 0.5 * x[1], prm[1] * (prm[2] - x[1])],
-                         lambda x, u: [np.sqrt(x[1]), prm[3] * np.sqrt(x[1])], lambda x, u: 0.0, psi, psi, psi)
+    return fl.callbacks2d(lambda x, u: [prm[0] - 0.5 * x[1], prm[1] * (prm[2] - x[1])],
+                          lambda x, u: [np.sqrt(x[1]), prm[3] * np.sqrt(x[1])], lambda x, u: 0.0, psi, psi, psi)
 
 
 def fh_child(out_path, delta=HESTON_DELTA, nstages=HESTON_STAGES):
@@ -442,20 +372,17 @@ def fh_child(out_path, delta=HESTON_DELTA, nstages=HESTON_STAGES):
     the terminal value psi, V_s at every node of every stage saved"""
     import ctypes as C
 
+    import facade_lib as fl
     from c3sc_amd import engine as E
 
     mid = E.compile_model(HESTON, 2, 1, ranks=(4, 8, 12), name="heston_api", horizon=True, stop=True, corr_pairs=HESTON_PAIRS, **HESTON_MASKS)
     w = heston_workload(mid, rank=11)
     cbs, stop_cb = heston_callbacks(HESTON_PRM)
-    L, ctl, aa = SL._api_setup(w, cbs, stop_cb)
+    L, ctl, aa = fl.stop_control(w, cbs, stop_cb)
     keep = add_covariance(L, ctl, heston_covar, HESTON_PRM, 2, HESTON_PAIRS)
-    vt, keep2 = SL._init_value(L, ctl, aa, lambda xx: heston_psi(HESTON_PRM, xx))
+    vt, keep2 = fl.init_value(L, ctl, aa, lambda xx: heston_psi(HESTON_PRM, xx))
     V = L.c3control_fh_solve(ctl.h, C.c_size_t(nstages), C.c_double(delta), vt, aa, ctl.opt, C.c_int(0))
-    n0, n1 = w.ngrid
-    if not V:
-        np.savez(out_path, V=np.zeros(0))
-        return
-    np.savez(out_path, V=np.array([SL._nodal(L, V[s], n0, n1) for s in range(nstages + 1)]))
+    fl.save_stages(out_path, L, V, nstages, *w.ngrid)
 
 
 def vi_child(out_path, nsweeps=LQR_VI_SWEEPS):
@@ -468,17 +395,14 @@ def vi_child(out_path, nsweeps=LQR_VI_SWEEPS):
 
     mid = E.compile_model(LQR, 2, 2, ranks=(4, 8, 12), name="lqr_cd_api", corr_pairs=LQR_PAIRS, **LQR_MASKS)
     w = lqr_vi_workload(mid)
-    L = fl.lib()
-    for n in ("c3control_init_value", "c3control_vi_solve"):
-        getattr(L, n).restype = C.c_void_p
-    L.valuef_eval_ind.restype = C.c_double
+    L = fl.solver_lib()
     ctl = fl.Control(w, callbacks=H.lqr_callbacks(w.params), consistent_ends=None)
     keep = add_covariance(L, ctl, lqr_covar, w.params, 2, LQR_PAIRS)
-    aa = JL._approx_args(L)
-    v, keep2 = SL._init_value(L, ctl, aa, lambda xx: H.lqr_terminal(w.params, xx))
+    aa = fl.approx_args(L)
+    v, keep2 = fl.init_value(L, ctl, aa, lambda xx: H.lqr_terminal(w.params, xx))
     n0, n1 = w.ngrid
-    out = [SL._nodal(L, v.value, n0, n1)]
+    out = [fl.nodal(L, v.value, n0, n1)]
     for _ in range(nsweeps):
         v = C.c_void_p(L.c3control_vi_solve(ctl.h, C.c_size_t(1), C.c_double(0.0), v, aa, ctl.opt, C.c_int(0), None))
-        out.append(SL._nodal(L, v.value, n0, n1))
+        out.append(fl.nodal(L, v.value, n0, n1))
     np.savez(out_path, V=np.array(out))

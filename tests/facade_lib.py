@@ -180,3 +180,101 @@ class Control:
     def close(self):
         self.L.c3opt_free(self.opt)
         self.L.c3control_destroy(self.h)
+
+
+# ---------------------------------------------------------------------------------------------------- solver child programs
+# what the child processes of the feature libraries (horizon_lib .. game_lib: vi_child, pi_child, fh_child) share when they drive
+# c3control_vi_solve / pi_solve / fh_solve on a 2-D workload
+def solver_lib():
+    """lib() with the return types of the solver entry points set"""
+    L = lib()
+    for n in ("c3control_init_value", "c3control_vi_solve", "c3control_pi_solve"):
+        getattr(L, n).restype = C.c_void_p
+    L.c3control_fh_solve.restype = C.POINTER(C.c_void_p)
+    return L
+
+
+def approx_args(L, rank=11):
+    """interpolation arguments of fixed rank `rank`: no adaptation, no kick, cross to 1e-12, rounding to 1e-15"""
+    aa = C.c_void_p(L.approx_args_init())
+    L.approx_args_set_cross_tol(aa, C.c_double(1e-12))
+    L.approx_args_set_round_tol(aa, C.c_double(1e-15))
+    L.approx_args_set_kickrank(aa, C.c_size_t(0))
+    L.approx_args_set_adapt(aa, C.c_int(0))
+    L.approx_args_set_startrank(aa, C.c_size_t(rank))
+    L.approx_args_set_maxrank(aa, C.c_size_t(rank))
+    return aa
+
+
+def init_value(L, ctl, aa, fn):
+    """c3control_init_value of the numpy function fn(x [n, 2]) -> [n]; returns (value function, the callback to keep alive)"""
+    def _term(n, x, out, a):
+        xx = np.ctypeslib.as_array(x, shape=(n, 2))
+        np.ctypeslib.as_array(out, shape=(n,))[:] = fn(xx)
+        return 0
+
+    term = FIBER_FN(_term)
+    return C.c_void_p(L.c3control_init_value(ctl.h, term, None, aa, 0)), term
+
+
+def nodal(L, vf, n0, n1):
+    """the value function vf (a pointer or its integer) at every node of an n0 x n1 grid"""
+    out = np.empty((n0, n1))
+    ind = np.zeros(2, dtype=np.uintp)
+    for a in range(n0):
+        for b in range(n1):
+            ind[:] = (a, b)
+            out[a, b] = L.valuef_eval_ind(C.c_void_p(vf), sp(ind))
+    return out
+
+
+def save_stages(out_path, L, V, nstages, n0, n1):
+    """the tail of an fh_child: V_s at every node of every stage saved under "V"; None from the solve (a CFL stop) saves an
+    empty array"""
+    if not V:
+        np.savez(out_path, V=np.zeros(0))
+        return
+    np.savez(out_path, V=np.array([nodal(L, V[s], n0, n1) for s in range(nstages + 1)]))
+
+
+def callbacks2d(drift_fn, diag_fn, stage_fn, psi_like_b, psi_like_o, psi_fn):
+    """ctypes callbacks (drift, diff, stage, boundcost, obscost) and the stopping cost, from functions of numpy (x[2], u)"""
+    def _x(p):
+        return np.array([p[0], p[1]])
+
+    def drift(t, x, u, out, jac, args):
+        out[0], out[1] = drift_fn(_x(x), u)
+        return 0
+
+    def diff(t, x, u, out, grad, args):
+        s = diag_fn(_x(x), u)
+        out[0], out[1], out[2], out[3] = s[0], 0.0, 0.0, s[1]
+        return 0
+
+    def stage(t, x, u, out, grad):
+        out[0] = stage_fn(_x(x), u)
+        return 0
+
+    def bcost(t, x, out):
+        out[0] = psi_like_b(_x(x))
+        return 0
+
+    def ocost(x, out):
+        out[0] = psi_like_o(_x(x))
+        return 0
+
+    def stop(t, x, out):
+        out[0] = psi_fn(_x(x))
+        return 0
+
+    return (DYN_FN(drift), DYN_FN(diff), STAGE_FN(stage), BOUND_FN(bcost), OBS_FN(ocost)), BOUND_FN(stop)
+
+
+def stop_control(w, callbacks, stop_cb, rank=11):
+    """(library, a Control in stop mode over workload w with its host callbacks, rank-`rank` interpolation arguments)"""
+    L = solver_lib()
+    ctl = Control(w, callbacks=callbacks, consistent_ends=None)
+    L.c3control_add_stopcost(ctl.h, stop_cb)
+    L.c3control_set_stopping.argtypes = [C.c_void_p, C.c_int]
+    L.c3control_set_stopping(ctl.h, 1)
+    return L, ctl, approx_args(L, rank)

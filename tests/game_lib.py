@@ -1,10 +1,11 @@
-"""Zero-sum games (c3sc_hip_set_game): device sources of two game models and a dense numpy restatement of the
-game backup of one node (in the style of tools/dense_truth.py), shared by the CPU and GPU tests and tools/game_bench.py.
+"""Zero-sum games (c3sc_hip_set_game): device sources of two game models and the game backup of one node, shared
+by the CPU and GPU tests and tools/game_bench.py.
 
-The restatement follows node_backup candidate for candidate: upwind rates with the +-1e-14 dead zone, Q = sum of the rates, a
-candidate with Q < 1e-14 skipped, dt = h2 / Q, value = dt stage + exp(-beta dt) (PV / Q + (1 - Q / Q) V_node); then the min-max
-over the (nu, nw) matrix of values: first strict '<' / '>' in both reductions, skipped candidates and emptied groups out."""
+The values of the pairs are backup_ref.candidate_values over the candidate list product(U, W); then the min-max over the
+(nu, nw) matrix of values: first strict '<' / '>' in both reductions, skipped candidates and emptied groups out."""
 import numpy as np
+
+import backup_ref as BR
 
 # 2-D linear-quadratic game: x0' = x1, x1' = u + w; stage x'x + r u^2 - g2 w^2.  prm = {sig0, sig1, r, g2}
 LQGAME = r"""
@@ -66,27 +67,8 @@ def product(U, W):
 def candidate_values(host, prm, x, V, U, W, h2, t, beta):
     """values [P, nu, nw] of every pair at P nodes x[P, D] with stencils V[P, 2D+1]; NaN = skipped (Q < 1e-14); and the
     per-node stationary flag"""
-    D = x.shape[1]
-    C = product(U, W)
-    nu, nw = len(np.atleast_2d(U)), len(np.atleast_2d(W))
-    xx = np.broadcast_to(x[:, None, :], (x.shape[0], len(C), D))
-    uu = np.broadcast_to(C[None], (x.shape[0],) + C.shape)
-    b, s, st = host(prm, xx, uu)
-    Q = np.zeros(b.shape[:-1])
-    PV = np.zeros(b.shape[:-1])
-    for m in range(D):
-        half = t[2 * m + 1] * (s[..., m] * s[..., m]) / 2.0
-        tb = t[2 * m] * b[..., m]
-        pm = np.where(b[..., m] < -1e-14, half - tb, half)
-        pp = np.where(b[..., m] > 1e-14, half + tb, half)
-        Q += pm + pp
-        PV += pm * V[:, None, 2 * m] + pp * V[:, None, 2 * m + 1]
-    bad = Q < 1e-14
-    Qs = np.where(bad, 1.0, Q)
-    dt = h2 / Qs
-    val = dt * st + np.exp(-beta * dt) * (PV / Qs + (1.0 - Qs / Qs) * V[:, None, 2 * D])
-    val = np.where(bad, np.nan, val)
-    return val.reshape(-1, nu, nw), bad.any(axis=1)
+    vals, stat, _ = BR.candidate_values(host, prm, x, V, product(U, W), h2, t, beta)
+    return vals.reshape(-1, len(np.atleast_2d(U)), len(np.atleast_2d(W))), stat
 
 
 def minmax(vals, order="minmax"):
@@ -123,42 +105,12 @@ def minmax(vals, order="minmax"):
     return out, idx, margin
 
 
-def node_states(w, k, idx):
-    """coordinates [F, N, D] of the nodes of fibers idx along dim k"""
-    xg = w.xgrid()
-    F, N, D = idx.shape[0], w.ngrid[k], w.dx
-    x = np.empty((F, N, D))
-    for m in range(D):
-        x[:, :, m] = xg[m][np.arange(N)][None, :] if m == k else xg[m][idx[:, m]][:, None]
-    return x
-
-
-def mca_constants(w):
-    """(h2, t) as BellmanEngine.configure sets them"""
-    xg = w.xgrid()
-    hs = [g[1] - g[0] for g in xg]
-    hmin = min([w.ub[0] - w.lb[0]] + hs)
-    h2 = hmin * hmin
-    t = []
-    for h in hs:
-        t += [h2 / h, h2 / h / h]
-    return h2, t
-
-
 def game_backup(w, host, k, idx, costs, absorbed, U, W, order, bcost, ocost):
-    """the game backup of every node of fibers idx from their stencils (costs [F, N, 2D+1], absorbed [F, N]): (value, pair
-    index, margin, stationary) of shape [F, N]"""
-    h2, t = mca_constants(w)
-    x = node_states(w, k, idx).reshape(-1, w.dx)
-    V = costs.reshape(-1, 2 * w.dx + 1)
-    vals, st = candidate_values(host, w.params, x, V, U, W, h2, t, w.discount)
-    out, ui, mg = minmax(vals, order)
-    ab = absorbed.reshape(-1)
-    out = np.where(ab == 1, bcost, np.where(ab == -1, ocost, out))
-    ui = np.where(ab != 0, -1, ui)
-    st = st & (ab == 0)
-    sh = absorbed.shape
-    return out.reshape(sh), ui.reshape(sh), mg.reshape(sh), st.reshape(sh)
+    """the game backup of every node of fibers idx from their stencils (costs [F, N, 2D+1], absorbed [F, N]); bcost, ocost: the
+    constant boundary and obstacle costs.  Returns (value, pair index, margin, stationary) of shape [F, N]"""
+    nu, nw = len(np.atleast_2d(U)), len(np.atleast_2d(W))
+    return BR.fibers(w, host, k, idx, costs, absorbed, lambda x: bcost, lambda x: ocost, cands=product(U, W),
+                     decide=lambda vals: minmax(vals.reshape(-1, nu, nw), order))[:4]
 
 
 # ---------------------------------------------------------------------------------------------------- the reference API
@@ -202,20 +154,10 @@ def lq_vi_workload(mid, n=11, rank=11, discount=0.1):
 def dense_sweep(w, V, U, W, order, bcost=100.0):
     """one sweep of the game's Markov chain on the whole grid of a 2-D workload with dim 0 absorbing and dim 1 reflecting
     (the library's neighbour rules, nodeutil.c:513-624 with consistent ends): V[n0, n1] -> (T V, saddle pair index, margin)"""
-    n0, n1 = V.shape
-    i0, i1 = np.meshgrid(np.arange(n0), np.arange(n1), indexing="ij")
-    lo1, hi1 = np.maximum(i1 - 1, 0), np.minimum(i1 + 1, n1 - 1)
-    lo0, hi0 = np.clip(i0 - 1, 0, n0 - 1), np.clip(i0 + 1, 0, n0 - 1)
-    S = np.stack([V[lo0, i1], V[hi0, i1], V[i0, lo1], V[i0, hi1], V], axis=-1).reshape(-1, 5)
-    xg = w.xgrid()
-    x = np.stack([xg[0][i0], xg[1][i1]], axis=-1).reshape(-1, 2)
-    h2, t = mca_constants(w)
-    vals, _ = candidate_values(lqgame_host, w.params, x, S, U, W, h2, t, w.discount)
-    out, ui, mg = minmax(vals, order)
-    ab = ((i0 == 0) | (i0 == n0 - 1)).reshape(-1)
-    out = np.where(ab, bcost, out)
-    ui = np.where(ab, -1, ui)
-    return out.reshape(n0, n1), ui.reshape(n0, n1), mg.reshape(n0, n1)
+    nu, nw = len(np.atleast_2d(U)), len(np.atleast_2d(W))
+    out, ui, mg, _, _ = BR.sweeps(w, lqgame_host, V, bcost, 1, cands=product(U, W),
+                                  decide=lambda vals: minmax(vals.reshape(-1, nu, nw), order))
+    return out[1], ui[0], mg[0]
 
 
 def vi_child(order, sweeps, out_path):
@@ -229,40 +171,15 @@ def vi_child(order, sweeps, out_path):
 
     mid = E.compile_model(LQGAME, 2, 2, ranks=(12,), name="lqgame_vi", game=True, **LQGAME_MASKS)
     w, U, W = lq_vi_workload(mid)
-    L = fl.lib()
-    for n in ("c3control_init_value", "c3control_vi_solve"):
-        getattr(L, n).restype = C.c_void_p
-    L.valuef_eval_ind.restype = C.c_double
+    L = fl.solver_lib()
     ctl = fl.Control(w, callbacks=lq_callbacks(), consistent_ends=None)
     u, ww = fl.f64(U), fl.f64(W)
     L.c3opt_set_brute_force_game(ctl.opt, C.c_size_t(1), C.c_size_t(len(u)), fl.dp(u), C.c_size_t(len(ww)), fl.dp(ww),
                                  C.c_int(GAME_ORDERS[order]))
-    aa = C.c_void_p(L.approx_args_init())
-    L.approx_args_set_cross_tol(aa, C.c_double(1e-12))
-    L.approx_args_set_round_tol(aa, C.c_double(1e-15))
-    L.approx_args_set_kickrank(aa, C.c_size_t(0))
-    L.approx_args_set_adapt(aa, C.c_int(0))
-    L.approx_args_set_startrank(aa, C.c_size_t(11))
-    L.approx_args_set_maxrank(aa, C.c_size_t(11))
-
-    def _start(n, x, out, a):
-        xx = np.ctypeslib.as_array(x, shape=(n, 2))
-        np.ctypeslib.as_array(out, shape=(n,))[:] = 1.0 + 0.3 * xx[:, 0] ** 2 + 0.2 * xx[:, 0] * xx[:, 1] + 0.1 * np.sin(xx[:, 1])
-        return 0
-
-    start = fl.FIBER_FN(_start)
-    cur = C.c_void_p(L.c3control_init_value(ctl.h, start, None, aa, 0))
+    aa = fl.approx_args(L)
+    cur, keep = fl.init_value(L, ctl, aa, lambda xx: 1.0 + 0.3 * xx[:, 0] ** 2 + 0.2 * xx[:, 0] * xx[:, 1] + 0.1 * np.sin(xx[:, 1]))
     n0, n1 = w.ngrid
-
-    def nodes(vf):
-        V = np.empty((n0, n1))
-        ind = np.zeros(2, dtype=np.uintp)
-        for a in range(n0):
-            for b in range(n1):
-                ind[:] = (a, b)
-                V[a, b] = L.valuef_eval_ind(vf, fl.sp(ind))
-        return V
-
+    nodes = lambda vf: fl.nodal(L, vf.value, n0, n1)
     hist = [nodes(cur)]
     for _ in range(sweeps):
         nxt = C.c_void_p(L.c3control_vi_solve(ctl.h, C.c_size_t(1), C.c_double(0.0), cur, aa, ctl.opt, C.c_int(0), None))

@@ -1,11 +1,10 @@
 """Finite-horizon problems (c3sc_hip_set_horizon_step): device sources of a decoupled 2-D LQR and a nonlinear
-model, a numpy restatement of the explicit backup of one node (in the style of game_lib.py), a dense explicit-chain recursion
-over a whole small grid and the Riccati solution of the LQR.  Shared by the CPU and GPU tests and tools/horizon_bench.py.
-
-The restatement follows node_backup's HORIZON branch candidate for candidate: upwind rates with the +-1e-14 dead zone,
-Q = sum of the rates, PV = sum p_i V_i, value = g delta + exp(-beta delta) (V_self + (delta / h^2) (PV - Q V_self)); no
-candidate is skipped (Q = 0 is "stay"); Q delta / h^2 > 1 flags CFL; the first strict minimum wins."""
+model, the explicit backup of the nodes of fibers and the dense explicit-chain recursion over a whole small grid (both
+backup_ref's, with the horizon step delta) and the Riccati solution of the LQR.  Shared by the CPU and GPU tests and
+tools/horizon_bench.py."""
 import numpy as np
+
+import backup_ref as BR
 
 # decoupled 2-D LQR: x_i' = u_i, diffusion sig per dimension, stage q |x|^2 + r |u|^2, boundary (terminal) cost s |x|^2.
 # prm = {sig, q, r, s}; s != q, so that P(t) and with it the optimal feedback change from stage to stage
@@ -60,85 +59,11 @@ def pendulum_host(prm, x, u):
     return b, s, st
 
 
-def mca_constants(w):
-    """(h2, t) as BellmanEngine.configure sets them"""
-    xg = w.xgrid()
-    hs = [g[1] - g[0] for g in xg]
-    hmin = min([w.ub[0] - w.lb[0]] + hs)
-    h2 = hmin * hmin
-    t = []
-    for h in hs:
-        t += [h2 / h, h2 / h / h]
-    return h2, t
-
-
-def candidate_values(host, prm, x, V, C, h2, t, beta, delta):
-    """explicit-scheme values [P, nc] of every candidate C[nc, du] at P nodes x[P, D] with stencils V[P, 2D+1], and the
-    per-candidate CFL flags [P, nc] (Q delta / h^2 > 1)"""
-    D = x.shape[1]
-    xx = np.broadcast_to(x[:, None, :], (x.shape[0], len(C), D))
-    uu = np.broadcast_to(C[None], (x.shape[0],) + C.shape)
-    b, s, st = host(prm, xx, uu)
-    Q = np.zeros(b.shape[:-1])
-    PV = np.zeros(b.shape[:-1])
-    for m in range(D):
-        half = t[2 * m + 1] * (s[..., m] * s[..., m]) / 2.0
-        tb = t[2 * m] * b[..., m]
-        pm = np.where(b[..., m] < -1e-14, half - tb, half)
-        pp = np.where(b[..., m] > 1e-14, half + tb, half)
-        Q += pm + pp
-        PV += pm * V[:, None, 2 * m] + pp * V[:, None, 2 * m + 1]
-    dh2 = delta / h2
-    Vs = V[:, None, 2 * D]
-    val = st * delta + np.exp(-beta * delta) * (Vs + dh2 * (PV - Q * Vs))
-    return val, Q * dh2 > 1.0
-
-
-def backup(vals, forced=None):
-    """(value, index, margin) per node of vals[P, nc]: the first strict minimum (np.argmin keeps the first of equal values);
-    forced: the index to apply per node instead.  margin: the relative gap to the runner-up (inf with one candidate)"""
-    P, nc = vals.shape
-    if forced is not None:
-        fi = np.asarray(forced).reshape(-1)
-        ok = (fi >= 0) & (fi < nc)
-        out = np.where(ok, vals[np.arange(P), np.clip(fi, 0, nc - 1)], 0.0)
-        return out, np.where(ok, fi, -1), np.full(P, np.inf)
-    ui = np.argmin(vals, axis=1)
-    out = vals[np.arange(P), ui]
-    srt = np.sort(vals, axis=1)
-    margin = (srt[:, 1] - srt[:, 0]) / np.maximum(1.0, np.abs(srt[:, 0])) if nc > 1 else np.full(P, np.inf)
-    return out, ui, margin
-
-
-def node_states(w, k, idx):
-    """coordinates [F, N, D] of the nodes of fibers idx along dim k"""
-    xg = w.xgrid()
-    F, N, D = idx.shape[0], w.ngrid[k], w.dx
-    x = np.empty((F, N, D))
-    for m in range(D):
-        x[:, :, m] = xg[m][np.arange(N)][None, :] if m == k else xg[m][idx[:, m]][:, None]
-    return x
-
-
 def horizon_backup(w, host, k, idx, costs, absorbed, delta, bcost, ocost, forced=None):
     """the explicit backup of every node of fibers idx from their stencils (costs [F, N, 2D+1], absorbed [F, N]); bcost, ocost:
     callables of x[P, D] (the model's boundary and obstacle costs).  Returns (value, index, margin, cfl) of shape [F, N]"""
-    h2, t = mca_constants(w)
-    x = node_states(w, k, idx).reshape(-1, w.dx)
-    V = costs.reshape(-1, 2 * w.dx + 1)
-    vals, cfl = candidate_values(host, w.params, x, V, np.asarray(w.cands, dtype=np.float64), h2, t, w.discount, delta)
-    out, ui, mg = backup(vals, forced)
-    if forced is not None:
-        fi = np.asarray(forced).reshape(-1)
-        cfl = cfl[np.arange(len(fi)), np.clip(fi, 0, vals.shape[1] - 1)] & (fi >= 0)
-    else:
-        cfl = cfl.any(axis=1)
-    ab = absorbed.reshape(-1)
-    out = np.where(ab == 1, bcost(x), np.where(ab == -1, ocost(x), out))
-    ui = np.where(ab != 0, -1, ui)
-    cfl = cfl & (ab == 0)
-    sh = absorbed.shape
-    return out.reshape(sh), ui.reshape(sh), mg.reshape(sh), cfl.reshape(sh)
+    out, ui, mg, _, cfl = BR.fibers(w, host, k, idx, costs, absorbed, bcost, ocost, delta=delta, forced=forced)
+    return out, ui, mg, cfl
 
 
 # ---------------------------------------------------------------------------------------------------- the LQR problem
@@ -168,26 +93,9 @@ def dense_chain(w, host, terminal, bcost, delta, nstages):
     """the explicit chain on the whole grid of a 2-D workload whose dimensions both absorb (the boundary nodes are absorbed and
     keep their boundary cost, every interior node's neighbours are grid nodes): V[s] for s = 0 .. nstages, V[nstages] =
     terminal at the nodes (bcost on the boundary); returns (V [nstages + 1, n0, n1], cfl seen)"""
-    n0, n1 = w.ngrid
-    xg = w.xgrid()
-    i0, i1 = np.meshgrid(np.arange(n0), np.arange(n1), indexing="ij")
-    x = np.stack([xg[0][i0], xg[1][i1]], axis=-1).reshape(-1, 2)
-    ab = ((i0 == 0) | (i0 == n0 - 1) | (i1 == 0) | (i1 == n1 - 1)).reshape(-1)
-    h2, t = mca_constants(w)
-    C = np.asarray(w.cands, dtype=np.float64)
-    Vn = np.where(ab, bcost(x), terminal(x)).reshape(n0, n1)
-    out = [Vn]
-    anycfl = False
-    lo0, hi0 = np.clip(i0 - 1, 0, n0 - 1), np.clip(i0 + 1, 0, n0 - 1)
-    lo1, hi1 = np.clip(i1 - 1, 0, n1 - 1), np.clip(i1 + 1, 0, n1 - 1)
-    for _ in range(nstages):
-        S = np.stack([Vn[lo0, i1], Vn[hi0, i1], Vn[i0, lo1], Vn[i0, hi1], Vn], axis=-1).reshape(-1, 5)
-        vals, cfl = candidate_values(host, w.params, x, S, C, h2, t, w.discount, delta)
-        v, _, _ = backup(vals)
-        anycfl |= bool((cfl.any(axis=1) & ~ab).any())
-        Vn = np.where(ab, bcost(x), v).reshape(n0, n1)
-        out.append(Vn)
-    return np.array(out[::-1]), anycfl
+    x, ab, _ = BR.grid2(w)
+    V, _, _, anycfl, _ = BR.sweeps(w, host, np.where(ab, bcost(x), terminal(x)), bcost(x), nstages, delta=delta)
+    return V[::-1].copy(), anycfl
 
 
 def riccati(prm, T, beta=0.0, nsub=20000):
@@ -261,37 +169,9 @@ def fh_child(out_path, delta=LQR_DELTA, nstages=LQR_STAGES):
 
     mid = E.compile_model(LQR, 2, 2, ranks=(4, 8, 12), name="lqr_fh_api", horizon=True, **LQR_MASKS)
     w = lqr_workload(mid, rank=11)
-    L = fl.lib()
-    for n in ("c3control_init_value", "c3control_fh_solve"):
-        getattr(L, n).restype = C.c_void_p
-    L.c3control_fh_solve.restype = C.POINTER(C.c_void_p)
-    L.valuef_eval_ind.restype = C.c_double
+    L = fl.solver_lib()
     ctl = fl.Control(w, callbacks=lqr_callbacks(), consistent_ends=None)
-    aa = C.c_void_p(L.approx_args_init())
-    L.approx_args_set_cross_tol(aa, C.c_double(1e-12))
-    L.approx_args_set_round_tol(aa, C.c_double(1e-15))
-    L.approx_args_set_kickrank(aa, C.c_size_t(0))
-    L.approx_args_set_adapt(aa, C.c_int(0))
-    L.approx_args_set_startrank(aa, C.c_size_t(11))
-    L.approx_args_set_maxrank(aa, C.c_size_t(11))
-
-    def _term(n, x, out, a):
-        xx = np.ctypeslib.as_array(x, shape=(n, 2))
-        np.ctypeslib.as_array(out, shape=(n,))[:] = lqr_terminal(LQR_PRM, xx)
-        return 0
-
-    term = fl.FIBER_FN(_term)
-    vt = C.c_void_p(L.c3control_init_value(ctl.h, term, None, aa, 0))
+    aa = fl.approx_args(L)
+    vt, keep = fl.init_value(L, ctl, aa, lambda xx: lqr_terminal(LQR_PRM, xx))
     V = L.c3control_fh_solve(ctl.h, C.c_size_t(nstages), C.c_double(delta), vt, aa, ctl.opt, C.c_int(0))
-    n0, n1 = w.ngrid
-    if not V:
-        np.savez(out_path, V=np.zeros(0))
-        return
-    out = np.empty((nstages + 1, n0, n1))
-    ind = np.zeros(2, dtype=np.uintp)
-    for s in range(nstages + 1):
-        for a in range(n0):
-            for b in range(n1):
-                ind[:] = (a, b)
-                out[s, a, b] = L.valuef_eval_ind(C.c_void_p(V[s]), fl.sp(ind))
-    np.savez(out_path, V=out)
+    fl.save_stages(out_path, L, V, nstages, *w.ngrid)

@@ -5,16 +5,17 @@ problem on its whole 11 x 11 grid (dense_vi), the replay of a rollout with inter
 rollouts (inv_rollouts).  Shared by the CPU and GPU tests.  It shares no code with the kernels; the value at a target and the interpolants are jump_lib's.
 
 The operator is the quasi-variational inequality V(x) = min(min_u backup_u(x), min_m [k_m(x) + Vt(y_m(x))]).  The candidates are
-scanned first (jump_lib.candidate_values: the plain backup, with the Poisson term where jumps are on), then the interventions,
+scanned first (backup_ref.candidate_values: the plain backup, with the Poisson term where jumps are on), then the interventions,
 m ascending: c_m = k_m(x) + Vt(y_m); the running minimum of the c_m starts at +inf and is taken by the first strict '<', a cost
 that is not finite never wins; the best intervention then beats the scan's winner where it is strictly smaller and where the
-scan left no valid candidate.  Intervention m has the index ncand + 1 + m (ncand is the stop action's).  Vt is jump_lib.vjump:
+scan left no valid candidate (backup_ref.backup with c).  Intervention m has the index ncand + 1 + m (ncand is the stop
+action's).  Vt is jump_lib.vjump:
 periodic wrap, the obstacle or boundary cost at a target that left the domain, otherwise the interpolant clamped to the hull."""
 import dataclasses
 
 import numpy as np
 
-import horizon_lib as H
+import backup_ref as BR
 import jump_lib as JL
 import stop_lib as SL
 
@@ -174,82 +175,29 @@ def impulse_values(w, impulses, interp, x, bcost, ocost, constelm=False):
     return c
 
 
-def best_impulse(c):
-    """(ival [P], imark [P]) of c [P, M]: the running minimum from +inf by the first strict '<', m ascending; -1: none finite"""
-    P, M = c.shape
-    ival, imark = np.full(P, np.inf), np.full(P, -1)
-    for m in range(M):
-        take = c[:, m] < ival
-        ival = np.where(take, c[:, m], ival)
-        imark = np.where(take, m, imark)
-    return ival, imark
-
-
-def backup(vals, c, forced=None, fault=None):
-    """(value, index, margin) per node of the candidates' values vals [P, nc] (NaN = skipped) and the interventions' c [P, M]:
-    the first strict minimum of the candidates, then the best intervention, which wins where strictly smaller and where no
-    candidate was valid; its index is nc + 1 + m.  forced: the index to apply (nc + 1 + m: intervention m; -1, nc or a skipped
-    candidate: 0.0 and -1).  margin: best against second best over every action, relative to max(1, |best|).
-    fault: a planted mistake for the tests of this file's own comparisons ("index": the index nc + m, "le": '<=' for '<')"""
-    P, nc = vals.shape
-    M = c.shape[1]
-    if forced is not None:
-        fi = np.asarray(forced).reshape(-1)
-        v = vals[np.arange(P), np.clip(fi, 0, nc - 1)]
-        ok = (fi >= 0) & (fi < nc) & ~np.isnan(v)
-        imp = fi > nc
-        ci = c[np.arange(P), np.clip(fi - nc - 1, 0, M - 1)]
-        return np.where(imp, ci, np.where(ok, v, 0.0)), np.where(imp, fi, np.where(ok, fi, -1)), np.full(P, np.inf)
-    filled = np.where(np.isnan(vals), np.inf, vals)
-    cu = np.argmin(filled, axis=1)  # the first of equal minima
-    cont = filled[np.arange(P), cu]
-    any_ok = np.isfinite(cont)
-    ival, imark = best_impulse(c)
-    if fault == "le":
-        ival, imark = c.min(axis=1), M - 1 - np.argmin(c[:, ::-1], axis=1)  # the last of equal minima
-        imark = np.where(np.isfinite(ival), imark, -1)
-    take = (imark >= 0) & (~any_ok | ((ival <= cont) if fault == "le" else (ival < cont)))
-    out = np.where(take, ival, np.where(any_ok, cont, 0.0))
-    ui = np.where(take, nc + (0 if fault == "index" else 1) + imark, np.where(any_ok, cu, -1))
-    allv = np.sort(np.concatenate([filled, c], axis=1), axis=1)
-    with np.errstate(invalid="ignore"):  # inf - inf where fewer than two actions are valid: replaced below
-        margin = (allv[:, 1] - allv[:, 0]) / np.maximum(1.0, np.abs(np.where(np.isfinite(allv[:, 0]), allv[:, 0], 1.0)))
-    margin = np.where(np.isfinite(allv[:, 0]), np.where(np.isfinite(allv[:, 1]), margin, np.inf), np.inf)
-    return out, ui, margin
-
-
 def impulse_fibers(w, host, impulses, interp, k, idx, costs, absorbed, bcost, ocost, forced=None, constelm=False, jumps=None,
                    with_impulses=True):
     """the backup with interventions of every node of fibers idx from their stencils (costs [F, N, 2D+1], absorbed [F, N]) and
     the interpolant `interp` of the same value function; jumps: a jump model of jump_lib to add the Poisson term (None: no
     jumps).  Returns (value, index, margin, stationary, c [F, N, M]) of shape [F, N]"""
-    h2, t = H.mca_constants(w)
-    x = H.node_states(w, k, idx).reshape(-1, w.dx)
-    V = costs.reshape(-1, 2 * w.dx + 1)
-    C = np.asarray(w.cands, dtype=np.float64)
+    x = BR.node_states(w, k, idx).reshape(-1, w.dx)
     if jumps is not None:
         jrate, J = JL.jump_terms(w, jumps, interp, x, bcost, ocost, constelm)
     else:
         jrate, J = np.zeros(len(x)), np.zeros(len(x))
-    vals, stat, _ = JL.candidate_values(host, w.params, x, V, C, h2, t, w.discount, jrate, J)
     c = impulse_values(w, impulses, interp, x, bcost, ocost, constelm)
     if not with_impulses:
         c = np.full(c.shape, np.inf)
-    out, ui, mg = backup(vals, c, forced)
-    ab = absorbed.reshape(-1)
-    out = np.where(ab == 1, bcost(x), np.where(ab == -1, ocost(x), out))
-    ui = np.where(ab != 0, -1, ui)
-    sh = absorbed.shape
-    return out.reshape(sh), ui.reshape(sh), mg.reshape(sh), (stat & (ab == 0)).reshape(sh), c.reshape(sh + (c.shape[1],))
+    out, ui, mg, stat, _ = BR.fibers(w, host, k, idx, costs, absorbed, bcost, ocost, jrate, jrate * J, c=c, forced=forced)
+    return out, ui, mg, stat, c.reshape(absorbed.shape + (c.shape[1],))
 
 
 def point_decisions(w, host, impulses, interp, x, V, ab, bcost, ocost, constelm=False):
     """the controller's decision at arbitrary states x [n, D] from their off-grid stencils V [n, 2D+1] (ab: -1 inside an
     obstacle): (index [n], margin [n]) of the backup with interventions, -1 where absorbed"""
-    h2, t = H.mca_constants(w)
-    zero = np.zeros(len(x))
-    vals, _, _ = JL.candidate_values(host, w.params, x, V, np.asarray(w.cands, dtype=np.float64), h2, t, w.discount, zero, zero)
-    _, ui, mg = backup(vals, impulse_values(w, impulses, interp, x, bcost, ocost, constelm))
+    h2, t = BR.mca_constants(w)
+    vals, _, _ = BR.candidate_values(host, w.params, x, V, np.asarray(w.cands, dtype=np.float64), h2, t, w.discount)
+    _, ui, mg = BR.backup(vals, c=impulse_values(w, impulses, interp, x, bcost, ocost, constelm))
     return np.where(ab != 0, -1, ui), mg
 
 
@@ -327,28 +275,25 @@ def dense_vi(w, host, impulses, bcost, V0, nsweeps, with_impulses=True, fault=No
     boundary nodes keep their boundary cost, and the targets read the bilinear interpolant of the sweep's input V (a target
     beyond a face pays the boundary cost there).  Returns ([V_0, V_1, .. V_nsweeps], the indices of every sweep).
     fault = "stale": the obstacle k_m + V(y_m) is read from the continuation values of the sweep before instead of from V"""
-    n0, n1 = w.ngrid
-    x, ab, sten = JL._grid2(w)
-    h2, t = H.mca_constants(w)
-    C = np.asarray(w.cands, dtype=np.float64)
-    zero = np.zeros(len(x))
+    x, ab, sten = BR.grid2(w)
+    h2, t = BR.mca_constants(w)
     ocost = lambda xx: np.zeros(len(xx))
-    Vn = np.where(ab, bcost(x), np.asarray(V0).reshape(-1)).reshape(n0, n1)
-    out, dec = [Vn], []
-    cont_prev = Vn
-    for _ in range(nsweeps):
-        vals, _, _ = JL.candidate_values(host, w.params, x, sten(Vn), C, h2, t, w.discount, zero, zero)
-        src = cont_prev if fault == "stale" else Vn
+    start = np.where(ab, bcost(x), np.asarray(V0).reshape(-1)).reshape(w.ngrid)
+    before = [None]  # the input of the sweep before
+
+    def terms(Vn):
+        src = Vn
+        if fault == "stale":
+            src = start
+            if before[0] is not None:
+                vals, _, _ = BR.candidate_values(host, w.params, x, sten(before[0]), np.asarray(w.cands, dtype=np.float64), h2, t, w.discount)
+                src = np.where(ab, bcost(x), np.nanmin(vals, axis=1)).reshape(w.ngrid)
+            before[0] = Vn
         c = impulse_values(w, impulses, JL.Nodal(w, src), x, bcost, ocost)
-        if not with_impulses:
-            c = np.full(c.shape, np.inf)
-        v, ui, _ = backup(vals, c, fault=fault if fault in ("index", "le") else None)
-        cont = np.nanmin(vals, axis=1)
-        cont_prev = np.where(ab, bcost(x), cont).reshape(n0, n1)
-        Vn = np.where(ab, bcost(x), v).reshape(n0, n1)
-        out.append(Vn)
-        dec.append(np.where(ab, -1, ui).reshape(n0, n1))
-    return np.array(out), np.array(dec)
+        return None, None, c if with_impulses else np.full(c.shape, np.inf), None
+
+    V, dec, _, _, _ = BR.sweeps(w, host, start, bcost(x), nsweeps, terms, fault=fault if fault in ("index", "le") else None)
+    return V, dec
 
 
 # ---------------------------------------------------------------------------------------------------- rollouts
@@ -412,9 +357,11 @@ def impulse_callback(impulses, prm, d):
 
 
 def inv_callbacks(prm):
-    return SL._callbacks(lambda x, u: (u[0] - prm[1], u[1] - prm[1]), lambda x, u: (prm[0], prm[0]),
-                         lambda x, u: float(inv_run(prm, np.asarray(x)[None])[0]) + prm[4] * (u[0] * u[0] + u[1] * u[1]),
-                         lambda x: float(inv_bcost(prm, np.asarray(x)[None])[0]), lambda x: 0.0, lambda x: 0.0)[0]
+    import facade_lib as fl
+
+    return fl.callbacks2d(lambda x, u: (u[0] - prm[1], u[1] - prm[1]), lambda x, u: (prm[0], prm[0]),
+                          lambda x, u: float(inv_run(prm, np.asarray(x)[None])[0]) + prm[4] * (u[0] * u[0] + u[1] * u[1]),
+                          lambda x: float(inv_bcost(prm, np.asarray(x)[None])[0]), lambda x: 0.0, lambda x: 0.0)[0]
 
 
 def vi_child(out_path, nsweeps=INV_VI_SWEEPS):
@@ -431,23 +378,20 @@ def vi_child(out_path, nsweeps=INV_VI_SWEEPS):
 
     mid = E.compile_model(INV, 2, 2, ranks=(4, 8, 12), name="inventory_api", nimpulse=INV_NIMPULSE, **INV_MASKS)
     w = inv_workload(mid)
-    L = fl.lib()
-    for n in ("c3control_init_value", "c3control_vi_solve"):
-        getattr(L, n).restype = C.c_void_p
-    L.valuef_eval_ind.restype = C.c_double
+    L = fl.solver_lib()
     ctl = fl.Control(w, callbacks=inv_callbacks(INV_PRM), consistent_ends=None)
     cb = impulse_callback(inv_impulses, INV_PRM, 2)
     L.c3control_add_impulses.argtypes = [C.c_void_p, C.c_int, type(cb)]
     L.c3control_add_impulses(ctl.h, INV_NIMPULSE, cb)
     L.c3control_set_impulses.argtypes = [C.c_void_p, C.c_int]
     L.c3control_set_impulses(ctl.h, 1)
-    aa = JL._approx_args(L)
-    v, keep = SL._init_value(L, ctl, aa, lambda xx: inv_bcost(INV_PRM, xx))
+    aa = fl.approx_args(L)
+    v, keep = fl.init_value(L, ctl, aa, lambda xx: inv_bcost(INV_PRM, xx))
     n0, n1 = w.ngrid
-    out = [SL._nodal(L, v.value, n0, n1)]
+    out = [fl.nodal(L, v.value, n0, n1)]
     for s in range(nsweeps):
         v = C.c_void_p(L.c3control_vi_solve(ctl.h, C.c_size_t(1), C.c_double(0.0), v, aa, ctl.opt, C.c_int(0), None))
-        out.append(SL._nodal(L, v.value, n0, n1))
+        out.append(fl.nodal(L, v.value, n0, n1))
         if s == 0:
             sys.stdout.flush()
             sys.stderr.flush()
@@ -489,7 +433,7 @@ def inv_rollouts(w, V, x0, n, dt, nsteps, rng, chunk=1 << 16):
     the step slot still takes dt --; otherwise the discounted stage cost times dt and x + b dt + sigma sqrt(dt) xi.  A path
     alive after the last step adds the discounted V(x_N).  Returns (costs [n], interventions per path [n])"""
     prm, beta = w.params, w.discount
-    h2, t = H.mca_constants(w)
+    h2, t = BR.mca_constants(w)
     g = w.xgrid()[0]
     h, lb, ub = g[1] - g[0], g[0], g[-1]
     C = np.asarray(w.cands, dtype=np.float64)
@@ -502,7 +446,6 @@ def inv_rollouts(w, V, x0, n, dt, nsteps, rng, chunk=1 << 16):
         m = min(chunk, n - c0)
         x = np.tile(np.asarray(x0, dtype=np.float64), (m, 1))
         J, alive, niv = np.zeros(m), np.ones(m, dtype=bool), np.zeros(m, dtype=int)
-        zero = np.zeros(m)
         for s in range(nsteps + 1):
             disc = np.exp(-beta * (s * dt))
             gone = alive & ((x < lb) | (x > ub)).any(axis=1)
@@ -514,8 +457,8 @@ def inv_rollouts(w, V, x0, n, dt, nsteps, rng, chunk=1 << 16):
             xc = cl(x)  # exited paths are frozen outside: their controller's result is not used
             S = np.stack([Vn.value(cl(xc - [h, 0])), Vn.value(cl(xc + [h, 0])), Vn.value(cl(xc - [0, h])), Vn.value(cl(xc + [0, h])),
                           Vn.value(xc)], axis=-1)
-            vals, _, _ = JL.candidate_values(inv_host, prm, xc, S, C, h2, t, beta, zero, zero)
-            _, ui, _ = backup(vals, impulse_values(w, inv_impulses, Vn, xc, bc, oc))
+            vals, _, _ = BR.candidate_values(inv_host, prm, xc, S, C, h2, t, beta)
+            _, ui, _ = BR.backup(vals, c=impulse_values(w, inv_impulses, Vn, xc, bc, oc))
             iv = alive & (ui > len(C))
             mk = np.where(iv, ui - len(C) - 1, 0)
             k, y = inv_impulses(prm, x)

@@ -6,8 +6,7 @@ the kernels.
 
 The chain is the rate form of Kushner and Dupuis, section 5.6: a jump is one more transition with the un-normalised rate
 h2 lambda(x) to the mark average J(x) = sum_m pi_m(x) Vjump(y_m), so Q and PV of every candidate gain h2 lambda and h2 lambda J
-and everything downstream is the backup without jumps (horizon_lib / stop_lib state it; it is written out again here with the
-two extra terms).  Vjump(y): periodic dimensions are wrapped into [lb, ub); a target inside an obstacle pays the obstacle
+and everything downstream is the backup without jumps (backup_ref states it; the two terms are its q0 and pv0).  Vjump(y): periodic dimensions are wrapped into [lb, ub); a target inside an obstacle pays the obstacle
 cost, one outside [lb, ub] on an absorbing dimension the boundary cost (the obstacle first, as the rollouts' exit test chooses);
 any other target pays the interpolant of the function train -- multilinear, or the nearer node with constelm -- clamped to
 the grid hull."""
@@ -16,6 +15,7 @@ import os
 
 import numpy as np
 
+import backup_ref as BR
 import horizon_lib as H
 import stop_lib as SL
 
@@ -273,7 +273,7 @@ def vjump(w, interp, y, bcost, ocost, constelm=False):
 
 def jump_terms(w, jumps, interp, x, bcost, ocost, constelm=False):
     """(h2 lambda [P], J [P]) at the states x [P, D]; J sums the marks in ascending order"""
-    h2, _ = H.mca_constants(w)
+    h2, _ = BR.mca_constants(w)
     lam, pi, y = jumps(w.params, x)
     J = np.zeros(len(x))
     for m in range(pi.shape[1]):
@@ -282,117 +282,39 @@ def jump_terms(w, jumps, interp, x, bcost, ocost, constelm=False):
 
 
 # ---------------------------------------------------------------------------------------------------- one node
-def candidate_values(host, prm, x, V, C, h2, t, beta, jrate, J, delta=None):
-    """values [P, nc] of every candidate with the jump term (NaN = skipped: infinite horizon and Q < 1e-14), the per-node
-    stationary flag and the CFL flags [P, nc]; delta: the horizon step (None: the infinite-horizon form)"""
-    D = x.shape[1]
-    xx = np.broadcast_to(x[:, None, :], (x.shape[0], len(C), D))
-    uu = np.broadcast_to(C[None], (x.shape[0],) + C.shape)
-    b, s, st = host(prm, xx, uu)
-    Q = np.zeros(b.shape[:-1]) + jrate[:, None]
-    PV = np.zeros(b.shape[:-1]) + (jrate * J)[:, None]
-    for m in range(D):
-        half = t[2 * m + 1] * (s[..., m] * s[..., m]) / 2.0
-        tb = t[2 * m] * b[..., m]
-        pm = np.where(b[..., m] < -1e-14, half - tb, half)
-        pp = np.where(b[..., m] > 1e-14, half + tb, half)
-        Q += pm + pp
-        PV += pm * V[:, None, 2 * m] + pp * V[:, None, 2 * m + 1]
-    Vs = V[:, None, 2 * D]
-    if delta is not None:
-        dh2 = delta / h2
-        val = st * delta + np.exp(-beta * delta) * (Vs + dh2 * (PV - Q * Vs))
-        return val, np.zeros(len(x), dtype=bool), Q * dh2 > 1.0
-    bad = Q < 1e-14
-    Qs = np.where(bad, 1.0, Q)
-    dt = h2 / Qs
-    val = dt * st + np.exp(-beta * dt) * (PV / Qs + (1.0 - Qs / Qs) * Vs)
-    return np.where(bad, np.nan, val), bad.any(axis=1), np.zeros(val.shape, dtype=bool)
-
-
-def backup(vals, psi=None, forced=None):
-    """(value, index, margin) per node of vals [P, nc] (NaN = skipped): the first strict minimum, then -- with psi [P] -- the
-    stop action of index nc, which wins where strictly smaller and where no candidate was valid.  forced: the index to apply
-    (nc: psi).  margin: |best - second| over every action, relative to max(1, |best|); inf with a single action"""
-    P, nc = vals.shape
-    if forced is not None:
-        fi = np.asarray(forced).reshape(-1)
-        v = vals[np.arange(P), np.clip(fi, 0, nc - 1)]
-        ok = (fi >= 0) & (fi < nc) & ~np.isnan(v)
-        stop = (fi == nc) & (psi is not None)
-        out = np.where(stop, psi if psi is not None else 0.0, np.where(ok, v, 0.0))
-        return out, np.where(stop, nc, np.where(ok, fi, -1)), np.full(P, np.inf)
-    allv = np.where(np.isnan(vals), np.inf, vals)
-    if psi is not None:
-        allv = np.concatenate([allv, psi[:, None]], axis=1)
-    ui = np.argmin(allv, axis=1)  # the first of equal minima; psi comes last
-    out = allv[np.arange(P), ui]
-    none = ~np.isfinite(out)
-    srt = np.sort(allv, axis=1)
-    margin = (srt[:, 1] - srt[:, 0]) / np.maximum(1.0, np.abs(np.where(none, 1.0, srt[:, 0]))) if allv.shape[1] > 1 else np.full(P, np.inf)
-    return np.where(none, 0.0, out), np.where(none, -1, ui), np.where(none, np.inf, margin)
-
-
 def jump_fibers(w, host, jumps, interp, k, idx, costs, absorbed, bcost, ocost, delta=None, psi_fn=None, forced=None, constelm=False,
                 with_jumps=True):
     """the backup with jumps of every node of fibers idx from their stencils (costs [F, N, 2D+1], absorbed [F, N]) and the
     interpolant `interp` of the same value function.  Returns (value, index, margin, stationary, cfl, rate, J) of shape [F, N]"""
-    h2, t = H.mca_constants(w)
-    x = H.node_states(w, k, idx).reshape(-1, w.dx)
-    V = costs.reshape(-1, 2 * w.dx + 1)
-    C = np.asarray(w.cands, dtype=np.float64)
+    x = BR.node_states(w, k, idx).reshape(-1, w.dx)
     if with_jumps:
         jrate, J = jump_terms(w, jumps, interp, x, bcost, ocost, constelm)
     else:
         jrate, J = np.zeros(len(x)), np.zeros(len(x))
-    vals, stat, cfl = candidate_values(host, w.params, x, V, C, h2, t, w.discount, jrate, J, delta)
-    out, ui, mg = backup(vals, None if psi_fn is None else psi_fn(x), forced)
-    if forced is not None:
-        fi = np.asarray(forced).reshape(-1)
-        cfl = cfl[np.arange(len(fi)), np.clip(fi, 0, len(C) - 1)] & (fi >= 0) & (fi < len(C))
-    else:
-        cfl = cfl.any(axis=1)
-    ab = absorbed.reshape(-1)
-    out = np.where(ab == 1, bcost(x), np.where(ab == -1, ocost(x), out))
-    ui = np.where(ab != 0, -1, ui)
-    sh = absorbed.shape
-    return (out.reshape(sh), ui.reshape(sh), mg.reshape(sh), (stat & (ab == 0)).reshape(sh), (cfl & (ab == 0)).reshape(sh),
-            jrate.reshape(sh), J.reshape(sh))
+    res = BR.fibers(w, host, k, idx, costs, absorbed, bcost, ocost, jrate, jrate * J, None if psi_fn is None else psi_fn(x),
+                    delta=delta, forced=forced)
+    return res + (jrate.reshape(absorbed.shape), J.reshape(absorbed.shape))
 
 
 # ---------------------------------------------------------------------------------------------------- dense chains
-def _grid2(w):
-    n0, n1 = w.ngrid
-    xg = w.xgrid()
-    i0, i1 = np.meshgrid(np.arange(n0), np.arange(n1), indexing="ij")
-    x = np.stack([xg[0][i0], xg[1][i1]], axis=-1).reshape(-1, 2)
-    ab = ((i0 == 0) | (i0 == n0 - 1) | (i1 == 0) | (i1 == n1 - 1)).reshape(-1)
-    lo0, hi0 = np.clip(i0 - 1, 0, n0 - 1), np.clip(i0 + 1, 0, n0 - 1)
-    lo1, hi1 = np.clip(i1 - 1, 0, n1 - 1), np.clip(i1 + 1, 0, n1 - 1)
-    sten = lambda Vn: np.stack([Vn[lo0, i1], Vn[hi0, i1], Vn[i0, lo1], Vn[i0, hi1], Vn], axis=-1).reshape(-1, 5)
-    return x, ab, sten
+def dense_terms(w, jumps, bcost, ocost):
+    """the per-sweep callable of backup_ref.sweeps: the jump terms read from the bilinear interpolant of the sweep's input"""
+    x = BR.grid2(w)[0]
+
+    def terms(Vn):
+        jrate, J = jump_terms(w, jumps, Nodal(w, Vn), x, bcost, ocost)
+        return jrate, jrate * J, None, None
+
+    return terms
 
 
 def dense_chain(w, host, jumps, psi_fn, delta, nstages, stopping=True):
     """the explicit chain with jumps of a 2-D workload whose dimensions both absorb: V[s] for s = 0 .. nstages with
     V[nstages] = psi, the boundary nodes keep psi (the boundary cost of the put); the jump targets read the bilinear
     interpolant of V[s + 1].  Returns (V [nstages + 1, n0, n1], index [nstages, n0, n1], cfl seen)"""
-    n0, n1 = w.ngrid
-    x, ab, sten = _grid2(w)
-    h2, t = H.mca_constants(w)
-    C = np.asarray(w.cands, dtype=np.float64)
-    psi = psi_fn(x)
-    Vn = psi.reshape(n0, n1)
-    out, dec, anycfl = [Vn], [], False
-    for _ in range(nstages):
-        jrate, J = jump_terms(w, jumps, Nodal(w, Vn), x, psi_fn, psi_fn)
-        vals, _, cfl = candidate_values(host, w.params, x, sten(Vn), C, h2, t, w.discount, jrate, J, delta)
-        v, ui, _ = backup(vals, psi if stopping else None)
-        anycfl |= bool((cfl.any(axis=1) & ~ab).any())
-        Vn = np.where(ab, psi, v).reshape(n0, n1)
-        out.append(Vn)
-        dec.append(np.where(ab, -1, ui).reshape(n0, n1))
-    return np.array(out[::-1]), np.array(dec[::-1]), anycfl
+    psi = psi_fn(BR.grid2(w)[0])
+    V, ui, _, anycfl, _ = BR.sweeps(w, host, psi, psi, nstages, dense_terms(w, jumps, psi_fn, psi_fn), psi if stopping else None, delta)
+    return V[::-1].copy(), ui[::-1].copy(), anycfl
 
 
 # ---------------------------------------------------------------------------------------------------- rollouts
@@ -469,7 +391,7 @@ def put_rollouts(w, stack, x0, n, dt, rng, chunk=1 << 16):
     last step adds the discounted V_N(x_N).  Returns the costs [n]"""
     N = len(stack) - 1
     prm, beta = w.params, w.discount
-    h2, t = H.mca_constants(w)
+    h2, t = BR.mca_constants(w)
     g = w.xgrid()[0]
     h, lb, ub = g[1] - g[0], g[0], g[-1]
     C = np.asarray(w.cands, dtype=np.float64)
@@ -492,8 +414,8 @@ def put_rollouts(w, stack, x0, n, dt, rng, chunk=1 << 16):
             S = np.stack([V.value(cl(x - [h, 0])), V.value(cl(x + [h, 0])), V.value(cl(x - [0, h])), V.value(cl(x + [0, h])),
                           V.value(x)], axis=-1)
             jrate, Jv = jump_terms(w, put_jumps, V, x, psi_fn, psi_fn)
-            vals, _, _ = candidate_values(SL.put_host, prm, x, S, C, h2, t, beta, jrate, Jv, dt)
-            _, ui, _ = backup(vals, psi_fn(x))
+            vals, _, _ = BR.candidate_values(SL.put_host, prm, x, S, C, h2, t, beta, jrate, jrate * Jv, dt)
+            _, ui, _ = BR.backup(vals, psi_fn(x))
             stop = alive & (ui == len(C))
             J = J + np.where(stop, disc * psi_fn(x), 0.0)
             alive = alive & ~stop
@@ -563,19 +485,9 @@ def dense_vi(w, host, jumps, bcost, V0, nsweeps):
     """value iteration sweeps of the jump operator on the whole grid of a 2-D workload whose dimensions both absorb (the
     boundary nodes keep their boundary cost; the jump targets read the bilinear interpolant of the sweep's input):
     [V_0, V_1, .. V_nsweeps]"""
-    n0, n1 = w.ngrid
-    x, ab, sten = _grid2(w)
-    h2, t = H.mca_constants(w)
-    C = np.asarray(w.cands, dtype=np.float64)
-    Vn = np.where(ab, bcost(x), V0.reshape(-1)).reshape(n0, n1)
-    out = [Vn]
-    for _ in range(nsweeps):
-        jrate, J = jump_terms(w, jumps, Nodal(w, Vn), x, bcost, lambda xx: np.full(len(xx), 5.0))
-        vals, _, _ = candidate_values(host, w.params, x, sten(Vn), C, h2, t, w.discount, jrate, J)
-        v, _, _ = backup(vals)
-        Vn = np.where(ab, bcost(x), v).reshape(n0, n1)
-        out.append(Vn)
-    return np.array(out)
+    x, ab, _ = BR.grid2(w)
+    terms = dense_terms(w, jumps, bcost, lambda xx: np.full(len(xx), 5.0))
+    return BR.sweeps(w, host, np.where(ab, bcost(x), V0.reshape(-1)), bcost(x), nsweeps, terms)[0]
 
 
 def dense_pi(w, host, jumps, bcost, P, nsweeps, mu=None):
@@ -584,24 +496,12 @@ def dense_pi(w, host, jumps, bcost, P, nsweeps, mu=None):
     policy's backup of V_s at the live nodes (jump terms from the interpolant of V_s), the boundary cost at the absorbed ones --
     what c3control_pi_solve(maxiter = s, policy = P) applies.  mu [n0, n1]: a policy to evaluate in place of the greedy one.
     Returns (mu [n0, n1] (-1: absorbed), margin [n0, n1] (inf: absorbed), [V_0, V_1, .. V_nsweeps])"""
-    n0, n1 = w.ngrid
-    x, ab, sten = _grid2(w)
-    h2, t = H.mca_constants(w)
-    C = np.asarray(w.cands, dtype=np.float64)
-
-    def vals(Vn):
-        jrate, J = jump_terms(w, jumps, Nodal(w, Vn), x, bcost, lambda xx: np.full(len(xx), 5.0))
-        return candidate_values(host, w.params, x, sten(Vn), C, h2, t, w.discount, jrate, J)[0]
-
-    Vn = np.asarray(P, dtype=np.float64).reshape(n0, n1)
-    _, greedy, margin = backup(vals(Vn))
-    pol = greedy if mu is None else np.asarray(mu).reshape(-1)
-    out = [Vn]
-    for _ in range(nsweeps):
-        v, _, _ = backup(vals(Vn), forced=pol)
-        Vn = np.where(ab, bcost(x), v).reshape(n0, n1)
-        out.append(Vn)
-    return np.where(ab, -1, pol).reshape(n0, n1), np.where(ab, np.inf, margin).reshape(n0, n1), np.array(out)
+    x, ab, _ = BR.grid2(w)
+    terms = dense_terms(w, jumps, bcost, lambda xx: np.full(len(xx), 5.0))
+    _, greedy, margin, _, _ = BR.sweeps(w, host, P, bcost(x), 1, terms)
+    pol = greedy[0] if mu is None else np.where(ab.reshape(w.ngrid), -1, np.asarray(mu).reshape(w.ngrid))
+    V = BR.sweeps(w, host, P, bcost(x), nsweeps, terms, forced=pol)[0]
+    return pol, np.where(ab.reshape(w.ngrid), np.inf, margin[0]), V
 
 
 def vi_child(out_path, nsweeps=LQR_VI_SWEEPS):
@@ -615,19 +515,16 @@ def vi_child(out_path, nsweeps=LQR_VI_SWEEPS):
 
     mid = E.compile_model(LQR, 2, 2, ranks=(4, 8, 12), name="lqr_jd_api", njump=LQR_NJUMP, **LQR_MASKS)
     w = lqr_vi_workload(mid)
-    L = fl.lib()
-    for n in ("c3control_init_value", "c3control_vi_solve"):
-        getattr(L, n).restype = C.c_void_p
-    L.valuef_eval_ind.restype = C.c_double
+    L = fl.solver_lib()
     ctl = fl.Control(w, callbacks=H.lqr_callbacks(LQR_PRM), consistent_ends=None)
     keep = add_jumps(L, ctl, lqr_jumps, LQR_PRM, 2, LQR_NJUMP)
-    aa = _approx_args(L)
-    v, keep2 = SL._init_value(L, ctl, aa, lambda xx: H.lqr_terminal(LQR_PRM, xx))
+    aa = fl.approx_args(L)
+    v, keep2 = fl.init_value(L, ctl, aa, lambda xx: H.lqr_terminal(LQR_PRM, xx))
     n0, n1 = w.ngrid
-    out = [SL._nodal(L, v.value, n0, n1)]
+    out = [fl.nodal(L, v.value, n0, n1)]
     for _ in range(nsweeps):
         v = C.c_void_p(L.c3control_vi_solve(ctl.h, C.c_size_t(1), C.c_double(0.0), v, aa, ctl.opt, C.c_int(0), None))
-        out.append(SL._nodal(L, v.value, n0, n1))
+        out.append(fl.nodal(L, v.value, n0, n1))
     L.c3control_add_policy_sim(ctl.h, v, ctl.opt, None)
     n, N = SIM_N, SIM_STEPS
     x0 = np.ascontiguousarray(np.random.default_rng(9).uniform(-1.6, 1.6, size=(n, 2)))
@@ -640,19 +537,6 @@ def vi_child(out_path, nsweeps=LQR_VI_SWEEPS):
 
 
 SIM_N, SIM_STEPS, SIM_DT, SIM_SEED = 48, 32, 0.02, 77
-
-
-def _approx_args(L, rank=11):
-    import ctypes as C
-
-    aa = C.c_void_p(L.approx_args_init())
-    L.approx_args_set_cross_tol(aa, C.c_double(1e-12))
-    L.approx_args_set_round_tol(aa, C.c_double(1e-15))
-    L.approx_args_set_kickrank(aa, C.c_size_t(0))
-    L.approx_args_set_adapt(aa, C.c_int(0))
-    L.approx_args_set_startrank(aa, C.c_size_t(rank))
-    L.approx_args_set_maxrank(aa, C.c_size_t(rank))
-    return aa
 
 
 PI_BEFORE, PI_AFTER = (1, 3), (1, 3, 6)  # evaluation sweeps asked of c3control_pi_solve before and after the vi step
@@ -673,19 +557,16 @@ def pi_child(out_path):
 
     mid = E.compile_model(LQR, 2, 2, ranks=(12,), name="lqr_jd_pi_api", njump=LQR_NJUMP, **LQR_MASKS)
     w = lqr_vi_workload(mid)
-    L = fl.lib()
-    for n in ("c3control_init_value", "c3control_vi_solve", "c3control_pi_solve"):
-        getattr(L, n).restype = C.c_void_p
-    L.valuef_eval_ind.restype = C.c_double
+    L = fl.solver_lib()
     ctl = fl.Control(w, callbacks=H.lqr_callbacks(LQR_PRM), consistent_ends=None)
     keep = add_jumps(L, ctl, lqr_jumps, LQR_PRM, 2, LQR_NJUMP)
-    aa = _approx_args(L)
-    v0, keep2 = SL._init_value(L, ctl, aa, lambda xx: H.lqr_terminal(LQR_PRM, xx))
+    aa = fl.approx_args(L)
+    v0, keep2 = fl.init_value(L, ctl, aa, lambda xx: H.lqr_terminal(LQR_PRM, xx))
     n0, n1 = w.ngrid
 
     def pi(K):
         v = C.c_void_p(L.c3control_pi_solve(ctl.h, C.c_size_t(K), C.c_double(0.0), v0, aa, ctl.opt, C.c_int(0), None))
-        return SL._nodal(L, v.value, n0, n1)
+        return fl.nodal(L, v.value, n0, n1)
 
     def mark(line):
         sys.stdout.flush()
@@ -695,10 +576,10 @@ def pi_child(out_path):
     before = [pi(K) for K in PI_BEFORE]
     mark(PI_MARKERS[0])
     v1 = C.c_void_p(L.c3control_vi_solve(ctl.h, C.c_size_t(1), C.c_double(0.0), v0, aa, ctl.opt, C.c_int(0), None))
-    vi = SL._nodal(L, v1.value, n0, n1)
+    vi = fl.nodal(L, v1.value, n0, n1)
     mark(PI_MARKERS[1])
     after = [pi(K) for K in PI_AFTER]
-    np.savez(out_path, V0=SL._nodal(L, v0.value, n0, n1), before=np.array(before), vi=vi, after=np.array(after))
+    np.savez(out_path, V0=fl.nodal(L, v0.value, n0, n1), before=np.array(before), vi=vi, after=np.array(after))
 
 
 def fh_child(out_path, delta=PUT_DELTA, nstages=PUT_STAGES):
@@ -712,12 +593,8 @@ def fh_child(out_path, delta=PUT_DELTA, nstages=PUT_STAGES):
     mid = E.compile_model(PUT, 2, 1, ranks=(4, 8, 12), name="put_jd_api", horizon=True, stop=True, njump=PUT_NJUMP, **PUT_MASKS)
     w = put_workload(mid, rank=11)
     cbs, stop_cb = SL.put_callbacks(PUT_PRM)
-    L, ctl, aa = SL._api_setup(w, cbs, stop_cb)
+    L, ctl, aa = fl.stop_control(w, cbs, stop_cb)
     keep = add_jumps(L, ctl, put_jumps, PUT_PRM, 2, PUT_NJUMP)
-    vt, keep2 = SL._init_value(L, ctl, aa, lambda xx: SL.put_psi(PUT_PRM, xx))
+    vt, keep2 = fl.init_value(L, ctl, aa, lambda xx: SL.put_psi(PUT_PRM, xx))
     V = L.c3control_fh_solve(ctl.h, C.c_size_t(nstages), C.c_double(delta), vt, aa, ctl.opt, C.c_int(0))
-    n0, n1 = w.ngrid
-    if not V:
-        np.savez(out_path, V=np.zeros(0))
-        return
-    np.savez(out_path, V=np.array([SL._nodal(L, V[s], n0, n1) for s in range(nstages + 1)]))
+    fl.save_stages(out_path, L, V, nstages, *w.ngrid)

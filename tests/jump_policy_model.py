@@ -5,7 +5,7 @@ JumpPolicyProblem has the interface cross_reference.check_iteration and simulate
 .bellman_fibers) and the rules of cross_memo_model.PolicyMemoProblem: per live node the greedy candidate of the POLICY train, the
 first one stored stays for a policy tag; the value is that candidate's backup on the context's OWN train; absorbed and obstacle
 nodes are never stored; a batch is refused (CaseRefused) unless best and second-best of the policy train differ by GAP_TOL of
-the scale at every stored node.  The per-candidate values are jump_lib's (candidate_values with the jump terms of jump_terms, the
+the scale at every stored node.  The per-candidate values are backup_ref's (candidate_values with the jump terms of jump_lib.jump_terms, the
 targets read from jump_lib.Train): no oracle run has a jump term.  The 2d + 1 stencil values and the flags are the oracle's
 (Problem.stencil_fibers under consistent ends), which reads the grid, the boundary types and the train, and no model.
 
@@ -17,9 +17,9 @@ import dataclasses
 
 import numpy as np
 
+import backup_ref as BR
 import cross_memo_model as mm
 import cross_singular_cases as sc
-import horizon_lib as H
 import jump_lib as JL
 import stop_lib as SL
 from c3sc_amd import workloads as wl
@@ -62,14 +62,14 @@ class JumpPolicyProblem:
         """(Q [F, N, nc] of every candidate with the jump term, flags [F, N], x [F * N, D])"""
         w = self.w
         costs, ab = problem.stencil_fibers(k, idx)
-        h2, t = H.mca_constants(w)
-        x = H.node_states(w, k, idx).reshape(-1, w.dx)
+        h2, t = BR.mca_constants(w)
+        x = BR.node_states(w, k, idx).reshape(-1, w.dx)
         if with_jumps:
             jrate, J = JL.jump_terms(w, self.jumps, train, x, self.bcost, self.ocost)
         else:
             jrate, J = np.zeros(len(x)), np.zeros(len(x))
-        vals, stat, _ = JL.candidate_values(self.host, w.params, x, costs.reshape(-1, 2 * w.dx + 1), np.asarray(w.cands, dtype=np.float64),
-                                            h2, t, w.discount, jrate, J)
+        vals, stat, _ = BR.candidate_values(self.host, w.params, x, costs.reshape(-1, 2 * w.dx + 1), np.asarray(w.cands, dtype=np.float64),
+                                            h2, t, w.discount, jrate, jrate * J)
         assert not np.isnan(vals).any() and not stat.any(), "sigma > 0: no candidate is skipped"
         return vals.reshape(ab.shape + (w.ncand,)), ab, x
 

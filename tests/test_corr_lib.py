@@ -9,8 +9,8 @@ import numpy as np
 import pytest
 
 from c3sc_amd import workloads as wl
+import backup_ref as BR
 import corr_lib as CL
-import horizon_lib as H
 import jump_lib as JL
 import stop_lib as SL
 
@@ -38,16 +38,16 @@ def test_known_answer(a):
     xg = w.xgrid()
     np.testing.assert_allclose(V, np.outer(xg[0], xg[1]), rtol=0, atol=1e-15)
     ix, x, S = _dense_stencils(w, V)
-    h2, t = H.mca_constants(w)
+    h2, t = BR.mca_constants(w)
     C = np.asarray(w.cands, dtype=np.float64)
     interior = np.all((ix > 0) & (ix < np.array(w.ngrid) - 1), axis=1)
     cq, cpv, r = CL.corr_terms(w, CL.known_covar, CL.KNOWN_PAIRS, V, ix, x, S)
     assert not CL.dominance(w, CL.known_host, CL.KNOWN_PAIRS, x, r).any()
-    vals, _, cfl = CL.candidate_values(CL.known_host, w.params, x, S, C, h2, t, 0.0, cq, cpv, CL.KNOWN_DELTA)
+    vals, _, cfl = BR.candidate_values(CL.known_host, w.params, x, S, C, h2, t, 0.0, cq, cpv, CL.KNOWN_DELTA)
     assert not cfl.any()
     ref = x[:, 0] * x[:, 1] + CL.KNOWN_DELTA * a
     assert np.abs(vals[interior, 0] - ref[interior]).max() <= 1e-14
-    plain, _, _ = CL.candidate_values(CL.known_host, w.params, x, S, C, h2, t, 0.0, 0.0 * cq, 0.0 * cpv, CL.KNOWN_DELTA)
+    plain, _, _ = BR.candidate_values(CL.known_host, w.params, x, S, C, h2, t, 0.0, 0.0 * cq, 0.0 * cpv, CL.KNOWN_DELTA)
     assert np.abs(plain[interior, 0] - x[interior, 0] * x[interior, 1]).max() <= 1e-14
 
 
@@ -80,7 +80,7 @@ def test_chain_rows_sum_to_one_are_non_negative_and_have_the_right_moments(model
     rng = np.random.default_rng(5)
     xg = [np.asarray(g) for g in w.xgrid()]
     hs = np.array([g[1] - g[0] for g in xg])
-    h2, _ = H.mca_constants(w)
+    h2, _ = BR.mca_constants(w)
     C = np.asarray(w.cands, dtype=np.float64)
     for ix in _sample_nodes(w, rng):
         x = np.array([xg[m][ix[m]] for m in range(w.dx)])
@@ -145,7 +145,7 @@ def test_precondition_the_references_decisions_are_clear(name, horizon):
     cores = wl.synth_cores(w)
     V = CL.full_values(w, cores)
     ix, x, S = _dense_stencils(w, V)
-    h2, t = H.mca_constants(w)
+    h2, t = BR.mca_constants(w)
     C = np.asarray(w.cands, dtype=np.float64)
     live = np.ones(len(ix), dtype=bool)
     for m in range(w.dx):
@@ -155,6 +155,6 @@ def test_precondition_the_references_decisions_are_clear(name, horizon):
     live &= ~inobs
     cq, cpv, r = CL.corr_terms(w, covar, pairs, V, ix, x, S)
     assert not CL.dominance(w, SL.lqrn_host, pairs, x, r)[live].any(), "the well-posed models satisfy dominance"
-    vals, _, _ = CL.candidate_values(SL.lqrn_host, w.params, x[live], S[live], C, h2, t, w.discount, cq[live], cpv[live], delta if horizon else None)
-    _, _, mg = JL.backup(vals)
+    vals, _, _ = BR.candidate_values(SL.lqrn_host, w.params, x[live], S[live], C, h2, t, w.discount, cq[live], cpv[live], delta if horizon else None)
+    _, _, mg = BR.backup(vals)
     assert (mg <= 1e-9).mean() <= 0.001, (name, (mg <= 1e-9).mean())

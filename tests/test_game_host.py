@@ -123,7 +123,7 @@ def test_game_lib_with_nw_1_is_the_oracle_backup(oracle):
     """anchor of the tests' reference: game_lib's dense restatement, run with nw = 1 (a dummy maximiser the physics ignore), equals
     the oracle's Bellman backup (bellman_optimal over the brute-force list) on every node of a small lqg2d grid"""
     from c3sc_amd import workloads as wl
-    from game_lib import mca_constants
+    from backup_ref import mca_constants
 
     w = wl.c1_lqg2d().scaled(ngrid=(13, 11), rank=4)
     cores = wl.synth_cores(w)

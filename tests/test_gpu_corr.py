@@ -16,14 +16,15 @@
   equal the dense chains to 1e-9 at every stage / sweep."""
 import ctypes as C
 import dataclasses
-import os
 
 import numpy as np
 import pytest
 
 from c3sc_amd import engine as E
 from c3sc_amd import workloads as wl
+import backup_ref as BR
 import corr_lib as CL
+import gpu_case_lib as GC
 import horizon_lib as H
 import jump_lib as JL
 import stop_lib as SL
@@ -76,7 +77,7 @@ def _case(ids, model, rank, discount, horizon, stop, prm=None):
         idx = wl.synth_fibers(w, k0, 64)
         costs, ab = eng.stencil_fibers_host(k0, idx)
         out = CL.corr_fibers(w, SL.lqrn_host, covar, pairs, Vfull, k0, idx, costs, ab, bcost, ocost, delta, jumps=jumps, interp=tr)[0]
-        x = H.node_states(w, k0, idx).reshape(-1, w.dx)
+        x = BR.node_states(w, k0, idx).reshape(-1, w.dx)
         live = ab.reshape(-1) == 0
         c1 = w.params[5]
         v = np.unique(out.reshape(-1)[live] - c1 * (x[live] ** 2).sum(-1))
@@ -133,7 +134,7 @@ def _check_case(ids, model, rank, discount, horizon, stop, ks=(0, 1), prm=None, 
         assert bool(dom.any()) == expect_dominance
         if not expect_dominance:
             assert status == 0, "the cases stay inside the CFL rule and dominance and have no stationary node"
-        a = covar(w.params, H.node_states(w, k, idx).reshape(-1, w.dx)[live.reshape(-1)])
+        a = covar(w.params, BR.node_states(w, k, idx).reshape(-1, w.dx)[live.reshape(-1)])
         signs |= np.array([(a > 0).any(), (a < 0).any()])
         # the forced path shares Q0 and PV0: the minimising run's own indices reproduce its values, a random policy its own
         f_out, f_ab = eng.policy_fibers_host(k, idx, ui)
@@ -159,13 +160,6 @@ def test_per_wave_corr_vs_numpy(ids, rank, discount, horizon, stop):
     assert any(",1>" in k for k in kernels) and any(",2>" in k for k in kernels), kernels  # N = 21 and N = 70: both NPL forms
 
 
-def _fpw_lds_bytes(w, k, rp, npl, cw):
-    """dynamic LDS of a staged fiber-per-wave launch (launch_fpw.hpp: fpw_geometry), as tests/test_gpu_stop.py states it"""
-    ws = 4 * rp + 2 * w.dx * rp + 64 * npl
-    per = (rp if k in (0, w.dx - 1) else rp * rp) | 1
-    return 8 * (4 * ws + w.ngrid[k] * per + w.ncand * cw)
-
-
 @pytest.mark.parametrize("discount", [0.3, 0.0])
 @pytest.mark.parametrize("horizon", [False, True], ids=["infinite", "horizon"])
 @pytest.mark.parametrize("stop", [False, True], ids=["nostop", "stop"])
@@ -174,8 +168,8 @@ def test_per_wave_corr_rank_12_l2_form(ids, discount, horizon, stop):
     stages in, so the corr kernel that reads the varying core from global memory runs"""
     w = CL.lqr3_workload(ids["lqr3"], discount=discount)
     cw = 3 + 1 + 2 * 3 + 1
-    assert _fpw_lds_bytes(w, 1, 12, 2, cw) > 160 * 1024, "the staged form would fit: this case would not run the L2 form"
-    assert _fpw_lds_bytes(w, 1, 12, 2, cw) - 8 * 128 * 145 < 160 * 1024  # ... and the L2 form's own layout fits
+    assert GC.fpw_lds_bytes(w, 1, 12, 2, cw) > 160 * 1024, "the staged form would fit: this case would not run the L2 form"
+    assert GC.fpw_lds_bytes(w, 1, 12, 2, cw) - 8 * 128 * 145 < 160 * 1024  # ... and the L2 form's own layout fits
     kernels, _ = _check_case(ids, "lqr3", 12, discount, horizon, stop, ks=(1,))
     assert kernels == {"k_fiber_per_wave<rtc:lqr3_cd,12,2>"}, kernels
 
@@ -197,8 +191,8 @@ def test_known_answer(ids, a):
     xg = w.xgrid()
     for k in (0, 1):
         idx = wl.synth_fibers(w, k, 16)
-        x = H.node_states(w, k, idx)
-        ixs = CL.node_indices(w, k, idx).reshape(x.shape)
+        x = BR.node_states(w, k, idx)
+        ixs = BR.node_indices(w, k, idx).reshape(x.shape)
         interior = np.all((ixs > 0) & (ixs < np.array(w.ngrid) - 1), axis=-1)
         eng.set_correlation(False)
         out, ui, ab = eng.bellman_fibers_host(k, idx)
@@ -256,10 +250,6 @@ def test_with_jumps_horizon_and_stop(ids):
     assert all("lqr_cd_jump,4," in k for k in kernels), kernels
 
 
-def _ptrs(ts):
-    return (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-
-
 @pytest.mark.parametrize("model", ["lqr", "lqr3_small"])
 def test_all_forms_equal_the_per_dimension_calls(ids, model):
     import torch
@@ -287,7 +277,7 @@ def test_all_forms_equal_the_per_dimension_calls(ids, model):
         assert L.c3sc_hip_bellman_fibers(h, k, sizes[s], idx[s].data_ptr(), out[s].data_ptr(), ui[s].data_ptr(), ab[s].data_ptr(), None) == 0
         assert eng.last_kernel().startswith("k_fiber_per_wave<rtc:"), eng.last_kernel()
     a_out, a_ui, a_ab = fresh()
-    assert L.c3sc_hip_bellman_fibers_all(h, d, KS, FS, _ptrs(idx), _ptrs(a_out), _ptrs(a_ui), _ptrs(a_ab), C.c_void_p(None)) == 0
+    assert L.c3sc_hip_bellman_fibers_all(h, d, KS, FS, GC.ptrs(idx), GC.ptrs(a_out), GC.ptrs(a_ui), GC.ptrs(a_ab), C.c_void_p(None)) == 0
     torch.cuda.synchronize()
     for s in range(d):
         assert not torch.isnan(out[s]).any() and (ab[s] == 0).any()
@@ -295,7 +285,7 @@ def test_all_forms_equal_the_per_dimension_calls(ids, model):
     # the switch is honoured: without it the same calls give other values
     eng.set_correlation(False)
     n_out, n_ui, n_ab = fresh()
-    assert L.c3sc_hip_bellman_fibers_all(h, d, KS, FS, _ptrs(idx), _ptrs(n_out), _ptrs(n_ui), _ptrs(n_ab), C.c_void_p(None)) == 0
+    assert L.c3sc_hip_bellman_fibers_all(h, d, KS, FS, GC.ptrs(idx), GC.ptrs(n_out), GC.ptrs(n_ui), GC.ptrs(n_ab), C.c_void_p(None)) == 0
     torch.cuda.synchronize()
     assert any(not torch.equal(n_out[s], out[s]) for s in range(d))
     eng.set_correlation(True)
@@ -303,7 +293,7 @@ def test_all_forms_equal_the_per_dimension_calls(ids, model):
     for s, k in enumerate(ks):
         assert L.c3sc_hip_policy_fibers(h, k, sizes[s], idx[s].data_ptr(), pol[s].data_ptr(), p_out[s].data_ptr(), p_ab[s].data_ptr(), None) == 0
     q_out, _, q_ab = fresh()
-    assert L.c3sc_hip_policy_fibers_all(h, d, KS, FS, _ptrs(idx), _ptrs(pol), _ptrs(q_out), _ptrs(q_ab), C.c_void_p(None)) == 0
+    assert L.c3sc_hip_policy_fibers_all(h, d, KS, FS, GC.ptrs(idx), GC.ptrs(pol), GC.ptrs(q_out), GC.ptrs(q_ab), C.c_void_p(None)) == 0
     torch.cuda.synchronize()
     for s in range(d):
         assert torch.equal(q_out[s], p_out[s]) and torch.equal(q_ab[s], p_ab[s]) and torch.equal(p_ab[s], ab[s]), f"policy, dimension {s}"
@@ -374,23 +364,12 @@ def test_refusals(ids):
 
 
 # ---------------------------------------------------------------------------------------------------- the reference API
-def _child(prog):
-    import subprocess
-    import sys
-
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, C3SC_CROSS_TRACE="1")
-    env["PYTHONPATH"] = os.pathsep.join([root, os.path.join(root, "tests")] + ([env["PYTHONPATH"]] if env.get("PYTHONPATH") else []))
-    return subprocess.run([sys.executable, "-c", prog], cwd=os.path.dirname(os.path.abspath(__file__)), env=env, capture_output=True,
-                          text=True, timeout=900)
-
-
 def test_vi_solve_through_the_reference_api(tmp_path):
     """the correlated LQR through libc3sc.so in a child process: c3control_vi_solve sweep by sweep (11 x 11, rank 11, host
     callbacks and c3control_add_covariance beside the device model).  The first sweep passes the first-fiber check against the
     host twin; every sweep equals the dense Markov-chain value iteration to 1e-9"""
     out = tmp_path / "vi.npz"
-    r = _child(f"import corr_lib; corr_lib.vi_child({str(out)!r})")
+    r = GC.child(f"import corr_lib; corr_lib.vi_child({str(out)!r})")
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     V = np.load(out)["V"]
     w = CL.lqr_vi_workload(0)
@@ -411,7 +390,7 @@ def test_fh_solve_of_the_heston_put_through_the_reference_api(tmp_path):
     """the American put under Heston through libc3sc.so in a child process: c3control_fh_solve in stop and correlation mode on
     11 x 11 with 20 stages equals the dense chain stage by stage to 1e-9, and differs from the rho = 0 chain by far more"""
     out = tmp_path / "fh.npz"
-    r = _child(f"import corr_lib; corr_lib.fh_child({str(out)!r})")
+    r = GC.child(f"import corr_lib; corr_lib.fh_child({str(out)!r})")
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     assert "C3SC_STATUS_DOMINANCE" not in r.stderr and "C3SC_STATUS_CFL" not in r.stderr
     V = np.load(out)["V"]

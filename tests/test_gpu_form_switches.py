@@ -14,8 +14,8 @@ import pytest
 
 from c3sc_amd import engine as E
 from c3sc_amd import workloads as wl
+import backup_ref as BR
 import corr_lib as CL
-import horizon_lib as H
 import impulse_lib as IL
 import jump_lib as JL
 import stop_lib as SL
@@ -58,7 +58,7 @@ def test_gray_code_walk_of_the_switches_leaves_no_stale_bit():
                               interp=tr, with_corr=bool(s & CORR))[0]
 
     # psi's constant between two nodes' continuation values at their median, so that both decisions occur (test_gpu_corr.py: _case)
-    x = H.node_states(w, K, idx).reshape(-1, w.dx)
+    x = BR.node_states(w, K, idx).reshape(-1, w.dx)
     live = ab.reshape(-1) == 0
     v = np.unique(reference(JUMP | CORR, None).reshape(-1)[live] - w.params[5] * (x[live] ** 2).sum(-1))
     c0 = float(0.5 * (v[len(v) // 2 - 1] + v[len(v) // 2]))

@@ -24,6 +24,7 @@ import pytest
 
 from c3sc_amd import engine as E
 from c3sc_amd import workloads as wl
+import backup_ref as BR
 import game_lib
 from game_lib import (LQGAME, LQGAME_MASKS, LQGAME_PRM, PURSUIT, PURSUIT_MASKS, PURSUIT_PRM, game_backup, lqgame_host, product,
                       pursuit_host)
@@ -153,7 +154,7 @@ def test_closed_loops_apply_the_saddle_pair(ids, order):
     np.testing.assert_array_equal(sim["u"].cpu().numpy(), ode["u"].cpu().numpy())
     V, ab = eng.stencil_points(x0)
     V, ab = V.cpu().numpy(), ab.cpu().numpy()
-    h2, t = game_lib.mca_constants(w)
+    h2, t = BR.mca_constants(w)
     vals, _ = game_lib.candidate_values(lqgame_host, w.params, x0.cpu().numpy(), V, U_LQ, W_LQ, h2, t, w.discount)
     _, ui, mg = game_lib.minmax(vals, order)
     u0 = ode["u"].cpu().numpy()[:, 0, :]
@@ -177,8 +178,8 @@ def test_policy_evaluation_applies_the_given_pair(ids, order):
         pol = rng.integers(0, len(U_LQ) * len(W_LQ), (100, w.ngrid[k])).astype(np.int32)
         out, ab = eng.policy_fibers_host(k, idx, pol)
         costs, _ = eng.stencil_fibers_host(k, idx)
-        h2, t = game_lib.mca_constants(w)
-        x = game_lib.node_states(w, k, idx).reshape(-1, 2)
+        h2, t = BR.mca_constants(w)
+        x = BR.node_states(w, k, idx).reshape(-1, 2)
         vals, _ = game_lib.candidate_values(lqgame_host, w.params, x, costs.reshape(-1, 5), U_LQ, W_LQ, h2, t, w.discount)
         ref = vals.reshape(len(x), -1)[np.arange(len(x)), pol.reshape(-1)].reshape(out.shape)
         ref = np.where(ab == 1, 100.0, np.where(ab == -1, 0.0, ref))

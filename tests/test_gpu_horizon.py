@@ -12,19 +12,17 @@
   dt or with too many steps."""
 import ctypes as C
 import dataclasses
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from c3sc_amd import engine as E
 from c3sc_amd import workloads as wl
+import backup_ref as BR
+import gpu_case_lib as GC
 import horizon_lib as H
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ERR_ARG, ERR_UNSUPPORTED = 1, 3
 STATUS_CFL = 2
 
@@ -98,7 +96,7 @@ def test_per_wave_horizon_vs_numpy(ids, case, rank, discount):
 
 def test_cfl_violation_raises_the_status_bit(ids):
     w = lqr_random_workload(ids["lqr"], 4, 0.1)
-    h2, t = H.mca_constants(w)
+    h2, t = BR.mca_constants(w)
     for delta, flagged in ((0.02, False), (2.0, True)):
         eng = _engine(w, delta)
         eng.status(clear=True)
@@ -112,15 +110,6 @@ def test_cfl_violation_raises_the_status_bit(ids):
         assert np.all(np.abs(out - r_out) <= 1e-12 * np.maximum(1.0, np.abs(r_out)))
 
 
-def _train(V):
-    U, S, Vt = np.linalg.svd(V)
-    r = int((S > 1e-13 * S[0]).sum())
-    assert r <= 8, r
-    c0 = (U[:, :r] * S[None, :r]).reshape(V.shape[0], 1, r)
-    c1 = np.ascontiguousarray(Vt[:r, :].T).reshape(V.shape[1], r, 1)
-    return [1, r, 1], [c0, c1]
-
-
 @pytest.fixture(scope="module")
 def lqr_solve(ids):
     """the LQR solved stage by stage on the device and by the dense chain: (engine, device stages, dense stages, trains)"""
@@ -131,7 +120,7 @@ def lqr_solve(ids):
     eng = E.BellmanEngine(0)
     n = H.LQR_N
     Vn = dense[-1]
-    ranks, cores = _train(Vn)
+    ranks, cores = GC.train(Vn, 8)
     eng.configure(dataclasses.replace(w, ranks=tuple(ranks)), cores)
     eng.set_horizon_step(H.LQR_DELTA)
     idx = np.zeros((n, 2), dtype=np.int32)
@@ -143,7 +132,7 @@ def lqr_solve(ids):
         out, ui, ab = eng.bellman_fibers_host(0, idx)  # fiber j along dim 0: out[j, i] = V_n(x_i, x_j)
         Vn = np.ascontiguousarray(out.T)
         dev.append(Vn)
-        ranks, cores = _train(Vn)
+        ranks, cores = GC.train(Vn, 8)
         trains.append((ranks, cores))
     assert eng.status() == 0
     return eng, np.array(dev[::-1]), dense, trains[::-1]
@@ -249,16 +238,6 @@ def test_errors(ids, lqr_solve):
     assert L.c3sc_hip_set_horizon_step(seng.h, C.c_double(H.LQR_DELTA)) == 0
 
 
-def _interp(G, xg, y):
-    """bilinear interpolant of the nodal matrix G on the grid xg x xg at the points y[P, 2] (inside the grid)"""
-    h = xg[1] - xg[0]
-    i = np.clip(np.floor((y[:, 0] - xg[0]) / h).astype(int), 0, len(xg) - 2)
-    j = np.clip(np.floor((y[:, 1] - xg[0]) / h).astype(int), 0, len(xg) - 2)
-    a = (y[:, 0] - xg[i]) / h
-    b = (y[:, 1] - xg[j]) / h
-    return (1 - a) * (1 - b) * G[i, j] + a * (1 - b) * G[i + 1, j] + (1 - a) * b * G[i, j + 1] + a * b * G[i + 1, j + 1]
-
-
 def test_noise_free_rollouts_apply_the_stage_policy_and_pay_v_n(lqr_solve):
     """without noise every step is checkable: the control of step k is the explicit scheme's argmin over the stencil of V_{k+1}
     at x_k, and J is the discounted stage costs plus V_N(x_N).  LQR_PRM has s != q, so the stages' policies differ"""
@@ -269,7 +248,7 @@ def test_noise_free_rollouts_apply_the_stage_policy_and_pay_v_n(lqr_solve):
     w = H.lqr_workload(0)
     xg = w.xgrid()[0]
     h = xg[1] - xg[0]
-    h2, t = H.mca_constants(w)
+    h2, t = BR.mca_constants(w)
     C2 = H.lqr_cands()
     x0 = np.array([[0.8, -0.4], [0.4, 0.75], [-0.7, 0.3], [0.55, 0.55]])
     n, N = len(x0), H.LQR_STAGES
@@ -282,33 +261,26 @@ def test_noise_free_rollouts_apply_the_stage_policy_and_pay_v_n(lqr_solve):
     sure = differ = 0
     for k in range(N):
         xk = traj[:, k]
-        S = np.stack([_interp(dev[k + 1], xg, xk - [h, 0]), _interp(dev[k + 1], xg, xk + [h, 0]),
-                      _interp(dev[k + 1], xg, xk - [0, h]), _interp(dev[k + 1], xg, xk + [0, h]), _interp(dev[k + 1], xg, xk)], axis=-1)
-        vals, _ = H.candidate_values(H.lqr_host, H.LQR_PRM, xk, S, C2, h2, t, 0.0, H.LQR_DELTA)
-        _, ui, mg = H.backup(vals)
+        S = np.stack([GC.interp(dev[k + 1], xg, xk - [h, 0]), GC.interp(dev[k + 1], xg, xk + [h, 0]),
+                      GC.interp(dev[k + 1], xg, xk - [0, h]), GC.interp(dev[k + 1], xg, xk + [0, h]), GC.interp(dev[k + 1], xg, xk)], axis=-1)
+        vals, _, _ = BR.candidate_values(H.lqr_host, H.LQR_PRM, xk, S, C2, h2, t, 0.0, delta=H.LQR_DELTA)
+        _, ui, mg = BR.backup(vals)
         ok = mg > 1e-9
         np.testing.assert_array_equal(u[ok, k], C2[ui[ok]])
         sure += ok.sum()
         # the policy of another stage would have chosen differently somewhere: the stage index is tested
-        S0 = np.stack([_interp(dev[0], xg, xk - [h, 0]), _interp(dev[0], xg, xk + [h, 0]), _interp(dev[0], xg, xk - [0, h]),
-                       _interp(dev[0], xg, xk + [0, h]), _interp(dev[0], xg, xk)], axis=-1)
-        v0, _ = H.candidate_values(H.lqr_host, H.LQR_PRM, xk, S0, C2, h2, t, 0.0, H.LQR_DELTA)
-        differ += (H.backup(v0)[1] != ui).sum()
+        S0 = np.stack([GC.interp(dev[0], xg, xk - [h, 0]), GC.interp(dev[0], xg, xk + [h, 0]), GC.interp(dev[0], xg, xk - [0, h]),
+                       GC.interp(dev[0], xg, xk + [0, h]), GC.interp(dev[0], xg, xk)], axis=-1)
+        v0, _, _ = BR.candidate_values(H.lqr_host, H.LQR_PRM, xk, S0, C2, h2, t, 0.0, delta=H.LQR_DELTA)
+        differ += (BR.backup(v0)[1] != ui).sum()
         np.testing.assert_allclose(traj[:, k + 1], xk + u[:, k] * H.LQR_DELTA, rtol=0, atol=1e-14)
     assert sure >= 0.8 * n * N and differ > 0
     stage = H.LQR_PRM[1] * (traj[:, :N] ** 2).sum(-1) + H.LQR_PRM[2] * (u ** 2).sum(-1)
-    ref = (stage * H.LQR_DELTA).sum(axis=1) + _interp(dev[N], xg, traj[:, N])
+    ref = (stage * H.LQR_DELTA).sum(axis=1) + GC.interp(dev[N], xg, traj[:, N])
     np.testing.assert_allclose(J, ref, rtol=1e-12, atol=1e-12)
-    np.testing.assert_allclose(r["vend"].cpu().numpy(), _interp(dev[N], xg, traj[:, N]), rtol=1e-12, atol=1e-12)
+    np.testing.assert_allclose(r["vend"].cpu().numpy(), GC.interp(dev[N], xg, traj[:, N]), rtol=1e-12, atol=1e-12)
     # and V_{N-1} at the end would be a different number: the terminal stage is tested
-    assert np.abs(_interp(dev[N - 1], xg, traj[:, N]) - _interp(dev[N], xg, traj[:, N])).min() > 1e-6
-
-
-def _child(prog, tmp_path):
-    env = dict(os.environ, C3SC_CROSS_TRACE="1")
-    env["PYTHONPATH"] = os.pathsep.join([ROOT, os.path.join(ROOT, "tests")] + ([env["PYTHONPATH"]] if env.get("PYTHONPATH") else []))
-    return subprocess.run([sys.executable, "-c", prog], cwd=os.path.dirname(os.path.abspath(__file__)), env=env, capture_output=True,
-                          text=True, timeout=900)
+    assert np.abs(GC.interp(dev[N - 1], xg, traj[:, N]) - GC.interp(dev[N], xg, traj[:, N])).min() > 1e-6
 
 
 def test_fh_solve_through_the_reference_api(tmp_path):
@@ -316,7 +288,7 @@ def test_fh_solve_through_the_reference_api(tmp_path):
     model).  The first stage passes the first-fiber check against the host twin, the next ones take the device-resident cross
     (c3sc_hip_cross_iteration with its node memo); every stage equals the dense explicit chain to 1e-9"""
     out = tmp_path / "fh.npz"
-    r = _child(f"import horizon_lib; horizon_lib.fh_child({str(out)!r})", tmp_path)
+    r = GC.child(f"import horizon_lib; horizon_lib.fh_child({str(out)!r})")
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     assert "c3sc cross trace: speculate" in r.stderr  # the device-resident cross iterations ran
     V = np.load(out)["V"]
@@ -331,7 +303,7 @@ def test_fh_solve_through_the_reference_api(tmp_path):
 
 def test_fh_solve_stops_on_cfl(tmp_path):
     out = tmp_path / "fh_cfl.npz"
-    r = _child(f"import horizon_lib; horizon_lib.fh_child({str(out)!r}, delta=2.0, nstages=2)", tmp_path)
+    r = GC.child(f"import horizon_lib; horizon_lib.fh_child({str(out)!r}, delta=2.0, nstages=2)")
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     assert np.load(out)["V"].size == 0
     assert "C3SC_STATUS_CFL" in r.stderr

@@ -26,7 +26,8 @@ import pytest
 
 from c3sc_amd import engine as E
 from c3sc_amd import workloads as wl
-import horizon_lib as H
+import backup_ref as BR
+import gpu_case_lib as GC
 import impulse_lib as IL
 import jump_lib as JL
 import stop_lib as SL
@@ -104,7 +105,7 @@ def _check_case(ids, model, rank, discount, jumps, ks=(0, 1), constelm=False):
         kind, mark = E.decode_action(ui, nc)
         assert set(np.unique(kind)) == {"absorbed", "control", "impulse"} and mark[kind == "impulse"].max() == M - 1
         assert not stat.any() and status == 0, "no stationary node, and an intervention raises no bit"
-        x = H.node_states(w, k, idx).reshape(-1, w.dx)[live.reshape(-1)]
+        x = BR.node_states(w, k, idx).reshape(-1, w.dx)[live.reshape(-1)]
         kk, y = imp(w.params, x)
         for m in range(M):
             adm = np.isfinite(kk[:, m])
@@ -140,13 +141,6 @@ def test_per_wave_impulse_vs_numpy(ids, rank, discount, jumps):
     eng.close()
 
 
-def _fpw_lds_bytes(w, k, rp, npl, cw):
-    """dynamic LDS of a staged fiber-per-wave launch (launch_fpw.hpp: fpw_geometry), as tests/test_gpu_stop.py states it"""
-    ws = 4 * rp + 2 * w.dx * rp + 64 * npl
-    per = (rp if k in (0, w.dx - 1) else rp * rp) | 1
-    return 8 * (4 * ws + w.ngrid[k] * per + w.ncand * cw)
-
-
 @pytest.mark.parametrize("discount", [0.3, 0.0])
 @pytest.mark.parametrize("jumps", [False, True], ids=["nojump", "jump"])
 def test_per_wave_impulse_rank_12_l2_form(ids, discount, jumps):
@@ -154,8 +148,8 @@ def test_per_wave_impulse_rank_12_l2_form(ids, discount, jumps):
     stages in, so the impulse kernel that reads the varying core from global memory runs"""
     w = IL.lqr3_workload(ids["lqr3"], discount=discount)
     cw = 3 + 1 + 2 * 3 + 1
-    assert _fpw_lds_bytes(w, 1, 12, 2, cw) > 160 * 1024, "the staged form would fit: this case would not run the L2 form"
-    assert _fpw_lds_bytes(w, 1, 12, 2, cw) - 8 * 128 * 145 < 160 * 1024  # ... and the L2 form's own layout fits
+    assert GC.fpw_lds_bytes(w, 1, 12, 2, cw) > 160 * 1024, "the staged form would fit: this case would not run the L2 form"
+    assert GC.fpw_lds_bytes(w, 1, 12, 2, cw) - 8 * 128 * 145 < 160 * 1024  # ... and the L2 form's own layout fits
     kernels, kinds, eng = _check_case(ids, "lqr3", 12, discount, jumps, ks=(1,))
     assert kernels == {"k_fiber_per_wave<rtc:lqr3_ic,12,2>"}, kernels
     assert kinds[0] and kinds[3]
@@ -247,10 +241,6 @@ def test_forced_indices_that_name_nothing_give_zero(ids):
 
 
 # ---------------------------------------------------------------------------------------------------- the _all forms
-def _ptrs(ts):
-    return (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-
-
 @pytest.mark.parametrize("model", ["lqr", "lqr3"])
 @pytest.mark.parametrize("jumps", [False, True], ids=["nojump", "jump"])
 def test_all_forms_equal_the_per_dimension_calls(ids, model, jumps):
@@ -286,7 +276,7 @@ def test_all_forms_equal_the_per_dimension_calls(ids, model, jumps):
         assert L.c3sc_hip_bellman_fibers(h, k, sizes[s], idx[s].data_ptr(), out[s].data_ptr(), ui[s].data_ptr(), ab[s].data_ptr(), None) == 0
         assert eng.last_kernel().startswith("k_fiber_per_wave<rtc:"), eng.last_kernel()
     a_out, a_ui, a_ab = fresh()
-    assert L.c3sc_hip_bellman_fibers_all(h, d, KS, FS, _ptrs(idx), _ptrs(a_out), _ptrs(a_ui), _ptrs(a_ab), C.c_void_p(None)) == 0
+    assert L.c3sc_hip_bellman_fibers_all(h, d, KS, FS, GC.ptrs(idx), GC.ptrs(a_out), GC.ptrs(a_ui), GC.ptrs(a_ab), C.c_void_p(None)) == 0
     torch.cuda.synchronize()
     assert any((t > nc).any() for t in ui), "interventions win in these batches"
     for s in range(d):
@@ -296,7 +286,7 @@ def test_all_forms_equal_the_per_dimension_calls(ids, model, jumps):
     for s, k in enumerate(ks):
         assert L.c3sc_hip_policy_fibers(h, k, sizes[s], idx[s].data_ptr(), pol[s].data_ptr(), p_out[s].data_ptr(), p_ab[s].data_ptr(), None) == 0
     q_out, _, q_ab = fresh()
-    assert L.c3sc_hip_policy_fibers_all(h, d, KS, FS, _ptrs(idx), _ptrs(pol), _ptrs(q_out), _ptrs(q_ab), C.c_void_p(None)) == 0
+    assert L.c3sc_hip_policy_fibers_all(h, d, KS, FS, GC.ptrs(idx), GC.ptrs(pol), GC.ptrs(q_out), GC.ptrs(q_ab), C.c_void_p(None)) == 0
     torch.cuda.synchronize()
     for s in range(d):
         # inf == inf where a forced intervention is not admissible
@@ -538,15 +528,6 @@ def test_vi_solve_through_the_reference_api(tmp_path):
 
 
 # ---------------------------------------------------------------------------------------------------- noisy rollouts
-def _train(V, maxrank):
-    U, S, Vt = np.linalg.svd(V)
-    r = int((S > 1e-13 * S[0]).sum())
-    assert r <= maxrank, r
-    c0 = (U[:, :r] * S[None, :r]).reshape(V.shape[0], 1, r)
-    c1 = np.ascontiguousarray(Vt[:r, :].T).reshape(V.shape[1], r, 1)
-    return [1, r, 1], [c0, c1]
-
-
 def test_noisy_rollouts_estimate_the_value_function():
     """8192 noisy rollouts of the inventory problem from three states under its dense fixed point V: the mean of the cost, with
     the discounted V(x_N) of the trajectories still alive after N steps, estimates V(x_0) within 4 standard errors plus the
@@ -558,7 +539,7 @@ def test_noisy_rollouts_estimate_the_value_function():
     mid = E.compile_model(IL.INV, 2, 2, ranks=(12,), name="inventory_sim", nimpulse=IL.INV_NIMPULSE, **IL.INV_MASKS)
     w = IL.inv_workload(mid)
     V, dec = IL.inv_fixed_point(w)
-    ranks, cores = _train(V, 12)
+    ranks, cores = GC.train(V, 12)
     eng = E.BellmanEngine(0)
     eng.configure(dataclasses.replace(w, ranks=tuple(ranks)), cores)
     eng.set_impulses(True)

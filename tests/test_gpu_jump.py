@@ -16,13 +16,14 @@
   without njump (also one set after the switch)."""
 import ctypes as C
 import dataclasses
-import os
 
 import numpy as np
 import pytest
 
 from c3sc_amd import engine as E
 from c3sc_amd import workloads as wl
+import backup_ref as BR
+import gpu_case_lib as GC
 import horizon_lib as H
 import jump_lib as JL
 import stop_lib as SL
@@ -68,7 +69,7 @@ def _case(ids, model, rank, discount, horizon, stop):
         idx = wl.synth_fibers(w, k0, 64)
         costs, ab = eng.stencil_fibers_host(k0, idx)
         out, _, _, _, _, _, _ = JL.jump_fibers(w, SL.lqrn_host, jumps, tr, k0, idx, costs, ab, bcost, ocost, delta)
-        x = H.node_states(w, k0, idx).reshape(-1, w.dx)
+        x = BR.node_states(w, k0, idx).reshape(-1, w.dx)
         live = ab.reshape(-1) == 0
         c1 = w.params[5]
         v = np.unique(out.reshape(-1)[live] - c1 * (x[live] ** 2).sum(-1))
@@ -118,7 +119,7 @@ def _check_case(ids, model, rank, discount, horizon, stop, ks=(0, 1), constelm=F
         assert bool(status & STATUS_STATIONARY) == bool(stat.any()) and bool(status & STATUS_CFL) == bool(cfl.any()), status
         assert status == 0, "the cases stay inside the CFL rule and have no stationary node"
         # the kinds of target the marks reach from the live nodes of these fibers
-        x = H.node_states(w, k, idx).reshape(-1, w.dx)[live.reshape(-1)]
+        x = BR.node_states(w, k, idx).reshape(-1, w.dx)[live.reshape(-1)]
         _, _, y = jumps(w.params, x)
         for m in range(y.shape[1]):
             _, inobs, beyond, moved = JL.target_kinds(w, y[:, m])
@@ -146,13 +147,6 @@ def test_per_wave_jump_vs_numpy(ids, rank, discount, horizon, stop):
     assert kinds.all(), ("interior, beyond the absorbing face, inside the obstacle, across the seam", kinds)
 
 
-def _fpw_lds_bytes(w, k, rp, npl, cw):
-    """dynamic LDS of a staged fiber-per-wave launch (launch_fpw.hpp: fpw_geometry), as tests/test_gpu_stop.py states it"""
-    ws = 4 * rp + 2 * w.dx * rp + 64 * npl
-    per = (rp if k in (0, w.dx - 1) else rp * rp) | 1
-    return 8 * (4 * ws + w.ngrid[k] * per + w.ncand * cw)
-
-
 @pytest.mark.parametrize("discount", [0.3, 0.0])
 @pytest.mark.parametrize("horizon", [False, True], ids=["infinite", "horizon"])
 @pytest.mark.parametrize("stop", [False, True], ids=["nostop", "stop"])
@@ -161,8 +155,8 @@ def test_per_wave_jump_rank_12_l2_form(ids, discount, horizon, stop):
     stages in, so the jump kernel that reads the varying core from global memory runs"""
     w = JL.lqr3_workload(ids["lqr3"], discount=discount)
     cw = 3 + 1 + 2 * 3 + 1
-    assert _fpw_lds_bytes(w, 1, 12, 2, cw) > 160 * 1024, "the staged form would fit: this case would not run the L2 form"
-    assert _fpw_lds_bytes(w, 1, 12, 2, cw) - 8 * 128 * 145 < 160 * 1024  # ... and the L2 form's own layout fits
+    assert GC.fpw_lds_bytes(w, 1, 12, 2, cw) > 160 * 1024, "the staged form would fit: this case would not run the L2 form"
+    assert GC.fpw_lds_bytes(w, 1, 12, 2, cw) - 8 * 128 * 145 < 160 * 1024  # ... and the L2 form's own layout fits
     kernels, kinds, _ = _check_case(ids, "lqr3", 12, discount, horizon, stop, ks=(1,))
     assert kernels == {"k_fiber_per_wave<rtc:lqr3_jd,12,2>"}, kernels
     assert kinds[0] and kinds[1] and kinds[3]
@@ -232,15 +226,6 @@ def test_known_answer(ids):
 
 
 # ---------------------------------------------------------------------------------------------------- the Merton put, stage by stage
-def _train(V, maxrank):
-    U, S, Vt = np.linalg.svd(V)
-    r = int((S > 1e-13 * S[0]).sum())
-    assert r <= maxrank, r
-    c0 = (U[:, :r] * S[None, :r]).reshape(V.shape[0], 1, r)
-    c1 = np.ascontiguousarray(Vt[:r, :].T).reshape(V.shape[1], r, 1)
-    return [1, r, 1], [c0, c1]
-
-
 @pytest.fixture(scope="module")
 def put_solve(ids):
     """Merton's put solved stage by stage on the device (jump, stop and horizon forms, each stage uploaded as its exact train)
@@ -254,7 +239,7 @@ def put_solve(ids):
     eng = E.BellmanEngine(0)
     n = SL.PUT_N
     Vn = dense[-1]
-    ranks, cores = _train(Vn, 12)
+    ranks, cores = GC.train(Vn, 12)
     eng.configure(dataclasses.replace(w, ranks=tuple(ranks)), cores)
     eng.set_horizon_step(JL.PUT_DELTA)
     eng.set_stopping(True)
@@ -268,7 +253,7 @@ def put_solve(ids):
         Vn = np.ascontiguousarray(out.T)
         dev.append(Vn)
         uis.append(np.ascontiguousarray(ui.T))
-        ranks, cores = _train(Vn, 12)
+        ranks, cores = GC.train(Vn, 12)
         trains.append((ranks, cores))
     assert eng.status() == 0
     return eng, np.array(dev[::-1]), dense, trains[::-1], w, uis, dec
@@ -456,23 +441,12 @@ def test_jumps_leave_the_diffusion_noise_its_bits(ids):
 
 
 # ---------------------------------------------------------------------------------------------------- the reference API
-def _child(prog):
-    import subprocess
-    import sys
-
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, C3SC_CROSS_TRACE="1")
-    env["PYTHONPATH"] = os.pathsep.join([root, os.path.join(root, "tests")] + ([env["PYTHONPATH"]] if env.get("PYTHONPATH") else []))
-    return subprocess.run([sys.executable, "-c", prog], cwd=os.path.dirname(os.path.abspath(__file__)), env=env, capture_output=True,
-                          text=True, timeout=900)
-
-
 def test_vi_solve_through_the_reference_api(tmp_path):
     """the jump LQR through libc3sc.so in a child process: c3control_vi_solve sweep by sweep (11 x 11, rank 11, host callbacks and
     c3control_add_jumps beside the jump model).  The first sweep passes the first-fiber check against the host twin; every sweep
     equals the dense Markov-chain value iteration to 1e-9"""
     out = tmp_path / "vi.npz"
-    r = _child(f"import jump_lib; jump_lib.vi_child({str(out)!r})")
+    r = GC.child(f"import jump_lib; jump_lib.vi_child({str(out)!r})")
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     V = np.load(out)["V"]
     w = JL.lqr_vi_workload(0)
@@ -504,7 +478,7 @@ def test_fh_solve_of_the_merton_put_through_the_reference_api(tmp_path):
     """Merton's American put through libc3sc.so in a child process: c3control_fh_solve in stop and jump mode equals the dense chain
     stage by stage to 1e-9"""
     out = tmp_path / "fh.npz"
-    r = _child(f"import jump_lib; jump_lib.fh_child({str(out)!r})")
+    r = GC.child(f"import jump_lib; jump_lib.fh_child({str(out)!r})")
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     V = np.load(out)["V"]
     w = JL.put_workload(0)

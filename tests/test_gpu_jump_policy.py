@@ -24,6 +24,7 @@ import pytest
 from c3sc_amd import engine as E
 from c3sc_amd import workloads as wl
 import game_lib as GL
+import gpu_case_lib as GC
 import horizon_lib as H
 import jump_lib as JL
 import jump_policy_model as JP
@@ -157,10 +158,6 @@ def test_the_policy_memo_in_jump_mode_keeps_the_first_candidate_for_a_tag(oracle
 
 
 # ---------------------------------------------------------------------------------------------------- the _all forms
-def _ptrs(ts):
-    return (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-
-
 def _all_equals_the_per_dimension_calls(eng, w, nact, label):
     """bellman_fibers_all and policy_fibers_all against c3sc_hip_bellman_fibers / c3sc_hip_policy_fibers per dimension: values,
     indices and flags bit for bit, no status bit.  nact: the forced indices are drawn from 0 .. nact - 1"""
@@ -189,7 +186,7 @@ def _all_equals_the_per_dimension_calls(eng, w, nact, label):
     torch.cuda.synchronize()
     assert eng.status(clear=True) == 0, label
     a_out, a_ui, a_ab = fresh()
-    rc = L.c3sc_hip_bellman_fibers_all(h, d, KS, FS, _ptrs(idx), _ptrs(a_out), _ptrs(a_ui), _ptrs(a_ab), C.c_void_p(None))
+    rc = L.c3sc_hip_bellman_fibers_all(h, d, KS, FS, GC.ptrs(idx), GC.ptrs(a_out), GC.ptrs(a_ui), GC.ptrs(a_ab), C.c_void_p(None))
     assert rc == 0, (label, eng.L.c3sc_hip_last_error(h))
     torch.cuda.synchronize()
     assert eng.status(clear=True) == 0, label
@@ -204,7 +201,7 @@ def _all_equals_the_per_dimension_calls(eng, w, nact, label):
     torch.cuda.synchronize()
     assert eng.status(clear=True) == 0, label
     q_out, _, q_ab = fresh()
-    rc = L.c3sc_hip_policy_fibers_all(h, d, KS, FS, _ptrs(idx), _ptrs(pol), _ptrs(q_out), _ptrs(q_ab), C.c_void_p(None))
+    rc = L.c3sc_hip_policy_fibers_all(h, d, KS, FS, GC.ptrs(idx), GC.ptrs(pol), GC.ptrs(q_out), GC.ptrs(q_ab), C.c_void_p(None))
     assert rc == 0, (label, eng.L.c3sc_hip_last_error(h))
     torch.cuda.synchronize()
     assert eng.status(clear=True) == 0, label
@@ -265,7 +262,7 @@ def test_all_forms_in_the_other_modes(ids, mode):
 # ---------------------------------------------------------------------------------------------------- no control at a live node
 @pytest.mark.parametrize("combined", [False, True], ids=["jump", "jump-stop-horizon"])
 def test_a_forced_index_of_minus_one_gives_zero_in_jump_mode(ids, combined):
-    """what pi_core passes for a node without a cached control, and what jump_lib.backup(forced=...) gives: 0.0 at the live nodes,
+    """what pi_core passes for a node without a cached control, and what backup_ref.backup(forced=...) gives: 0.0 at the live nodes,
     the boundary and obstacle costs and every flag unchanged; beside other indices it touches its own node only"""
     eng, w = _jump_engine(ids, "lqr", combined)
     rng = np.random.default_rng(2)

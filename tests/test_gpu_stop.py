@@ -21,18 +21,18 @@
   calls, cross_iteration_pi, integrate, set_game in either order."""
 import ctypes as C
 import dataclasses
-import os
 
 import numpy as np
 import pytest
 
 from c3sc_amd import engine as E
 from c3sc_amd import workloads as wl
+import backup_ref as BR
+import gpu_case_lib as GC
 import horizon_lib as H
 import stop_lib as SL
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ERR_ARG, ERR_UNSUPPORTED = 1, 3
 STATUS_STATIONARY, STATUS_CFL = 1, 2
 
@@ -97,9 +97,9 @@ def _case(ids, model, rank, discount, horizon):
     idx = wl.synth_fibers(w, k0, 64)
     costs, ab = eng.stencil_fibers_host(k0, idx)
     if model != "put":
-        h2, t = H.mca_constants(w)
-        x = H.node_states(w, k0, idx).reshape(-1, w.dx)
-        vals, _, _ = SL.node_values(host, w.params, x, costs.reshape(-1, 2 * w.dx + 1), np.asarray(w.cands), h2, t, discount, delta)
+        h2, t = BR.mca_constants(w)
+        x = BR.node_states(w, k0, idx).reshape(-1, w.dx)
+        vals, _, _ = BR.candidate_values(host, w.params, x, costs.reshape(-1, 2 * w.dx + 1), np.asarray(w.cands), h2, t, discount, delta=delta)
         cont = np.nanmin(vals, axis=1)[ab.reshape(-1) == 0]
         c1 = SL.LQR_PRM[5]
         c0 = float(np.median(cont - c1 * (x[ab.reshape(-1) == 0] ** 2).sum(-1)))
@@ -147,7 +147,7 @@ def _check_case(ids, model, rank, discount, horizon, ks=(0, 1)):
         np.testing.assert_array_equal(f_ab, ab)
         assert np.all(np.abs(f_out - out) <= 1e-12 * scale), (k, np.abs(f_out - out).max())
         s_out, _ = eng.policy_fibers_host(k, idx, np.full(ab.shape, nc, dtype=np.int32))
-        x = H.node_states(w, k, idx).reshape(-1, w.dx)
+        x = BR.node_states(w, k, idx).reshape(-1, w.dx)
         p_ref = np.where(live.reshape(-1), psi(x), r_out.reshape(-1)).reshape(ab.shape)
         assert np.all(np.abs(s_out - p_ref) <= 1e-12 * np.maximum(1.0, np.abs(p_ref)))
         # a random forced candidate applies it and does not compare with psi
@@ -179,22 +179,14 @@ def test_per_wave_stop_rank_12(ids, horizon):
     assert all(",12," in k for k in kernels), kernels
 
 
-def _fpw_lds_bytes(w, k, rp, npl, cw):
-    """dynamic LDS of a staged fiber-per-wave launch (launch_fpw.hpp: fpw_geometry): the four waves' scratch, the varying core
-    with its odd stride, the candidate table of cw doubles per row"""
-    ws = 4 * rp + 2 * w.dx * rp + 64 * npl
-    per = (rp if k in (0, w.dx - 1) else rp * rp) | 1
-    return 8 * (4 * ws + w.ngrid[k] * per + w.ncand * cw)
-
-
 @pytest.mark.parametrize("horizon", [False, True], ids=["infinite", "horizon"])
 def test_per_wave_stop_rank_12_l2_form(ids, horizon):
     """the L2 form of the rank-12 stop kernels: a launch along the 128-node middle dimension of a 3-D grid, whose staged layout
     needs more than the 160 KB the launcher stages in, so the kernel that reads the varying core from global memory runs"""
     w = lqr3_workload(ids["lqr3"], 12, 0.3)
     cw = 3 + 1 + 2 * 3 + 1  # CandLds row: u, one feature slot, the constant rates of three dimensions, their sum
-    assert _fpw_lds_bytes(w, 1, 12, 2, cw) > 160 * 1024, "the staged form would fit: this case would not run the L2 form"
-    assert _fpw_lds_bytes(w, 1, 12, 2, cw) - 8 * 128 * 145 < 160 * 1024  # ... and the L2 form's own layout fits
+    assert GC.fpw_lds_bytes(w, 1, 12, 2, cw) > 160 * 1024, "the staged form would fit: this case would not run the L2 form"
+    assert GC.fpw_lds_bytes(w, 1, 12, 2, cw) - 8 * 128 * 145 < 160 * 1024  # ... and the L2 form's own layout fits
     kernels = _check_case(ids, "lqr3", 12, 0.3, horizon, ks=(1,))
     assert kernels == {"k_fiber_per_wave<rtc:lqr3_os,12,2>"}, kernels
 
@@ -275,32 +267,13 @@ def test_cfl_bit_is_the_scanned_candidates_alone(ids):
 
 
 # ---------------------------------------------------------------------------------------------------- rollouts
-def _interp(G, xg, y):
-    """bilinear interpolant of the nodal matrix G on the grid xg x xg at the points y[P, 2] (inside the grid)"""
-    h = xg[1] - xg[0]
-    i = np.clip(np.floor((y[:, 0] - xg[0]) / h).astype(int), 0, len(xg) - 2)
-    j = np.clip(np.floor((y[:, 1] - xg[0]) / h).astype(int), 0, len(xg) - 2)
-    a = (y[:, 0] - xg[i]) / h
-    b = (y[:, 1] - xg[j]) / h
-    return (1 - a) * (1 - b) * G[i, j] + a * (1 - b) * G[i + 1, j] + (1 - a) * b * G[i, j + 1] + a * b * G[i + 1, j + 1]
-
-
 def _stencil(G, xg, x):
     """the off-grid stencil on a grid whose dimensions both absorb (mca_get_neighbor_node_costs): the neighbours one spacing away,
     the face itself where that would leave the grid; every point is read inside the grid (the interpolant clamps)"""
     h = xg[1] - xg[0]
     c = lambda y: np.clip(y, xg[0], xg[-1])
-    return np.stack([_interp(G, xg, c(x - [h, 0])), _interp(G, xg, c(x + [h, 0])), _interp(G, xg, c(x - [0, h])),
-                     _interp(G, xg, c(x + [0, h])), _interp(G, xg, c(x))], axis=-1)
-
-
-def _train(V, maxrank):
-    U, S, Vt = np.linalg.svd(V)
-    r = int((S > 1e-13 * S[0]).sum())
-    assert r <= maxrank, r
-    c0 = (U[:, :r] * S[None, :r]).reshape(V.shape[0], 1, r)
-    c1 = np.ascontiguousarray(Vt[:r, :].T).reshape(V.shape[1], r, 1)
-    return [1, r, 1], [c0, c1]
+    return np.stack([GC.interp(G, xg, c(x - [h, 0])), GC.interp(G, xg, c(x + [h, 0])), GC.interp(G, xg, c(x - [0, h])),
+                     GC.interp(G, xg, c(x + [0, h])), GC.interp(G, xg, c(x))], axis=-1)
 
 
 def _check_noise_free(r, n_inside, w, host, psi, stage_fn, drift_fn, stacks, xg, beta, dt, N, horizon, bcost, push=None):
@@ -311,7 +284,7 @@ def _check_noise_free(r, n_inside, w, host, psi, stage_fn, drift_fn, stacks, xg,
     traj, u, J = r["traj"].cpu().numpy(), r["u"].cpu().numpy(), r["cost"].cpu().numpy()
     step, stopped = E.decode_exit(r["exit"].cpu().numpy())
     assert (stopped[n_inside:] == 0).all() and (step[n_inside:] == 0).all(), "lanes that start outside decode as exits at step 0"
-    h2, t = H.mca_constants(w)
+    h2, t = BR.mca_constants(w)
     Cn = np.asarray(w.cands, dtype=np.float64)
     nc = len(Cn)
     n = n_inside
@@ -327,9 +300,9 @@ def _check_noise_free(r, n_inside, w, host, psi, stage_fn, drift_fn, stacks, xg,
         exited[gone] = k
         alive = alive & ~gone
         S = _stencil(stacks[k], xg, xk)
-        vals, _, _ = SL.node_values(host, w.params, xk, S, Cn, h2, t, beta, dt if horizon else None)
+        vals, _, _ = BR.candidate_values(host, w.params, xk, S, Cn, h2, t, beta, delta=dt if horizon else None)
         _, ui, mg = SL.stop_backup(vals, psi(xk))
-        _, ci, cmg = H.backup(np.where(np.isnan(vals), np.inf, vals))
+        _, ci, cmg = BR.backup(np.where(np.isnan(vals), np.inf, vals))
         disc = np.exp(-beta * k * dt)
         dev_stop = alive & (stopped[:n] == 1) & (step[:n] == k)
         sure = alive & (mg > 1e-9)
@@ -356,7 +329,7 @@ def _check_noise_free(r, n_inside, w, host, psi, stage_fn, drift_fn, stacks, xg,
     assert (step[:n][~alive & ~left] >= 0).all() and (stopped[:n][~alive & ~left] == 1).all()
     assert (step[:n][alive] == -1).all() and (stopped[:n][alive] == 0).all()
     if horizon:
-        Jref += np.where(alive, np.exp(-beta * N * dt) * _interp(stacks[N], xg, traj[:n, N]), 0.0)
+        Jref += np.where(alive, np.exp(-beta * N * dt) * GC.interp(stacks[N], xg, traj[:n, N]), 0.0)
     np.testing.assert_allclose(J[:n], Jref, rtol=1e-12, atol=1e-12)
     return step[:n], stopped[:n], sure_n
 
@@ -372,7 +345,7 @@ def test_noise_free_rollouts_infinite_horizon(ids):
     xg = w.xgrid()[0]
     X = np.stack(np.meshgrid(xg, xg, indexing="ij"), axis=-1)
     V = 0.8 * (X ** 2).sum(-1) + 0.3
-    ranks, cores = _train(V, 4)
+    ranks, cores = GC.train(V, 4)
     eng = E.BellmanEngine(0)
     eng.configure(dataclasses.replace(w, ranks=tuple(ranks)), cores)
     eng.set_stopping(True)
@@ -410,7 +383,7 @@ def put_solve(ids):
     eng = E.BellmanEngine(0)
     n = SL.PUT_N
     Vn = dense[-1]
-    ranks, cores = _train(Vn, 12)
+    ranks, cores = GC.train(Vn, 12)
     eng.configure(dataclasses.replace(w, ranks=tuple(ranks)), cores)
     eng.set_horizon_step(SL.PUT_DELTA)
     eng.set_stopping(True)
@@ -423,7 +396,7 @@ def put_solve(ids):
         Vn = np.ascontiguousarray(out.T)
         dev.append(Vn)
         uis.append(np.ascontiguousarray(ui.T))
-        ranks, cores = _train(Vn, 12)
+        ranks, cores = GC.train(Vn, 12)
         trains.append((ranks, cores))
     assert eng.status() == 0
     return eng, np.array(dev[::-1]), dense, trains[::-1], w, np.array(uis[::-1]), dec
@@ -560,22 +533,12 @@ def test_errors(ids):
 
 
 # ---------------------------------------------------------------------------------------------------- the reference API
-def _child(prog):
-    import subprocess
-    import sys
-
-    env = dict(os.environ, C3SC_CROSS_TRACE="1")
-    env["PYTHONPATH"] = os.pathsep.join([ROOT, os.path.join(ROOT, "tests")] + ([env["PYTHONPATH"]] if env.get("PYTHONPATH") else []))
-    return subprocess.run([sys.executable, "-c", prog], cwd=os.path.dirname(os.path.abspath(__file__)), env=env, capture_output=True,
-                          text=True, timeout=900)
-
-
 def test_vi_solve_through_the_reference_api(tmp_path):
     """the stopping LQR through libc3sc.so in a child process: c3control_vi_solve sweep by sweep (11 x 11, rank 11, host
     callbacks beside the stop model).  The first sweep passes the first-fiber check against the host twin, the next ones take the
     device-resident cross; every sweep equals the dense Markov-chain value iteration to 1e-9"""
     out = tmp_path / "vi.npz"
-    r = _child(f"import stop_lib; stop_lib.vi_child({str(out)!r})")
+    r = GC.child(f"import stop_lib; stop_lib.vi_child({str(out)!r})")
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     assert "c3sc cross trace: speculate" in r.stderr  # the device-resident cross iterations ran
     V = np.load(out)["V"]
@@ -596,7 +559,7 @@ def test_fh_solve_of_the_put_through_the_reference_api(tmp_path):
     """the American put through libc3sc.so in a child process: c3control_fh_solve in stop mode equals the dense chain stage by
     stage to 1e-9"""
     out = tmp_path / "fh.npz"
-    r = _child(f"import stop_lib; stop_lib.fh_child({str(out)!r})")
+    r = GC.child(f"import stop_lib; stop_lib.fh_child({str(out)!r})")
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     assert "c3sc cross trace: speculate" in r.stderr
     V = np.load(out)["V"]

@@ -15,28 +15,8 @@ import os
 import numpy as np
 import pytest
 
+import backup_ref as BR
 import horizon_lib as H
-
-
-def _loop_backup(host, prm, x, V, C, h2, t, beta, delta):
-    """one node, candidate by candidate: g delta + e^{-beta delta} (V_self + (delta / h^2) (PV - Q V_self)), first strict '<'"""
-    D = len(x)
-    best, ui, cfl = math.inf, -1, False
-    for c, u in enumerate(C):
-        b, s, st = host(prm, x[None], u[None])
-        Q = PV = 0.0
-        for m in range(D):
-            half = t[2 * m + 1] * (s[0, m] * s[0, m]) / 2.0
-            tb = t[2 * m] * b[0, m]
-            pm = half - tb if b[0, m] < -1e-14 else half
-            pp = half + tb if b[0, m] > 1e-14 else half
-            Q += pm + pp
-            PV += pm * V[2 * m] + pp * V[2 * m + 1]
-        val = st[0] * delta + math.exp(-beta * delta) * (V[2 * D] + delta / h2 * (PV - Q * V[2 * D]))
-        cfl |= Q * delta > h2
-        if val < best:
-            best, ui = val, c
-    return best, ui, cfl
 
 
 @pytest.mark.parametrize("beta", [0.4, 0.0])
@@ -52,13 +32,13 @@ def test_restatement_matches_the_operator_node_by_node(case, beta):
     x = rng.uniform(-2.0, 2.0, size=(P, 2))
     V = rng.uniform(0.0, 3.0, size=(P, 5))
     h2, t, delta = 0.04, [0.2, 1.0, 0.18, 0.81], 0.03
-    vals, cfl = H.candidate_values(host, prm, x, V, C, h2, t, beta, delta)
-    out, ui, _ = H.backup(vals)
+    vals, _, cfl = BR.candidate_values(host, prm, x, V, C, h2, t, beta, delta=delta)
+    out, ui, _ = BR.backup(vals)
+    l_out, l_ui, _, l_cfl = BR.loop_backup(host, prm, x, V, C, h2, t, beta, delta=delta)
     for p in range(P):
-        b, i, c = _loop_backup(host, prm, x[p], V[p], C, h2, t, beta, delta)
-        assert abs(out[p] - b) <= 1e-13 * max(1.0, abs(b))
-        assert ui[p] == i
-        assert bool(cfl[p].any()) == c
+        assert abs(out[p] - l_out[p]) <= 1e-13 * max(1.0, abs(l_out[p]))
+        assert ui[p] == l_ui[p]
+        assert bool(cfl[p].any()) == l_cfl[p]
 
 
 def test_stay_candidates_are_not_skipped():
@@ -67,8 +47,8 @@ def test_stay_candidates_are_not_skipped():
     C = np.array([(0.0, 0.0), (0.5, 0.0), (-0.5, 0.0)])
     x = np.array([[0.3, 0.2]])
     V = np.array([[9.0, 9.0, 9.0, 9.0, 1.0]])  # every neighbour costs more: staying is best
-    vals, cfl = H.candidate_values(H.lqr_host, prm, x, V, C, 0.04, [0.2, 1.0, 0.2, 1.0], 0.1, 0.02)
-    out, ui, _ = H.backup(vals)
+    vals, _, cfl = BR.candidate_values(H.lqr_host, prm, x, V, C, 0.04, [0.2, 1.0, 0.2, 1.0], 0.1, delta=0.02)
+    out, ui, _ = BR.backup(vals)
     assert ui[0] == 0 and not cfl.any()
     assert out[0] == pytest.approx(0.13 * 0.02 + math.exp(-0.1 * 0.02) * 1.0, rel=1e-15)
     assert np.isfinite(vals).all()
@@ -78,9 +58,9 @@ def test_cfl_candidates_take_part():
     C = np.array([(0.0, 0.0), (1.5, 1.5)])
     x = np.array([[0.0, 0.0]])
     V = np.array([[0.0, -50.0, 0.0, -50.0, 0.0]])  # a negative self-loop makes the fast candidate's value very low
-    vals, cfl = H.candidate_values(H.lqr_host, H.LQR_PRM, x, V, C, 0.04, [0.2, 1.0, 0.2, 1.0], 0.0, 0.2)
+    vals, _, cfl = BR.candidate_values(H.lqr_host, H.LQR_PRM, x, V, C, 0.04, [0.2, 1.0, 0.2, 1.0], 0.0, delta=0.2)
     assert cfl[0, 1] and not cfl[0, 0]
-    out, ui, _ = H.backup(vals)
+    out, ui, _ = BR.backup(vals)
     assert ui[0] == 1 and out[0] == vals[0, 1]
 
 
@@ -155,7 +135,7 @@ def test_host_twin_picks_the_numpy_argmin_at_every_interior_node(beta):
     rng = np.random.default_rng(11)
     V = rng.uniform(0.0, 3.0, size=(11, 11))
     L, ctl, w, keep = _policy_control(V, H.LQR_PRM, beta, 0.05)
-    h2, t = H.mca_constants(w)
+    h2, t = BR.mca_constants(w)
     xg = w.xgrid()
     C2 = np.asarray(w.cands, dtype=np.float64)
     checked = 0
@@ -163,8 +143,8 @@ def test_host_twin_picks_the_numpy_argmin_at_every_interior_node(beta):
         for b in range(1, 10):
             x = np.array([xg[0][a], xg[1][b]])
             S = np.array([[V[a - 1, b], V[a + 1, b], V[a, b - 1], V[a, b + 1], V[a, b]]])
-            vals, _ = H.candidate_values(H.lqr_host, w.params, x[None], S, C2, h2, t, beta, 0.05)
-            _, ui, mg = H.backup(vals)
+            vals, _, _ = BR.candidate_values(H.lqr_host, w.params, x[None], S, C2, h2, t, beta, delta=0.05)
+            _, ui, mg = BR.backup(vals)
             u = np.zeros(2)
             assert L.c3control_policy_eval(ctl.h, C.c_double(0.0), fl.dp(fl.f64(x)), fl.dp(u)) == 0
             if mg[0] > 1e-9:

@@ -15,6 +15,8 @@ import textwrap
 import numpy as np
 import pytest
 
+import backup_ref as BR
+import facade_lib as fl
 import horizon_lib as H
 import impulse_lib as IL
 import jump_lib as JL
@@ -81,7 +83,7 @@ def test_host_twin_equals_impulse_lib_node_by_node(beta, jumps):
     V[:, -1] = V[:, 0]  # node 0 and node n - 1 of the periodic dimension are one point
     prm = w.params
     L, ctl, keep = _control(w, H.lqr_callbacks(prm), V, IL.lqr_impulses, IL.LQR_NIMPULSE, JL.lqr_jumps if jumps else None, JL.LQR_NJUMP)
-    h2, t = H.mca_constants(w)
+    h2, t = BR.mca_constants(w)
     xg = w.xgrid()
     Cn = np.asarray(w.cands, dtype=np.float64)
     bcost, ocost = (lambda x: SL.lqrn_terminal(prm, x)), (lambda x: np.full(len(x), 5.0))
@@ -92,9 +94,9 @@ def test_host_twin_equals_impulse_lib_node_by_node(beta, jumps):
     S = np.array([[V[a - 1, b], V[a + 1, b], V[a, b - 1], V[a, b + 1], V[a, b]] for a, b in nodes])
     interp = JL.Nodal(w, V)
     jrate, J = JL.jump_terms(w, JL.lqr_jumps, interp, x, bcost, ocost) if jumps else (np.zeros(len(x)), np.zeros(len(x)))
-    vals, _, _ = JL.candidate_values(SL.lqrn_host, prm, x, S, Cn, h2, t, beta, jrate, J)
+    vals, _, _ = BR.candidate_values(SL.lqrn_host, prm, x, S, Cn, h2, t, beta, jrate, jrate * J)
     c = IL.impulse_values(w, IL.lqr_impulses, interp, x, bcost, ocost)
-    ref, ui, mg = IL.backup(vals, c)
+    ref, ui, mg = BR.backup(vals, c=c)
     nc = len(Cn)
     worst, taken = 0.0, np.zeros(IL.LQR_NIMPULSE, dtype=int)
     for p in range(len(x)):
@@ -117,9 +119,9 @@ def test_known_answer_through_the_host_path():
     w = IL.known_workload(0)
     prm = w.params
     c = prm[4]
-    cbs = SL._callbacks(lambda x, u: (u[0], u[1]), lambda x, u: (prm[0], prm[0]),
-                        lambda x, u: prm[1] * (x[0] * x[0] + x[1] * x[1]) + prm[2] * (u[0] * u[0] + u[1] * u[1]), lambda x: c, lambda x: -1.0,
-                        lambda x: 0.0)[0]
+    cbs = fl.callbacks2d(lambda x, u: (u[0], u[1]), lambda x, u: (prm[0], prm[0]),
+                         lambda x, u: prm[1] * (x[0] * x[0] + x[1] * x[1]) + prm[2] * (u[0] * u[0] + u[1] * u[1]), lambda x: c, lambda x: -1.0,
+                         lambda x: 0.0)[0]
     V = np.random.default_rng(2).uniform(0.3, 0.8, size=w.ngrid)
     L, ctl, keep = _control(w, cbs, V, IL.known_impulses, IL.KNOWN_NIMPULSE)
     xg = w.xgrid()

@@ -20,7 +20,7 @@ import numpy as np
 import pytest
 
 from c3sc_amd import workloads as wl
-import horizon_lib as H
+import backup_ref as BR
 import impulse_lib as IL
 import jump_lib as JL
 import oracle_lib
@@ -40,25 +40,6 @@ def _case(model, rank, discount, jumps, k):
     return w, JL.Train(w, cores), idx, V, ab, bcost, ocost
 
 
-def _loop_backup(vals, c):
-    """the rule in words, one node at a time"""
-    P, nc = vals.shape
-    out, idx = np.zeros(P), np.full(P, -1)
-    for p in range(P):
-        best, bi = 0.0, -1
-        for a in range(nc):
-            if not np.isnan(vals[p, a]) and (bi < 0 or vals[p, a] < best):
-                best, bi = vals[p, a], a
-        ival, imark = np.inf, -1
-        for m in range(c.shape[1]):
-            if np.isfinite(c[p, m]) and c[p, m] < ival:
-                ival, imark = c[p, m], m
-        if imark >= 0 and (bi < 0 or ival < best):
-            best, bi = ival, nc + 1 + imark
-        out[p], idx[p] = best, bi
-    return out, idx
-
-
 def test_vectorised_backup_equals_the_loop():
     rng = np.random.default_rng(5)
     vals = rng.uniform(0.0, 1.0, size=(400, 7))
@@ -69,8 +50,8 @@ def test_vectorised_backup_equals_the_loop():
     c[10:30] = np.inf
     c[40:60, 1] = c[40:60, 2]  # ties among the interventions
     c[60:80, 0] = np.nanmin(np.where(np.isnan(vals[60:80]), np.inf, vals[60:80]), axis=1)  # a tie with the scan's winner: the candidate stays
-    out, ui, _ = IL.backup(vals, c)
-    l_out, l_ui = _loop_backup(vals, c)
+    out, ui, _ = BR.backup(vals, c=c)
+    l_out, l_ui = BR.loop_decide(vals, c=c)
     np.testing.assert_array_equal(out, l_out)
     np.testing.assert_array_equal(ui, l_ui)
     assert (ui[10:20] == -1).all() and (out[10:20] == 0.0).all()
@@ -78,7 +59,7 @@ def test_vectorised_backup_equals_the_loop():
     assert (ui[60:80] <= 7 + 3).all() and not (ui[60:80] == 7 + 1).any()
     # forced: an intervention's index applies it, a candidate's index the candidate, -1 / the stop index / a skipped candidate 0.0
     forced = rng.integers(-1, 7 + 1 + 3, size=400)
-    f_out, f_ui, _ = IL.backup(vals, c, forced)
+    f_out, f_ui, _ = BR.backup(vals, c=c, forced=forced)
     for p in range(400):
         f = forced[p]
         if f > 7:
@@ -198,12 +179,12 @@ def test_planted_faults_are_seen(inventory):
     assert (idec[n - 1] != dec[n - 1]).sum() >= 10, "intervention m has the index ncand + 1 + m"
     # '<=' for '<': the known model's tie k_1 = k_2 goes to mark 2, and a tie with the scan's winner to the intervention
     kw, tr, idx, costs, ab, bcost, ocost = _known_case()
-    h2, t = H.mca_constants(kw)
-    x = H.node_states(kw, 1, idx).reshape(-1, 2)
+    h2, t = BR.mca_constants(kw)
+    x = BR.node_states(kw, 1, idx).reshape(-1, 2)
     zero = np.zeros(len(x))
-    vals, _, _ = JL.candidate_values(SL.lqrn_host, kw.params, x, costs.reshape(-1, 5), np.asarray(kw.cands), h2, t, kw.discount, zero, zero)
+    vals, _, _ = BR.candidate_values(SL.lqrn_host, kw.params, x, costs.reshape(-1, 5), np.asarray(kw.cands), h2, t, kw.discount)
     c = IL.impulse_values(kw, IL.known_impulses, tr, x, bcost, ocost)
-    good, bad = IL.backup(vals, c), IL.backup(vals, c, fault="le")
+    good, bad = BR.backup(vals, c=c), BR.backup(vals, c=c, fault="le")
     wins = good[1] > kw.ncand
     assert wins.any() and (good[1][wins] == kw.ncand + 2).all() and (bad[1][wins] == kw.ncand + 3).all()
     np.testing.assert_array_equal(good[0], bad[0])  # only the index tells: the tests compare indices where the margin is clear

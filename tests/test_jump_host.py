@@ -13,6 +13,8 @@ import textwrap
 import numpy as np
 import pytest
 
+import backup_ref as BR
+import facade_lib as fl
 import horizon_lib as H
 import jump_lib as JL
 import stop_lib as SL
@@ -74,7 +76,7 @@ def test_host_twin_equals_jump_lib_node_by_node(beta, delta, stop):
         w = dataclasses.replace(w, params=prm)
     psi_cb = (lambda t, x, out: (out.__setitem__(0, prm[4] + prm[5] * (x[0] * x[0] + x[1] * x[1])), 0)[1]) if stop else None
     L, ctl, keep = _control(w, H.lqr_callbacks(prm), V, JL.lqr_jumps, JL.LQR_NJUMP, delta, psi_cb)
-    h2, t = H.mca_constants(w)
+    h2, t = BR.mca_constants(w)
     xg = w.xgrid()
     Cn = np.asarray(w.cands, dtype=np.float64)
     bcost, ocost = (lambda x: SL.lqrn_terminal(prm, x)), (lambda x: np.full(len(x), 5.0))
@@ -84,8 +86,8 @@ def test_host_twin_equals_jump_lib_node_by_node(beta, delta, stop):
     x, nodes = x[keepn], [nd for nd, k in zip(nodes, keepn) if k]
     S = np.array([[V[a - 1, b], V[a + 1, b], V[a, b - 1], V[a, b + 1], V[a, b]] for a, b in nodes])
     jrate, J = JL.jump_terms(w, JL.lqr_jumps, JL.Nodal(w, V), x, bcost, ocost)
-    vals, _, _ = JL.candidate_values(SL.lqrn_host, prm, x, S, Cn, h2, t, beta, jrate, J, delta)
-    ref, ui, mg = JL.backup(vals, SL.lqr_psi(prm, x) if stop else None)
+    vals, _, _ = BR.candidate_values(SL.lqrn_host, prm, x, S, Cn, h2, t, beta, jrate, jrate * J, delta)
+    ref, ui, mg = BR.backup(vals, SL.lqr_psi(prm, x) if stop else None)
     kinds = np.zeros(4, dtype=bool)
     _, _, y = JL.lqr_jumps(prm, x)
     for m in range(3):
@@ -108,7 +110,7 @@ def test_host_twin_equals_jump_lib_node_by_node(beta, delta, stop):
 def test_known_answer_through_the_host_path():
     w = JL.known_workload(0)
     g, lam, c = w.params
-    cbs, _ = SL._callbacks(lambda x, u: (0.0, 0.0), lambda x, u: (0.0, 0.0), lambda x, u: g, lambda x: c, lambda x: -1.0, lambda x: 0.0)
+    cbs, _ = fl.callbacks2d(lambda x, u: (0.0, 0.0), lambda x, u: (0.0, 0.0), lambda x, u: g, lambda x: c, lambda x: -1.0, lambda x: 0.0)
     jumps = lambda prm, x: (np.full(len(x), prm[1]), np.broadcast_to(np.array([0.25, 0.25, 0.5]), (len(x), 3)),
                             np.stack([x + np.array([10.0 + m, 0.0]) for m in range(3)], axis=1))
     V = np.random.default_rng(2).uniform(0.0, 5.0, size=w.ngrid)

@@ -24,6 +24,7 @@ import pytest
 from c3sc_amd import engine as E
 from c3sc_amd import workloads as wl
 import cross_memo_model as mm
+import backup_ref as BR
 import horizon_lib as H
 import jump_lib as JL
 import jump_policy_model as JP
@@ -100,7 +101,7 @@ def _periodic_fibers(w, tr, idx):
     an absorbing face is absorbed, its end points are live again (the end-point rule), neighbours across the seam"""
     xg = w.xgrid()
     n0, N = w.ngrid
-    x = H.node_states(w, 1, idx)
+    x = BR.node_states(w, 1, idx)
     F = len(idx)
     inobs = JL.target_kinds(w, x.reshape(-1, 2))[1].reshape(F, N)
     V, ab = np.zeros((F, N, 5)), np.zeros((F, N), dtype=np.int32)

@@ -9,6 +9,7 @@ import os
 import numpy as np
 import pytest
 
+import backup_ref as BR
 import horizon_lib as H
 import stop_lib as SL
 
@@ -29,9 +30,9 @@ def test_stop_lib_equals_a_per_candidate_loop(beta, delta):
     x, V = _random_nodes(rng, 200, -2.0, 2.0)
     C = SL.lqr_cands()
     psi = SL.lqr_psi(SL.LQR_PRM, x)
-    vals, _, _ = SL.node_values(H.lqr_host, SL.LQR_PRM, x, V, C, H2, T, beta, delta)
+    vals, _, _ = BR.candidate_values(H.lqr_host, SL.LQR_PRM, x, V, C, H2, T, beta, delta=delta)
     out, ui, mg = SL.stop_backup(vals, psi)
-    l_out, l_ui = SL.loop_backup(lambda p, xx, u: H.lqr_host(p, xx, u), SL.LQR_PRM, x, V, C, H2, T, beta, psi, delta)
+    l_out, l_ui, _, _ = BR.loop_backup(H.lqr_host, SL.LQR_PRM, x, V, C, H2, T, beta, psi=psi, delta=delta)
     sure = mg > 1e-12
     assert sure.mean() > 0.99
     np.testing.assert_array_equal(ui[sure], l_ui[sure])
@@ -43,7 +44,7 @@ def test_stop_wins_where_no_candidate_is_valid():
     # the put at S = 0: no drift, no diffusion, Q = 0 -- the infinite-horizon scan skips its one candidate
     x = np.array([[0.0, 0.0], [1.0, 1.2]])
     V = np.ones((2, 5))
-    vals, stat, _ = SL.node_values(SL.put_host, SL.PUT_PRM, x, V, SL.PUT_CANDS, H2, T, 0.1, None)
+    vals, stat, _ = BR.candidate_values(SL.put_host, SL.PUT_PRM, x, V, SL.PUT_CANDS, H2, T, 0.1)
     assert stat.tolist() == [True, False] and np.isnan(vals[0, 0])
     out, ui, mg = SL.stop_backup(vals, SL.put_psi(SL.PUT_PRM, x))
     assert ui[0] == 1 and out[0] == -1.0 and np.isinf(mg[0])
@@ -59,9 +60,9 @@ def test_a_psi_that_never_wins_leaves_the_plain_scan_bit_for_bit(delta):
     rng = np.random.default_rng(7)
     x, V = _random_nodes(rng, 300, -2.0, 2.0)
     C = SL.lqr_cands()
-    vals, _, _ = SL.node_values(H.lqr_host, SL.LQR_NEVER_PRM, x, V, C, H2, T, 0.2, delta)
+    vals, _, _ = BR.candidate_values(H.lqr_host, SL.LQR_NEVER_PRM, x, V, C, H2, T, 0.2, delta=delta)
     out, ui, _ = SL.stop_backup(vals, SL.lqr_psi(SL.LQR_NEVER_PRM, x))
-    p_out, p_ui, _ = H.backup(vals)
+    p_out, p_ui, _ = BR.backup(vals)
     np.testing.assert_array_equal(out, p_out)
     np.testing.assert_array_equal(ui, p_ui)
 
@@ -154,7 +155,7 @@ def test_host_twin_takes_stop_libs_decision_at_every_interior_node(beta, delta):
     rng = np.random.default_rng(11)
     V = rng.uniform(0.0, 3.0, size=(11, 11))
     L, ctl, w, keep = _stop_control(V, SL.LQR_PRM, beta, delta)
-    h2, t = H.mca_constants(w)
+    h2, t = BR.mca_constants(w)
     xg = w.xgrid()
     C2 = np.asarray(w.cands, dtype=np.float64)
     checked = stops = 0
@@ -162,9 +163,9 @@ def test_host_twin_takes_stop_libs_decision_at_every_interior_node(beta, delta):
         for b in range(1, 10):
             x = np.array([xg[0][a], xg[1][b]])
             S = np.array([[V[a - 1, b], V[a + 1, b], V[a, b - 1], V[a, b + 1], V[a, b]]])
-            vals, _, _ = SL.node_values(H.lqr_host, w.params, x[None], S, C2, h2, t, beta, delta)
+            vals, _, _ = BR.candidate_values(H.lqr_host, w.params, x[None], S, C2, h2, t, beta, delta=delta)
             _, ui, mg = SL.stop_backup(vals, SL.lqr_psi(w.params, x[None]))
-            _, _, cmg = H.backup(vals)
+            _, _, cmg = BR.backup(vals)
             u = np.full(2, 7.0)
             stopped = C.c_int(-1)
             assert L.c3control_policy_eval_stop(ctl.h, C.c_double(0.0), fl.dp(fl.f64(x)), fl.dp(u), C.byref(stopped)) == 0

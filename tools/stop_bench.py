@@ -21,7 +21,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 
 from c3sc_amd import engine as E  # noqa: E402
 from c3sc_amd import workloads as wl  # noqa: E402
-import horizon_lib as H  # noqa: E402
+import backup_ref as BR  # noqa: E402
 import stop_lib as SL  # noqa: E402
 
 
@@ -60,10 +60,10 @@ def main():
             # psi at the median of the continuation values of a sample of live nodes
             sidx = wl.synth_fibers(w, k, 64, seed=7)
             costs, ab = eng.stencil_fibers_host(k, sidx)
-            h2, t = H.mca_constants(w)
-            x = H.node_states(w, k, sidx).reshape(-1, 2)
-            vals, _, _ = SL.node_values(SL.lqrn_host, w.params, x, costs.reshape(-1, 5), np.asarray(w.cands), h2, t, w.discount,
-                                        delta if delta > 0.0 else None)
+            h2, t = BR.mca_constants(w)
+            x = BR.node_states(w, k, sidx).reshape(-1, 2)
+            vals, _, _ = BR.candidate_values(SL.lqrn_host, w.params, x, costs.reshape(-1, 5), np.asarray(w.cands), h2, t, w.discount,
+                                             delta=delta if delta > 0.0 else None)
             live = ab.reshape(-1) == 0
             c0 = float(np.median(np.nanmin(vals, axis=1)[live] - SL.LQR_PRM[5] * (x[live] ** 2).sum(-1)))
             eng.set_model(mid, SL.LQR_PRM[:4] + (c0, SL.LQR_PRM[5]))
