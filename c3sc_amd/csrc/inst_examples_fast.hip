@@ -12,6 +12,7 @@
 #include "models.hpp"
 namespace c3sc {
 C3SC_REG_FPW_BOX(C3SC_MODEL_COTHRUST6D, 10, 1, Cothrust6D) // small batches at the pair kernel's padded rank
+C3SC_REG_STENCIL(6, 10, 1) // stencil_fibers on a value uploaded at that rank (the other 6-D classes: inst_lqg.hip)
 C3SC_REG_FPP1(C3SC_MODEL_COTHRUST6D, 10, 0, Cothrust6D)
 C3SC_REG_FPP1(C3SC_MODEL_COTHRUST6D, 10, 1, Cothrust6D)
 C3SC_REG_FPP1(C3SC_MODEL_COTHRUST6D, 10, 2, Cothrust6D)

@@ -1356,6 +1356,41 @@ int orc_stencil_fibers(struct orc_problem *p, size_t k, size_t F, const int *idx
     return res;
 }
 
+/* The per-candidate table behind orc_bellman_fibers: q[(f N + j) U + c] = control_value of candidate c at node j of fiber f, on
+ * the same stencil and in the same arithmetic as optimal_value, whose result is the first strict minimum of a row.  An absorbed
+ * node carries its boundary / obstacle cost in every column.  A candidate that optimal_value fails on fails the call (101). */
+int orc_q_fibers(struct orc_problem *p, size_t k, size_t F, const int *idx, double *q, int *absorbed_out)
+{
+    const size_t dx = p->dx, N = p->ngrid[k], S = 2 * dx + 1, U = p->ncand;
+    double *x = malloc(N * dx * sizeof(double));
+    double *costs = malloc(N * S * sizeof(double));
+    int *ab = malloc(N * sizeof(int));
+    double drift[16], prob[33], diff[256];
+    int res = 0;
+    for (size_t f = 0; f < F && res == 0; f++) {
+        size_t fi[20], dv;
+        build_fiber_x(p, k, idx + f * dx, x);
+        res = orc_mca_get_neighbor_costs(dx, N, x, p->bound, p->vf, p->ngrid, (const double *const *)p->xgrid, fi, &dv, ab, costs);
+        for (size_t j = 0; j < N && res == 0; j++) {
+            double *row = q + (f * N + j) * U;
+            if (ab[j] != 0) {
+                double v = 0.0;
+                int ui;
+                res = optimal_value(p, ab[j], x + j * dx, costs + j * S, &v, &ui);
+                for (size_t c = 0; c < U; c++) row[c] = v;
+                continue;
+            }
+            for (size_t c = 0; c < U && res == 0; c++)
+                res = control_value(p, x + j * dx, p->cands + c * p->du, costs + j * S, drift, diff, prob, &row[c]);
+        }
+        if (absorbed_out) memcpy(absorbed_out + f * N, ab, N * sizeof(int));
+    }
+    free(x);
+    free(costs);
+    free(ab);
+    return res;
+}
+
 /* ---- the two fiber callbacks in the ABI the cross approximation calls (valuefunc.c:615-616:
  * int f(size_t N, const double *x, double *out, void *args)), so that a test can hand them to a cross driver as the
  * black box, the way c3control_step_vi / step_pi do (bellman.c:2201, 2254).  args = struct orc_cb_args. ---- */

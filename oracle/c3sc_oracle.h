@@ -166,6 +166,9 @@ int orc_mca_get_neighbor_node_costs(size_t d, const double *x, const struct orc_
 int orc_policy_eval(struct orc_problem *p, const double *x, int *uidx, double *val); /* bellman.c:2105-2158 */
 /* Same for the FT stencil only: out F*N*(2dx+1). */
 int orc_stencil_fibers(struct orc_problem *p, size_t k, size_t F, const int *idx, double *out, int *absorbed_out);
+/* The value of every candidate at every node: q F*N*ncand (an absorbed node: its cost in every column), so that a test can
+ * tell how far the runner-up of orc_bellman_fibers' minimum lies from it.  Fails (101) where orc_bellman_fibers does. */
+int orc_q_fibers(struct orc_problem *p, size_t k, size_t F, const int *idx, double *q, int *absorbed_out);
 
 /* The fiber callbacks in the cross approximation's ABI (valuefunc.c:615-616); args points to a struct orc_cb_args. */
 struct orc_cb_args { struct orc_problem *p; struct orc_valuef *policy; int use_memo; size_t ncalls; };

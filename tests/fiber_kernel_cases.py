@@ -266,6 +266,11 @@ def _rows():
                 add("stencil", d, rp, "npl2", name, GRIDS2[name], _ranks(d, hi), 0, 23, _mid(d), f"k_fiber_per_wave<stencil,{d},{rp},2>",
                     unstaged=(1,) if (d, rp) == (3, 20) else ())
     add("stencil", 3, 20, "unstaged", "dubins3d", (21, 60, 16), _ranks(3, 19), 0, 23, (1,), "k_fiber_per_wave<stencil,3,20,1>", unstaged=(1,))
+    # classes that only one model of the dimension has -- Cothrust6D's 10 (LqgNd<6> has none), Perch7D's 8 (Car7D has none): found
+    # missing by the random sweep (tests/random_cases.py: case('cothrust6d', 0), bond ranks 9 and 10, and case('perch7d', 18), bond
+    # ranks 5 .. 8, whose stencil launches were refused before the registrations)
+    add("stencil", 6, 10, "", "cothrust6d", GRIDS["cothrust6d"], _ranks(6, 9), 0, 23, _mid(6), "k_fiber_per_wave<stencil,6,10,1>")
+    add("stencil", 7, 8, "", "perch7d", GRIDS["perch7d"], _ranks(7, 7), 0, 23, _mid(7), "k_fiber_per_wave<stencil,7,8,1>")
     return rows
 
 

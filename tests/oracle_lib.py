@@ -303,6 +303,16 @@ class Problem:
         assert res == 0
         return out, ab
 
+    def q_fibers(self, k, idx):
+        """(Q [F, N, ncand], absorbed [F, N]): every candidate's value at every node (orc_q_fibers); None where the oracle
+        refuses the batch (a stationary candidate)"""
+        idx = np.ascontiguousarray(idx, dtype=np.int32)
+        F, N = idx.shape[0], self.w.ngrid[k]
+        q = np.zeros((F, N, self.w.ncand))
+        ab = np.zeros((F, N), dtype=np.int32)
+        res = self.L.orc_q_fibers(self.h, C.c_size_t(k), C.c_size_t(F), ip(idx), dp(q), ip(ab))
+        return (q, ab) if res == 0 else None
+
     def bellman_vi(self, x, use_memo=True):
         x = f64(x)
         N = x.shape[0]

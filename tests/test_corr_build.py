@@ -3,7 +3,7 @@ The new symbols are exported; a correlated model's code object is for gfx950 and
 that the other flags select (at rank 12 the L2 form too) next to the forms without the term, never a rollout form, with no
 private segment at ranks 4 and 8; ncorr = 0 yields the _ic code object instruction for instruction and needs no covar in the
 source; a bad pair list is an argument error, pairs with a game, the box or interventions are refused; the library itself holds
-no corr kernel and keeps its 664 entries; KArgs keeps its size."""
+no corr kernel and keeps its 666 entries; KArgs keeps its size."""
 import ctypes as C
 import os
 import subprocess
@@ -211,7 +211,7 @@ def test_pairs_with_game_box_or_interventions_are_refused(kw):
 
 def test_library_kernels_have_no_corr_form(tmp_path):
     """the compiler's resource remarks of this build, regenerated from the *.res files: no library kernel is a corr
-    instantiation, and the library still has its 664 entries"""
+    instantiation, and the library still has its 666 entries"""
     import glob
     import json
     import shutil
@@ -222,7 +222,7 @@ def test_library_kernels_have_no_corr_form(tmp_path):
         shutil.copy(f, tmp_path)
     subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"), str(tmp_path)], check=True, capture_output=True)
     names = json.load(open(tmp_path / "kernel_resources.json"))
-    assert len(names) == 664
+    assert len(names) == 666
     assert not any("CorrOf" in n for n in names)
 
 

@@ -19,7 +19,7 @@ AUTO, PER_WAVE, PAIR, QUAD = 0, 1, 3, 4
 Entry = namedtuple("Entry", "kind model mtype d rp npl variant max_n k nwv dbuf name file order")
 REG_KINDS = ("C3SC_REG_FPW_BOX", "C3SC_REG_FPW", "C3SC_REG_FPP1", "C3SC_REG_FQ1", "C3SC_REG_FQD", "REG_FQD_SB", "C3SC_REG_STENCIL")
 EXPECTED = {"C3SC_REG_FPW": 61, "C3SC_REG_FPW_BOX": 35, "C3SC_REG_FPP1": 57, "C3SC_REG_FQ1": 60, "C3SC_REG_FQD": 17, "REG_FQD_SB": 4,
-            "C3SC_REG_STENCIL": 45}
+            "C3SC_REG_STENCIL": 47}
 HELPERS = {"REG7P", "REG7Q", "REG10Q", "REG10QD", "REG4Q", "REG6Q", "REG3P", "REG3R", "REG4P", "REG6P"}
 
 
@@ -89,9 +89,9 @@ REG = registrations()
 
 
 def test_registry_parse_counts():
-    """the expansion of the C3SC_REG_* lines, helper macros included: 279 registrations with distinct kernel names"""
+    """the expansion of the C3SC_REG_* lines, helper macros included: 281 registrations with distinct kernel names"""
     assert dict(Counter(e.kind for e in REG)) == EXPECTED
-    assert len(REG) == 279
+    assert len(REG) == 281
     names = [e.name for e in REG]
     assert len(names) == len(set(names)), [n for n, c in Counter(names).items() if c > 1]
     # ties that first-registered-wins decides (same model, dimension, rank, variant, nodes per lane, k) sit in one file: the order
@@ -101,6 +101,18 @@ def test_registry_parse_counts():
         groups.setdefault((e.model, e.d, e.rp, e.variant, e.npl, e.k), []).append(e)
     for g in groups.values():
         assert len({e.file for e in g}) == 1, g
+
+
+def test_every_model_class_has_a_stencil_kernel():
+    """stencil_fibers looks the model-independent kernel up at the padded rank of the upload, which pick_rp takes from the
+    MODEL's classes: every (dimension, padded rank, nodes per lane) some model has a Bellman kernel at has a stencil kernel too
+    (Cothrust6D's class 10 and Perch7D's class 8 had none: the random sweep's stencil launches were refused there)"""
+    stencil = {(e.d, e.rp, e.npl) for e in REG if e.kind == "C3SC_REG_STENCIL"}
+    for e in REG:
+        if e.kind in ("C3SC_REG_FPW", "C3SC_REG_FPW_BOX") and not e.mtype.startswith("TableModel"):
+            assert (e.d, e.rp, e.npl) in stencil, e.name
+        elif e.kind != "C3SC_REG_STENCIL" and not e.mtype.startswith("TableModel"):
+            assert (e.d, e.rp, 1) in stencil, e.name
 
 
 def test_case_table_covers_the_registry():

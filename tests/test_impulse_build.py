@@ -4,7 +4,7 @@ The new symbols are exported; an impulse model's code object is for gfx950 and h
 without interventions, never a k_rollout_ode form, with the rollouts' cross-lane rule and no scratch at ranks 4 and 8;
 nimpulse = 0 yields the _jd code object instruction for instruction and needs no impulse function in the source; nimpulse
 outside 0..8 is an argument error, interventions with a game, the box, horizon or stop are refused; the library itself holds no
-impulse kernel and keeps its 664 entries; KArgs keeps its size."""
+impulse kernel and keeps its 666 entries; KArgs keeps its size."""
 import ctypes as C
 import os
 import subprocess
@@ -182,7 +182,7 @@ def test_a_model_with_eight_interventions_compiles(tmp_path):
 
 def test_library_kernels_have_no_impulse_form(tmp_path):
     """the compiler's resource remarks of this build, regenerated from the *.res files: no library kernel is an impulse
-    instantiation, and the library still has its 664 entries"""
+    instantiation, and the library still has its 666 entries"""
     import glob
     import json
     import shutil
@@ -193,7 +193,7 @@ def test_library_kernels_have_no_impulse_form(tmp_path):
         shutil.copy(f, tmp_path)
     subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"), str(tmp_path)], check=True, capture_output=True)
     names = json.load(open(tmp_path / "kernel_resources.json"))
-    assert len(names) == 664
+    assert len(names) == 666
     assert not any("ImpulseOf" in n for n in names)
 
 

@@ -1,131 +1,76 @@
-"""Randomised parity of every kernel variant against the CPU oracle: grids (ragged N per dim, up to 128), ranks (mixed,
-up to the compiled maximum), boundary types per dim, obstacle boxes, discount, candidate lists (grid or random, with
-repeats), fibers (random + faces).  Values to 1e-12 relative, absorbed flags exact, argmin exact where the margin
-between the two best candidates is clear.
-    python tools/fuzz_parity.py [seconds] [seed]"""
-import os, sys, time
-import numpy as np
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
-import oracle_lib
-from c3sc_amd import workloads as wl
-from c3sc_amd.engine import BellmanEngine, C3scHipError
+"""Randomised parity of every Bellman fiber kernel variant against the CPU oracle, the long-running form of
+tests/test_gpu_random_sweep.py: the same generator and the same checker (tests/random_cases.py), walking seeds from `seed` upwards
+over every family (the eleven built-in workloads and the forms leg: lqr_cd_jump, lqr_ic, lqgame) instead of the committed seed lists.  Values to 1e-12 of the scale, absorbed flags exact, controls equal where
+the oracle pins them, the kernel name and every refusal as the selection restatement predicts; nothing is skipped without a count.
+    python tools/fuzz_parity.py [seconds] [seed]        walk seeds for `seconds` (120), from `seed` (1)
+    python tools/fuzz_parity.py --case FAMILY SEED      replay one case, every launch printed
+The summary counts launches and the worst relative error per kernel family, refusals by reason, and the draws the oracle does not
+accept (a stationary candidate).  Exit status 1 on a failure; a device error that is no refusal ends the run at once (2)."""
+import os
+import sys
+import time
 
-budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
-rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
-BASES = ["lqg2d", "dubins3d", "lqg6d", "car7d", "quad10d", "scar4d", "rossler3d", "perch7d", "tprob3d", "skid5d", "cothrust6d"]
-MAXN = {"lqg2d": 128, "dubins3d": 128, "lqg6d": 40, "car7d": 48, "quad10d": 28, "scar4d": 64, "rossler3d": 64, "perch7d": 40, "tprob3d": 64, "skid5d": 48, "cothrust6d": 40}
-MAXR = {"lqg2d": 20, "dubins3d": 20, "lqg6d": 20, "car7d": 20, "quad10d": 20, "scar4d": 20, "rossler3d": 20, "perch7d": 20, "tprob3d": 20, "skid5d": 20, "cothrust6d": 20}
-t0 = time.time(); ncase = nfail = nrun = 0
-last_note = t0
-worst = 0.0
-while time.time() - t0 < budget:
-    name = BASES[rng.integers(len(BASES))]
-    b = wl.WORKLOADS[name]()
-    d = b.dx
-    ngrid = tuple(int(rng.integers(5, MAXN[name] + 1)) for _ in range(d))
-    rmax = int(rng.integers(1, MAXR[name] + 1))
-    ranks = (1,) + tuple(int(rng.integers(1, rmax + 1)) for _ in range(d - 1)) + (1,)
-    bc = tuple(int(rng.choice([wl.BC_ABSORB, wl.BC_PERIODIC, wl.BC_REFLECT])) for _ in range(d)) if rng.random() < 0.7 else b.bc
-    obstacles = []
-    for _ in range(int(rng.integers(0, 3))):
-        cen = tuple(float(rng.uniform(b.lb[m], b.ub[m])) for m in range(d))
-        wid = tuple(float(rng.uniform(0.05, 0.8) * (b.ub[m] - b.lb[m])) for m in range(d))
-        obstacles.append((cen, wid))
-    discount = float(rng.choice([0.0, 0.1, 1.5])) if rng.random() < 0.5 else b.discount
-    cands = b.cands
-    if rng.random() < 0.4:  # random list: arbitrary order, a repeated row
-        U = int(rng.integers(1, 12)) if rng.random() < 0.85 else int(rng.integers(65, 150))  # sometimes longer than a wavefront
-        lo, hi = b.cands.min(axis=0), b.cands.max(axis=0)
-        cands = rng.uniform(lo, hi, size=(U, b.du))
-        if U > 2: cands[-1] = cands[0]
-    w = wl.Workload(name, b.model, b.params, d, b.du, b.lb, b.ub, ngrid, ranks, discount, bc, obstacles, np.ascontiguousarray(cands))
-    cores = [c * rng.uniform(0.5, 2.0) for c in wl.synth_cores(w, seed=int(rng.integers(1 << 30)))]
-    cends = bool(rng.random() < 0.3)  # the solver loops' consistent end-point rule (c3sc_hip_set_consistent_ends), not the reference's
-    try:
-        P = oracle_lib.Problem(w, cores, consistent_ends=cends)
-        eng = BellmanEngine(0); eng.configure(w, cores); eng.set_consistent_ends(cends)
-    except (C3scHipError, AssertionError) as e:
-        print("skip", name, ngrid, ranks, str(e)[:80]); continue
-    ncase += 1
-    if time.time() - last_note > 30.0:  # a silent GPU job is taken to be hung
-        print(f"... {ncase} problems, {nrun} kernel runs, {nfail} failures, {time.time() - t0:.0f} s", flush=True)
-        last_note = time.time()
-    eng_q = None  # the quad kernel pads ranks to multiples of 4: its own device copy of the value function
-    try:
-        eng_q = BellmanEngine(0); eng_q.set_variant(4); eng_q.configure(w, cores); eng_q.set_consistent_ends(cends)
-    except C3scHipError:
-        eng_q = None
-    for variant in (0, 1, 3, 4):
-        if variant == 4 and eng_q is None: continue
-        for k in range(d):
-            F = int(rng.choice([1, 3, 64, 65, 200]))
-            idx = wl.synth_fibers(w, k, F, seed=int(rng.integers(1 << 30)))
-            if F >= 3:
-                idx[0, :] = 0; idx[1, :] = np.array(ngrid) - 1
-            idx[:, k] = 0
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import oracle_lib
+import random_cases as R
+from c3sc_amd.engine import C3scHipError
+
+
+def summary(tally, ncase, nrejected, nfail, t0):
+    for line in tally.lines():
+        print(line)
+    print(f"{ncase} random problems, {sum(tally.runs.values())} kernel runs, {sum(tally.refused.values())} refused as predicted, "
+          f"{nrejected} draws the oracle does not accept, {nfail} failures, worst relative error {max(tally.worst.values(), default=0.0):.3e}, "
+          f"{time.time() - t0:.0f} s")
+
+
+def main(argv):
+    oracle_lib.build()
+    t0 = time.time()
+    tally = R.Tally()
+    make = lambda family, seed: R.case(family, seed) if family in R.FAMILIES else R.form_case(family, seed)
+    run = lambda c, **kw: R.run_case(c, tally, **kw) if c.family in R.FAMILIES else R.run_form_case(c, tally, **kw)
+    if argv[:1] == ["--case"]:
+        c = make(argv[1], int(argv[2]))
+        print(repr(c))
+        try:
+            run(c, verbose=True)
+        except AssertionError as e:
+            print("FAIL", e)
+            return 1
+        summary(tally, 1, 0, 0, t0)
+        return 0
+    budget = float(argv[0]) if argv else 120.0
+    seed = int(argv[1]) if len(argv) > 1 else 1
+    ncase = nfail = nrejected = 0
+    last_note = t0
+    while time.time() - t0 < budget:
+        for family in R.FAMILIES + R.FORM_FAMILIES:
+            c = make(family, seed)
             try:
-                e_use = eng_q if variant == 4 else eng
-                e_use.set_variant(variant)
-                out, ui, ab = e_use.bellman_fibers_host(k, idx)
-            except C3scHipError as e:
-                if "no kernel instantiation" in str(e) or "exceeds the 160 KB" in str(e) or "code 3" in str(e) or "serves this call" in str(e): continue
-                raise
-            ref, rui, rab = P.bellman_fibers(k, idx)
-            nrun += 1
-            scale = max(1.0, np.abs(ref).max())
-            err = np.abs(out - ref).max() / scale
-            worst = max(worst, err)
-            bad_ab = int((ab != rab).sum())
-            # argmin: only where the oracle's runner-up is clearly worse is the index pinned; compare values instead
-            if err > 1e-11 or bad_ab or not np.isfinite(out).all():
+                run(c)
+                ncase += 1
+            except R.Rejected:
+                nrejected += 1
+            except AssertionError as e:
+                ncase += 1
                 nfail += 1
-                print("FAIL", name, "ngrid", ngrid, "ranks", ranks, "bc", bc, "disc", discount, "U", len(cands), "obs", len(obstacles),
-                      "variant", variant, e_use.last_kernel(), "k", k, "F", F, "err", err, "absorbed mismatches", bad_ab, flush=True)
-    del eng_q
-    st = eng.status()
-    if st: print("status flags", st, name, ngrid, ranks)
-    # the batched valuef_eval_fiber_ind_nn (stencil of neighbour values) on its own
-    if rng.random() < 0.3:
-        for k in range(d):
-            idx = wl.synth_fibers(w, k, int(rng.choice([1, 30])), seed=int(rng.integers(1 << 30))); idx[:, k] = 0
-            try:
-                eng.set_variant(0)
-                costs, ab = eng.stencil_fibers_host(k, idx)
-            except C3scHipError as e:
-                if "no kernel instantiation" in str(e) or "no stencil" in str(e): continue
-                raise
-            ref, rab = P.stencil_fibers(k, idx)
-            nrun += 1
-            err = np.abs(costs - ref).max() / max(1.0, np.abs(ref).max())
-            worst = max(worst, err)
-            if err > 1e-11 or (ab != rab).any():
-                nfail += 1
-                print("FAIL stencil", name, "ngrid", ngrid, "ranks", ranks, "bc", bc, "k", k, "err", err, "absorbed mismatches", int((ab != rab).sum()), flush=True)
-    # policy evaluation (bellman_pi): greedy policy of a second value function applied to this one; the oracle's own
-    # argmin is forced on the device so that ties cannot matter
-    if rng.random() < 0.5:
-        cores_pol = wl.synth_cores(w, seed=int(rng.integers(1 << 30)))
-        pol_vf = oracle_lib.ValueF(w.ngrid, w.ranks, cores_pol)
-        eng_pol = BellmanEngine(0); eng_pol.configure(w, cores_pol); eng_pol.set_consistent_ends(cends)
-        eng.set_variant(0)
-        P.pi_begin(); P.pi_step_begin()
-        for k in range(d):
-            idx = wl.synth_fibers(w, k, int(rng.choice([2, 40])), seed=int(rng.integers(1 << 30))); idx[:, k] = 0
-            try:
-                ref, ref_ui = P.policy_fibers(pol_vf, k, idx)
-                _, ui, _ = eng_pol.bellman_fibers_host(k, idx)
-                out, _ = eng.policy_fibers_host(k, idx, np.where(ref_ui >= 0, ref_ui, ui).astype(np.int32))
-            except C3scHipError as e:
-                if "no kernel instantiation" in str(e): continue
-                raise
-            nrun += 1
-            err = np.abs(out - ref).max() / max(1.0, np.abs(ref).max())
-            worst = max(worst, err)
-            if err > 1e-11 or not np.isfinite(out).all():
-                nfail += 1
-                print("FAIL policy", name, "ngrid", ngrid, "ranks", ranks, "bc", bc, "disc", discount, "U", len(cands), "k", k, "err", err, flush=True)
-        del eng_pol
-    del eng
-print(f"{ncase} random problems, {nrun} kernel runs, {nfail} failures, worst relative error {worst:.3e}, {time.time() - t0:.0f} s")
-sys.exit(1 if nfail else 0)
+                print("FAIL", e, flush=True)
+            except C3scHipError as e:  # no refusal of launch_bellman's: nothing more is started on the device
+                print("DEVICE ERROR", repr(c), e, flush=True)
+                summary(tally, ncase, nrejected, nfail + 1, t0)
+                return 2
+            if time.time() - last_note > 30.0:  # a silent GPU job is taken to be hung
+                print(f"... seed {seed}: {ncase} problems, {sum(tally.runs.values())} kernel runs, {nfail} failures, {time.time() - t0:.0f} s", flush=True)
+                last_note = time.time()
+            if time.time() - t0 >= budget:
+                break
+        seed += 1
+    summary(tally, ncase, nrejected, nfail, t0)
+    return 1 if nfail else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main(sys.argv[1:]))
