@@ -13,6 +13,7 @@
 
 #include "../../include/c3sc_hip.h"
 #include "fiber_partition.hpp"
+#include "kernel_chain_walk.hpp"
 #include "kernel_common.hpp"
 #include "kernel_rollout.hpp"
 #include "kernel_rollout_ode.hpp"
@@ -655,6 +656,7 @@ int c3sc_hip_set_controls(c3sc_hip_ctx *c, int ncand, int du, const double *cand
 {
     if (!c || ncand < 1 || du < 1 || !cands) return fail(c, C3SC_ERR_ARG, "set_controls: bad arguments");
     c->ncand = ncand;
+    c->cands_placeholder = false;
     c->du = du;
     c->cands.assign(cands, cands + (size_t)ncand * du);
     c->static_dirty = true;
@@ -690,6 +692,7 @@ int c3sc_hip_set_game(c3sc_hip_ctx *c, int du_min, int nu, const double *U, int 
             for (int i = 0; i < dmax; i++) row[du_min + i] = W[(size_t)iw * dmax + i];
         }
     c->ncand = ncand;
+    c->cands_placeholder = false;
     c->du = mdu;
     c->cands.swap(cands);
     c->static_dirty = true;
@@ -713,6 +716,7 @@ int c3sc_hip_set_control_box(c3sc_hip_ctx *c, int du, const double *lb, const do
     c->box_du = du; c->box_grid = grid; c->box_polish = polish;
     if (c->ncand == 0) { // the arena layout wants at least one candidate row; it is not read in box mode
         c->ncand = 1; c->du = du;
+        c->cands_placeholder = true; // ... so a call that takes the list only (simulate_chain) knows there is none
         c->cands.assign(du, 0.0);
         c->static_dirty = true;
     }
@@ -1774,6 +1778,174 @@ int c3sc_hip_simulate_host(c3sc_hip_ctx *c, const c3sc_hip_sim_args *h)
                           a.d_x0 = b[0]; a.d_noise = b[1]; a.d_traj = b[2]; a.d_u = b[3];
                           a.d_cost = b[4]; a.d_exit = b[5]; a.d_vend = b[6]; a.d_xfinal = b[7];
                           return c3sc_hip_simulate(c, &a, nullptr);
+                      });
+}
+
+// ------------------------------------------------------------------ the approximating Markov chain (kernel_chain_walk.hpp)
+// What both chain calls need of the context, in the order that decides which error a bad call gets; on success A is filled
+// and e is the kernel of `variant`
+static int chain_setup(c3sc_hip_ctx *c, const char *who, int variant, KArgs &A, const KernelEntry *&e)
+{
+    if (c->model == C3SC_MODEL_TABLE) return failw(c, C3SC_ERR_UNSUPPORTED, who, ": the TABLE model has no device dynamics");
+    if (!c->have_mca || c->model == 0) return failw(c, C3SC_ERR_ARG, who, ": mca and model must be set");
+    for (const FormRow &r : FORM_ROWS)
+        if (ctx_form(c) & r.bit)
+            return fails(c, C3SC_ERR_UNSUPPORTED, std::string(who) + ": the chain is not offered " + r.problems + " (" + r.off + " first)");
+    if (c->model >= C3SC_MODEL_USER) return failw(c, C3SC_ERR_UNSUPPORTED, who, ": run-time compiled models have no chain kernels");
+    if (c->ncand == 0 || c->cands_placeholder)
+        return c->box_du > 0 ? failw(c, C3SC_ERR_UNSUPPORTED, who, ": the control box is not served (set_controls: the chain takes a candidate list)")
+                             : failw(c, C3SC_ERR_ARG, who, ": set_controls first");
+    int rc = fill_args(c, 0, 0, A, false);
+    if (rc != C3SC_OK) return rc;
+    rc = check_bounds_set(c, (std::string(who) + ": every dimension needs a boundary type").c_str());
+    if (rc != C3SC_OK) return rc;
+    e = find_sim_kernel(variant, c->model, c->d, c->rp);
+    if (!e) return failw(c, C3SC_ERR_UNSUPPORTED, who, ": no chain instantiation for this model at this padded rank");
+    A.cmode = 0;
+    return C3SC_OK;
+}
+
+// every index of the n nodes lies in the grid (the kernels clamp what they load, so this decides the error, not the addresses)
+static bool chain_nodes_in_range(const c3sc_hip_ctx *c, const int32_t *nodes, size_t n)
+{
+    for (size_t i = 0; i < n; i++)
+        for (int m = 0; m < c->d; m++)
+            if (nodes[i * c->d + m] < 0 || nodes[i * c->d + m] >= c->ngrid[m]) return false;
+    return true;
+}
+
+// the device entry points read the nodes back to check them: one copy and one synchronisation of the stream per call
+static int chain_check_device_nodes(c3sc_hip_ctx *c, const char *who, const int32_t *d_nodes, size_t n, void *stream)
+{
+    std::vector<int32_t> h(n * (size_t)c->d);
+    HIPCHK(c, hipMemcpyAsync(h.data(), d_nodes, h.size() * sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIPCHK(c, hipStreamSynchronize((hipStream_t)stream));
+    if (!chain_nodes_in_range(c, h.data(), n)) return failw(c, C3SC_ERR_ARG, who, ": a node index is out of range");
+    return C3SC_OK;
+}
+
+int c3sc_hip_chain_transitions(c3sc_hip_ctx *c, size_t n, const int32_t *d_nodes, int32_t *d_uidx, double *d_value, double *d_stage,
+                               double *d_dt, double *d_P, int32_t *d_flag, void *stream)
+{
+    const char *who = "chain_transitions";
+    if (!c) return C3SC_ERR_ARG;
+    KArgs A;
+    const KernelEntry *e = nullptr;
+    int rc = chain_setup(c, who, VARIANT_CHAIN_TRANSITIONS, A, e);
+    if (rc != C3SC_OK) return rc;
+    if (n == 0) return C3SC_OK;
+    if (!d_nodes) return failw(c, C3SC_ERR_ARG, who, ": null d_nodes");
+    if (n > SIM_MAX_TRAJ) return failw(c, C3SC_ERR_ARG, who, ": more than 2^31 nodes in one call");
+    rc = chain_check_device_nodes(c, who, d_nodes, n, stream);
+    if (rc != C3SC_OK) return rc;
+    ChainK S;
+    std::memset(&S, 0, sizeof(S));
+    S.n = (long)n;
+    S.node0 = d_nodes;
+    S.uidx = d_uidx;
+    S.value = d_value;
+    S.stage = d_stage;
+    S.dt = d_dt;
+    S.P = d_P;
+    S.flag = d_flag;
+    LaunchIO io{c->arena, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream, &S};
+    return launch_one(c, e, A, io, "chain_transitions: the chain kernels take a candidate list");
+}
+
+int c3sc_hip_chain_transitions_host(c3sc_hip_ctx *c, size_t n, const int32_t *nodes, int32_t *uidx, double *value, double *stage,
+                                    double *dt, double *P, int32_t *flag)
+{
+    if (!c) return C3SC_ERR_ARG;
+    if (n == 0) return c3sc_hip_chain_transitions(c, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    if (!nodes) return fail(c, C3SC_ERR_ARG, "chain_transitions_host: null nodes");
+    if (n > SIM_MAX_TRAJ) return fail(c, C3SC_ERR_ARG, "chain_transitions_host: sizes too large");
+    if (c->d == 0) return fail(c, C3SC_ERR_ARG, "chain_transitions_host: set_grid first");
+    const size_t d = (size_t)c->d, D = sizeof(double), I = sizeof(int32_t);
+    return stage_host(c, STAGE_PER_CALL, "chain_transitions_host",
+                      {{nodes, n * d * I, SEG_IN}, {uidx, n * I, SEG_OUT}, {value, n * D, SEG_OUT}, {stage, n * D, SEG_OUT},
+                       {dt, n * D, SEG_OUT}, {P, n * 2 * d * D, SEG_OUT}, {flag, n * I, SEG_OUT}},
+                      [&](const DevPtr *b) { return c3sc_hip_chain_transitions(c, n, b[0], b[1], b[2], b[3], b[4], b[5], b[6], nullptr); });
+}
+
+int c3sc_hip_simulate_chain(c3sc_hip_ctx *c, const c3sc_hip_chain_args *a, void *stream)
+{
+    const char *who = "simulate_chain";
+    if (!c) return C3SC_ERR_ARG;
+    if (!a) return failw(c, C3SC_ERR_ARG, who, ": null argument struct");
+    KArgs A;
+    const KernelEntry *e = nullptr;
+    int rc = chain_setup(c, who, VARIANT_CHAIN_WALK, A, e);
+    if (rc != C3SC_OK) return rc;
+    if (a->nsteps > (size_t)1 << 30) return failw(c, C3SC_ERR_ARG, who, ": nsteps too large");
+    if (a->n > SIM_MAX_TRAJ) return failw(c, C3SC_ERR_ARG, who, ": more than 2^31 walks in one call (split the batch, traj_offset)");
+    if (a->save_every == 0 && (a->d_traj || a->d_uidx)) return failw(c, C3SC_ERR_ARG, who, ": d_traj / d_uidx need save_every > 0");
+    if (a->save_every > a->nsteps && a->save_every > 1 && (a->d_traj || a->d_uidx))
+        return failw(c, C3SC_ERR_ARG, who, ": save_every larger than nsteps");
+    if (a->steps_per_launch < 0) return failw(c, C3SC_ERR_ARG, who, ": steps_per_launch < 0");
+    if (a->n == 0) return C3SC_OK;
+    if (!a->d_node0) return failw(c, C3SC_ERR_ARG, who, ": null d_node0");
+    const size_t n = a->n, d = (size_t)c->d;
+    rc = chain_check_device_nodes(c, who, a->d_node0, n, stream);
+    if (rc != C3SC_OK) return rc;
+    // the state between launches: cost | disc | time | exit_step | node (the doubles first: every block stays aligned)
+    rc = closed_loop_state(c, n * 4 * sizeof(double) + n * d * sizeof(int32_t));
+    if (rc != C3SC_OK) return rc;
+    ChainK S;
+    std::memset(&S, 0, sizeof(S));
+    S.n = (long)n;
+    S.traj_offset = (long long)a->traj_offset;
+    S.nsteps = (int)a->nsteps;
+    S.save_every = (int)a->save_every;
+    S.seed = a->seed;
+    S.node0 = a->d_node0;
+    S.uniform = a->d_uniform;
+    S.cost = (double *)c->sim_state;
+    S.disc = S.cost + n;
+    S.time = S.disc + n;
+    S.exit_step = (long long *)(S.time + n);
+    S.node = (int32_t *)(S.exit_step + n);
+    S.traj = a->d_traj;
+    S.uidx = a->d_uidx;
+    S.vend = a->d_vend;
+    const int chunk = a->steps_per_launch > 0 ? a->steps_per_launch : 64;
+    int s0 = 0;
+    do { // at least one launch: nsteps = 0 still tests xi_0 and evaluates V_end
+        S.s0 = s0;
+        S.s1 = (int)std::min<long long>((long long)s0 + chunk, (long long)a->nsteps);
+        LaunchIO io{c->arena, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream, &S};
+        rc = launch_one(c, e, A, io, "simulate_chain: the chain kernels take a candidate list");
+        if (rc != C3SC_OK) return rc;
+        s0 = S.s1;
+    } while (s0 < (int)a->nsteps);
+    rc = copy_back(c, a->d_cost, S.cost, n * sizeof(double), stream);
+    if (rc == C3SC_OK) rc = copy_back(c, a->d_disc, S.disc, n * sizeof(double), stream);
+    if (rc == C3SC_OK) rc = copy_back(c, a->d_time, S.time, n * sizeof(double), stream);
+    if (rc == C3SC_OK) rc = copy_back(c, a->d_exit, S.exit_step, n * sizeof(int64_t), stream);
+    if (rc == C3SC_OK) rc = copy_back(c, a->d_node, S.node, n * d * sizeof(int32_t), stream);
+    return rc;
+}
+
+int c3sc_hip_simulate_chain_host(c3sc_hip_ctx *c, const c3sc_hip_chain_args *h)
+{
+    if (!c) return C3SC_ERR_ARG;
+    if (!h) return fail(c, C3SC_ERR_ARG, "simulate_chain_host: null argument struct");
+    if (h->n == 0) return c3sc_hip_simulate_chain(c, h, nullptr);
+    if (!h->d_node0) return fail(c, C3SC_ERR_ARG, "simulate_chain_host: null node0");
+    if (h->n > SIM_MAX_TRAJ || h->nsteps > ((size_t)1 << 30)) return fail(c, C3SC_ERR_ARG, "simulate_chain_host: sizes too large");
+    if (h->save_every == 0 && (h->d_traj || h->d_uidx)) return fail(c, C3SC_ERR_ARG, "simulate_chain: d_traj / d_uidx need save_every > 0");
+    if (c->d == 0) return fail(c, C3SC_ERR_ARG, "simulate_chain_host: set_grid first");
+    const size_t n = h->n, d = (size_t)c->d, se = h->save_every, D = sizeof(double), I = sizeof(int32_t);
+    const size_t nrow = se ? h->nsteps / se + 1 : 0, nurow = se ? (h->nsteps + se - 1) / se : 0;
+    return stage_host(c, STAGE_PER_CALL, "simulate_chain_host",
+                      {{h->d_node0, n * d * I, SEG_IN}, {h->d_uniform, h->d_uniform ? n * h->nsteps * D : 0, SEG_IN},
+                       {h->d_cost, n * D, SEG_OUT}, {h->d_disc, n * D, SEG_OUT}, {h->d_time, n * D, SEG_OUT}, {h->d_vend, n * D, SEG_OUT},
+                       {h->d_node, n * d * I, SEG_OUT}, {h->d_exit, n * sizeof(int64_t), SEG_OUT},
+                       {h->d_traj, h->d_traj ? n * nrow * d * I : 0, SEG_OUT}, {h->d_uidx, h->d_uidx ? n * nurow * I : 0, SEG_OUT}},
+                      [&](const DevPtr *b) {
+                          c3sc_hip_chain_args a = *h;
+                          a.d_node0 = b[0]; a.d_uniform = b[1]; a.d_cost = b[2]; a.d_disc = b[3]; a.d_time = b[4]; a.d_vend = b[5];
+                          a.d_node = b[6]; a.d_exit = b[7]; a.d_traj = b[8]; a.d_uidx = b[9];
+                          return c3sc_hip_simulate_chain(c, &a, nullptr);
                       });
 }
 

@@ -29,6 +29,7 @@ struct c3sc_hip_ctx {
     int model = 0;
     double prm[C3SC_MAX_PARAMS] = {0};
     int ncand = 0, du = 0;
+    bool cands_placeholder = false; // the single zero row set_control_box puts where no list was set (nothing reads it in box mode)
     std::vector<double> cands;
     // zero-sum game (c3sc_hip_set_game): cands is the product list, game_ngrp groups of game_gsz; game_gsz = 0: no game
     int game_gsz = 0, game_ngrp = 0, game_order = 0;

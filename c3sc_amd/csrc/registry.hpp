@@ -38,6 +38,8 @@ struct LaunchIO {
 // KernelEntry::variant of the rollout, off-grid stencil and integrate kernels (c3sc_hip_simulate / c3sc_hip_stencil_points /
 // c3sc_hip_integrate): not Bellman-operator kernels, so the fiber paths never select them (find_kernel, pick_rp)
 constexpr int VARIANT_ROLLOUT = 100, VARIANT_STENCIL_POINTS = 101, VARIANT_ROLLOUT_ODE = 102;
+// ... and of the Markov-chain kernels (c3sc_hip_simulate_chain / c3sc_hip_chain_transitions, kernel_chain_walk.hpp)
+constexpr int VARIANT_CHAIN_WALK = 103, VARIANT_CHAIN_TRANSITIONS = 104;
 __host__ __device__ constexpr bool is_fiber_variant(int v) { return v < VARIANT_ROLLOUT; }
 
 #ifndef __HIPCC_RTC__

@@ -41,6 +41,7 @@ EXPORTS = [
     "c3sc_hip_model_compile_jd", "c3sc_hip_model_code_object_jd", "c3sc_hip_set_jumps", "c3sc_hip_jump_uniforms",
     "c3sc_hip_model_compile_ic", "c3sc_hip_model_code_object_ic", "c3sc_hip_set_impulses",
     "c3sc_hip_model_compile_cd", "c3sc_hip_model_code_object_cd", "c3sc_hip_set_correlation",
+    "c3sc_hip_chain_transitions", "c3sc_hip_chain_transitions_host", "c3sc_hip_simulate_chain", "c3sc_hip_simulate_chain_host",
 ]
 
 class SimArgs(C.Structure):
@@ -50,6 +51,14 @@ class SimArgs(C.Structure):
                 ("box", C.c_int), ("steps_per_launch", C.c_int), ("save_every", C.c_size_t), ("d_traj", C.c_void_p),
                 ("d_u", C.c_void_p), ("d_cost", C.c_void_p), ("d_exit", C.c_void_p), ("d_vend", C.c_void_p),
                 ("d_xfinal", C.c_void_p)]
+
+
+class ChainArgs(C.Structure):
+    """struct c3sc_hip_chain_args (include/c3sc_hip.h)"""
+    _fields_ = [("n", C.c_size_t), ("d_node0", C.c_void_p), ("nsteps", C.c_size_t), ("traj_offset", C.c_uint64),
+                ("seed", C.c_uint64), ("d_uniform", C.c_void_p), ("steps_per_launch", C.c_int), ("save_every", C.c_size_t),
+                ("d_cost", C.c_void_p), ("d_disc", C.c_void_p), ("d_time", C.c_void_p), ("d_vend", C.c_void_p),
+                ("d_node", C.c_void_p), ("d_exit", C.c_void_p), ("d_traj", C.c_void_p), ("d_uidx", C.c_void_p)]
 
 
 ODE_FORWARD_EULER, ODE_RK4 = 0, 1  # C3SC_ODE_*
@@ -176,6 +185,10 @@ def load_library():
         L.c3sc_hip_stencil_points.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.c3sc_hip_simulate.argtypes = [C.c_void_p, C.POINTER(SimArgs), C.c_void_p]
         L.c3sc_hip_integrate.argtypes = [C.c_void_p, C.POINTER(OdeArgs), C.c_void_p]
+        L.c3sc_hip_chain_transitions.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 8
+        L.c3sc_hip_chain_transitions_host.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 7
+        L.c3sc_hip_simulate_chain.argtypes = [C.c_void_p, C.POINTER(ChainArgs), C.c_void_p]
+        L.c3sc_hip_simulate_chain_host.argtypes = [C.c_void_p, C.POINTER(ChainArgs)]
         L.c3sc_hip_integrate_host.argtypes = [C.c_void_p, C.POINTER(OdeArgs)]
         L.c3sc_hip_normals.argtypes = [C.c_uint64, C.c_uint64, C.c_size_t, C.c_uint64, C.c_size_t, C.c_int, c_double_p]
         L.c3sc_hip_model_compile.argtypes = [C.POINTER(ModelSpec), c_int_p]
@@ -323,6 +336,18 @@ def decode_action(uidx, ncand: int):
     if np.ndim(uidx) == 0:
         return str(kind), int(idx)
     return kind, idx
+
+
+def decode_chain_exit(exit_step):
+    """d_exit of a chain walk (c3sc_hip_simulate_chain) as (step, kind): -1 is (-1, "running"), s >= 0 is (s, "exit") -- an absorbed
+    or obstacle node at step s -- and -(s + 2) is (s, "stuck"); works elementwise on arrays."""
+    e = np.asarray(exit_step)
+    stuck = e <= -2
+    step = np.where(stuck, -e - 2, e)
+    kind = np.where(stuck, "stuck", np.where(e >= 0, "exit", "running"))
+    if np.ndim(exit_step) == 0:
+        return int(step), str(kind)
+    return step, kind
 
 
 def jump_uniforms(seed: int, traj: int, step: int):
@@ -629,6 +654,100 @@ class BellmanEngine:
     def simulate_rc(self, args: "SimArgs", stream_ptr: int = 0) -> int:
         """c3sc_hip_simulate's return code as is (for callers that check the error codes)."""
         return int(self.L.c3sc_hip_simulate(self.h, C.byref(args), C.c_void_p(stream_ptr)))
+
+    # ------------------------------------------------------------------ the approximating Markov chain (DESIGN.md 4.18)
+    def chain_transitions(self, nodes_t, stream_ptr: Optional[int] = None):
+        """Device API (c3sc_hip_chain_transitions): nodes_t int32 CUDA tensor (n, d) of multi-indices.  Returns a dict of CUDA
+        tensors: uidx int32 (n,) the greedy candidate (-1 on absorbed, obstacle and stuck nodes), value, stage, dt (n,),
+        P (n, 2d) the transition probabilities in stencil order (lo, hi per dimension) and flag int32 (n,): 1 absorbing face,
+        -1 obstacle, 0 live."""
+        import torch
+
+        assert nodes_t.is_cuda and nodes_t.dtype == torch.int32 and nodes_t.is_contiguous() and nodes_t.shape[1] == self.d
+        n, d, dev = nodes_t.shape[0], self.d, nodes_t.device
+        f64 = dict(dtype=torch.float64, device=dev)
+        res = {"uidx": torch.empty((n,), dtype=torch.int32, device=dev), "value": torch.empty((n,), **f64),
+               "stage": torch.empty((n,), **f64), "dt": torch.empty((n,), **f64), "P": torch.empty((n, 2 * d), **f64),
+               "flag": torch.empty((n,), dtype=torch.int32, device=dev)}
+        if stream_ptr is None:
+            stream_ptr = torch.cuda.current_stream(dev).cuda_stream
+        self._chk(self.L.c3sc_hip_chain_transitions(self.h, n, nodes_t.data_ptr(), res["uidx"].data_ptr(), res["value"].data_ptr(),
+                                                    res["stage"].data_ptr(), res["dt"].data_ptr(), res["P"].data_ptr(),
+                                                    res["flag"].data_ptr(), C.c_void_p(stream_ptr)), "chain_transitions")
+        return res
+
+    def chain_transitions_host(self, nodes: np.ndarray):
+        """c3sc_hip_chain_transitions_host: the same on numpy arrays (nodes int32 (n, d)), staged through device memory."""
+        nodes = np.ascontiguousarray(nodes, dtype=np.int32)
+        n, d = nodes.shape[0], self.d
+        res = {"uidx": np.empty((n,), np.int32), "value": np.empty((n,)), "stage": np.empty((n,)), "dt": np.empty((n,)),
+               "P": np.empty((n, 2 * d)), "flag": np.empty((n,), np.int32)}
+        self._chk(self.L.c3sc_hip_chain_transitions_host(self.h, n, nodes.ctypes.data, *[res[k].ctypes.data for k in
+                                                                                          ("uidx", "value", "stage", "dt", "P", "flag")]),
+                  "chain_transitions_host")
+        return res
+
+    def simulate_chain(self, node0_t, nsteps: int, seed: int = 0, uniform_t=None, save_every: int = 0, traj_offset: int = 0,
+                       steps_per_launch: int = 0, stream_ptr: Optional[int] = None):
+        """Device API (c3sc_hip_simulate_chain): node0_t int32 CUDA tensor (n, d) of start nodes.  Returns a dict of CUDA tensors:
+        cost J, disc D, time T, vend V(xi_nsteps) (n,), node int32 (n, d), exit int64 (n,) (decode_chain_exit) and, with
+        save_every > 0, traj int32 (n, nsteps//save_every + 1, d) and uidx int32 (n, ceil(nsteps/save_every)).  uniform_t:
+        float64 (n, nsteps) uniforms in [0, 1), else Philox(seed).  cost + disc * J(node) estimates the greedy policy's exact cost
+        in the discrete problem without bias."""
+        import torch
+
+        assert node0_t.is_cuda and node0_t.dtype == torch.int32 and node0_t.is_contiguous() and node0_t.shape[1] == self.d
+        n, d, dev = node0_t.shape[0], self.d, node0_t.device
+        f64 = dict(dtype=torch.float64, device=dev)
+        res = {"cost": torch.empty((n,), **f64), "disc": torch.empty((n,), **f64), "time": torch.empty((n,), **f64),
+               "vend": torch.empty((n,), **f64), "node": torch.empty((n, d), dtype=torch.int32, device=dev),
+               "exit": torch.empty((n,), dtype=torch.int64, device=dev)}
+        a = ChainArgs()
+        a.n, a.d_node0, a.nsteps, a.traj_offset, a.seed = n, node0_t.data_ptr(), int(nsteps), int(traj_offset), int(seed)
+        a.steps_per_launch, a.save_every = int(steps_per_launch), int(save_every)
+        if uniform_t is not None:
+            assert uniform_t.is_cuda and uniform_t.dtype == torch.float64 and uniform_t.is_contiguous()
+            assert tuple(uniform_t.shape) == (n, nsteps)
+            a.d_uniform = uniform_t.data_ptr()
+        if save_every > 0:
+            res["traj"] = torch.empty((n, nsteps // save_every + 1, d), dtype=torch.int32, device=dev)
+            res["uidx"] = torch.empty((n, (nsteps + save_every - 1) // save_every), dtype=torch.int32, device=dev)
+            a.d_traj, a.d_uidx = res["traj"].data_ptr(), res["uidx"].data_ptr()
+        a.d_cost, a.d_disc, a.d_time, a.d_vend = (res["cost"].data_ptr(), res["disc"].data_ptr(), res["time"].data_ptr(),
+                                                  res["vend"].data_ptr())
+        a.d_node, a.d_exit = res["node"].data_ptr(), res["exit"].data_ptr()
+        if stream_ptr is None:
+            stream_ptr = torch.cuda.current_stream(dev).cuda_stream
+        self._chk(self.L.c3sc_hip_simulate_chain(self.h, C.byref(a), C.c_void_p(stream_ptr)), "simulate_chain")
+        return res
+
+    def simulate_chain_host(self, node0: np.ndarray, nsteps: int, seed: int = 0, uniform=None, save_every: int = 0,
+                            traj_offset: int = 0, steps_per_launch: int = 0):
+        """c3sc_hip_simulate_chain_host: simulate_chain on numpy arrays, staged through device memory."""
+        node0 = np.ascontiguousarray(node0, dtype=np.int32)
+        n, d = node0.shape[0], self.d
+        res = {"cost": np.empty((n,)), "disc": np.empty((n,)), "time": np.empty((n,)), "vend": np.empty((n,)),
+               "node": np.empty((n, d), np.int32), "exit": np.empty((n,), np.int64)}
+        a = ChainArgs()
+        a.n, a.d_node0, a.nsteps, a.traj_offset, a.seed = n, node0.ctypes.data, int(nsteps), int(traj_offset), int(seed)
+        a.steps_per_launch, a.save_every = int(steps_per_launch), int(save_every)
+        if uniform is not None:
+            uniform = _f64(uniform)
+            assert uniform.shape == (n, nsteps)
+            a.d_uniform = uniform.ctypes.data
+        if save_every > 0:
+            res["traj"] = np.empty((n, nsteps // save_every + 1, d), np.int32)
+            res["uidx"] = np.empty((n, (nsteps + save_every - 1) // save_every), np.int32)
+            a.d_traj, a.d_uidx = res["traj"].ctypes.data, res["uidx"].ctypes.data
+        a.d_cost, a.d_disc, a.d_time, a.d_vend = (res["cost"].ctypes.data, res["disc"].ctypes.data, res["time"].ctypes.data,
+                                                  res["vend"].ctypes.data)
+        a.d_node, a.d_exit = res["node"].ctypes.data, res["exit"].ctypes.data
+        self._chk(self.L.c3sc_hip_simulate_chain_host(self.h, C.byref(a)), "simulate_chain_host")
+        return res
+
+    def simulate_chain_rc(self, args: "ChainArgs", stream_ptr: int = 0) -> int:
+        """c3sc_hip_simulate_chain's return code as is (for callers that check the error codes)."""
+        return int(self.L.c3sc_hip_simulate_chain(self.h, C.byref(args), C.c_void_p(stream_ptr)))
 
     def integrate(self, x0_t, dt_out: float, nout: int, method: str = "rk4", dt_int: Optional[float] = None, goal=None,
                   keep_in=None, wrap_periodic: bool = False, box: bool = False, save_every: int = 0, evals_per_launch: int = 0,

@@ -2294,3 +2294,175 @@ int c3control_simulate(struct C3Control *c, const double *x0, double dt, size_t 
     free(b); free(s); free(u);
     return 0;
 }
+
+/* ---- the approximating Markov chain itself */
+
+/* the modes the chain is not offered in: every form of the backup other than the plain one */
+static int chain_mode_check(const char *who, const struct C3Control *c)
+{
+    if (c->dp->stopping || c->dp->jumps || c->dp->impulses || c->dp->correlation || c->dp->hz_dt > 0.0)
+        return reject(who, "the chain is offered for the plain backup only: not in stopping, jump, impulse, correlation or horizon mode");
+    if (c->opt_sim != NULL && c3opt_get_game(c->opt_sim, NULL, NULL, NULL, NULL, NULL) >= 0)
+        return reject(who, "the chain is offered for the plain backup only: not for games");
+    return 0;
+}
+
+/* lo / hi of index i on n nodes by the fixed-dimension rule of process_fibers_neighbor (nodeutil.c:513-566) */
+static void chain_neighbors(size_t i, size_t n, enum EBTYPE b, size_t *lo, size_t *hi)
+{
+    *lo = i == 0 ? (b == PERIODIC ? n - 2 : i) : i - 1;
+    *hi = i == n - 1 ? (b == PERIODIC ? 1 : i) : i + 1;
+    if (b == ABSORB && (i == 0 || i == n - 1)) *lo = *hi = i;
+}
+
+int c3control_simulate_chain(struct C3Control *c, const int32_t *node0, size_t nsteps, const double *uniforms, int32_t *traj,
+                             int32_t *uidx, double *cost, double *disc, double *time, double *vend, long *exit_step)
+{ /* new: ONE walk of the approximating chain on the host, over the user's callbacks: the stencil of policy_sim at the node and its
+     2 dx index-rule neighbours, bellman_optimal for the decision, transition_assemble for the winner's probabilities and dt.
+     The twin c3sc_hip_simulate_chain is held to: the same outcome order (lo, hi per dimension), sampling rule and accumulation */
+    const char *who = "c3control_simulate_chain";
+    if (c == NULL || node0 == NULL) return reject(who, "null control or node0");
+    if (c->policy_sim == NULL || c->opt_sim == NULL) return reject(who, "no implicit policy (c3control_add_policy_sim)");
+    if (c->dp->stagecost == NULL) return reject(who, "the host callbacks (add_drift/diff/stagecost/...) are needed");
+    if (!c3opt_is_bruteforce(c->opt_sim)) return reject(who, "the chain takes a candidate list (a BRUTEFORCE opt_sim), not a control box");
+    int rc = chain_mode_check(who, c);
+    if (rc != 0) return rc;
+    if (nsteps > 0 && uniforms == NULL) return reject(who, "null uniforms");
+    const size_t dx = c->dx, du = c->du, dw = c->dw;
+    if (dx > C3SC_MAX_DIM) return reject(who, "too many dimensions");
+    size_t ix[C3SC_MAX_DIM], y[C3SC_MAX_DIM];
+    double x[C3SC_MAX_DIM];
+    for (size_t m = 0; m < dx; m++) {
+        if (node0[m] < 0 || (size_t)node0[m] >= c->ngrid[m]) return reject(who, "a node index is out of range");
+        ix[m] = (size_t)node0[m];
+    }
+    const size_t ncand = c3opt_get_nbrute(c->opt_sim);
+    const double *cands = c3opt_get_brute_vals(c->opt_sim);
+    double *u = xcalloc(du, sizeof(double)), *drift = xcalloc(dx, sizeof(double)), *diff = xcalloc(dx * dw, sizeof(double));
+    double *prob = xcalloc(2 * dx + 1, sizeof(double));
+    int *absorbed = workspace_get_absorbed(c->work, 0);
+    double *costs = workspace_get_costs(c->work, 0);
+    struct ControlParams *cp = control_params_create(dx, dw, c->dp, c->mca, c->work, c->opt_sim);
+    cp->vf = c->policy_sim;
+    double J = 0.0, D = 1.0, T = 0.0;
+    long ex = -1;
+    for (size_t s = 0; s <= nsteps; s++) {
+        if (traj != NULL)
+            for (size_t m = 0; m < dx; m++) traj[s * dx + m] = (int32_t)ix[m];
+        int face = 0;
+        for (size_t m = 0; m < dx; m++) {
+            x[m] = c->xgrid[m][ix[m]];
+            if (boundary_type_dim(c->bound, m, 0) == ABSORB && (ix[m] == 0 || ix[m] == c->ngrid[m] - 1)) face = 1;
+        }
+        const int flag = face ? 1 : (boundary_in_obstacle(c->bound, x) ? -1 : 0);
+        /* the stencil: the function train at the index-rule neighbours, then at the node */
+        for (size_t m = 0; m < dx; m++) {
+            size_t lo, hi;
+            chain_neighbors(ix[m], c->ngrid[m], boundary_type_dim(c->bound, m, 0), &lo, &hi);
+            memcpy(y, ix, dx * sizeof(size_t));
+            y[m] = lo;
+            costs[2 * m] = valuef_eval_ind(c->policy_sim, y);
+            y[m] = hi;
+            costs[2 * m + 1] = valuef_eval_ind(c->policy_sim, y);
+        }
+        costs[2 * dx] = valuef_eval_ind(c->policy_sim, ix);
+        if (ex == -1 && flag != 0) { /* the flag test: the face wins over the obstacle */
+            double term;
+            rc = flag == 1 ? c->dp->boundcost(0.0, x, &term) : c->dp->obscost(x, &term);
+            if (rc != 0) break;
+            J += D * term;
+            ex = (long)s;
+        }
+        if (s == nsteps) {
+            if (vend != NULL) *vend = costs[2 * dx];
+            break;
+        }
+        if (uidx != NULL) uidx[s] = -1;
+        if (ex != -1) continue; /* frozen */
+        *absorbed = 0;
+        control_params_add_time_and_states(cp, 0.0, 1, x);
+        struct Memory mem = {cp, 0};
+        double val, stage, dt = 0.0;
+        for (size_t i = 0; i < du; i++) u[i] = 0.0;
+        rc = bellman_optimal(du, u, &val, &mem);
+        if (rc != 0) break;
+        /* the winner's transitions (the workspace holds the last candidate's, not the winner's) */
+        rc = drift_eval(c->dp->drift, 0.0, x, u, drift, NULL);
+        if (rc == 0) rc = diff_eval(c->dp->diff, 0.0, x, u, diff, NULL);
+        if (rc == 0) rc = c->dp->stagecost(0.0, x, u, &stage, NULL);
+        if (rc != 0) break;
+        if (transition_assemble(dx, du, dw, c->mca->h2, c->mca->t, drift, NULL, diff, NULL, prob, NULL, &dt, NULL, NULL) != 0) {
+            ex = -((long)s + 2); /* stuck: no rate to leave with */
+            continue;
+        }
+        if (uidx != NULL) /* the list position of the winner: the first candidate with its bits */
+            for (size_t q = 0; q < ncand; q++)
+                if (memcmp(cands + q * du, u, du * sizeof(double)) == 0) { uidx[s] = (int32_t)q; break; }
+        J += D * stage * dt;
+        T += dt;
+        D *= exp(-c->dp->discount * dt);
+        /* the first k with v < c_k (probabilities: v C < c_k C), else the last k with p_k > 0 */
+        const double v = uniforms[s];
+        double cum = 0.0;
+        long pick = -1, lastpos = -1;
+        for (size_t k = 0; k < 2 * dx; k++) {
+            cum += prob[k];
+            if (pick < 0 && v < cum) pick = (long)k;
+            if (prob[k] > 0.0) lastpos = (long)k;
+        }
+        if (pick < 0) pick = lastpos;
+        size_t lo, hi;
+        const size_t m = (size_t)pick / 2;
+        chain_neighbors(ix[m], c->ngrid[m], boundary_type_dim(c->bound, m, 0), &lo, &hi);
+        ix[m] = (pick & 1) ? hi : lo;
+    }
+    control_params_destroy(cp);
+    free(u); free(drift); free(diff); free(prob);
+    if (rc != 0) return rc;
+    if (cost != NULL) *cost = J;
+    if (disc != NULL) *disc = D;
+    if (time != NULL) *time = T;
+    if (exit_step != NULL) *exit_step = ex;
+    return 0;
+}
+
+int c3control_simulate_chain_batch(struct C3Control *c, size_t ntraj, const int32_t *node0, size_t nsteps, uint64_t seed,
+                                   const double *uniforms, size_t save_every, int32_t *traj, int32_t *uidx, double *cost,
+                                   double *disc, double *time, double *vend, long *exit_step, int32_t *node)
+{ /* new: ntraj walks of the chain on the device (c3sc_hip_simulate_chain_host): the policy_sim value function, opt_sim's
+     candidate list and the device model; c3control_simulate_batch's rejections */
+    const char *who = "c3control_simulate_chain_batch";
+    int rc = batch_policy_check(who, c, 1); /* a walk never leaves the grid: a state transform has nothing to act on */
+    if (rc != 0) return rc;
+    if (c->dw != c->dx) return reject(who, "the device models have dw = dx (diagonal diffusion)");
+    rc = chain_mode_check(who, c);
+    if (rc != 0) return rc;
+    if (ntraj == 0) return 0;
+    if (node0 == NULL) return reject(who, "null node0");
+    if ((traj != NULL || uidx != NULL) && save_every == 0) return reject(who, "traj / uidx need save_every > 0");
+    if (ntraj > ((size_t)1 << 31) || nsteps > ((size_t)1 << 30)) return reject(who, "more than 2^31 walks or 2^30 steps");
+    if (!c3opt_is_bruteforce(c->opt_sim)) return reject(who, "the chain takes a candidate list (a BRUTEFORCE opt_sim), not a control box");
+    struct c3sc_hip_ctx *ctx;
+    int box;
+    rc = batch_device_ctx(who, c, &ctx, &box);
+    if (rc != 0) return rc;
+    c3sc_hip_chain_args a;
+    memset(&a, 0, sizeof(a));
+    a.n = ntraj;
+    a.d_node0 = node0;
+    a.nsteps = nsteps;
+    a.seed = seed;
+    a.d_uniform = uniforms;
+    a.save_every = save_every;
+    a.d_traj = traj;
+    a.d_uidx = uidx;
+    a.d_cost = cost;
+    a.d_disc = disc;
+    a.d_time = time;
+    a.d_vend = vend;
+    a.d_exit = (int64_t *)exit_step;
+    a.d_node = node;
+    rc = c3sc_hip_simulate_chain_host(ctx, &a);
+    if (rc != C3SC_OK) fprintf(stderr, "%s: %s (code %d)\n", who, c3sc_hip_last_error(ctx), rc);
+    return rc;
+}

@@ -136,6 +136,27 @@ int c3control_simulate(struct C3Control *, const double *x0, double dt, size_t n
 int c3control_simulate_batch(struct C3Control *, size_t ntraj, const double *x0, double dt, size_t nsteps, uint64_t seed,
                              const double *noise, int wrap_periodic, size_t save_every, double *traj, double *utraj, double *cost,
                              long *exit_step, double *vend);
+/* new: the approximating Markov chain itself (c3sc_hip.h has the operator, the outcome order and the sampling
+ * rule).  c3control_simulate_chain walks ONE trajectory of the chain on the host: from the multi-index node0[dx], at each step
+ * the stencil of policy_sim at the node and its 2 dx index-rule neighbours, bellman_optimal over opt_sim's candidate list for the
+ * decision, the user's callbacks and transition_assemble for the winner's probabilities P_k and dt; J += D stage dt, T += dt,
+ * D *= exp(-beta dt), then uniforms[s] in [0, 1) picks the first outcome k with v < P_0 + .. + P_k (k = 2m lo, 2m + 1 hi of
+ * dimension m), else the last with P_k > 0.  An absorbing-face node pays D boundcost, an obstacle node D obscost (exit_step = s;
+ * the face wins); a node whose winner has no rate to leave with freezes the walk with exit_step = -(s + 2); -1: still running.
+ * traj (nsteps+1) x dx nodes and uidx[nsteps] list positions of the decisions (-1 once frozen) may be NULL, as may cost (J), disc
+ * (D), time (T), vend (policy_sim at the final node) and exit_step.  This is the twin c3sc_hip_simulate_chain is tested against.
+ * c3control_simulate_chain_batch runs ntraj walks on the GPU (c3sc_hip_simulate_chain_host): policy_sim's value function,
+ * opt_sim's candidate list and the DEVICE model, with c3control_simulate_batch's rejections.  Host arrays: node0 ntraj x dx;
+ * uniforms NULL (Philox, keyed by (seed, walk, step)) or ntraj x nsteps; traj ntraj x (nsteps/save_every + 1) x dx and uidx
+ * ntraj x ceil(nsteps/save_every) (NULL, or save_every > 0); cost, disc, time, vend, exit_step [ntraj], node ntraj x dx (final).
+ * Both return C3SC_ERR_ARG with a message on stderr for: no policy_sim, a control box, a node index out of range, and every mode
+ * other than the plain backup (stopping, jumps, impulses, correlation, the horizon step, a game); the batch form also for no
+ * device model, and C3SC_ERR_UNSUPPORTED where the model has no chain kernel at this rank. */
+int c3control_simulate_chain(struct C3Control *, const int32_t *node0, size_t nsteps, const double *uniforms, int32_t *traj,
+                             int32_t *uidx, double *cost, double *disc, double *time, double *vend, long *exit_step);
+int c3control_simulate_chain_batch(struct C3Control *, size_t ntraj, const int32_t *node0, size_t nsteps, uint64_t seed,
+                                   const double *uniforms, size_t save_every, int32_t *traj, int32_t *uidx, double *cost,
+                                   double *disc, double *time, double *vend, long *exit_step, int32_t *node);
 /* new: the examples' closed-loop tail without cdyn (integrator_create_controlled + trajectory_step + their goal test, e.g.
  * dubinscar.c:379-412, perch.c:447-480) for ONE trajectory on the host, over the user's callbacks and c3control_controller
  * (transform_sim as given): nout outer steps of dt_out, each dt_out / dt_int substeps (an integer to 1e-9 relative; dt_int = 0:

@@ -351,6 +351,62 @@ int c3sc_hip_integrate_host(c3sc_hip_ctx *ctx, const c3sc_hip_ode_args *args);
  * traj0 + t under `seed` -- the same bits the device draws (philox.hpp) */
 int c3sc_hip_normals(uint64_t seed, uint64_t traj0, size_t ntraj, uint64_t step0, size_t nsteps, int dw, double *out);
 
+/* The approximating Markov chain itself.  At a live node xi the chain of the greedy policy of the uploaded
+ * value function moves to the 2d index-rule neighbours with probabilities p_k / C after the interval dt = h^2 / C, C = sum p_k.
+ * Outcome order = stencil order: k = 2m is the lo and k = 2m + 1 the hi neighbour of dimension m, by the fixed-dimension index
+ * rule in EVERY dimension (a reflecting end names the node itself -- a self-loop that still costs its dt; the periodic seam is
+ * n - 2 / 1).  Node flags: 1 on an absorbing face (index 0 or N - 1 of any ABSORB dimension), else -1 inside an obstacle, else 0;
+ * this is the consistent end-point rule and does not depend on c3sc_hip_set_consistent_ends (a walk has no fiber direction).
+ *
+ * c3sc_hip_chain_transitions: the deterministic half for n nodes, d_nodes int32 [n*d] multi-indices.  Per node (each output may
+ * be NULL): d_uidx int32 the greedy candidate (plain backup over the candidate list, first minimum), d_value the backup's value,
+ * d_stage g(x, u), d_dt, d_P [n*2d] the probabilities in outcome order, d_flag int32.  A flagged node has uidx = -1, dt = 0,
+ * P = 0 and value = stage = the bound / obstacle cost.  A stuck node -- live, with no valid candidate or a winner with
+ * C < 1e-14 -- raises C3SC_STATUS_STATIONARY and has uidx = -1, dt = 0, P = 0.
+ *
+ * c3sc_hip_simulate_chain: n walks of that chain, one GPU lane each.  Step s of a walk at the node xi_s:
+ *   flag test    an absorbed node pays D boundcost(x), an obstacle node D obscost(x); exit = s and the walk is frozen
+ *   stuck        a stuck node freezes the walk: exit = -(s + 2)   (C3SC_CHAIN_STUCK(s); -1 stays "still running")
+ *   accumulate   J += D stage dt, T += dt, D *= exp(-beta dt)   (D starts at 1)
+ *   sample       v = d_uniform[i*nsteps + s] when given, else the first uniform of c3sc_hip_jump_uniforms(seed, traj_offset + i, s);
+ *                with c_k = p_0 + .. + p_k the outcome is the first k with v C < c_k, else the last k with p_k > 0
+ * xi_nsteps gets the flag test as well and d_vend = V(xi_nsteps).  With J^pi, the exact cost of the greedy policy pi in the discrete
+ * problem, J_n + D_n J^pi(xi_n) is an unbiased estimator of J^pi(xi_0); with d_vend in its place the mean equals V(xi_0) only where V
+ * is the fixed point of its own greedy operator.  The call is cut into launches of steps_per_launch steps (0 = 64); results do not
+ * depend on that, on n, or on how a batch is split (traj_offset).  The state between launches shares c3sc_hip_simulate's buffer
+ * of the context: calls on one context must not overlap.
+ * Errors: C3SC_ERR_ARG (state not set, null inputs, a node index out of range, a C3SC_EB_NONE dimension, save_every = 0 with
+ * d_traj / d_uidx, a save_every above nsteps and above 1 with either, as c3sc_hip_simulate); C3SC_ERR_UNSUPPORTED, the context staying usable: the TABLE model, a run-time compiled model, no
+ * instantiation at the padded rank, a context in game, horizon, stopping, jump, impulse or correlation mode.  The control box is
+ * not served: the calls take the candidate list.  Both calls read the node indices back to check them, so they synchronise
+ * `stream` once before they launch.  last_kernel names the kernel. */
+#define C3SC_CHAIN_STUCK(s) (-((int64_t)(s) + 2))
+int c3sc_hip_chain_transitions(c3sc_hip_ctx *ctx, size_t n, const int32_t *d_nodes, int32_t *d_uidx, double *d_value, double *d_stage,
+                               double *d_dt, double *d_P, int32_t *d_flag, void *stream);
+int c3sc_hip_chain_transitions_host(c3sc_hip_ctx *ctx, size_t n, const int32_t *nodes, int32_t *uidx, double *value, double *stage,
+                                    double *dt, double *P, int32_t *flag);
+typedef struct c3sc_hip_chain_args {
+    size_t n;                /* walks */
+    const int32_t *d_node0;  /* [n*d] start nodes */
+    size_t nsteps;
+    uint64_t traj_offset;    /* global index of walk 0 (Philox counter) */
+    uint64_t seed;
+    const double *d_uniform; /* [n*nsteps] uniforms in [0, 1) or NULL (seeded Philox); wins when non-NULL */
+    int steps_per_launch;    /* 0 = 64 */
+    size_t save_every;       /* 0 = none; else nodes s = 0, e, 2e, ... <= nsteps and decisions s = 0, e, ... < nsteps */
+    double *d_cost;          /* [n] J or NULL */
+    double *d_disc;          /* [n] D or NULL */
+    double *d_time;          /* [n] T or NULL */
+    double *d_vend;          /* [n] V(xi_nsteps) or NULL */
+    int32_t *d_node;         /* [n*d] final node or NULL */
+    int64_t *d_exit;         /* [n] -1 running, s >= 0 absorbed / obstacle at step s, C3SC_CHAIN_STUCK(s) stuck at step s; or NULL */
+    int32_t *d_traj;         /* [n][nsteps/save_every + 1][d] or NULL */
+    int32_t *d_uidx;         /* [n][ceil(nsteps/save_every)] (-1 once frozen) or NULL */
+} c3sc_hip_chain_args;
+int c3sc_hip_simulate_chain(c3sc_hip_ctx *ctx, const c3sc_hip_chain_args *args, void *stream);
+/* the same with HOST arrays in every pointer of args: staged through device memory, synchronous */
+int c3sc_hip_simulate_chain_host(c3sc_hip_ctx *ctx, const c3sc_hip_chain_args *args);
+
 /* Device-resident core steps of the cross approximation that calls the path (valuefunc.c:603-767 hands bellman_vi to C3's
  * ftapprox_cross; c3sc_amd/host/c3sc_cross.c is this library's driver).  A cross iteration is 2 d sequential core steps of
  * r_k r_{k+1} fibers each; with fibers on the GPU and factorisation + node memo on the host a sweep is host-bound.  These
