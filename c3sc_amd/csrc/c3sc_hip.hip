@@ -13,11 +13,13 @@
 
 #include "../../include/c3sc_hip.h"
 #include "fiber_partition.hpp"
+#include "fiber_partition_sort.hpp"
 #include "kernel_chain_walk.hpp"
 #include "kernel_common.hpp"
 #include "kernel_rollout.hpp"
 #include "kernel_rollout_ode.hpp"
 #include "model_tables.hpp"
+#include "pad_cores.hpp"
 #include "registry.hpp"
 
 namespace c3sc {
@@ -31,6 +33,9 @@ std::vector<KernelEntry> &kernel_registry()
 // Re-pack one FT core from the reference layout cores[m][j*r0*r1 + a + b*r0] (valuefunc.c:165-189)
 // into the rank-padded device layout: first core [N][RP] (index b), last core [N][RP] (index a),
 // middle cores [N][RP*RP] (a + b*RP); padding entries are zero, which leaves every contraction exact.
+// One core per launch; c3sc_hip_upload_value_device pads all cores in one launch of k_pad_cores (pad_cores.hpp, prepass.hip) and
+// launches this kernel no more.  It stays because tests/test_chain_build.py holds every kernel of the build before the chain
+// kernels, by name, to that build's resource remarks.
 __global__ void k_pad_core(const double *__restrict__ src, double *__restrict__ dst, int N, int r0, int r1, int RP,
                            int kind /*0 first, 1 middle, 2 last*/)
 {
@@ -97,20 +102,22 @@ __global__ void k_core_images(double *__restrict__ arena, const ImgJobs J)
     }
 }
 
-// The fiber-pair kernel's three-core product tables (kernel_common.hpp: pair_tab3L_off), one thread per entry, blockIdx.y = side:
+// The fiber-pair kernel's three-core product tables (kernel_common.hpp: pair_tab3L_off), one thread per entry:
 //   left:  row (c, a, b)[beta]  = sum_alpha tabL(a, b)[alpha] G_2[c][alpha + beta RP]
 //   right: row (a, b, c)[alpha] = sum_beta  G_{d-3}[a][alpha + beta RP] tabR(b, c)[beta]
 // Each entry is ONE fma chain from 0.0 with the summed index ascending, as in k_core_images: a row is bit for bit the two-core row
 // pushed through the third core by vecmat_lds / matvec_lds or the uniform products.  Inputs are the padded core and the two-core
 // table, so padding stays exact zero.
+// Only the sides that some instantiation reads are built (kernel_common.hpp: fpp_table3_sides): blockIdx.y = job.
 struct Tab3Jobs {
     long tab2[2], core[2], dst[2]; // the side's two-core table, its third core, the three-core table
     int n3[2], npairs[2];          // nodes of the third core; index pairs of the two-core table
+    int left[2];                   // the job's side
 };
 __global__ void k_pair_tab3(double *__restrict__ arena, const Tab3Jobs J, int RP)
 {
     const int sd = blockIdx.y;
-    const bool left = sd == 0;
+    const bool left = J.left[sd] != 0;
     const double *tab2 = arena + J.tab2[sd], *core = arena + J.core[sd];
     double *dst = arena + J.dst[sd];
     const long np = J.npairs[sd], total = (long)J.n3[sd] * np * RP;
@@ -959,13 +966,18 @@ int c3sc_hip_upload_value_device(c3sc_hip_ctx *c, const size_t *ranks, const dou
     int rc = prepare_value(c, ranks, &cd);
     if (rc != C3SC_OK) return rc;
     const int d = c->d, rp = c->rp;
+    PadJobs J{};
+    J.d = d;
+    long maxtotal = 1;
     for (int m = 0; m < d; m++) {
-        const int kind = (m == 0) ? 0 : (m == d - 1 ? 2 : 1);
-        const long total = (long)c->ngrid[m] * (kind == 1 ? rp * rp : rp);
-        const int grid = (int)std::min<long>((total + 255) / 256, 1024);
-        hipLaunchKernelGGL(k_pad_core, dim3(grid), dim3(256), 0, (hipStream_t)stream, d_cores[m], c->arena + c->core_off[m],
-                           c->ngrid[m], (int)ranks[m], (int)ranks[m + 1], rp, kind);
+        J.src[m] = d_cores[m];
+        J.dst[m] = c->core_off[m];
+        J.N[m] = c->ngrid[m];
+        J.r0[m] = (int)ranks[m];
+        J.r1[m] = (int)ranks[m + 1];
+        maxtotal = std::max(maxtotal, (long)c->ngrid[m] * ((m == 0 || m == d - 1) ? rp : rp * rp));
     }
+    HIPCHK(c, pad_cores_launch(c->arena, J, rp, (unsigned)std::min<long>((maxtotal + 255) / 256, 1024), (hipStream_t)stream));
     HIPCHK(c, hipGetLastError());
     rc = make_quad_aux(c, stream);
     if (rc != C3SC_OK) return rc;
@@ -1070,14 +1082,17 @@ static int launch_one(c3sc_hip_ctx *c, const KernelEntry *e, const KArgs &A, con
 }
 
 // Smallest batch the fiber-pair launches partition (fiber_partition.hpp).  C3SC_FIBER_PARTITION, read at every launch, replaces
-// it: 0 switches the pass off, n > 0 runs it from n fibers on.  The three partition launches cost about 10 us in front of every
-// pair launch whatever the batch, what the absorbed tiles save grows with it: car7d loses 5 % at 2^17 fibers per launch
-// (1.469 -> 1.543 ms per step), gains 3.3 % at 2^20 and breaks even near 2^18 by those two figures.
+// it: 0 switches the pass off, n > 0 runs it from n fibers on.  The three partition launches stand in front of every pair launch
+// whatever the batch, what the absorbed and the grouped tiles save grows with it.  Traced at 2^20 fibers and 1682 bins the pass
+// takes 40 us per launch (count 20.5, scan 9.2, scatter 10.9; 53 us while the scatter sorted, 42 us before the grouping, and never
+// the 10 us first inferred here).  car7d, ms per step (profiles/r10_car7d_prepass.txt), pass off -> on:
+//   2^17 fibers  1.469 -> 1.543 (an earlier build; not measured again)
+//   2^18 fibers  2.660-2.711 -> 2.577-2.605, three alternating runs each way: the slowest run with the pass is 2.0 % under the
+//                fastest without it, so the threshold came down from 2^19 to here
+//   2^19 fibers  4.969-4.980 -> 4.789-4.827 and 2^20 fibers 9.320-9.365 -> 8.870-8.895 (profiles/r07_car7d_grouped_fold.txt)
 // The grouping by the fold's key levels rides in the same three launches (FPART_MIN_PER_BIN in fiber_partition.hpp: two keys from
-// 128 fibers per key on).  Traced, the pass takes 53 us per launch at 2^20 fibers (42 us before the grouping; the 10 us above was
-// an inference).  car7d at the threshold, 2^19 fibers (312 per key): 4.969-4.980 -> 4.789-4.827 ms per step; at 2^20 (624 per key)
-// 9.320-9.365 -> 8.870-8.895 (profiles/r07_car7d_grouped_fold.txt).
-constexpr long FIBER_PARTITION_MIN = 524288;
+// 128 fibers per key on; 2^18 fibers are 156 per key).
+constexpr long FIBER_PARTITION_MIN = 262144;
 static long fiber_partition_min()
 {
     const char *e = getenv("C3SC_FIBER_PARTITION");
@@ -1099,6 +1114,14 @@ static long fiber_group_floor()
     if (!e || !*e) return FPART_MIN_PER_BIN;
     const long v = atol(e);
     return v > 0 ? v : -1;
+}
+
+// C3SC_FIBER_RANK, read at every launch like C3SC_FIBER_PARTITION: 0 runs the pre-pass with the sorting kernels of
+// fiber_partition.hpp in the same build (the same permutation; for comparing the two)
+static bool fiber_rank()
+{
+    const char *e = getenv("C3SC_FIBER_RANK");
+    return !(e && *e && atol(e) == 0);
 }
 
 // whether partition_fibers runs its pass for this launch
@@ -1133,14 +1156,28 @@ static int ensure_tab3(c3sc_hip_ctx *c, hipStream_t st)
     }
     const int d = c->d, rp = c->rp;
     if (!c->tab3_ev) HIPCHK(c, hipEventCreateWithFlags(&c->tab3_ev, hipEventDisableTiming));
-    Tab3Jobs J;
-    J.tab2[0] = c->tabL_off; J.core[0] = c->core_off[2]; J.dst[0] = c->tab3L_off;
-    J.n3[0] = c->ngrid[2]; J.npairs[0] = c->ngrid[0] * c->ngrid[1];
-    J.tab2[1] = c->tabR_off; J.core[1] = c->core_off[d - 3]; J.dst[1] = c->tab3R_off;
-    J.n3[1] = c->ngrid[d - 3]; J.npairs[1] = c->ngrid[d - 2] * c->ngrid[d - 1];
-    const long total = std::max((long)J.n3[0] * J.npairs[0], (long)J.n3[1] * J.npairs[1]) * rp;
-    hipLaunchKernelGGL(k_pair_tab3, dim3((unsigned)std::min<long>((total + 255) / 256, 4096), 2), dim3(256), 0, st, c->arena, J, rp);
-    HIPCHK(c, hipGetLastError());
+    Tab3Jobs J{};
+    const Tab3Sides sides = fpp_table3_sides(d, rp); // a table no kernel of this (dimension count, rank) reads stays unbuilt
+    int n = 0;
+    long total = 0;
+    if (sides.left) {
+        J.left[n] = 1;
+        J.tab2[n] = c->tabL_off; J.core[n] = c->core_off[2]; J.dst[n] = c->tab3L_off;
+        J.n3[n] = c->ngrid[2]; J.npairs[n] = c->ngrid[0] * c->ngrid[1];
+        total = std::max(total, (long)J.n3[n] * J.npairs[n] * rp);
+        n++;
+    }
+    if (sides.right) {
+        J.left[n] = 0;
+        J.tab2[n] = c->tabR_off; J.core[n] = c->core_off[d - 3]; J.dst[n] = c->tab3R_off;
+        J.n3[n] = c->ngrid[d - 3]; J.npairs[n] = c->ngrid[d - 2] * c->ngrid[d - 1];
+        total = std::max(total, (long)J.n3[n] * J.npairs[n] * rp);
+        n++;
+    }
+    if (n > 0) {
+        hipLaunchKernelGGL(k_pair_tab3, dim3((unsigned)std::min<long>((total + 255) / 256, 4096), (unsigned)n), dim3(256), 0, st, c->arena, J, rp);
+        HIPCHK(c, hipGetLastError());
+    }
     HIPCHK(c, hipEventRecord(c->tab3_ev, st));
     c->tab3_stream = st;
     c->tab3_stale = false;
@@ -1170,7 +1207,7 @@ static int partition_fibers(c3sc_hip_ctx *c, const KernelEntry *e, const KArgs &
     }
     const PartScratch ps = fpart_carve(c->part[slot], A.F, P.nbins);
     c->part_last[slot] = {ps.perm, ps.nlive, A.F, io.stream};
-    HIPCHK(c, fpart_launch(P, io.idx, ps, io.stream));
+    HIPCHK(c, fiber_rank() ? fpart_launch(P, io.idx, ps, io.stream) : fpart_launch_sorting(P, io.idx, ps, io.stream));
     launched = 3;
     io.perm = ps.perm;
     io.nlive = ps.nlive;

@@ -168,6 +168,22 @@ __host__ __device__ constexpr bool pair_tab3_reserved(int d, const int *ngrid, i
 //   which the grouped-fold and absorbed-tiles tests hold at every K.  At K = 0 .. 3 no merged vector exists ahead of an absorbed
 //   level and every row is bit for bit the vector the two-core kernel folds.  They carry 12 of the 47 products the tables remove.
 __host__ __device__ constexpr bool fpp_table3_optout(int d, int rp, int k) { return d == 7 && rp == 10 && k >= 2; }
+// Which of the two tables some K off that list reads, so that the build (c3sc_hip.hip: ensure_tab3) leaves the other out: the left
+// table folds cores 0 .. 2, which lie left of K from K = 3 on; the right one cores d-3 .. d-1, right of K up to K = d - 4.
+struct Tab3Sides {
+    bool left, right;
+};
+__host__ __device__ constexpr Tab3Sides fpp_table3_sides(int d, int rp)
+{
+    Tab3Sides s{false, false};
+    for (int k = 0; k < d; k++) {
+        if (fpp_table3_optout(d, rp, k)) continue;
+        s.left = s.left || k >= 3;
+        s.right = s.right || k <= d - 4;
+    }
+    return s;
+}
+static_assert(!fpp_table3_sides(7, 10).left && fpp_table3_sides(7, 10).right, "car7d at rank 10: K = 0, 1 read the right table alone");
 // the key levels of the fiber-pair instantiation (d, padded rank, k), for the host's pre-pass and the kernel alike: none for the
 // direct-fold kernels (nothing is staged) and the opt-outs
 __host__ __device__ constexpr KeyLevels fpp_group_levels(int d, int rp, int k)
