@@ -1067,6 +1067,10 @@ static void arm_memo(c3sc_hip_ctx *c, const KernelEntry *e, KArgs &A)
 static hipError_t ctx_launch(const c3sc_hip_ctx *c, const KernelEntry &e, const KArgs &A, LaunchIO io)
 {
     io.form = c->switches;
+    // Parked node split of the pair kernels (kernel_fiber_pair.hpp: fpp_parked).  C3SC_PAIR_PARKED, read at every launch like
+    // C3SC_PAIR_TABLE3: 0 runs the rank-split kernels it replaces, in the same build
+    const char *pk = getenv("C3SC_PAIR_PARKED");
+    io.parked = !(pk && *pk && atol(pk) == 0);
     return launch_entry(e, A, io);
 }
 

@@ -35,6 +35,9 @@ CAR7_PLAN3(3, 0, 0)
 CAR7_PLAN3(4, 1, 6)
 CAR7_PLAN3(5, 2, 8)
 CAR7_PLAN3(6, 3, 16)
+// parked node split of the middle K at rank 10: the kernels stand in inst_car7d_fpp_pk.hip
+C3SC_FPP_PARKED(Car7D, 10, 2)
+C3SC_FPP_PARKED(Car7D, 10, 4)
 REG7P(4)
 REG7P(10)
 } // namespace c3sc

@@ -54,6 +54,9 @@
 #ifndef FPP_NODE_SPLIT_VGPRS
 #define FPP_NODE_SPLIT_VGPRS 140 // what the full-length vectors of a lane may take: 7 vectors at rank 10, the half-length cost of 12 + merging
 #endif
+#ifndef FPP_PARKED_K4
+#define FPP_PARKED_K4 1 // vectors car7d's K = 4 keeps in LDS under the parked node split (fpp_parked_count): 1 leaves six in registers, 2 five
+#endif
 
 namespace c3sc {
 
@@ -458,6 +461,40 @@ __host__ __device__ constexpr bool fpp_node_split()
                !fpp_node_split_optout(Model::D, RP, K);
 }
 
+// Parked node split.  A middle K carries more vectors than a lane holds at full length (car7d at rank 10: K = 2, 3, 4 carry
+// 9 / 11 / 7; six is what compiles without scratch in the node loop, K = 1's count), but in the node split both wavefronts hold
+// identical copies of every vector -- the same 64 fibers, alternate nodes -- so a vector kept in LDS is kept once for both, and
+// the node-split node loop needs far fewer rows than the rank split's three partial-sum blocks.  The last P node-loop slots (right
+// of K: dotted with a, behind the register dots) are written by their owner straight to home rows above L, R, VX and PX and
+// read back inside `stencil`; the other NV - P stay in Wf.  P by (dimension count, padded rank, K), 0 = form not used; the kernels
+// of the form are k_fiber_pair_pk / k_fiber_pair_part_pk, instantiated where an instantiation file says so (launch_fpp.hpp:
+// C3SC_FPP_PARKED).
+__host__ __device__ constexpr int fpp_parked_count(int d, int rp, int k) { return (d == 7 && rp == 10) ? (k == 2 ? 3 : (k == 4 ? FPP_PARKED_K4 : 0)) : 0; }
+template <class Model, int RP, int K>
+__host__ __device__ constexpr int fpp_parked()
+{
+    if constexpr (!FPP_NODE_SPLIT || fpp_direct<Model, RP>() || fpp_node_split<Model, RP, K>()) return 0;
+    else {
+        constexpr int P = PairPark<Model, K>::merged() != 0u ? fpp_parked_count(Model::D, RP, K) : 0;
+        // every parked slot lies right of K, and something stays in registers
+        return (P > 0 && PairMap<Model, K>::nv() - P >= PairMap<Model, K>::SL::nv() && PairMap<Model, K>::nv() - P > 0) ? P : 0;
+    }
+}
+// LDS rows (64 doubles) of a parked tile: the hand-over X[g][RH] of the register-held vectors from row 0; in the node loop L, R
+// (2 RP rows), VX (4), PX from fpp_parked_px_row; the homes above all of them, so the barrier that closes the hand-over closes
+// them too.  A home keeps the elements 2i, 2i + 1 of a lane side by side: RP / 2 reads of 16 bytes per vector.
+template <int RP>
+__host__ __device__ constexpr int fpp_parked_px_row() { return 2 * RP + 4; }
+template <class Model, int RP, int K>
+__host__ __device__ constexpr int fpp_parked_home_row()
+{
+    constexpr int hand = (PairMap<Model, K>::nv() - fpp_parked<Model, RP, K>()) * (RP / 2);
+    constexpr int low = fpp_parked_px_row<RP>() + PairPark<Model, K>::rows();
+    return hand > low ? hand : low;
+}
+template <class Model, int RP, int K>
+__host__ __device__ constexpr int fpp_parked_rows() { return fpp_parked_home_row<Model, RP, K>() + fpp_parked<Model, RP, K>() * RP; }
+
 // the parked rates as node_backup's Pre
 template <class Model, int K>
 struct PairPre {
@@ -559,7 +596,7 @@ __device__ __attribute__((always_inline)) inline void fold_step(const KArgs &A, 
     fold_level<GROUP && (m == KL.major || (KL.n > 1 && m == KL.minor))>(fi[m], body);
 }
 
-template <class Model, int RP, int K, int H, bool FORCED, bool PART, bool T3 = false>
+template <class Model, int RP, int K, int H, bool FORCED, bool PART, bool T3 = false, int PKD = 0>
 __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArgs &A, const double *__restrict__ ro,
                                                                      const int32_t *__restrict__ idx, double *__restrict__ outv,
                                                                      int32_t *__restrict__ uidx, int32_t *__restrict__ absorbed,
@@ -637,7 +674,14 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
             // by parity as in the node loop.  x as finalize forms it (PairPark: a coordinate no node reads is not kept).  The
             // block stands in front of the tile set-up and reads its own coordinates: nothing of a live tile is live across it.
             const bool whole = A.bctype[K] == C3SC_ABSORB || A.cends != 0;
-            const int jb = whole ? 0 : 1, je = whole ? N : N - 1;
+            int jb = whole ? 0 : 1;
+            const int je = whole ? N : N - 1;
+            // parked node split: the first node's output addresses are formed here, per absorbed tile; as constants of the launch
+            // they are hoisted out of the tile loop and spilled for the whole kernel (three VGPR pairs)
+            if constexpr (PKD > 0) {
+                asm volatile("" : "+v"(jb));
+                jb = __builtin_amdgcn_readfirstlane(jb);
+            }
             double xb[D];
 #pragma unroll
             for (int m = 0; m < D; m++) xb[m] = (m != K && PK::need_x(m)) ? ro[A.xg_off[m] + idx[f * D + m]] : 0.0;
@@ -683,7 +727,25 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
             Model::sigma(A.prm, x, u0, s0);
 #pragma unroll
             for (int m = 0; m < D; m++)
-                if ((PK::constd() >> m) & 1u) upwind_rates(A.t[2 * m], A.t[2 * m + 1], b0[m], s0[m], rpm[m], rpp[m]);
+                if ((PK::constd() >> m) & 1u) {
+                    if constexpr (PKD > 0) {
+                        // parked node split: t2 sigma^2 / 2 of a constant sigma is a constant of the launch, and hoisted out of the
+                        // tile loop it sits in a VGPR pair that is spilled for the whole kernel; formed per tile it is one product
+                        double t2 = A.t[2 * m + 1];
+                        asm volatile("" : "+s"(t2));
+                        upwind_rates(A.t[2 * m], t2, b0[m], s0[m], rpm[m], rpp[m]);
+                    } else
+                        upwind_rates(A.t[2 * m], A.t[2 * m + 1], b0[m], s0[m], rpm[m], rpp[m]);
+                }
+        }
+
+        // parked node split: Qc (the merged dimensions' share of Q = sum p, parked behind the hand-over) is summed here, in the order
+        // it is summed there, so that the merged rates are not held across the hand-over for it
+        double qc_pk = 0.0;
+        if constexpr (PKD > 0 && PK::merged() != 0u) {
+#pragma unroll
+            for (int m = 0; m < D; m++)
+                if (PM::mg(m)) { qc_pk += rpm[m]; qc_pk += rpp[m]; }
         }
 
         double L[RP], R[RP], W[NOWN][RP];
@@ -891,10 +953,66 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
         } // dbg & 1
         FPP_STAMP(1) // folding
         // ------------------------------------------------------------ swap halves: Wh[g][i] = component H*RH + i of vector g
-        constexpr bool NS = fpp_node_split<Model, RP, K>();
+        constexpr bool NS = fpp_node_split<Model, RP, K>() || PKD > 0;
+        constexpr int NR = NV - PKD; // parked node split (PKD > 0): the slots [NR, NV) live in LDS homes, not in Wf
+        static_assert(PKD == 0 || (PKD == fpp_parked<Model, RP, K>() && K > 0 && K < D - 1 && NR >= NVL && !T3), "parked slots are right of a middle K");
         double Wh[NS ? 1 : NV][RH];
-        double Wf[NS ? NV : 1][RP]; // node split: every vector at full length in both wavefronts
-        if constexpr (NS) {
+        double Wf[NS ? NR : 1][RP]; // node split: every vector at full length in both wavefronts
+        double *HM = sK;            // parked node split: the homes
+        if constexpr (PKD > 0) {
+            // the hand-over of the node split for the NR register-held vectors; a parked vector goes whole from its owner to its
+            // home rows in the first pass -- it never enters X and is not read back.  The homes lie above X and above everything
+            // the node loop keeps below them, so the barriers of the hand-over order them as well.
+            typedef double v2d __attribute__((ext_vector_type(2)));
+            double *X = sK; // [NR][RH][64]
+            HM = sK + fpp_parked_home_row<Model, RP, K>() * 64;
+            static_assert(fpp_parked_home_row<Model, RP, K>() >= NR * RH, "homes above the hand-over rows");
+            auto put_get_own = [&](auto ic, auto pc) __attribute__((always_inline)) {
+                constexpr int it = decltype(ic)::value, P = decltype(pc)::value;
+                if constexpr (PM::valid(it) && PM::owner(it) == H) {
+                    constexpr int slot = PM::template lslot<H>(it);
+                    static_for<PM::count(it)>([&](auto sc) __attribute__((always_inline)) {
+                        constexpr int s = decltype(sc)::value, g = PM::gslot(it) + s;
+                        if constexpr (g < NR) {
+#pragma unroll
+                            for (int i = 0; i < RH; i++) {
+                                X[(g * RH + i) * 64 + lane] = W[slot + s][P * RH + i];
+                                Wf[g][P * RH + i] = W[slot + s][P * RH + i];
+                            }
+                        } else if constexpr (P == 0) {
+#pragma unroll
+                            for (int i = 0; i < RH; i++) {
+                                v2d t;
+                                t.x = W[slot + s][2 * i];
+                                t.y = W[slot + s][2 * i + 1];
+                                *reinterpret_cast<v2d *>(HM + (((g - NR) * RH + i) * 64 + lane) * 2) = t;
+                            }
+                        }
+                    });
+                }
+            };
+            auto get_other = [&](auto ic, auto pc) __attribute__((always_inline)) {
+                constexpr int it = decltype(ic)::value, P = decltype(pc)::value;
+                if constexpr (PM::valid(it) && PM::owner(it) != H) {
+                    static_for<PM::count(it)>([&](auto sc) __attribute__((always_inline)) {
+                        constexpr int g = PM::gslot(it) + decltype(sc)::value;
+                        if constexpr (g < NR) {
+#pragma unroll
+                            for (int i = 0; i < RH; i++) Wf[g][P * RH + i] = X[(g * RH + i) * 64 + lane];
+                        }
+                    });
+                }
+            };
+            auto half = [&](auto pc) __attribute__((always_inline)) {
+                pair_barrier();
+                static_for<PM::NIT>([&](auto ic) __attribute__((always_inline)) { put_get_own(ic, pc); });
+                pair_barrier();
+                static_for<PM::NIT>([&](auto ic) __attribute__((always_inline)) { get_other(ic, pc); });
+            };
+            half(std::integral_constant<int, 0>{});
+            half(std::integral_constant<int, 1>{});
+            pair_barrier();
+        } else if constexpr (NS) {
             // hand-over of whole vectors, one half of the components at a time: each wavefront writes the vectors it folded and
             // reads the ones its partner folded, so NV * RH rows are in flight -- the half swap's buffer
             double *X = sK; // [NV][RH][64]
@@ -970,6 +1088,15 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
         // L and R move to LDS (rows of 64 lanes): both waves hold the same values, wave 0 stores L, wave 1 R.
         // The node loop re-reads them per use; that frees 2*RP*2 VGPRs for the 256-register budget.
         double *sL = sK, *sR = sK + RP * 64;
+        if constexpr (PKD > 0) {
+            // parked node split: the fiber number is read again rather than held across the fold and the hand-over (neither uses it)
+            int ln = lane;
+            asm volatile("" : "+v"(ln));
+            const long fr2 = tile * 64 + ln;
+            const long fp2 = fr2 < A.F ? fr2 : A.F - 1;
+            f = fp2;
+            if constexpr (PART) f = (long)perm[fp2];
+        }
         {
 #pragma unroll
             for (int a = 0; a < RP; a++) {
@@ -980,20 +1107,39 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
             // (wave 0 writes; both waves hold the same numbers) they do not occupy VGPRs during the partial sums
             if constexpr (H == 0) {
                 static_assert(PK::rows() <= NP, "parking rows exceed the reserved block");
-                double *PXw = sK + (2 * RP + 2 * (NP + 1) + NP) * 64;
+                double *PXw = sK + (PKD > 0 ? fpp_parked_px_row<RP>() : 2 * RP + 2 * (NP + 1) + NP) * 64; // parked node split: behind VX
+                if constexpr (PKD > 0) {
+                    // parked node split: coordinates and table values are read again here (the same loads, through a fiber
+                    // number the compiler cannot match with the first one) and not held across the fold and the hand-over
+                    long fr = f;
+                    asm volatile("" : "+v"(fr));
+                    int fi2[D];
+#pragma unroll
+                    for (int m = 0; m < D; m++) fi2[m] = (m == K || !(PK::need_x(m) || PK::nt() > 0)) ? 0 : idx[fr * D + m];
+                    double tv2[Model::NTAB > 0 ? Model::NTAB : 1];
+                    table_values<Model>(A, ro, fi2, tv2);
+#pragma unroll
+                    for (int m = 0; m < D; m++)
+                        if (PK::need_x(m)) PXw[PK::row_x(m) * 64 + lane] = ro[A.xg_off[m] + fi2[m]];
+#pragma unroll
+                    for (int t = 0; t < Model::NTAB; t++)
+                        if (PK::need_t(t)) PXw[PK::row_t(t) * 64 + lane] = tv2[t];
+                } else {
 #pragma unroll
                 for (int m = 0; m < D; m++)
                     if (PK::need_x(m)) PXw[PK::row_x(m) * 64 + lane] = x[m];
 #pragma unroll
                 for (int t = 0; t < Model::NTAB; t++)
                     if (PK::need_t(t)) PXw[PK::row_t(t) * 64 + lane] = tv[t];
+                }
 #pragma unroll
                 for (int m = 0; m < D; m++)
                     if ((PK::rates() >> m) & 1u) {
                         PXw[PK::row_pm(m) * 64 + lane] = rpm[m];
                         PXw[(PK::row_pm(m) + 1) * 64 + lane] = rpp[m];
                     }
-                if constexpr (PK::merged() != 0u) { // Qc: the merged dimensions' share of Q = sum p
+                if constexpr (PKD > 0 && PK::merged() != 0u) PXw[PK::row_q() * 64 + lane] = qc_pk;
+                else if constexpr (PK::merged() != 0u) { // Qc: the merged dimensions' share of Q = sum p
                     double qc = 0.0;
 #pragma unroll
                     for (int m = 0; m < D; m++)
@@ -1157,6 +1303,8 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
         double *B1 = B0 + (NP + 1) * 64;  // wave 1 -> wave 0 : P_1(j0)[NP], then v_1(j1)
         double *B2 = B1 + (NP + 1) * 64;  // wave 1 own       : P_1(j1)[NP]
         double *PX = B2 + NP * 64;        // parked per-fiber constants: x[m] (m != K) rows 0..D-1, model tables after
+        if constexpr (PKD > 0) PX = sK + fpp_parked_px_row<RP>() * 64; // no partial-sum blocks: behind the four rows of VX
+        static_assert(PKD == 0 || fpp_parked_px_row<RP>() + PK::rows() <= fpp_parked_home_row<Model, RP, K>(), "the parked rows end below the homes");
 
         // finalise one node from its assembled stencil (NV totals in PairMap order, node value last)
         auto finalize = [&](int jn, const double (&Vt)[NP], double vlo, double vhi) __attribute__((always_inline)) {
@@ -1259,7 +1407,21 @@ __device__ __attribute__((always_inline)) inline void fiber_pair_body(const KArg
 #pragma unroll
                 for (int g = 0; g < NVL; g++) Vt[g] = dot_reg<RP>(Wf[g], c);
 #pragma unroll
-                for (int g = NVL; g < NV; g++) Vt[g] = dot_reg<RP>(a, Wf[g]);
+                for (int g = NVL; g < NR; g++) Vt[g] = dot_reg<RP>(a, Wf[g]);
+                if constexpr (PKD > 0) { // the parked vectors last: their home rows are read under the register dots above
+                    typedef double v2d __attribute__((ext_vector_type(2)));
+#pragma unroll
+                    for (int p = 0; p < PKD; p++) {
+                        double w[RP];
+#pragma unroll
+                        for (int i = 0; i < RH; i++) {
+                            const v2d t = *reinterpret_cast<const v2d *>(HM + ((p * RH + i) * 64 + lane) * 2);
+                            w[2 * i] = t.x;
+                            w[2 * i + 1] = t.y;
+                        }
+                        Vt[NR + p] = dot_reg<RP>(a, w);
+                    }
+                }
             }
             Vt[NV] = v;
         };
@@ -1506,6 +1668,39 @@ __global__ void __launch_bounds__(FPP_THREADS, (fpp_waves_per_simd<Model, RP>())
     const int h = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (h == 0) fiber_pair_body<Model, RP, K, 0, FORCED, true, true>(A, ro, idx, outv, uidx, absorbed, perm, nlive_p, sKp, st);
     else fiber_pair_body<Model, RP, K, 1, FORCED, true, true>(A, ro, idx, outv, uidx, absorbed, perm, nlive_p, sKp, st);
+    if (st) atomicOr(A.status, st);
+}
+
+// the two kernels above under the parked node split (fpp_parked > 0): kernels of their own once more, with the argument lists of
+// the ones they stand in for; the launcher picks them unless LaunchIO::parked is off
+template <class Model, int RP, int K, bool FORCED>
+__global__ void __launch_bounds__(FPP_THREADS, (fpp_waves_per_simd<Model, RP>()))
+    k_fiber_pair_pk(const KArgs A, const double *__restrict__ ro, const int32_t *__restrict__ idx, double *__restrict__ outv,
+                    int32_t *__restrict__ uidx, int32_t *__restrict__ absorbed)
+{
+    extern __shared__ double sKp[];
+    constexpr int P = fpp_parked<Model, RP, K>();
+    static_assert(P > 0, "no parked node split for this instantiation");
+    unsigned st = 0;
+    const int h = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (h == 0) fiber_pair_body<Model, RP, K, 0, FORCED, false, false, P>(A, ro, idx, outv, uidx, absorbed, nullptr, nullptr, sKp, st);
+    else fiber_pair_body<Model, RP, K, 1, FORCED, false, false, P>(A, ro, idx, outv, uidx, absorbed, nullptr, nullptr, sKp, st);
+    if (st) atomicOr(A.status, st);
+}
+
+template <class Model, int RP, int K, bool FORCED>
+__global__ void __launch_bounds__(FPP_THREADS, (fpp_waves_per_simd<Model, RP>()))
+    k_fiber_pair_part_pk(const KArgs A, const double *__restrict__ ro, const int32_t *__restrict__ idx, double *__restrict__ outv,
+                         int32_t *__restrict__ uidx, int32_t *__restrict__ absorbed, const int32_t *__restrict__ perm,
+                         const int32_t *__restrict__ nlive_p)
+{
+    extern __shared__ double sKp[];
+    constexpr int P = fpp_parked<Model, RP, K>();
+    static_assert(P > 0, "no parked node split for this instantiation");
+    unsigned st = 0;
+    const int h = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (h == 0) fiber_pair_body<Model, RP, K, 0, FORCED, true, false, P>(A, ro, idx, outv, uidx, absorbed, perm, nlive_p, sKp, st);
+    else fiber_pair_body<Model, RP, K, 1, FORCED, true, false, P>(A, ro, idx, outv, uidx, absorbed, perm, nlive_p, sKp, st);
     if (st) atomicOr(A.status, st);
 }
 

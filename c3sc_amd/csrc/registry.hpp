@@ -29,6 +29,7 @@ struct LaunchIO {
     const int32_t *perm = nullptr;
     const int32_t *nlive = nullptr;
     bool tab3 = false; // ... and the three-core product tables are built: a partitioned launch may run its three-core kernel
+    bool parked = true; // ... and a K with a parked node split (kernel_fiber_pair.hpp: fpp_parked) runs it; false: the rank-split kernels
     // the context's switches (FORM_STOP | FORM_JUMP | FORM_IMPULSE | FORM_CORR, kernel_common.hpp): a run-time compiled model's kernels
     // of that form run.  The game and horizon bits travel in KArgs (game_gsz, hz_off), whose data the kernels read
     unsigned form = 0;
