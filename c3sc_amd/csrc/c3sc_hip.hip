@@ -1829,10 +1829,16 @@ static int chain_setup(c3sc_hip_ctx *c, const char *who, int variant, KArgs &A, 
 {
     if (c->model == C3SC_MODEL_TABLE) return failw(c, C3SC_ERR_UNSUPPORTED, who, ": the TABLE model has no device dynamics");
     if (!c->have_mca || c->model == 0) return failw(c, C3SC_ERR_ARG, who, ": mca and model must be set");
+    // a run-time compiled model with chain kernels (c3sc_hip_model_compile_mc) serves the modes the chain has a form of, where it
+    // was compiled with them; every other model serves the plain chain only
+    int njump = 0;
+    const bool mc = c->model >= C3SC_MODEL_USER && rtc_model_chain(c->model, njump);
     for (const FormRow &r : FORM_ROWS)
-        if (ctx_form(c) & r.bit)
+        if ((ctx_form(c) & r.bit) && !(mc && form_offered(r.bit, FORM_CHAIN)))
             return fails(c, C3SC_ERR_UNSUPPORTED, std::string(who) + ": the chain is not offered " + r.problems + " (" + r.off + " first)");
-    if (c->model >= C3SC_MODEL_USER) return failw(c, C3SC_ERR_UNSUPPORTED, who, ": run-time compiled models have no chain kernels");
+    if (c->model >= C3SC_MODEL_USER && !mc)
+        return failw(c, C3SC_ERR_UNSUPPORTED, who, ": this model was compiled without chain kernels (c3sc_hip_model_compile_mc, chain = 1)");
+    if (check_form_model(c, who) != C3SC_OK) return C3SC_ERR_UNSUPPORTED;
     if (c->ncand == 0 || c->cands_placeholder)
         return c->box_du > 0 ? failw(c, C3SC_ERR_UNSUPPORTED, who, ": the control box is not served (set_controls: the chain takes a candidate list)")
                              : failw(c, C3SC_ERR_ARG, who, ": set_controls first");
@@ -1865,10 +1871,10 @@ static int chain_check_device_nodes(c3sc_hip_ctx *c, const char *who, const int3
     return C3SC_OK;
 }
 
-int c3sc_hip_chain_transitions(c3sc_hip_ctx *c, size_t n, const int32_t *d_nodes, int32_t *d_uidx, double *d_value, double *d_stage,
-                               double *d_dt, double *d_P, int32_t *d_flag, void *stream)
+static int chain_outcomes(c3sc_hip_ctx *c, const char *who, bool extra, size_t n, const int32_t *d_nodes, int32_t *d_uidx, double *d_value,
+                          double *d_stage, double *d_dt, double *d_P, int32_t *d_flag, double *d_pself, double *d_pmark, double *d_markval,
+                          void *stream)
 {
-    const char *who = "chain_transitions";
     if (!c) return C3SC_ERR_ARG;
     KArgs A;
     const KernelEntry *e = nullptr;
@@ -1877,11 +1883,21 @@ int c3sc_hip_chain_transitions(c3sc_hip_ctx *c, size_t n, const int32_t *d_nodes
     if (n == 0) return C3SC_OK;
     if (!d_nodes) return failw(c, C3SC_ERR_ARG, who, ": null d_nodes");
     if (n > SIM_MAX_TRAJ) return failw(c, C3SC_ERR_ARG, who, ": more than 2^31 nodes in one call");
+    if (extra) { // the outcomes call: the kernels of a chain-compiled model only (chain_setup let a built-in model through)
+        int njump = 0;
+        if (!(c->model >= C3SC_MODEL_USER && rtc_model_chain(c->model, njump)))
+            return failw(c, C3SC_ERR_UNSUPPORTED, who, ": needs a model compiled with chain kernels (c3sc_hip_model_compile_mc, chain = 1)");
+        if ((d_pmark || d_markval) && !(ctx_form(c) & FORM_JUMP))
+            return failw(c, C3SC_ERR_ARG, who, ": d_pmark / d_markval need jumps on (c3sc_hip_set_jumps)");
+    }
     rc = chain_check_device_nodes(c, who, d_nodes, n, stream);
     if (rc != C3SC_OK) return rc;
     ChainK S;
     std::memset(&S, 0, sizeof(S));
     S.n = (long)n;
+    S.pself = d_pself;
+    S.pmark = d_pmark;
+    S.markval = d_markval;
     S.node0 = d_nodes;
     S.uidx = d_uidx;
     S.value = d_value;
@@ -1891,6 +1907,40 @@ int c3sc_hip_chain_transitions(c3sc_hip_ctx *c, size_t n, const int32_t *d_nodes
     S.flag = d_flag;
     LaunchIO io{c->arena, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream, &S};
     return launch_one(c, e, A, io, "chain_transitions: the chain kernels take a candidate list");
+}
+
+int c3sc_hip_chain_transitions(c3sc_hip_ctx *c, size_t n, const int32_t *d_nodes, int32_t *d_uidx, double *d_value, double *d_stage,
+                               double *d_dt, double *d_P, int32_t *d_flag, void *stream)
+{
+    return chain_outcomes(c, "chain_transitions", false, n, d_nodes, d_uidx, d_value, d_stage, d_dt, d_P, d_flag, nullptr, nullptr, nullptr, stream);
+}
+
+int c3sc_hip_chain_outcomes(c3sc_hip_ctx *c, size_t n, const int32_t *d_nodes, int32_t *d_uidx, double *d_value, double *d_stage,
+                            double *d_dt, double *d_P, int32_t *d_flag, double *d_pself, double *d_pmark, double *d_markval, void *stream)
+{
+    return chain_outcomes(c, "chain_outcomes", true, n, d_nodes, d_uidx, d_value, d_stage, d_dt, d_P, d_flag, d_pself, d_pmark, d_markval, stream);
+}
+
+int c3sc_hip_chain_outcomes_host(c3sc_hip_ctx *c, size_t n, const int32_t *nodes, int32_t *uidx, double *value, double *stage, double *dt,
+                                 double *P, int32_t *flag, double *pself, double *pmark, double *markval)
+{
+    if (!c) return C3SC_ERR_ARG;
+    if (n == 0) return c3sc_hip_chain_outcomes(c, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    if (!nodes) return fail(c, C3SC_ERR_ARG, "chain_outcomes_host: null nodes");
+    if (n > SIM_MAX_TRAJ) return fail(c, C3SC_ERR_ARG, "chain_outcomes_host: sizes too large");
+    if (c->d == 0) return fail(c, C3SC_ERR_ARG, "chain_outcomes_host: set_grid first");
+    int njump = 0;
+    (void)rtc_model_chain(c->model, njump);
+    if ((pmark || markval) && (njump == 0 || !(ctx_form(c) & FORM_JUMP)))
+        return fail(c, C3SC_ERR_ARG, "chain_outcomes_host: pmark / markval need a jump model with jumps on (c3sc_hip_set_jumps)");
+    const size_t d = (size_t)c->d, D = sizeof(double), I = sizeof(int32_t), M = (size_t)njump;
+    return stage_host(c, STAGE_PER_CALL, "chain_outcomes_host",
+                      {{nodes, n * d * I, SEG_IN}, {uidx, n * I, SEG_OUT}, {value, n * D, SEG_OUT}, {stage, n * D, SEG_OUT},
+                       {dt, n * D, SEG_OUT}, {P, n * 2 * d * D, SEG_OUT}, {flag, n * I, SEG_OUT}, {pself, n * D, SEG_OUT},
+                       {pmark, n * M * D, SEG_OUT}, {markval, n * M * D, SEG_OUT}},
+                      [&](const DevPtr *b) {
+                          return c3sc_hip_chain_outcomes(c, n, b[0], b[1], b[2], b[3], b[4], b[5], b[6], b[7], b[8], b[9], nullptr);
+                      });
 }
 
 int c3sc_hip_chain_transitions_host(c3sc_hip_ctx *c, size_t n, const int32_t *nodes, int32_t *uidx, double *value, double *stage,
@@ -1923,6 +1973,16 @@ int c3sc_hip_simulate_chain(c3sc_hip_ctx *c, const c3sc_hip_chain_args *a, void 
     if (a->save_every > a->nsteps && a->save_every > 1 && (a->d_traj || a->d_uidx))
         return failw(c, C3SC_ERR_ARG, who, ": save_every larger than nsteps");
     if (a->steps_per_launch < 0) return failw(c, C3SC_ERR_ARG, who, ": steps_per_launch < 0");
+    const bool hz = c->hz_dt > 0.0; // horizon mode: one launch per step, step s decides on the cores of V_{s+1} (as c3sc_hip_simulate)
+    if (hz) {
+        if (c->hz_nstack == 0) return failw(c, C3SC_ERR_ARG, who, ": horizon mode needs the value stack (c3sc_hip_upload_value_stack)");
+        if (a->nsteps + 1 > (size_t)c->hz_nstack) return failw(c, C3SC_ERR_ARG, who, ": nsteps exceeds the value stack (nstack - 1 stages)");
+        if (c->hz_stack_static != c->static_doubles)
+            return failw(c, C3SC_ERR_ARG, who, ": static data changed size after upload_value_stack; upload the stack again");
+        for (size_t s = 0; s <= a->nsteps; s++)
+            if (!find_sim_kernel(VARIANT_CHAIN_WALK, c->model, c->d, c->hz_rp[s]))
+                return failw(c, C3SC_ERR_UNSUPPORTED, who, ": no chain instantiation for a stage's padded rank");
+    }
     if (a->n == 0) return C3SC_OK;
     if (!a->d_node0) return failw(c, C3SC_ERR_ARG, who, ": null d_node0");
     const size_t n = a->n, d = (size_t)c->d;
@@ -1948,13 +2008,21 @@ int c3sc_hip_simulate_chain(c3sc_hip_ctx *c, const c3sc_hip_chain_args *a, void 
     S.traj = a->d_traj;
     S.uidx = a->d_uidx;
     S.vend = a->d_vend;
-    const int chunk = a->steps_per_launch > 0 ? a->steps_per_launch : 64;
+    const int chunk = hz ? 1 : (a->steps_per_launch > 0 ? a->steps_per_launch : 64);
+    if (hz) HIPCHK(c, hipMemcpyAsync(c->hz_stack, c->arena, c->static_doubles * sizeof(double), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     int s0 = 0;
     do { // at least one launch: nsteps = 0 still tests xi_0 and evaluates V_end
         S.s0 = s0;
         S.s1 = (int)std::min<long long>((long long)s0 + chunk, (long long)a->nsteps);
-        LaunchIO io{c->arena, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream, &S};
-        rc = launch_one(c, e, A, io, "simulate_chain: the chain kernels take a candidate list");
+        const KernelEntry *ek = e;
+        const double *ro = c->arena;
+        if (hz) { // the launch of step s0 (or the terminal-only launch of nsteps = 0) reads stage s1: V_{s0+1}, and V_nsteps at the end
+            for (int m = 0; m < c->d; m++) A.core_off[m] = c->hz_core_off[(size_t)S.s1 * MAXD + m];
+            ek = find_sim_kernel(VARIANT_CHAIN_WALK, c->model, c->d, c->hz_rp[S.s1]);
+            ro = c->hz_stack;
+        }
+        LaunchIO io{ro, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream, &S};
+        rc = launch_one(c, ek, A, io, "simulate_chain: the chain kernels take a candidate list");
         if (rc != C3SC_OK) return rc;
         s0 = S.s1;
     } while (s0 < (int)a->nsteps);
@@ -1978,7 +2046,7 @@ int c3sc_hip_simulate_chain_host(c3sc_hip_ctx *c, const c3sc_hip_chain_args *h)
     const size_t n = h->n, d = (size_t)c->d, se = h->save_every, D = sizeof(double), I = sizeof(int32_t);
     const size_t nrow = se ? h->nsteps / se + 1 : 0, nurow = se ? (h->nsteps + se - 1) / se : 0;
     return stage_host(c, STAGE_PER_CALL, "simulate_chain_host",
-                      {{h->d_node0, n * d * I, SEG_IN}, {h->d_uniform, h->d_uniform ? n * h->nsteps * D : 0, SEG_IN},
+                      {{h->d_node0, n * d * I, SEG_IN}, {h->d_uniform, h->d_uniform ? n * h->nsteps * D * ((ctx_form(c) & FORM_JUMP) ? 2 : 1) : 0, SEG_IN},
                        {h->d_cost, n * D, SEG_OUT}, {h->d_disc, n * D, SEG_OUT}, {h->d_time, n * D, SEG_OUT}, {h->d_vend, n * D, SEG_OUT},
                        {h->d_node, n * d * I, SEG_OUT}, {h->d_exit, n * sizeof(int64_t), SEG_OUT},
                        {h->d_traj, h->d_traj ? n * nrow * d * I : 0, SEG_OUT}, {h->d_uidx, h->d_uidx ? n * nurow * I : 0, SEG_OUT}},

@@ -41,11 +41,13 @@ struct ChainK {
     int save_every;         // 0: nothing saved
     unsigned long long seed;
     const int32_t *node0;   // [n][D] start nodes (walk, read when s0 == 0) / the nodes (transitions)
-    const double *uniform;  // [n][nsteps] uniforms in [0, 1), or null: Philox (philox_jump_uniforms' u0)
+    const double *uniform;  // [n][nsteps] uniforms in [0, 1), or null: Philox (philox_jump_uniforms' u0); a jump form's walk
+                            // reads [n][nsteps][2] = (v, u1)
     // walk: the state between launches ...
     int32_t *node;          // [n][D]
     double *cost, *disc, *time; // [n] J, D, T
-    long long *exit_step;   // [n] -1 running, s >= 0: absorbed / obstacle at step s, -(s + 2): stuck at step s
+    long long *exit_step;   // [n] -1 running, s >= 0: absorbed / obstacle at step s, -(s + 2): stuck at step s,
+                            // -(s + 2) - 2^32: stopped at step s (the forms with the stop action)
     // ... and what it saves
     int32_t *traj;          // [n][nsteps / save_every + 1][D] or null
     int32_t *uidx;          // walk: [n][ceil(nsteps / save_every)] or null; transitions: [n] or null
@@ -53,6 +55,8 @@ struct ChainK {
     // transitions: each may be null
     double *value, *stage, *dt, *P; // [n], [n], [n], [n][2D]
     int32_t *flag;          // [n]
+    // outcomes (k_chain_outcomes_form): each may be null
+    double *pself, *pmark, *markval; // [n], [n][NJUMP], [n][NJUMP]
 };
 
 // The function train at the node ix and at its 2D index-rule neighbours: V[2m] = lo, V[2m + 1] = hi, V[2D] = the node.  The
@@ -355,6 +359,311 @@ __global__ void __launch_bounds__(256) k_chain_walk(const KArgs A, const ChainK 
     S.exit_step[i] = ex;
     if (st) atomicOr(A.status, st);
 }
+
+// ------------------------------------------------------------------------------------------------ the chain of a form
+// The chain of the backup node_backup<.., FORM> applies, FORM a subset of {horizon, stop, jump} (form_offered, FORM_CHAIN); built
+// by hipRTC only, for models compiled with the chain flag (rtc.hip).  The kernels above keep their own chain_node: sharing it
+// would move their registers.
+//
+// Outcome order: the 2D axis neighbours (stencil order), then the marks m ascending with the weight rJ pi_m, rJ = h^2 lambda(x),
+// then -- in horizon mode only -- the self-loop with the weight W - C, C = sum p_k + rJ.  The total is W = C without the horizon
+// and W = h^2 / delta with it; the interval is h^2 / C, and delta with the horizon.  Sampling: the first outcome with v W < c_k
+// (cumulative sums in outcome order), else the last one with a positive weight -- so a negative self-loop is never drawn.
+// A mark outcome lands on a node of offgrid_cell's cell of the wrapped target: with whi the weight of the upper node of
+// dimension m, m ascending and t = u1 at the start, the upper node is taken iff t < whi, and t becomes t / whi if it was taken,
+// else (t - whi) / (1 - whi).  Under set_interp(ctx, 1) whi is 0 or 1, so the same rule names the nearer node.  A target inside
+// an obstacle or outside an absorbing dimension's range ends the walk where it stands: it pays D_{s+1} times jump_target_value's
+// cost and its exit word is s + 1.
+template <int D>
+struct ChainNodeForm {
+    int flag;      // chain_flag
+    int ui;        // the greedy candidate; ncand where the stop action wins; -1 on an absorbed, obstacle or stuck node
+    bool stuck;    // live, no horizon, no stop, and no valid candidate or a winner with C < 1e-14
+    bool stops;    // live, and the decision is the stop action
+    double value;  // the backup's value; the bound / obstacle cost on a flagged node
+    double stage;  // g(x, u); psi on a stopping node; the bound / obstacle cost on a flagged node
+    double W, dt;  // the total weight and the interval; 0 where the chain does not move
+    double rJ;     // the jump rate h^2 lambda(x); 0 where the chain does not move
+    double pself;  // the self-loop's weight W - C (horizon mode); 0 otherwise
+    double p[2 * D]; // the winner's un-normalised rates, stencil order; 0 where the chain does not move
+    double vnode;  // the function train at the node
+    double x[D];   // the node's coordinates
+};
+
+constexpr long long CHAIN_STOPPED_BIAS = (long long)1 << 32; // C3SC_CHAIN_STOPPED(s) = -(s + 2) - 2^32
+
+template <int MID, class Model, int RP, unsigned FORM>
+__device__ inline void chain_node_form(const KArgs &A, const double *__restrict__ ro, const CandLds<Model> &cr, const int (&ix)[Model::D],
+                                       ChainNodeForm<Model::D> &o, unsigned &st)
+{
+    static_assert(form_offered(FORM, FORM_CHAIN), "the chain has no such form (form_offered, FORM_CHAIN)");
+    constexpr bool HORIZON = (FORM & FORM_HORIZON) != 0, STOP = (FORM & FORM_STOP) != 0, JUMP = (FORM & FORM_JUMP) != 0;
+    constexpr int D = Model::D, DU = Model::DU, NT = Model::NTAB > 0 ? Model::NTAB : 1, NCFa = Model::NCF > 0 ? Model::NCF : 1;
+    double V[2 * D + 1];
+    node_stencil<D, RP>(A, ro, ix, V);
+    o.vnode = V[2 * D];
+    o.flag = chain_flag<D>(A, ro, ix, o.x);
+    double tv[NT];
+    table_values<Model>(A, ro, ix, tv);
+    double jrate = 0.0, jval = 0.0;
+    if constexpr (JUMP) jump_term<Model, RP>(A, ro, o.x, jump_constelm<Model>(A, ro), jrate, jval);
+    int ui;
+    unsigned stb = 0; // of the backup's bits the chain passes on the CFL bit only; it reports stuck nodes itself
+    o.value = node_backup<Model, 1, 1, CandLds<Model>, true, NoPre, FORM>(A, ro, o.x, tv, cr, V, o.flag, ui, stb, false, -1, NoPre(), jrate, jval);
+    const bool live = o.flag == 0;
+    bool stops = false;
+    if constexpr (STOP) stops = live && (ui == A.ncand);
+    // the winner's rates, by the statements of the backup's own dimensions
+    const int uc = ((ui < 0) || (ui >= A.ncand)) ? 0 : ui;
+    double u[DU], cf[NCFa];
+    cf[0] = 0.0;
+#pragma unroll
+    for (int k = 0; k < DU; k++) u[k] = ro[A.cands_off + uc * DU + k];
+#pragma unroll
+    for (int q = 0; q < Model::NCF; q++) cf[q] = ro[A.cfeat_off + uc * Model::NCF + q];
+    typename Model::Node nd;
+    Model::prep(A.prm, o.x, tv, nd);
+    double b[D], sg[D];
+    Model::drift(A.prm, nd, o.x, u, cf, b);
+    Model::sigma(A.prm, o.x, u, sg);
+    double C = 0.0;
+#pragma unroll
+    for (int m = 0; m < D; m++) {
+        upwind_rates(A.t[2 * m], A.t[2 * m + 1], b[m], sg[m], o.p[2 * m], o.p[2 * m + 1]);
+        C += o.p[2 * m];
+        C += o.p[2 * m + 1];
+    }
+    C += jrate;
+    o.stuck = HORIZON ? false : (live && !stops && ((ui < 0) || (C < 1e-14)));
+    const bool moves = live && !stops && !o.stuck;
+    st |= o.stuck ? (unsigned)C3SC_STATUS_STATIONARY : 0u;
+    st |= live ? (stb & (unsigned)C3SC_STATUS_CFL) : 0u;
+    const double g = Model::stage(A.prm, o.x, u);
+    o.stops = stops;
+    o.ui = moves ? ui : (stops ? A.ncand : -1);
+    o.stage = (live && !stops) ? g : o.value;
+    double W = C, dt = A.h2 / (moves ? C : 1.0);
+    if constexpr (HORIZON) {
+        dt = ro[A.hz_off];
+        W = A.h2 / dt;
+    }
+    o.W = moves ? W : 0.0;
+    o.dt = moves ? dt : 0.0;
+    o.rJ = moves ? jrate : 0.0;
+    o.pself = (HORIZON && moves) ? W - C : 0.0;
+#pragma unroll
+    for (int k = 0; k < 2 * D; k++) o.p[k] = moves ? o.p[k] : 0.0;
+}
+
+// one lane per node: chain_transitions' outputs, and with them the self-loop's and the marks' probabilities and the marks' values
+template <int MID, class Model, int RP, unsigned FORM>
+__global__ void __launch_bounds__(256) k_chain_outcomes_form(const KArgs A, const ChainK S, const double *__restrict__ ro)
+{
+    constexpr int D = Model::D;
+    extern __shared__ double smem[];
+    CandLds<Model> cr;
+    rollout_cands<Model>(A, ro, smem, cr);
+    const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long i = min(gid, S.n - 1); // tail lanes repeat the last node ...
+    const bool own = gid < S.n;       // ... and store nothing
+    int ix[D];
+    chain_load_node<D>(A, S.node0 + (size_t)i * D, ix);
+    ChainNodeForm<D> o;
+    unsigned st = 0;
+    chain_node_form<MID, Model, RP, FORM>(A, ro, cr, ix, o, st);
+    const double inv = o.W > 0.0 ? o.W : 1.0;
+    if constexpr ((FORM & FORM_JUMP) != 0) {
+        const int ce = jump_constelm<Model>(A, ro);
+#pragma unroll 1
+        for (int m = 0; m < Model::NJUMP; m++) {
+            double y[D];
+            const double pi = Model::jump(A.prm, o.x, m, y);
+            const double vj = jump_target_value<Model, RP>(A, ro, y, ce);
+            if (S.pmark && own) S.pmark[(size_t)i * Model::NJUMP + m] = (o.rJ * pi) / inv;
+            if (S.markval && own) S.markval[(size_t)i * Model::NJUMP + m] = vj;
+        }
+    }
+    if (!own) return;
+    if (S.uidx) S.uidx[i] = o.ui;
+    if (S.value) S.value[i] = o.value;
+    if (S.stage) S.stage[i] = o.stage;
+    if (S.dt) S.dt[i] = o.dt;
+    if (S.flag) S.flag[i] = o.flag;
+    if (S.pself) S.pself[i] = o.pself / inv;
+    if (S.P) {
+#pragma unroll
+        for (int k = 0; k < 2 * D; k++) S.P[(size_t)i * (2 * D) + k] = o.p[k] / inv;
+    }
+    if (st) atomicOr(A.status, st);
+}
+
+// one lane per trajectory
+template <int MID, class Model, int RP, unsigned FORM>
+__global__ void __launch_bounds__(256) k_chain_walk_form(const KArgs A, const ChainK S, const double *__restrict__ ro)
+{
+    constexpr bool HORIZON = (FORM & FORM_HORIZON) != 0, STOP = (FORM & FORM_STOP) != 0, JUMP = (FORM & FORM_JUMP) != 0;
+    constexpr int D = Model::D;
+    extern __shared__ double smem[];
+    CandLds<Model> cr;
+    rollout_cands<Model>(A, ro, smem, cr);
+    const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long i = min(gid, S.n - 1); // tail lanes repeat the last trajectory ...
+    const bool own = gid < S.n;       // ... and store nothing
+    const int se = S.save_every;
+    const long nrow = se > 0 ? S.nsteps / se + 1 : 0, nurow = se > 0 ? (S.nsteps + se - 1) / se : 0;
+    int ix[D];
+    double J, Dc, T;
+    long long ex;
+    if (S.s0 == 0) {
+        chain_load_node<D>(A, S.node0 + (size_t)i * D, ix);
+        J = 0.0;
+        Dc = 1.0;
+        T = 0.0;
+        ex = -1;
+        if (S.traj && own)
+#pragma unroll
+            for (int m = 0; m < D; m++) S.traj[(size_t)i * nrow * D + m] = ix[m];
+    } else {
+        chain_load_node<D>(A, S.node + (size_t)i * D, ix);
+        J = S.cost[i];
+        Dc = S.disc[i];
+        T = S.time[i];
+        ex = S.exit_step[i];
+    }
+    const double beta = A.discount;
+    unsigned st = 0;
+    // the launch that ends the call makes one more trip, at xi_nsteps (fin, wave-uniform): the flag test and V_end only
+    const int send = S.s1 == S.nsteps ? S.s1 + 1 : S.s1;
+    for (int s = S.s0; s < send; s++) {
+        const bool fin = s == S.nsteps;
+        ChainNodeForm<D> o;
+        unsigned stn = 0;
+        chain_node_form<MID, Model, RP, FORM>(A, ro, cr, ix, o, stn);
+        const bool running = ex == -1;
+        st |= (running && !fin) ? stn : 0u; // a frozen lane raises nothing more
+        // 1. the flag test
+        const bool exits = running && (o.flag != 0);
+        J = exits ? J + Dc * o.value : J;
+        ex = exits ? (long long)s : ex;
+        if (fin && S.vend && own) S.vend[i] = o.vnode;
+        // 2. a stuck node freezes the lane where it is; so does the stop action, which pays psi (o.value there)
+        const bool sticks = running && o.stuck && !fin;
+        ex = sticks ? -((long long)s + 2) : ex;
+        bool halts = false;
+        if constexpr (STOP) {
+            halts = running && !exits && o.stops && !fin;
+            J = halts ? J + Dc * o.value : J;
+            ex = halts ? -((long long)s + 2) - CHAIN_STOPPED_BIAS : ex;
+        }
+        const bool alive = running && !exits && !sticks && !halts && !fin;
+        if (S.uidx && se > 0 && s % se == 0 && !fin && own) S.uidx[(size_t)i * nurow + s / se] = (alive || halts) ? o.ui : -1;
+        // 3. the interval's cost, the clock and the discount, in this order
+        J = alive ? J + Dc * o.stage * o.dt : J;
+        T = alive ? T + o.dt : T;
+        Dc = alive ? Dc * exp(-beta * o.dt) : Dc;
+        // 4. the outcome: the first k with v W < c_k, else the last k with a positive weight
+        double v = 0.0, u1 = 0.0;
+        if (fin) { // no draw: row s of the uniforms does not exist
+        } else if (S.uniform) {
+            if constexpr (JUMP) {
+                v = S.uniform[((size_t)i * S.nsteps + s) * 2];
+                u1 = S.uniform[((size_t)i * S.nsteps + s) * 2 + 1];
+            } else v = S.uniform[(size_t)i * S.nsteps + s];
+        } else philox_jump_uniforms(S.seed, (unsigned long long)(S.traj_offset + i), (unsigned)s, v, u1);
+        const double vW = v * o.W;
+        double cum = 0.0;
+        int pick = -1, lastpos = -1;
+#pragma unroll
+        for (int k = 0; k < 2 * D; k++) {
+            cum += o.p[k];
+            pick = ((pick < 0) && (vW < cum)) ? k : pick;
+            lastpos = (o.p[k] > 0.0) ? k : lastpos;
+        }
+        int nmark = 0;
+        double ysel[D], ylast[D];
+#pragma unroll
+        for (int m = 0; m < D; m++) ysel[m] = ylast[m] = o.x[m];
+        if constexpr (JUMP) {
+            nmark = Model::NJUMP;
+#pragma unroll 1
+            for (int mk = 0; mk < Model::NJUMP; mk++) {
+                double y[D];
+                const double w = o.rJ * Model::jump(A.prm, o.x, mk, y);
+                cum += w;
+                const bool take = (pick < 0) && (vW < cum), pos = w > 0.0;
+                pick = take ? 2 * D + mk : pick;
+                lastpos = pos ? 2 * D + mk : lastpos;
+#pragma unroll
+                for (int m = 0; m < D; m++) {
+                    ysel[m] = take ? y[m] : ysel[m];
+                    ylast[m] = pos ? y[m] : ylast[m];
+                }
+            }
+        }
+        if constexpr (HORIZON) {
+            cum += o.pself;
+            pick = ((pick < 0) && (vW < cum)) ? 2 * D + nmark : pick;
+            lastpos = (o.pself > 0.0) ? 2 * D + nmark : lastpos;
+        }
+        const bool fell = pick < 0;
+        pick = fell ? lastpos : pick;
+        // a mark outcome: the wrapped target, its exit test (jump_target_value's) and its cell
+        bool lands = false;
+        int land[D];
+#pragma unroll
+        for (int m = 0; m < D; m++) land[m] = ix[m];
+        if constexpr (JUMP) {
+            const bool ismark = alive && (pick >= 2 * D) && (pick < 2 * D + nmark);
+            double yin[D], y[D];
+#pragma unroll
+            for (int m = 0; m < D; m++) yin[m] = fell ? ylast[m] : ysel[m];
+            wrap_periodic<D>(A, ro, yin, y);
+            const bool inobs = in_obstacle<D>(A, ro, y);
+            bool out = false;
+#pragma unroll
+            for (int m = 0; m < D; m++) {
+                const double *g = ro + A.xg_off[m];
+                out = out || ((A.bctype[m] == C3SC_ABSORB) && ((y[m] < g[0]) || (y[m] > g[A.ngrid[m] - 1])));
+            }
+            const double term = inobs ? Model::obscost(A.prm, y) : Model::boundcost(A.prm, y);
+            const bool leaves = ismark && (inobs || out);
+            J = leaves ? J + Dc * term : J; // Dc is D_{s+1} here
+            ex = leaves ? (long long)s + 1 : ex;
+            lands = ismark && !leaves;
+            const int ce = jump_constelm<Model>(A, ro);
+            double t = u1;
+#pragma unroll
+            for (int m = 0; m < D; m++) {
+                int ic;
+                double whi;
+                offgrid_cell(ro + A.xg_off[m], A.ngrid[m], y[m], ce, ic, whi);
+                const bool up = t < whi;
+                t = up ? t / whi : (t - whi) / (1.0 - whi);
+                land[m] = up ? ic + 1 : ic;
+            }
+        }
+#pragma unroll
+        for (int m = 0; m < D; m++) {
+            int lo, hi;
+            (void)fixed_neighbors(ix[m], A.ngrid[m], A.bctype[m], lo, hi);
+            const int nx = (pick == 2 * m) ? lo : ((pick == 2 * m + 1) ? hi : ix[m]);
+            ix[m] = alive ? (lands ? land[m] : nx) : ix[m];
+        }
+        // 5. the node after the step
+        if (S.traj && se > 0 && (s + 1) % se == 0 && !fin && own)
+#pragma unroll
+            for (int m = 0; m < D; m++) S.traj[((size_t)i * nrow + (s + 1) / se) * D + m] = ix[m];
+    }
+    if (!own) return;
+#pragma unroll
+    for (int m = 0; m < D; m++) S.node[(size_t)i * D + m] = ix[m];
+    S.cost[i] = J;
+    S.disc[i] = Dc;
+    S.time[i] = T;
+    S.exit_step[i] = ex;
+    if (st) atomicOr(A.status, st);
+}
+
 
 #ifndef __HIPCC_RTC__
 // the launcher of both kernels (rollout geometry: one lane per trajectory / node, the candidate table in dynamic LDS)

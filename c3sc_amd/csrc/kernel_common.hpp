@@ -332,11 +332,14 @@ constexpr unsigned model_form()
 // or with jumps, and horizon, stop, jump and corr combine freely (1 + 2 + 16 = 19 of the 64 masks).  k_rollout has those without
 // corr (11), k_rollout_ode the plain form and the game (2), the control-box minimiser the plain form only.  The model-independent
 // stencil kernels have no forms: a launch of one carries the mask 0.
-enum FormKind { FORM_PER_WAVE, FORM_ROLLOUT, FORM_ROLLOUT_ODE, FORM_BOX };
+// The Markov-chain kernels of a run-time compiled model (kernel_chain_walk.hpp) have every subset of horizon, stop
+// and jump (8).
+enum FormKind { FORM_PER_WAVE, FORM_ROLLOUT, FORM_ROLLOUT_ODE, FORM_BOX, FORM_CHAIN };
 __host__ __device__ constexpr bool form_offered(unsigned form, FormKind kind = FORM_PER_WAVE)
 {
     if (form & ~FORM_ALL) return false;
     if (kind == FORM_BOX) return form == 0u;
+    if (kind == FORM_CHAIN) return (form & ~(FORM_HORIZON | FORM_STOP | FORM_JUMP)) == 0u;
     if (kind == FORM_ROLLOUT_ODE) return (form & ~FORM_GAME) == 0u;
     if (kind == FORM_ROLLOUT && (form & FORM_CORR)) return false;
     if (form & FORM_GAME) return form == FORM_GAME;

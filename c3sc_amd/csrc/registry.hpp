@@ -119,6 +119,7 @@ RtcEntries rtc_entries();
 hipError_t rtc_launch(const KernelEntry &e, const KArgs &A, const LaunchIO &io);
 bool rtc_model_known(int model); // an id c3sc_hip_model_compile returned
 bool rtc_model_info(int model, int &du); // its control dimension (false: unknown id)
+bool rtc_model_chain(int model, int &njump); // compiled with the Markov-chain kernels (c3sc_hip_model_compile_mc, chain = 1); its marks
 unsigned rtc_model_forms(int model); // the FORM_* bits of the features it was compiled with (0: none, or an unknown id)
 inline hipError_t launch_entry(const KernelEntry &e, const KArgs &A, const LaunchIO &io) { return e.rtc ? rtc_launch(e, A, io) : e.fn(A, io); }
 #endif

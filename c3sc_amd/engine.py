@@ -42,6 +42,8 @@ EXPORTS = [
     "c3sc_hip_model_compile_ic", "c3sc_hip_model_code_object_ic", "c3sc_hip_set_impulses",
     "c3sc_hip_model_compile_cd", "c3sc_hip_model_code_object_cd", "c3sc_hip_set_correlation",
     "c3sc_hip_chain_transitions", "c3sc_hip_chain_transitions_host", "c3sc_hip_simulate_chain", "c3sc_hip_simulate_chain_host",
+    "c3sc_hip_model_compile_mc", "c3sc_hip_model_code_object_mc", "c3sc_hip_chain_outcomes", "c3sc_hip_chain_outcomes_host",
+    "c3sc_hip_model_has_chain",
 ]
 
 class SimArgs(C.Structure):
@@ -117,6 +119,11 @@ CORR_MAX = 8  # C3SC_CORR_MAX: most pairs of dimensions with a cross-diffusion t
 class ModelSpecCd(C.Structure):
     """struct c3sc_hip_model_spec_cd (include/c3sc_hip.h): the _ic spec plus the pairs of correlated dimensions"""
     _fields_ = [("ic", ModelSpecIc), ("ncorr", C.c_int), ("corr_dims", C.c_int * (2 * CORR_MAX))]
+
+
+class ModelSpecMc(C.Structure):
+    """struct c3sc_hip_model_spec_mc (include/c3sc_hip.h): the _cd spec plus the chain flag"""
+    _fields_ = [("cd", ModelSpecCd), ("chain", C.c_int)]
 
 
 STATUS_STATIONARY, STATUS_CFL, STATUS_DOMINANCE = 1, 2, 4  # C3SC_STATUS_*
@@ -215,6 +222,10 @@ def load_library():
         L.c3sc_hip_model_compile_cd.argtypes = [C.POINTER(ModelSpecCd), c_int_p]
         L.c3sc_hip_model_code_object_cd.argtypes = [C.POINTER(ModelSpecCd), C.c_void_p, c_size_p]
         L.c3sc_hip_set_correlation.argtypes = [C.c_void_p, C.c_int]
+        L.c3sc_hip_model_compile_mc.argtypes = [C.POINTER(ModelSpecMc), c_int_p]
+        L.c3sc_hip_model_code_object_mc.argtypes = [C.POINTER(ModelSpecMc), C.c_void_p, c_size_p]
+        L.c3sc_hip_chain_outcomes.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 11
+        L.c3sc_hip_chain_outcomes_host.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 10
         _LIB = L
     return _LIB
 
@@ -238,19 +249,21 @@ def _model_spec(source, d, du, ranks, box, udep_mask, uconst_mask, stage_udep, n
     return spec
 
 
-def _form_spec(spec, game, horizon, stop, njump, nimpulse, corr_pairs):
+def _form_spec(spec, game, horizon, stop, njump, nimpulse, corr_pairs, chain=0):
     """The shallowest of the nested spec structs that carries the request, and the suffix of the entry points that take it
     ("", "_ex", "_fh", "_os", "_jd", "_ic", "_cd": c3sc_hip_model_compile<suffix>, c3sc_hip_model_code_object<suffix>).  The
     pair list is passed as given (the library validates it), cut at CORR_MAX + 1 pairs' count."""
     pairs = [(int(i), int(j)) for i, j in corr_pairs]
     levels = [(ModelSpecEx, "_ex", 1 if game else 0), (ModelSpecFh, "_fh", 1 if horizon else 0), (ModelSpecOs, "_os", 1 if stop else 0),
-              (ModelSpecJd, "_jd", int(njump)), (ModelSpecIc, "_ic", int(nimpulse)), (ModelSpecCd, "_cd", len(pairs))]
+              (ModelSpecJd, "_jd", int(njump)), (ModelSpecIc, "_ic", int(nimpulse)), (ModelSpecCd, "_cd", len(pairs)),
+              (ModelSpecMc, "_mc", int(chain))]
     depth = max((q + 1 for q, (_, _, v) in enumerate(levels) if v), default=0)
     suffix = ""
     for struct, suffix, v in levels[:depth]:
         spec = struct(spec, v)
-    for p, (i, j) in enumerate(pairs[:CORR_MAX]):
-        spec.corr_dims[2 * p], spec.corr_dims[2 * p + 1] = i, j
+        if struct is ModelSpecCd:
+            for p, (i, j) in enumerate(pairs[:CORR_MAX]):
+                spec.corr_dims[2 * p], spec.corr_dims[2 * p + 1] = i, j
     return spec, suffix
 
 
@@ -261,7 +274,7 @@ def _model_fail(rc, what):
 
 def compile_model(source: str, d: int, du: int, ranks=(4, 8), box: bool = False, udep_mask: int = 0, uconst_mask: int = 0,
                   stage_udep: bool = True, name: Optional[str] = None, game: bool = False, horizon: bool = False,
-                  stop: bool = False, njump: int = 0, nimpulse: int = 0, corr_pairs=()) -> int:
+                  stop: bool = False, njump: int = 0, nimpulse: int = 0, corr_pairs=(), chain=False) -> int:
     """Compile a device model from source (c3sc_hip_model_compile, include/c3sc_hip.h states the source contract) and return
     its model id (>= MODEL_USER), usable wherever a built-in model id is.  No GPU is needed.  Raises C3scHipError with the
     compiler's log on failure; the error code is args[1].  game=True (c3sc_hip_model_compile_ex) adds the game kernels that
@@ -272,10 +285,12 @@ def compile_model(source: str, d: int, du: int, ranks=(4, 8), box: bool = False,
     jumprate and jump for M marks.  nimpulse=M > 0 (c3sc_hip_model_compile_ic) adds the impulse kernels that
     BellmanEngine.set_impulses needs: the source then defines impulse for M interventions.  corr_pairs=[(i, j), ...]
     (c3sc_hip_model_compile_cd) adds the corr kernels that BellmanEngine.set_correlation needs: the source then defines covar for
-    these pairs of dimensions, i < j."""
+    these pairs of dimensions, i < j.  chain=True (c3sc_hip_model_compile_mc) adds the Markov-chain kernels that
+    BellmanEngine.simulate_chain, chain_transitions and chain_outcomes need, in the plain form and in every combination of the
+    horizon, stop and jump features asked for here; chain=False is the model without the flag."""
     L = load_library()
     base = _model_spec(source, d, du, tuple(ranks), box, udep_mask, uconst_mask, stage_udep, name)
-    spec, suffix = _form_spec(base, game, horizon, stop, njump, nimpulse, corr_pairs)
+    spec, suffix = _form_spec(base, game, horizon, stop, njump, nimpulse, corr_pairs, chain)
     mid = C.c_int(0)
     rc = getattr(L, "c3sc_hip_model_compile" + suffix)(C.byref(spec), C.byref(mid))
     if rc != 0:
@@ -285,14 +300,15 @@ def compile_model(source: str, d: int, du: int, ranks=(4, 8), box: bool = False,
 
 def code_object(source: str, d: int, du: int, ranks=(4, 8), box: bool = False, udep_mask: int = 0, uconst_mask: int = 0,
                 stage_udep: bool = True, name: Optional[str] = None, game: bool = False, horizon: bool = False,
-                stop: bool = False, njump: int = 0, nimpulse: int = 0, corr_pairs=()) -> bytes:
+                stop: bool = False, njump: int = 0, nimpulse: int = 0, corr_pairs=(), chain=False) -> bytes:
     """The gfx950 code object of this spec (c3sc_hip_model_code_object): the loaded one if compile_model already compiled the
     spec, otherwise what compile_model would build now (its id and default name are in the kernel names), compiled and not
     registered.  game, horizon, stop, njump and nimpulse select the spec as in compile_model (stop: c3sc_hip_model_code_object_os,
-    njump: c3sc_hip_model_code_object_jd, nimpulse: c3sc_hip_model_code_object_ic, corr_pairs: c3sc_hip_model_code_object_cd)."""
+    njump: c3sc_hip_model_code_object_jd, nimpulse: c3sc_hip_model_code_object_ic, corr_pairs: c3sc_hip_model_code_object_cd,
+    chain: c3sc_hip_model_code_object_mc)."""
     L = load_library()
     base = _model_spec(source, d, du, tuple(ranks), box, udep_mask, uconst_mask, stage_udep, name)
-    spec, suffix = _form_spec(base, game, horizon, stop, njump, nimpulse, corr_pairs)
+    spec, suffix = _form_spec(base, game, horizon, stop, njump, nimpulse, corr_pairs, chain)
     cap = 16 << 20  # one compile when the code object fits; a larger one is compiled again into a buffer of its size
     for _ in range(2):
         buf = C.create_string_buffer(cap)
@@ -340,11 +356,13 @@ def decode_action(uidx, ncand: int):
 
 def decode_chain_exit(exit_step):
     """d_exit of a chain walk (c3sc_hip_simulate_chain) as (step, kind): -1 is (-1, "running"), s >= 0 is (s, "exit") -- an absorbed
-    or obstacle node at step s -- and -(s + 2) is (s, "stuck"); works elementwise on arrays."""
+    or obstacle node at step s, or with jumps on a jump out at step s - 1 -- -(s + 2) is (s, "stuck") and -(s + 2) - 2^32
+    (C3SC_CHAIN_STOPPED) is (s, "stopped"); works elementwise on arrays."""
     e = np.asarray(exit_step)
-    stuck = e <= -2
-    step = np.where(stuck, -e - 2, e)
-    kind = np.where(stuck, "stuck", np.where(e >= 0, "exit", "running"))
+    stopped = e <= -2 - (1 << 32)
+    stuck = (e <= -2) & ~stopped
+    step = np.where(stopped, -e - 2 - (1 << 32), np.where(stuck, -e - 2, e))
+    kind = np.where(stopped, "stopped", np.where(stuck, "stuck", np.where(e >= 0, "exit", "running")))
     if np.ndim(exit_step) == 0:
         return int(step), str(kind)
     return step, kind
@@ -687,6 +705,38 @@ class BellmanEngine:
                   "chain_transitions_host")
         return res
 
+    def chain_outcomes(self, nodes_t, njump: int = 0, stream_ptr: Optional[int] = None):
+        """Device API (c3sc_hip_chain_outcomes; models compiled with chain=True): chain_transitions' dict plus pself (n,), the
+        self-loop's probability (horizon mode, else 0), and with njump = M > 0 (jumps on) pmark (n, M), the marks' probabilities,
+        and markval (n, M), what a jump to each mark's target pays.  P, pmark and pself of a moving node sum to one."""
+        import torch
+
+        assert nodes_t.is_cuda and nodes_t.dtype == torch.int32 and nodes_t.is_contiguous() and nodes_t.shape[1] == self.d
+        n, d, dev = nodes_t.shape[0], self.d, nodes_t.device
+        f64 = dict(dtype=torch.float64, device=dev)
+        res = {"uidx": torch.empty((n,), dtype=torch.int32, device=dev), "value": torch.empty((n,), **f64),
+               "stage": torch.empty((n,), **f64), "dt": torch.empty((n,), **f64), "P": torch.empty((n, 2 * d), **f64),
+               "flag": torch.empty((n,), dtype=torch.int32, device=dev), "pself": torch.empty((n,), **f64)}
+        if njump > 0:
+            res["pmark"], res["markval"] = torch.empty((n, njump), **f64), torch.empty((n, njump), **f64)
+        if stream_ptr is None:
+            stream_ptr = torch.cuda.current_stream(dev).cuda_stream
+        ptr = [res[k].data_ptr() if k in res else None for k in ("uidx", "value", "stage", "dt", "P", "flag", "pself", "pmark", "markval")]
+        self._chk(self.L.c3sc_hip_chain_outcomes(self.h, n, nodes_t.data_ptr(), *ptr, C.c_void_p(stream_ptr)), "chain_outcomes")
+        return res
+
+    def chain_outcomes_host(self, nodes: np.ndarray, njump: int = 0):
+        """c3sc_hip_chain_outcomes_host: the same on numpy arrays (nodes int32 (n, d)), staged through device memory."""
+        nodes = np.ascontiguousarray(nodes, dtype=np.int32)
+        n, d = nodes.shape[0], self.d
+        res = {"uidx": np.empty((n,), np.int32), "value": np.empty((n,)), "stage": np.empty((n,)), "dt": np.empty((n,)),
+               "P": np.empty((n, 2 * d)), "flag": np.empty((n,), np.int32), "pself": np.empty((n,))}
+        if njump > 0:
+            res["pmark"], res["markval"] = np.empty((n, njump)), np.empty((n, njump))
+        ptr = [res[k].ctypes.data if k in res else None for k in ("uidx", "value", "stage", "dt", "P", "flag", "pself", "pmark", "markval")]
+        self._chk(self.L.c3sc_hip_chain_outcomes_host(self.h, n, nodes.ctypes.data, *ptr), "chain_outcomes_host")
+        return res
+
     def simulate_chain(self, node0_t, nsteps: int, seed: int = 0, uniform_t=None, save_every: int = 0, traj_offset: int = 0,
                        steps_per_launch: int = 0, stream_ptr: Optional[int] = None):
         """Device API (c3sc_hip_simulate_chain): node0_t int32 CUDA tensor (n, d) of start nodes.  Returns a dict of CUDA tensors:
@@ -707,7 +757,7 @@ class BellmanEngine:
         a.steps_per_launch, a.save_every = int(steps_per_launch), int(save_every)
         if uniform_t is not None:
             assert uniform_t.is_cuda and uniform_t.dtype == torch.float64 and uniform_t.is_contiguous()
-            assert tuple(uniform_t.shape) == (n, nsteps)
+            assert tuple(uniform_t.shape) in ((n, nsteps), (n, nsteps, 2))  # (v, u1) pairs with jumps on
             a.d_uniform = uniform_t.data_ptr()
         if save_every > 0:
             res["traj"] = torch.empty((n, nsteps // save_every + 1, d), dtype=torch.int32, device=dev)
@@ -733,7 +783,7 @@ class BellmanEngine:
         a.steps_per_launch, a.save_every = int(steps_per_launch), int(save_every)
         if uniform is not None:
             uniform = _f64(uniform)
-            assert uniform.shape == (n, nsteps)
+            assert uniform.shape in ((n, nsteps), (n, nsteps, 2))  # (v, u1) pairs with jumps on
             a.d_uniform = uniform.ctypes.data
         if save_every > 0:
             res["traj"] = np.empty((n, nsteps // save_every + 1, d), np.int32)

@@ -2297,10 +2297,11 @@ int c3control_simulate(struct C3Control *c, const double *x0, double dt, size_t 
 
 /* ---- the approximating Markov chain itself */
 
-/* the modes the chain is not offered in: every form of the backup other than the plain one */
-static int chain_mode_check(const char *who, const struct C3Control *c)
+/* the modes the chain is not offered in: every form of the backup other than the plain one; forms: the device model carries the
+   chain kernels of the stopping, jump and horizon forms (c3sc_hip_model_compile_mc), which are then let through */
+static int chain_mode_check(const char *who, const struct C3Control *c, int forms)
 {
-    if (c->dp->stopping || c->dp->jumps || c->dp->impulses || c->dp->correlation || c->dp->hz_dt > 0.0)
+    if (c->dp->impulses || c->dp->correlation || (!forms && (c->dp->stopping || c->dp->jumps || c->dp->hz_dt > 0.0)))
         return reject(who, "the chain is offered for the plain backup only: not in stopping, jump, impulse, correlation or horizon mode");
     if (c->opt_sim != NULL && c3opt_get_game(c->opt_sim, NULL, NULL, NULL, NULL, NULL) >= 0)
         return reject(who, "the chain is offered for the plain backup only: not for games");
@@ -2325,7 +2326,7 @@ int c3control_simulate_chain(struct C3Control *c, const int32_t *node0, size_t n
     if (c->policy_sim == NULL || c->opt_sim == NULL) return reject(who, "no implicit policy (c3control_add_policy_sim)");
     if (c->dp->stagecost == NULL) return reject(who, "the host callbacks (add_drift/diff/stagecost/...) are needed");
     if (!c3opt_is_bruteforce(c->opt_sim)) return reject(who, "the chain takes a candidate list (a BRUTEFORCE opt_sim), not a control box");
-    int rc = chain_mode_check(who, c);
+    int rc = chain_mode_check(who, c, 0); /* the host twin keeps the plain form */
     if (rc != 0) return rc;
     if (nsteps > 0 && uniforms == NULL) return reject(who, "null uniforms");
     const size_t dx = c->dx, du = c->du, dw = c->dw;
@@ -2435,7 +2436,7 @@ int c3control_simulate_chain_batch(struct C3Control *c, size_t ntraj, const int3
     int rc = batch_policy_check(who, c, 1); /* a walk never leaves the grid: a state transform has nothing to act on */
     if (rc != 0) return rc;
     if (c->dw != c->dx) return reject(who, "the device models have dw = dx (diagonal diffusion)");
-    rc = chain_mode_check(who, c);
+    rc = chain_mode_check(who, c, c3sc_hip_model_has_chain(c->dp->model));
     if (rc != 0) return rc;
     if (ntraj == 0) return 0;
     if (node0 == NULL) return reject(who, "null node0");

@@ -151,7 +151,12 @@ int c3control_simulate_batch(struct C3Control *, size_t ntraj, const double *x0,
  * ntraj x ceil(nsteps/save_every) (NULL, or save_every > 0); cost, disc, time, vend, exit_step [ntraj], node ntraj x dx (final).
  * Both return C3SC_ERR_ARG with a message on stderr for: no policy_sim, a control box, a node index out of range, and every mode
  * other than the plain backup (stopping, jumps, impulses, correlation, the horizon step, a game); the batch form also for no
- * device model, and C3SC_ERR_UNSUPPORTED where the model has no chain kernel at this rank. */
+ * device model, and C3SC_ERR_UNSUPPORTED where the model has no chain kernel at this rank.
+ * Where the device model carries chain kernels (c3sc_hip_model_compile_mc with chain = 1), c3control_simulate_chain_batch honours
+ * the control's stopping, jump and horizon switches: it walks the chain of that form (c3sc_hip.h; exit_step then also holds
+ * C3SC_CHAIN_STOPPED(s) and the word s + 1 of a jump out, and with jumps on uniforms is ntraj x nsteps x 2 = (v, u1)).  Horizon
+ * mode needs the device's value stack, which this API does not upload: the device's refusal (C3SC_ERR_ARG) is passed on.  The
+ * one-trajectory host twin c3control_simulate_chain keeps the plain form and rejects every mode as before. */
 int c3control_simulate_chain(struct C3Control *, const int32_t *node0, size_t nsteps, const double *uniforms, int32_t *traj,
                              int32_t *uidx, double *cost, double *disc, double *time, double *vend, long *exit_step);
 int c3control_simulate_chain_batch(struct C3Control *, size_t ntraj, const int32_t *node0, size_t nsteps, uint64_t seed,

@@ -376,8 +376,10 @@ int c3sc_hip_normals(uint64_t seed, uint64_t traj0, size_t ntraj, uint64_t step0
  * depend on that, on n, or on how a batch is split (traj_offset).  The state between launches shares c3sc_hip_simulate's buffer
  * of the context: calls on one context must not overlap.
  * Errors: C3SC_ERR_ARG (state not set, null inputs, a node index out of range, a C3SC_EB_NONE dimension, save_every = 0 with
- * d_traj / d_uidx, a save_every above nsteps and above 1 with either, as c3sc_hip_simulate); C3SC_ERR_UNSUPPORTED, the context staying usable: the TABLE model, a run-time compiled model, no
- * instantiation at the padded rank, a context in game, horizon, stopping, jump, impulse or correlation mode.  The control box is
+ * d_traj / d_uidx, a save_every above nsteps and above 1 with either, as c3sc_hip_simulate); C3SC_ERR_UNSUPPORTED, the context staying usable: the TABLE model, a run-time compiled model without chain
+ * kernels (c3sc_hip_model_compile_mc, below, adds them and the chain of the horizon, stopping and jump modes), no instantiation at
+ * the padded rank, a context in game, impulse or correlation mode, a built-in model in any mode, a mode the model's chain kernels
+ * were not compiled with.  The control box is
  * not served: the calls take the candidate list.  Both calls read the node indices back to check them, so they synchronise
  * `stream` once before they launch.  last_kernel names the kernel. */
 #define C3SC_CHAIN_STUCK(s) (-((int64_t)(s) + 2))
@@ -391,7 +393,8 @@ typedef struct c3sc_hip_chain_args {
     size_t nsteps;
     uint64_t traj_offset;    /* global index of walk 0 (Philox counter) */
     uint64_t seed;
-    const double *d_uniform; /* [n*nsteps] uniforms in [0, 1) or NULL (seeded Philox); wins when non-NULL */
+    const double *d_uniform; /* [n*nsteps] uniforms in [0, 1) or NULL (seeded Philox); wins when non-NULL; with jumps on
+                              * [n*nsteps*2] = (v, u1) */
     int steps_per_launch;    /* 0 = 64 */
     size_t save_every;       /* 0 = none; else nodes s = 0, e, 2e, ... <= nsteps and decisions s = 0, e, ... < nsteps */
     double *d_cost;          /* [n] J or NULL */
@@ -399,7 +402,8 @@ typedef struct c3sc_hip_chain_args {
     double *d_time;          /* [n] T or NULL */
     double *d_vend;          /* [n] V(xi_nsteps) or NULL */
     int32_t *d_node;         /* [n*d] final node or NULL */
-    int64_t *d_exit;         /* [n] -1 running, s >= 0 absorbed / obstacle at step s, C3SC_CHAIN_STUCK(s) stuck at step s; or NULL */
+    int64_t *d_exit;         /* [n] -1 running, s >= 0 absorbed / obstacle at step s, C3SC_CHAIN_STUCK(s) stuck at step s,
+                              * C3SC_CHAIN_STOPPED(s) stopped at step s, s + 1 a jump out at step s; or NULL */
     int32_t *d_traj;         /* [n][nsteps/save_every + 1][d] or NULL */
     int32_t *d_uidx;         /* [n][ceil(nsteps/save_every)] (-1 once frozen) or NULL */
 } c3sc_hip_chain_args;
@@ -756,6 +760,53 @@ int c3sc_hip_model_code_object_cd(const c3sc_hip_model_spec_cd *spec, void *buf,
  * as well.  Refused (C3SC_ERR_UNSUPPORTED): the box and TABLE calls, simulate and integrate -- a correlated rollout needs
  * correlated increments and off-grid diagonal targets, which are not offered. */
 int c3sc_hip_set_correlation(c3sc_hip_ctx *ctx, int on);
+
+/* The Markov chain of a run-time compiled model's own backup.  chain = 1 adds, per requested rank, the walk and
+ * the outcomes kernel of c3sc_hip_simulate_chain, c3sc_hip_chain_transitions and c3sc_hip_chain_outcomes, in the plain form and in
+ * every subset of {horizon, stop, jump} among the spec's features; game, impulse and corr features are allowed and add no chain
+ * kernel (the chain calls stay refused in those modes).  chain = 0 is exactly c3sc_hip_model_compile_cd: the same model id and
+ * code object, and a model the chain calls refuse.  C3SC_ERR_ARG: chain outside {0, 1}.
+ *
+ * The chain of a form, at a live node: the decision is the backup's (with jumps: jump_term under c3sc_hip_set_interp's class).
+ * With p_k the winner's 2d upwind rates, rJ = h^2 lambda(x) (0 without jumps), pi_m the mark weights and C = sum p_k + rJ, the
+ * outcomes are, in this order: the 2d axis neighbours (weights p_k), the marks m ascending (weights rJ pi_m) and, in horizon mode
+ * only, the self-loop (weight W - C).  The total is W = C and the interval dt = h^2 / C without the horizon; W = h^2 / delta and
+ * dt = delta with it.  J += D g dt, T += dt, D *= exp(-beta dt) as in the plain chain; then the outcome is the first k with
+ * v W < c_k (cumulative weights in outcome order), else the last k with a positive weight, so a negative self-loop weight (the
+ * backup raises C3SC_STATUS_CFL) is never drawn.  Stuck nodes: without the horizon a live node with no valid candidate or
+ * C < 1e-14, rJ inside C; in horizon mode none.
+ * A mark outcome m at step s has the target y = jump(x, m) with periodic coordinates wrapped.  If y lies inside an obstacle, or
+ * outside [lb, ub] on an absorbing dimension, the walk pays D_{s+1} (obscost | boundcost)(y) -- D after the interval -- its exit
+ * word is s + 1 and it stays at its node.  Otherwise it lands on a node of y's grid cell (clamped to the hull): with whi the
+ * interpolation weight of the upper node of dimension m and t = u1 at the start, for m ascending the upper node is taken iff
+ * t < whi, and then t = t / whi if it was taken, else t = (t - whi) / (1 - whi).  Under c3sc_hip_set_interp(ctx, 1) whi is 0 or 1
+ * and the walk lands on the nearer node.  The expectation of V over the corners is the interpolant the backup used.
+ * Stop: where the decision is the stop action (uidx = ncand) the walk pays D psi(x) and is frozen with the exit word
+ * C3SC_CHAIN_STOPPED(s); a saved decision row holds ncand there.  The transitions report uidx = ncand, dt = 0, P = 0,
+ * value = stage = psi.
+ * Horizon mode needs the value stack (c3sc_hip_upload_value_stack) with nsteps + 1 <= nstack, as c3sc_hip_simulate does: one
+ * launch per step, step s decides with V_{s+1}, d_vend = V_nsteps(xi_nsteps); J is not topped up with the terminal value.
+ * c3sc_hip_chain_transitions and c3sc_hip_chain_outcomes use the uploaded value: one stage of the operator.
+ * Uniforms: with jumps on, d_uniform is [n][nsteps][2] = (v, u1); Philox supplies both values of c3sc_hip_jump_uniforms.
+ *
+ * c3sc_hip_chain_outcomes: c3sc_hip_chain_transitions' outputs and d_pself [n], d_pmark [n*M] (the probabilities w / W) and
+ * d_markval [n*M] = Vjump(y_m) (what a jump to y_m pays in the backup), each NULL or given; M = njump, and without jumps
+ * d_pmark and d_markval must be NULL.  Over axis neighbours, marks and self-loop the probabilities of a moving node sum to one.
+ * Run-time compiled models with chain kernels only (C3SC_ERR_UNSUPPORTED otherwise). */
+#define C3SC_CHAIN_STOPPED(s) (-((int64_t)(s) + 2) - ((int64_t)1 << 32))
+typedef struct c3sc_hip_model_spec_mc {
+    c3sc_hip_model_spec_cd cd;
+    int chain;
+} c3sc_hip_model_spec_mc;
+int c3sc_hip_model_compile_mc(const c3sc_hip_model_spec_mc *spec, int *model_id);
+int c3sc_hip_model_code_object_mc(const c3sc_hip_model_spec_mc *spec, void *buf, size_t *size);
+/* 1 if model_id names a model compiled with chain = 1, else 0 */
+int c3sc_hip_model_has_chain(int model_id);
+int c3sc_hip_chain_outcomes(c3sc_hip_ctx *ctx, size_t n, const int32_t *d_nodes, int32_t *d_uidx, double *d_value, double *d_stage,
+                            double *d_dt, double *d_P, int32_t *d_flag, double *d_pself, double *d_pmark, double *d_markval,
+                            void *stream);
+int c3sc_hip_chain_outcomes_host(c3sc_hip_ctx *ctx, size_t n, const int32_t *nodes, int32_t *uidx, double *value, double *stage,
+                                 double *dt, double *P, int32_t *flag, double *pself, double *pmark, double *markval);
 
 int c3sc_hip_sync(c3sc_hip_ctx *ctx, void *stream);
 int c3sc_hip_get_status(c3sc_hip_ctx *ctx, unsigned *flags, int clear);
